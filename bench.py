@@ -10,13 +10,15 @@ One "step" = one pass of the hot path over the rank's resident shard of syntheti
    threshold are re-scored exactly on the owner rank at the end of the step].
 value = loop-candidate pairs/s summed over ranks (each pair includes building the descriptor of a 120k-point scan).
 
-Besides the contract line this prints (same JSON object): per-stage kernel times, HBM rooflines of the Cartesian and the
-polar BEV scatter, the Radon kernel's VALU / LDS figures, database-sweep legs in the shape of BASELINE configs[3]
-(10 k-entry RING / RING++ / DiSCO databases, 1 and 4 queries), the single-GPU shard of configs[4] (RING++ database of
-50 000 / 8 entries, one elevation-map frame, GICP), the GICP leg of configs[2] (20 forced iterations, a cold 5-iteration
-run and a run to convergence), single-call drop-in latencies, and the CPU baseline (oracle port, rank 0, N = 1).
+A plain run sets up, warms up, times the K steps and prints the contract line (with the per-stage kernel times of the timed
+steps).  With --full it also prints (same JSON object): HBM rooflines of the Cartesian and the polar BEV scatter, the Radon
+kernel's VALU / LDS figures, database-sweep legs in the shape of BASELINE configs[3] (10 k-entry RING / RING++ / DiSCO
+databases, 1 and 4 queries), the single-GPU shard of configs[4] (RING++ database of 50 000 / 8 entries, one elevation-map
+frame, GICP), the GICP leg of configs[2] (20 forced iterations, a cold 5-iteration run and a run to convergence), single-call
+drop-in latencies, the check of the timed outputs against the oracle, and the CPU baseline (oracle port, rank 0, N = 1).
+--dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy (see dump_outputs).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--chunks C]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--chunks C] [--full] [--dump-outputs DIR]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
          --master-port P bench.py --gpus N --steps K --warmup W
 """
@@ -288,6 +290,30 @@ def read_slot(c, parity, n_launch, depth, two_sets):
     if two_sets:
         return parity * n_launch + c - depth if c >= depth else (1 - parity) * n_launch + n_launch - depth + c
     return c - depth if c >= depth else n_launch + c
+
+
+DUMP_DB_SAMPLE = 128      # database entries (half spectra, 58 560 B each) in a --dump-outputs sample
+
+
+def dump_outputs(out_dir, out_dist, out_ang, sweep_val, sweep_row, spec32, write_slots, batch, seed=0):
+    """--dump-outputs: what the last timed step handed back, as out_dir/<name>.npy (float32 / float64, ~8 MB at the default size):
+      pair_dist, pair_angle [launches, batch]   distance and best rotation of every new scan against its loop candidate
+      sweep_dist, sweep_row [launches]          the best entry of every launch's database sweep
+      db_entry_sample [DUMP_DB_SAMPLE, 61, 120, 2]  a fixed, seeded sample of the database entries the step wrote (real / imaginary parts),
+      db_entry_sample_index [DUMP_DB_SAMPLE, 2]     at these (launch, scan) positions"""
+    os.makedirs(out_dir, exist_ok=True)
+    n_launch = len(write_slots)
+    rng = np.random.default_rng(seed)
+    pick = np.sort(rng.choice(n_launch * batch, size=min(DUMP_DB_SAMPLE, n_launch * batch), replace=False))
+    launch, scan = pick // batch, pick % batch
+    slots = torch.tensor([write_slots[c] for c in launch], dtype=torch.int64, device=spec32.device)
+    entries = spec32[slots, torch.from_numpy(scan).to(spec32.device)]
+    arrays = {"pair_dist": out_dist.cpu().numpy().astype(np.float32), "pair_angle": out_ang.cpu().numpy().astype(np.float32),
+              "sweep_dist": sweep_val.cpu().numpy().astype(np.float32), "sweep_row": sweep_row.cpu().numpy().astype(np.float64),
+              "db_entry_sample": torch.view_as_real(entries).cpu().numpy().astype(np.float32),
+              "db_entry_sample_index": np.stack([launch, scan], 1).astype(np.float64)}
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def verify_timed_outputs(n, whole, norm_group, group_first, out_dist, out_ang, cand_idx, db_launch_of, seed=0):
@@ -1057,7 +1083,7 @@ def after_timed_region(S):
 
     extra = {}
     gicp_res = None
-    if S.args.gicp_pairs > 0:
+    if S.args.full and S.args.gicp_pairs > 0:
         S.fence()
         gicp_res = gicp_leg(S.local_rank, S.rank, S.args.gicp_pairs, S.args.gicp_iters)
         if S.dist_on:   # whole-job GICP rate: all ranks' iterations / slowest rank's time
@@ -1091,7 +1117,7 @@ def after_timed_region(S):
                             all(verify.get(k, True) for k in ("fetched_rows_bit_identical", "sweep_value_equal", "sweep_row_equal")))
 
     topk_cmp = None
-    if S.dist_on:
+    if S.dist_on and S.args.full:
         # the two database designs of SURVEY.md 8(e) side by side: (a) replicate (all-gather the descriptors, every rank sweeps
         # everything: what the step does) vs (b) keep the database sharded, all-gather the QUERIES, exchange top-k rows only
         q_local = S.spec32[0, :4].contiguous()
@@ -1114,11 +1140,13 @@ def after_timed_region(S):
         # on the side stream the interval between a batch's events is STREAM time: it contains the wait for compute units the descriptor
         # kernel holds, so it is not a kernel duration and must not be added to the others.  The sweep's own duration is measured stand-alone
         # right here (same entries), the stream time is reported apart
-        S.fence()
         side_stream = {"sweeps_stream_time_ms_per_launch": kern_ms.pop("sweep"),
                        "note": "time between the events around a batch of sweeps on the side stream / launches in the batch: includes waiting for "
-                               "compute units held by the descriptor kernel on the compute stream; kernel_ms.sweep_standalone is the sweep's own duration"}
-        kern_ms["sweep_standalone"] = ev_ms(lambda: torch.min(ring.corr_sweep_fft(S.spec32[S.wslot(0), :1], S.spec32[S.db_slot(0)])[0], 1))
+                               "compute units held by the descriptor kernel on the compute stream; kernel_ms.sweep_standalone (--full) is the sweep's own "
+                               "duration"}
+        if S.args.full:
+            S.fence()
+            kern_ms["sweep_standalone"] = ev_ms(lambda: torch.min(ring.corr_sweep_fft(S.spec32[S.wslot(0), :1], S.spec32[S.db_slot(0)])[0], 1))
 
     return {"gicp_res": gicp_res, "kern_ms": kern_ms, "side_stream": side_stream, "topk_cmp": topk_cmp, "verify": verify}
 
@@ -1129,12 +1157,14 @@ def result_line(S):
     pmc = load_pmc()
     cells = 120 * 120
     bev_bytes = S.B * (12 * N_POINTS + 4 * cells)          # 12 B/point + 4 B/cell
+    full = S.args.full
     if S.FUSE:
         # the rasteriser no longer runs on its own in the timed region: its stand-alone roofline is measured right here (same
-        # scans, same box), the timed region's dominant kernel is the fused one (12 B/point in, one normalised sinogram out)
-        xyz0, offs0 = S.chunks[0]
-        S.kern_ms["bev_standalone"] = ev_ms(lambda: bev.cart_bev(xyz0, offs0, 1, 1, 120, 120, 1, out=S.img.view(S.B, -1)))
-        S.kern_ms["radon_standalone"] = ev_ms(lambda: S.plan.forward(S.img.view(S.B, 120, 120), raw=False, normalized=True))
+        # scans, same box; --full), the timed region's dominant kernel is the fused one (12 B/point in, one normalised sinogram out)
+        if full:
+            xyz0, offs0 = S.chunks[0]
+            S.kern_ms["bev_standalone"] = ev_ms(lambda: bev.cart_bev(xyz0, offs0, 1, 1, 120, 120, 1, out=S.img.view(S.B, -1)))
+            S.kern_ms["radon_standalone"] = ev_ms(lambda: S.plan.forward(S.img.view(S.B, 120, 120), raw=False, normalized=True))
         fused_bytes = S.B * (12 * N_POINTS + 4 * cells)
         achieved = fused_bytes / (S.kern_ms["bev_radon"] * 1e-3) / 1e9
     else:
@@ -1182,7 +1212,6 @@ def result_line(S):
             per = (r.get("launch_scans") or 1024) / 1024.0
             r = dict(r, hbm_bytes=r["hbm_bytes"] / per, valu_pipe_cycles_est=(r.get("valu_pipe_cycles_est") or 0) / per or None,
                      counters={k: v / per for k, v in (r.get("counters") or {}).items()})
-        sa = bev_bytes / (S.kern_ms["bev_standalone"] * 1e-3) / 1e9
         line["config"]["fused_launches"] = S.FUSE
         line["config"]["corr_launches_grouped"] = S.FUSE if S.GROUP_CORR else 1
         line["config"]["sweep_stream"] = "side" if (S.SIDE_SWEEP or S.EXCH == "fetch") else "main"
@@ -1199,9 +1228,11 @@ def result_line(S):
                             "valu_issue_frac": r.get("valu_issue_frac"), "lds_busy_frac": r.get("lds_busy_frac"),
                             "valu_roofline": valu_roofline(r, S.kern_ms["bev_radon"]),
                             "note": "per 1024 scans; the kernel also carries the VALU-bound Radon march (1.47 M two-tap samples per image), "
-                                    "so the HBM fraction of the fused kernel is below the stand-alone rasteriser's by construction",
-                            "ms_vs_separate_kernels": {"fused": S.kern_ms["bev_radon"], "bev_standalone": S.kern_ms["bev_standalone"],
-                                                       "radon_standalone": S.kern_ms["radon_standalone"]}}
+                                    "so the HBM fraction of the fused kernel is below the stand-alone rasteriser's by construction"}
+    if S.FUSE and full:
+        sa = bev_bytes / (S.kern_ms["bev_standalone"] * 1e-3) / 1e9
+        line["roofline"]["ms_vs_separate_kernels"] = {"fused": S.kern_ms["bev_radon"], "bev_standalone": S.kern_ms["bev_standalone"],
+                                                      "radon_standalone": S.kern_ms["radon_standalone"]}
         line["roofline_bev_scatter"] = {"kernel": "k_cart_lds (BEV scatter, stand-alone launch outside the timed region)", "bound": "hbm",
                                         "achieved": sa, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": sa / HBM_PEAK_GBS,
                                         "ms": S.kern_ms["bev_standalone"], "traffic": pmc.get("k_cart_lds", {}).get("hbm_bytes"),
@@ -1223,7 +1254,7 @@ def result_line(S):
             "gicp_knn_select_ms": S.gicp_res["kernel_ms"]["knn_select"], "gicp_cov_from_knn_ms": S.gicp_res["kernel_ms"]["cov_from_knn"],
             "gicp_pairs": S.gicp_res["pairs"]})
         line["roofline"]["gicp"] = gr
-    if S.FUSE:
+    if S.FUSE and full:
         line["roofline"]["bev_scatter_frac"] = line["roofline_bev_scatter"]["frac"]
         line["roofline"]["bev_scatter_gbs"] = line["roofline_bev_scatter"]["achieved"]
     if S.dist_on:
@@ -1265,7 +1296,7 @@ def result_line(S):
                             "compute_stream_wait_ms_per_launch": S.kern_ms.get("wait"),
                             "compute_stream_wait_ms_per_step": S.kern_ms.get("wait", 0.0) * S.CH,
                             "rescore": S.rescorer.stats if S.rescorer else None, "designs": S.topk_cmp, "verify": S.verify}
-    if not S.args.no_extra_legs:
+    if full and not S.args.no_extra_legs:
         # polar BEV (the rasteriser north_star names), DiSCO layout 40 x 120 x 20, same scans
         xyz0, offs0 = S.chunks[0]
         pcells = 40 * 120 * 20
@@ -1313,7 +1344,7 @@ def result_line(S):
         line["pipeline_shard"] = pipeline_shard_leg(S.device, S.spec32[:S.CH].reshape(-1, 61, 120), S.gicp_res)
         line["builds"] = build_legs(S.device, S.chunks)
         line["dropin_latency"] = dropin_latency_leg(host_scans(S.chunks[0][0], 1)[0])
-    if S.FUSE and not S.dist_on and S.args.verify > 0:
+    if full and S.FUSE and not S.dist_on and S.args.verify > 0:
         # the outputs of the timed loop's last fused launch are still in norm_group / out_dist / out_ang
         last = ((S.CH - 1) // S.FUSE) * S.FUSE
         line["verify"] = verify_timed_outputs(S.args.verify, make_shard.whole, S.norm_group[:(S.CH - last) * S.B], last, S.out_dist, S.out_ang, S.cand_idx,
@@ -1326,7 +1357,7 @@ def result_line(S):
             bad += int(float(v_f[0]) != float(S.sweep_val[int(c)]) or int(r_f[0]) != int(S.sweep_row[int(c)]))
         line["verify"]["sweep_mismatches"] = bad
         line["verify"]["ok"] = bool(line["verify"]["ok"] and bad == 0)
-    if S.FUSE and not S.args.no_extra_legs:
+    if full and S.FUSE and not S.args.no_extra_legs:
         # the other workgroup shape of the fused kernel on the same scans (N > 1 runs per_pair so that RCCL's kernels get in): measured, not assumed
         other = "per_pair" if S.fused_grid == "persistent" else "persistent"
         ng = min(S.FUSE, S.CH)
@@ -1345,7 +1376,7 @@ def result_line(S):
         S.plan.set_option(S.plan.OPT_FUSED_SKIP, 0)
         line["roofline"]["fused_phase_floors_ms_per_launch"] = fl
         line["roofline"]["frac_of_max_hbm_only_march_only"] = max(fl["hbm_only_no_march"], fl["march_only_no_rasteriser"]) / fl["full"]
-    if S.world == 1 and not S.args.no_cpu_baseline:
+    if full and S.world == 1 and not S.args.no_cpu_baseline:
         line["cpu_baseline"] = cpu_baseline(host_scans(S.chunks[0][0], min(S.args.cpu_sample, S.B)))
     return line
 
@@ -1353,18 +1384,18 @@ def result_line(S):
 def parse_args():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--steps", type=int, default=20, help="timed steps")
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--batch", type=int, default=1024, help="scan pairs per launch")
     ap.add_argument("--chunks", type=int, default=48, help="launches per step (resident shard = batch x chunks scans)")
     ap.add_argument("--fuse", type=int, default=FUSE_DEFAULT, help="BEV + Radon + normalisation of this many launches' scans in ONE persistent "
                     "kernel (mrs_ring_descriptors_batch; same bits); 0 = the two kernels per launch")
-    ap.add_argument("--gicp-pairs", type=int, default=256, help="120k-pt pairs per rank in the GICP leg (BASELINE configs[2]: 256; 0 = skip)")
+    ap.add_argument("--gicp-pairs", type=int, default=256, help="--full: 120k-pt pairs per rank in the GICP leg (BASELINE configs[2]: 256; 0 = skip)")
     ap.add_argument("--gicp-iters", type=int, default=20)
-    ap.add_argument("--cpu-sample", type=int, default=256, help="scans in the CPU baseline sample")
+    ap.add_argument("--cpu-sample", type=int, default=256, help="--full: scans in the CPU baseline sample")
     ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra-legs", action="store_true", help="only the headline step (+ GICP unless --gicp-pairs 0)")
-    ap.add_argument("--verify", type=int, default=8, help="after the timed region: this many random outputs of the last fused launch against the "
+    ap.add_argument("--no-extra-legs", action="store_true", help="--full: only the headline step (+ GICP unless --gicp-pairs 0)")
+    ap.add_argument("--verify", type=int, default=8, help="--full, after the timed region: this many random outputs of the last fused launch against the "
                     "oracle (N = 1, fused step only; 0 = skip)")
     ap.add_argument("--detail-file", default="bench_detail.json", help="every block of the result (kernel times, legs, rooflines per kernel, the CPU "
                     "baseline's settings) as one JSON object; the last stdout line is the compact contract line (< 4 KB).  '' = no file")
@@ -1396,7 +1427,15 @@ def parse_args():
                     "while the descriptor kernel runs), persistent otherwise")
     ap.add_argument("--replica", choices=("f16", "f32"), default="f16", help="--exchange allgather: fp16 replicas (29 280 B, half the bytes) + exact "
                     "owner re-scoring of every candidate within 2e-3 of the acceptance threshold, or the exact fp32 entries themselves (58 560 B, no re-scoring)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true", help="after the timed steps, also every other measurement and check: the GICP leg, the oracle "
+                    "check of the timed outputs (--verify), stand-alone kernel rooflines, the extra legs, the two database designs (N > 1) and the CPU "
+                    "baseline; without it only the headline figure is measured")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last one computed as DIR/<name>.npy "
+                    "(float32 / float64; rank 0)")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def main():
@@ -1802,6 +1841,8 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device=device)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out_dist, out_ang, sweep_val, sweep_row, spec32, [wslot(c) for c in range(CH)], B)
 
     S = types.SimpleNamespace(**locals())
     S.__dict__.update(after_timed_region(S))

@@ -69,3 +69,22 @@ def test_compact_line_is_small_strict_json():
     # strict detail: NaN / inf become null
     s = bench._strict({"a": float("nan"), "b": [np.int64(3), float("-inf")], "c": np.bool_(True)})
     assert s == {"a": None, "b": [3, None], "c": True}
+
+
+def test_full_and_dump_outputs_flags():
+    """a plain run is the headline only; --full adds every other leg; --dump-outputs names a directory; --steps is the number of timed steps"""
+    sys.path.insert(0, ROOT)
+    import importlib
+    bench = importlib.import_module("bench")
+    argv = sys.argv
+    try:
+        sys.argv = ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"]
+        a = bench.parse_args()
+        assert a.steps == 7 and a.warmup == 2 and a.full is False and a.dump_outputs is None
+        sys.argv = ["bench.py", "--full", "--dump-outputs", "out"]
+        a = bench.parse_args()
+        assert a.full is True and a.dump_outputs == "out"
+    finally:
+        sys.argv = argv
+    p = subprocess.run([sys.executable, BENCH, "--gpus", "1", "--steps", "0"], capture_output=True, text=True, env=_env(), timeout=300)
+    assert p.returncode != 0 and "--steps" in p.stderr

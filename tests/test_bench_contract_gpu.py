@@ -35,20 +35,67 @@ def _check_compact(last_line, detail):
     return c
 
 
-def _run(extra_env=None, extra_args=(), tmp=None):
+def _run(extra_env=None, extra_args=(), tmp=None, full=True, dump=None):
+    """a small bench run; full: with --full (every leg and check), the tests below read those blocks; dump: --dump-outputs directory"""
     import tempfile
     env = dict(os.environ)
     env.update(extra_env or {})
     with tempfile.TemporaryDirectory() as td:
         path = os.path.join(td, "detail.json")
         p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", "32",
-                            "--chunks", "3", "--cpu-sample", "8", "--gicp-pairs", "2", "--gicp-iters", "6", "--detail-file", path, *extra_args],
+                            "--chunks", "3", "--cpu-sample", "8", "--gicp-pairs", "2", "--gicp-iters", "6", "--detail-file", path,
+                            *(("--full",) if full else ()), *(("--dump-outputs", dump) if dump else ()), *extra_args],
                            capture_output=True, text=True, env=env, timeout=900)
         assert p.returncode == 0, p.stderr[-2000:]
         lines = [l for l in p.stdout.splitlines() if l.strip()]
         d = _strict_loads(open(path).read())          # every block of the result
     d["_compact"] = _check_compact(lines[-1], d)      # the contract line is the LAST line of stdout
     return d
+
+
+def test_plain_bench_run_measures_only_the_headline_and_dumps_its_outputs(tmp_path):
+    """Without --full the run sets up, warms up, times the steps and prints the line: no GICP leg, no oracle check, no extra legs, no CPU
+    baseline.  --dump-outputs writes the last timed step's outputs, the same bits for two runs with the same arguments."""
+    import numpy as np
+    runs = []
+    for i in range(2):
+        out = str(tmp_path / f"run{i}")
+        d = _run(full=False, dump=out)
+        assert d["steps"] == 3 and d["warmup"] == 1 and d["unit"] == "pairs/s" and d["higher_is_better"] is True and d["dtype"] == "f32"
+        assert abs(d["value"] - 32 * 3 * 3 / (d["ms_per_step"] * 3e-3)) < 1e-6 * d["value"]
+        assert d["gicp"] is None and "verify" not in d and "cpu_baseline" not in d and d["kernel_ms"]["bev_radon"] > 0
+        for leg in ("roofline_bev_scatter", "roofline_polar", "sweeps", "node_shape", "builds", "dropin_latency"):
+            assert leg not in d, leg
+        a = {f[:-4]: np.load(os.path.join(out, f)) for f in sorted(os.listdir(out))}
+        assert set(a) == {"pair_dist", "pair_angle", "sweep_dist", "sweep_row", "db_entry_sample", "db_entry_sample_index"}
+        assert all(x.dtype in (np.float32, np.float64) for x in a.values()) and sum(x.nbytes for x in a.values()) < 64 << 20
+        assert a["pair_dist"].shape == (3, 32) and a["sweep_row"].shape == (3,) and a["db_entry_sample"].shape == (96, 61, 120, 2)
+        assert np.isfinite(a["pair_dist"]).all() and np.isfinite(a["db_entry_sample"]).all() and np.abs(a["db_entry_sample"]).max() > 0
+        runs.append(a)
+    for k in runs[0]:
+        assert np.array_equal(runs[0][k], runs[1][k]), k
+    # the dumped arrays are what the timed step computed: recomputed here from the same seeded scans and candidates with the separate-kernel
+    # path (ring_descriptors + half_spectrum, corr_pairs_fft, corr_sweep_fft).  3 launches in one group: DEPTH = 3, so launch c reads the
+    # entries launch c wrote one step earlier, i.e. the spectra of its own scans
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    from mr_slam_amd import ring
+    a, dev = runs[0], "cuda:0"
+    chunks = bench.make_shard(32, 3, 0, dev)
+    spec = torch.stack([ring.half_spectrum(ring.ring_descriptors(xyz, offs)[2]) for xyz, offs in chunks])      # [3, 32, 61, 120]
+    cand = torch.randint(0, 32, (3, 32), generator=torch.Generator(device=dev).manual_seed(7), device=dev, dtype=torch.int32)
+    idx = a["db_entry_sample_index"].astype(np.int64)
+    want = torch.view_as_real(spec[torch.from_numpy(idx[:, 0]).to(dev), torch.from_numpy(idx[:, 1]).to(dev)]).cpu().numpy()
+    np.testing.assert_allclose(a["db_entry_sample"], want, rtol=1e-5, atol=1e-5)
+    for c in range(3):
+        d, ang = ring.corr_pairs_fft(spec[c], spec[c][cand[c].long()])
+        np.testing.assert_allclose(a["pair_dist"][c], d.cpu().numpy(), rtol=0, atol=1e-5)
+        assert np.array_equal(a["pair_angle"][c], ang.cpu().numpy().astype(np.float32)), c
+        ds, _ = ring.corr_sweep_fft(spec[c, :1], spec[c])
+        ds = ds[0].cpu().numpy()
+        row = int(a["sweep_row"][c])
+        assert row == a["sweep_row"][c] and 0 <= row < 32 and abs(float(a["sweep_dist"][c]) - float(ds.min())) <= 1e-6 and ds[row] - ds.min() <= 1e-6, c
 
 
 def test_bench_line_contract():
@@ -191,7 +238,7 @@ def _two_ranks(port, extra):
         path = os.path.join(td, "detail.json")
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
                "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "32",
-               "--chunks", "3", "--gicp-pairs", "2", "--gicp-iters", "4", "--no-extra-legs", "--verify-exchange", "--detail-file", path, *extra]
+               "--chunks", "3", "--gicp-pairs", "2", "--gicp-iters", "4", "--no-extra-legs", "--verify-exchange", "--full", "--detail-file", path, *extra]
         p = subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=900)
         assert p.returncode == 0, p.stdout[-1500:] + p.stderr[-3000:]
         lines = [l for l in p.stdout.splitlines() if l.strip().startswith("{")]

@@ -1,7 +1,7 @@
 """The reference's OWN Python (RING_ros/util.py, disco_ros/models/DiSCO.py, phase_corr of disco_ros/main.py), unmodified, executed on the
 GPU through the drop-in modules (`mr_slam_amd.compat.install()`): the glue the golden vectors cannot show -- tensor devices, dtypes,
-`.cpu()` round trips, constructor / retreive() call sequences.  The files are read from /root/reference where that tree exists and from
-the git-ignored scratch copies tools/stage_reference_py.py makes for the GPU box (tests/_refpy/); skipped when neither is there."""
+`.cpu()` round trips, constructor / retreive() call sequences.  The files are read where the reference tree exists (tests/golden/ref_import.py);
+skipped where it does not."""
 import os
 import sys
 

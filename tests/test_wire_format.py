@@ -53,24 +53,6 @@ def test_bench_valu_roofline_helper():
     assert bench.valu_roofline({}, 0.4) is None and bench.valu_roofline(None, 0.4) is None and bench.valu_roofline(e, 0.0) is None
 
 
-def test_reference_python_staging_for_the_gpu_box():
-    """tools/stage_reference_py.py: the five reference Python files the GPU-box test executes through the drop-in are copied into the git-ignored
-    scratch directory tests/_refpy/ (same relative layout), and tests/golden/ref_import.py falls back to it where /root/reference is absent."""
-    import os
-    import sys
-    sys.path.insert(0, os.path.join(ROOT, "tools"))
-    import stage_reference_py as S
-    assert "tests/_refpy/" in open(os.path.join(ROOT, ".gitignore")).read().split()
-    assert not any(l.strip().startswith("tests/_refpy") for l in open(os.path.join(ROOT, ".gpurunignore")).read().splitlines()) \
-        if os.path.exists(os.path.join(ROOT, ".gpurunignore")) else True
-    if not os.path.isdir(os.path.join(S.REF, "LoopDetection")):
-        pytest.skip("reference tree not present")
-    assert S.stage(quiet=True)
-    for f in S.FILES:
-        staged = os.path.join(ROOT, "tests", "_refpy", f)
-        assert os.path.isfile(staged) and open(staged, "rb").read() == open(os.path.join(S.REF, f), "rb").read()
-
-
 def test_committed_pmc_summary_prices_instructions_by_class():
     """profiles/r03_pmc.json: the VALU-pipe estimate of every profiled kernel lies between the all-2-cycle and the all-4-cycle bounds and the fused
     descriptor kernel carries the launch size it was profiled at (bench.py scales its counters to 1024 scans)."""
