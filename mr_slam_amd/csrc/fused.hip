@@ -222,19 +222,9 @@ template <int MAX_RAYS_PER_LANE, int STRIDE, int PF, bool ONCE = false>
 __global__ __launch_bounds__(kRadonWG) void k_bev_radon3(const float* __restrict__ xyz, const int64_t* __restrict__ offs, CartP cp, RadonP p, SlotP sp,
                                                          int batch, float* __restrict__ bev_out, float* __restrict__ sino_raw,
                                                          float* __restrict__ sino_norm, float* __restrict__ park, int* __restrict__ degenerate,
-                                                         unsigned* __restrict__ next_pair, unsigned stagger_ticks,
-                                                         unsigned long long* __restrict__ prof, int dev_skip)
+                                                         unsigned* __restrict__ next_pair, unsigned stagger_ticks, int dev_skip)
 {
-    // dev_skip (development aid, MRS_FUSED_SKIP): 1 = no rasterising, 2 = no ray march (results are then meaningless)
-    // prof (development aid, MRS_FUSED_PROF=1): 100 MHz ticks per phase summed over workgroups and rounds: clear, rasterise, march, normalise
-    unsigned long long tp = 0;
-    auto stamp = [&](int phase) {
-        if (prof && threadIdx.x == 0) {
-            const unsigned long long now = wall_clock64();
-            if (phase >= 0) atomicAdd(prof + phase, now - tp);
-            tp = now;
-        }
-    };
+    // dev_skip (plan option MRS_RADON_OPT_FUSED_SKIP, for phase floors): 1 = no rasterising, 2 = no ray march (results are then meaningless)
     extern __shared__ __attribute__((aligned(16))) int lds_i[];   // [rows][stride] cells of (A, B) texels, as ints while rasterising
     __shared__ double red[2][16];
     __shared__ unsigned s_next;
@@ -257,10 +247,8 @@ __global__ __launch_bounds__(kRadonWG) void k_bev_radon3(const float* __restrict
         const int b0 = 2 * (int)pair, b1 = b0 + 1;
         const bool two = b1 < batch;
         int2* z2 = reinterpret_cast<int2*>(lds_i);
-        stamp(-1);
         for (int i = threadIdx.x; i < rows * p.stride; i += kRadonWG) z2[i] = make_int2(0, 0);
         __syncthreads();
-        stamp(0);
         if (!(dev_skip & 1)) {
             const int64_t o = offs[b0];
             const int n = (int)(offs[b0 + 1] - o);
@@ -274,7 +262,6 @@ __global__ __launch_bounds__(kRadonWG) void k_bev_radon3(const float* __restrict
             rasterise_scan<PF>(lds_i, 1, px, px + n, px + 2 * (size_t)n, n, cp, p.stride);
         }
         __syncthreads();
-        stamp(1);
         if (bev_out) {   // the COMPACT layout of mrs_bev_cart_batch: [b][ix][iy]
             for (int i = threadIdx.x; i < hw; i += kRadonWG) {
                 const int y = i / p.W, x = i - y * p.W;
@@ -334,7 +321,6 @@ __global__ __launch_bounds__(kRadonWG) void k_bev_radon3(const float* __restrict
             }
             __syncthreads();
         }
-        stamp(2);
         if (sino_norm) {
             float va[MAX_RAYS_PER_LANE], vb[MAX_RAYS_PER_LANE];
 #pragma unroll
@@ -349,7 +335,6 @@ __global__ __launch_bounds__(kRadonWG) void k_bev_radon3(const float* __restrict
         }
         if (threadIdx.x == 0) s_next = gridDim.x + atomicAdd(next_pair, 1u);
         __syncthreads();
-        stamp(3);
         pair = s_next;
     }
 }
@@ -458,27 +443,10 @@ int mrs_ring_descriptors_batch(mrs_radon_plan* plan, const float* d_xyz, const i
             if ((st = parkbuf.alloc((size_t)grid * 2 * rays * sizeof(float), s)) != MRS_OK) return st;
             d_park = parkbuf.as<float>();
         }
-        static const bool want_prof = mrs::dev_env("MRS_FUSED_PROF") != nullptr;     // development aid: phase times on stderr (synchronises)
-        static const char* const dev_skip_s = mrs::dev_env("MRS_FUSED_SKIP");
-        static const int dev_skip_env = dev_skip_s ? atoi(dev_skip_s) : 0;
-        int dev_skip = dev_skip_env | plan->fused_skip;
-        unsigned long long* d_prof = nullptr;
-        if (want_prof) {
-            MRS_HIP_TRY(hipMalloc(&d_prof, 4 * sizeof(unsigned long long)));
-            MRS_HIP_TRY(hipMemsetAsync(d_prof, 0, 4 * sizeof(unsigned long long), s));
-        }
+        int dev_skip = plan->fused_skip;
         void* args[] = {(void*)&d_xyz, (void*)&d_offsets, (void*)&cp, (void*)&p, (void*)&sp, (void*)&batch, (void*)&d_bev, (void*)&d_sino,
-                        (void*)&d_sino_norm, (void*)&d_park, (void*)&d_deg, (void*)&d_ctr, (void*)&stagger_ticks, (void*)&d_prof, (void*)&dev_skip};
+                        (void*)&d_sino_norm, (void*)&d_park, (void*)&d_deg, (void*)&d_ctr, (void*)&stagger_ticks, (void*)&dev_skip};
         MRS_HIP_TRY(hipLaunchKernel(kern, dim3(grid), dim3(kRadonWG), args, lds, s));
-        if (want_prof) {
-            unsigned long long h[4];
-            MRS_HIP_TRY(hipStreamSynchronize(s));
-            MRS_HIP_TRY(hipMemcpy(h, d_prof, sizeof(h), hipMemcpyDeviceToHost));
-            (void)hipFree(d_prof);
-            const double per = 0.01 / (double)pairs;     // 100 MHz ticks -> microseconds per pair of scans
-            fprintf(stderr, "[fused prof] %d scans, grid %d, pf %d: clear %.1f us, rasterise %.1f us, march %.1f us, normalise + next %.1f us per pair\n", batch,
-                    grid, pf, h[0] * per, h[1] * per, h[2] * per, h[3] * per);
-        }
         return MRS_OK;
     }
     void* kern = per_lane <= 15 ? (p.stride == 125 ? fused_kernel<15, 125>(pf) : fused_kernel<15, 0>(pf)) : fused_kernel<16, 0>(pf);

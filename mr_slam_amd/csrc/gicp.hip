@@ -303,9 +303,9 @@ __device__ __forceinline__ void stream_minis(const float4* __restrict__ pts, int
 // Walk of the hierarchy for the 64 queries of a wave.  bound(): the lane's current bound (called by the whole wave before every tile; it may
 // do wave-wide bookkeeping first); a dead lane's bound is ignored.  visit(first index, 8 candidates): see stream_minis.  NEAREST: tiles nearest
 // first (pass 1: bounds shrink); otherwise tiles and minis in index order (pass 2 without the list of pass 1: candidates must arrive in
-// ascending index order).  rec(id): every mini visited.  Returns the number of tiles visited (a development counter).
+// ascending index order).  rec(id): every mini visited.
 template <bool NEAREST, class Bound, class Visit, class Rec>
-__device__ __forceinline__ int knn_walk(const float4* __restrict__ pts, int n, const Hier& H, bool live, const float4& q, int home_tile,
+__device__ __forceinline__ void knn_walk(const float4* __restrict__ pts, int n, const Hier& H, bool live, const float4& q, int home_tile,
                                          Bound bound, Visit visit, Rec rec)
 {
     const int lane = threadIdx.x & 63;
@@ -313,7 +313,6 @@ __device__ __forceinline__ int knn_walk(const float4* __restrict__ pts, int n, c
     quad_box(live, q, qlo, qhi);
     const int nchunks = (H.ntiles + 63) >> 6;
     const int hc = min(home_tile, H.ntiles - 1) >> 6;
-    int visited = 0;        // tiles (returned: a development counter)
     for (int ci = 0; ci < nchunks; ++ci) {
         const int ch = !NEAREST ? ci : (ci == 0 ? hc : (ci <= hc ? ci - 1 : ci));       // NEAREST: the chunk of the wave's own tile first
         const int t = ch * 64 + lane;
@@ -345,7 +344,6 @@ __device__ __forceinline__ int knn_walk(const float4* __restrict__ pts, int n, c
                 tl = (int)__builtin_ctzll(tmask);
             }
             tmask &= ~(1ull << tl);
-            ++visited;
             if (lane == tl) key = INFINITY;
             const int tt = ch * 64 + tl;
             float dmin;
@@ -357,7 +355,6 @@ __device__ __forceinline__ int knn_walk(const float4* __restrict__ pts, int n, c
             stream_minis(pts, cnt, [&](int) { const int m = (int)__builtin_ctzll(left); left &= left - 1; rec(tt * 64 + m); return tt * 64 + m; }, visit);
         }
     }
-    return visited;
 }
 
 // Exact 1-NN of P query points per lane over the Morton-ordered cloud tgt[0..m): squared distance and (sorted-space) index; `maxc2` is
@@ -654,13 +651,6 @@ __global__ __launch_bounds__(256) void k_boxes(const float4* __restrict__ pts, c
 //     2 VALU instructions per slot in place of the 8 of a (distance, index) insertion, and no index registers.
 // Exactly equal distances resolve to the smaller (Morton-space) index.  The whole workgroup must call it together.
 
-// development counters (MRS_KNN_DBG=1 prints them): per wave -- candidate groups of 8 visited in pass 1, groups in which some lane noted
-// a candidate, chain passes (seed excluded), pass 2 groups, entries ranked, query waves
-__device__ unsigned long long g_knn_dbg[8];
-__device__ unsigned long long g_knn_clk[4];       // wave clocks spent in the seed / the pass-1 walk / pass 2; tiles visited in pass 1
-__device__ int g_knn_dbg_on;       // set by the host when MRS_KNN_DBG is in the environment
-__device__ unsigned long long g_nn_trace[2 * 65536];        // the same for k_nn_scan (MRS_NN_TRACE_FILE, written by mrs_gicp_batch_profile)
-__device__ unsigned long long g_knn_trace[2 * 65536];       // MRS_KNN_DBG=1: (start, end) of every workgroup of the last launch on the 100 MHz wall clock
 __device__ int g_knn_norec;        // development aid (MRS_KNN_REC=0): pass 2 walks the hierarchy again instead of revisiting pass 1's minis
 
 constexpr int kHome = 64;         // Morton-curve neighbours that seed the bound (the walk skips exactly that index range)
@@ -710,7 +700,6 @@ __device__ __forceinline__ int knn_two_pass(int* __restrict__ list, const float4
 {
     static_assert(KMAX <= 32 && KMAX >= kKnnBuf, "rank mask is 32 bits; the note buffer lives in the list");
     const int tid = (int)threadIdx.x;
-    const long long t_begin = g_knn_dbg_on ? clock64() : 0;
     float dk[KMAX];
 #pragma unroll
     for (int s = 0; s < KMAX; ++s) dk[s] = INFINITY;
@@ -730,30 +719,25 @@ __device__ __forceinline__ int knn_two_pass(int* __restrict__ list, const float4
     const int home_tile = __builtin_amdgcn_readfirstlane(i) >> 10;      // kTile = 1024
     float* const buf = reinterpret_cast<float*>(list);
     int nb = 0;                     // candidates noted since the last flush
-    int c_g1 = 0, c_ins = 0, c_chain = 0, c_g2 = 0;
-    const long long t_seed = g_knn_dbg_on ? clock64() : 0;
     auto flush = [&]() {
 #pragma unroll 1
         for (int s = 0; s < kKnnBuf; ++s) {
             if (!__any(s < nb)) break;
             const float v = s < nb ? buf[s * kNNThreads + tid] : INFINITY;
             dist_insert<KMAX>(dk, v);
-            ++c_chain;
         }
         nb = 0;
     };
     int nrec = 0;       // wave-uniform
-    const int c_tiles = knn_walk<true>(pts, n, H, live, q, home_tile,
+    knn_walk<true>(pts, n, H, live, q, home_tile,
                [&]() { if (__any(nb > 0)) flush(); return dk[KMAX - 1]; },       // before every tile: bounds up to date
                [&](int j0, const Cand8& cand) {
-                   ++c_g1;
                    float qx = q.x, dd[8];
                    cand_pin(qx);
                    cand_dist(cand, j0, n, qx, q.y, q.z, dd);
                    const float T = dk[KMAX - 1];
                    const float mn = fminf(fminf(fminf(dd[0], dd[1]), fminf(dd[2], dd[3])), fminf(fminf(dd[4], dd[5]), fminf(dd[6], dd[7])));
                    if (!__any(live && mn < T)) return;
-                   ++c_ins;
 #pragma unroll
                    for (int u = 0; u < 8; ++u) {
                        const bool use = live && (unsigned)(j0 + u - home) >= (unsigned)kHome && dd[u] < T;       // NaN: false
@@ -766,7 +750,6 @@ __device__ __forceinline__ int knn_two_pass(int* __restrict__ list, const float4
                    ++nrec;
                });
     if (__any(nb > 0)) flush();
-    const long long t_walk = g_knn_dbg_on ? clock64() : 0;
     // pass 2: the candidates within the k-th distance, home range included, in ascending index order
     const int kk = k < KMAX ? k : KMAX;
     float tau = dk[KMAX - 1];
@@ -782,7 +765,6 @@ __device__ __forceinline__ int knn_two_pass(int* __restrict__ list, const float4
     const int room = kk - nless;                  // exact ties with tau that belong to the k nearest
     int cnt = 0, nt = 0;
     auto visit2 = [&](int j0, const Cand8& cand) {
-        ++c_g2;
         float qx = q.x, dd[8];
         cand_pin(qx);
         cand_dist(cand, j0, n, qx, q.y, q.z, dd);
@@ -813,20 +795,10 @@ __device__ __forceinline__ int knn_two_pass(int* __restrict__ list, const float4
     } else {
         knn_walk<false>(pts, n, H, live, q, 0, [&]() { return tau; }, visit2, [](int) {});
     }
-    const long long t_pass2 = g_knn_dbg_on ? clock64() : 0;
     cnt = min(cnt, kk);       // (cannot exceed it: nless candidates are closer than tau, at most room ties were taken)
     // order: rank = #{dk < d} + the equal ones placed before (entries arrive in ascending index order)
     int most = cnt;
     for (int o = 32; o > 0; o >>= 1) most = max(most, __shfl_xor(most, o, 64));
-    if (g_knn_dbg_on && (threadIdx.x & 63) == 0) {
-        atomicAdd(&g_knn_dbg[1], (unsigned long long)c_g1); atomicAdd(&g_knn_dbg[2], (unsigned long long)c_ins);
-        atomicAdd(&g_knn_dbg[3], (unsigned long long)c_chain);
-        atomicAdd(&g_knn_dbg[4], (unsigned long long)c_g2); atomicAdd(&g_knn_dbg[5], (unsigned long long)most);
-        atomicAdd(&g_knn_dbg[6], 1ull);
-        atomicMax(&g_knn_dbg[7], (unsigned long long)c_g1); atomicMax(&g_knn_dbg[0], (unsigned long long)c_chain);
-        atomicAdd(&g_knn_clk[0], (unsigned long long)(t_seed - t_begin)); atomicAdd(&g_knn_clk[1], (unsigned long long)(t_walk - t_seed));
-        atomicAdd(&g_knn_clk[2], (unsigned long long)(t_pass2 - t_walk)); atomicAdd(&g_knn_clk[3], (unsigned long long)c_tiles);
-    }
     unsigned used = 0;
     int j = cnt > 0 ? list[tid] : 0;
     float4 pj = pts[j];
@@ -870,8 +842,6 @@ __global__ __launch_bounds__(kNNThreads) __attribute__((amdgpu_waves_per_eu(WAVE
     H.tlo = tlo + tile_base[c]; H.thi = thi + tile_base[c];
     H.mlo = mlo + (size_t)64 * tile_base[c]; H.mhi = mhi + (size_t)64 * tile_base[c];
     H.ntiles = (n + kTile - 1) / kTile;
-    const unsigned wg = blockIdx.y * gridDim.x + blockIdx.x;
-    if (g_knn_dbg_on && threadIdx.x == 0 && wg < 65536) g_knn_trace[2 * wg] = wall_clock64();
     for (int base = blockIdx.x * kNNThreads; base < n; base += gridDim.x * kNNThreads) {
         const int i = base + threadIdx.x;
         const bool live = i < n;
@@ -881,10 +851,6 @@ __global__ __launch_bounds__(kNNThreads) __attribute__((amdgpu_waves_per_eu(WAVE
                                              [&](int r, int j) { out[r << 6] = j; });
         if (live && found < k)
             for (int s = found; s < k; ++s) out[s << 6] = -1;
-    }
-    if (g_knn_dbg_on && wg < 65536) {
-        __syncthreads();
-        if (threadIdx.x == 0) g_knn_trace[2 * wg + 1] = wall_clock64();
     }
 }
 
@@ -983,8 +949,6 @@ __global__ __launch_bounds__(kNNThreads) void k_nn_scan(
     float glo[3];
     const float gsc = morton_grid(tgt_bbox, pair, glo);
     const int per_block = kNNThreads * P;
-    const unsigned wg = blockIdx.y * gridDim.x + blockIdx.x;
-    if (g_knn_dbg_on && threadIdx.x == 0 && wg < 65536) g_nn_trace[2 * wg] = wall_clock64();
     for (int base = blockIdx.x * per_block; base < n; base += gridDim.x * per_block) {
         float qx[P], qy[P], qz[P];
         int si[P], seed[P];
@@ -1012,10 +976,6 @@ __global__ __launch_bounds__(kNNThreads) void k_nn_scan(
                 if (lb_out) lb_out[so + si[p]] = 0.0f;     // this search leaves no certificate
             }
     }
-    if (g_knn_dbg_on && wg < 65536) {
-        __syncthreads();
-        if (threadIdx.x == 0) g_nn_trace[2 * wg + 1] = wall_clock64();
-    }
 }
 
 // G3b + G4: Mahalanobis matrices, residuals and the 28 fp64 sums for the correspondences found by
@@ -1023,10 +983,9 @@ __global__ __launch_bounds__(kNNThreads) void k_nn_scan(
 // Two poses: the Mahalanobis matrices belong to the linearisation pose S.x (upstream caches them in
 // update_correspondences), the residuals to the evaluated pose S.xi.  Phase 0: xi == x, all 28 sums
 // (FastGICP::linearize); phase 1: only the error sum (FastGICP::compute_error of an LM trial).
-// WAVES: waves per SIMD the register budget is cut for; PREN: the normals of the lane's NEXT point (own 24 B streamed, neighbour's 24 B gathered)
-// travel one point ahead like the points themselves, instead of being requested where the algebra needs them
-template <int WAVES, bool PREN>
-__global__ __launch_bounds__(kNNThreads) __attribute__((amdgpu_waves_per_eu(WAVES, WAVES))) void k_linearize(
+// Three waves per SIMD (142 registers, no spills): the normals of the lane's NEXT point (own 24 B streamed, neighbour's 24 B gathered) travel one
+// point ahead like the points themselves, instead of being requested where the algebra needs them (four waves spill, in either form)
+__global__ __launch_bounds__(kNNThreads) __attribute__((amdgpu_waves_per_eu(3, 3))) void k_linearize(
     const float4* __restrict__ src_all, const int64_t* __restrict__ src_offs, const double* __restrict__ src_cov,
     const float4* __restrict__ tgt_all, const int64_t* __restrict__ tgt_offs, const double* __restrict__ tgt_cov,
     const LmState* __restrict__ st, const int* __restrict__ corr, double* __restrict__ partial, int max_blocks, int trial_only)
@@ -1066,7 +1025,7 @@ __global__ __launch_bounds__(kNNThreads) __attribute__((amdgpu_waves_per_eu(WAVE
         };
         if (j_cur >= 0) {
             a_nx = src[base + threadIdx.x]; b_nx = tgt[j_cur];
-            if (PREN) fetch_normals(base + (int)threadIdx.x, j_cur);
+            fetch_normals(base + (int)threadIdx.x, j_cur);
         }
 #pragma unroll 1
         for (int p = 0; p < kPts; ++p) {
@@ -1078,12 +1037,12 @@ __global__ __launch_bounds__(kNNThreads) __attribute__((amdgpu_waves_per_eu(WAVE
             j_nx = idx_of(p + 2);
             if (j_cur >= 0) {
                 a_nx = src[i + kNNThreads]; b_nx = tgt[j_cur];
-                if (PREN) fetch_normals(i + kNNThreads, j_cur);
+                fetch_normals(i + kNNThreads, j_cur);
             }
             if (j < 0) continue;
             double ca[6], cb[6];
-            cov6_from_normal(PREN ? na : src_cov + kCovDoubles * (size_t)(so + i), ca);
-            cov6_from_normal(PREN ? nbv : tgt_cov + kCovDoubles * (size_t)(to + j), cb);
+            cov6_from_normal(na, ca);
+            cov6_from_normal(nbv, cb);
             const double CA[9] = {ca[0], ca[1], ca[2], ca[1], ca[3], ca[4], ca[2], ca[4], ca[5]};
             double RC[9], RCR[9], M[9];
 #pragma unroll
@@ -1300,7 +1259,7 @@ __global__ void k_nn_store_pose(const LmState* __restrict__ st, int n_pairs, Cer
 // sorted space or -1 when d^2 >= max_corr^2; nn_seed = the neighbour found, warm start of the next pass), ties to the smaller index.
 // WORK: the queries are the entries of the pair's work list (k_nn_certify) instead of all source points.  Always leaves the certificate
 // bound of every query it searched in C.lb.
-template <bool PROF, bool WORK>
+template <bool WORK>
 __global__ __launch_bounds__(kNNThreads) __attribute__((amdgpu_waves_per_eu(4, 4))) void k_nn_scan_g(
     const float4* __restrict__ src_all, const int64_t* __restrict__ src_offs,
     const float4* __restrict__ tgt_all, const int64_t* __restrict__ tgt_offs, HierArrays HA,
@@ -1330,10 +1289,7 @@ __global__ __launch_bounds__(kNNThreads) __attribute__((amdgpu_waves_per_eu(4, 4
     float glo[3];
     const float gsc = morton_grid(tgt_bbox, pair, glo);
     nnc::GrpLds& L = lds[threadIdx.x >> 6];
-    const unsigned wg = blockIdx.y * gridDim.x + blockIdx.x;
-    if (g_knn_dbg_on && threadIdx.x == 0 && wg < 65536) g_nn_trace[2 * wg] = wall_clock64();
     for (int base = 0; base < n; base += kNNThreads) {
-        const unsigned long long t_wave = PROF ? __builtin_readcyclecounter() : 0ull;
         const int w = base + (int)threadIdx.x;
         const bool live = w < n;
         const int i = listed ? C.work[so + b0 + (live ? w : 0)] : b0 + (live ? w : 0);
@@ -1353,39 +1309,22 @@ __global__ __launch_bounds__(kNNThreads) __attribute__((amdgpu_waves_per_eu(4, 4
         const float4 sp = tgt[has_seed ? seed : 0];
         float best = INFINITY, second = INFINITY;
         int bidx = -1;
-        nnc::Prof prof;
-        const unsigned long long t_in = PROF ? __builtin_readcyclecounter() : 0ull;
         auto radius2 = [&]() {       // squared search radius: (distance of the best candidate so far + margin)^2, capped by the threshold
             const float r = sqrtf(fminf(has_seed ? dist2(qx, qy, qz, sp) : INFINITY, best)) + margin;
             return fminf(maxc2, r * r);
         };
-        nnc::grp_search<PROF>(tgt, H, L, qx, qy, qz, live, radius2,
-                              [&](int j, float d, bool ok) {
-                                  if (!ok) return;
-                                  second = __builtin_amdgcn_fmed3f(best, d, second);      // second smallest of everything evaluated
-                                  if (d < best) { best = d; bidx = j; }
-                              }, &prof);
-        if (PROF) {
-            const unsigned long long t_out = __builtin_readcyclecounter();
-            if ((threadIdx.x & 63) == 0) {
-                atomicAdd(&nnc::g_prof[0], 1ull); atomicAdd(&nnc::g_prof[1], t_in - t_wave); atomicAdd(&nnc::g_prof[2], prof.cyc_top);
-                atomicAdd(&nnc::g_prof[3], prof.cyc_leaf); atomicAdd(&nnc::g_prof[4], prof.cyc_drain); atomicAdd(&nnc::g_prof[5], prof.tiles_near);
-                atomicAdd(&nnc::g_prof[6], prof.tiles_needed); atomicAdd(&nnc::g_prof[7], prof.grp_tiles); atomicAdd(&nnc::g_prof[8], prof.query_tests);
-                atomicAdd(&nnc::g_prof[9], prof.queued); atomicAdd(&nnc::g_prof[10], prof.batches); atomicAdd(&nnc::g_prof[12], prof.drains);
-                atomicAdd(&nnc::g_prof[13], t_out - t_wave); atomicMax(&nnc::g_prof[14], t_out - t_wave);
-            }
-            if ((threadIdx.x & 63) == 63) atomicAdd(&nnc::g_prof[11], prof.staged);
-        }
+        nnc::grp_search(tgt, H, L, qx, qy, qz, live, radius2,
+                        [&](int j, float d, bool ok) {
+                            if (!ok) return;
+                            second = __builtin_amdgcn_fmed3f(best, d, second);      // second smallest of everything evaluated
+                            if (d < best) { best = d; bidx = j; }
+                        });
         if (live) {
             corr[so + i] = (bidx >= 0 && (double)best < prm.max_corr2) ? bidx : -1;
             nn_seed[so + i] = bidx;
             // every point that was not evaluated lies beyond the final radius (radii only shrink while the search runs)
             C.lb[so + i] = bidx >= 0 ? fminf(sqrtf(second), sqrtf(radius2()) * 0.9999f) : 0.0f;
         }
-    }
-    if (g_knn_dbg_on && wg < 65536) {
-        __syncthreads();
-        if (threadIdx.x == 0) g_nn_trace[2 * wg + 1] = wall_clock64();
     }
 }
 
@@ -2110,7 +2049,6 @@ struct mrs_gicp_batch {
     bool use_certificates = true;   // search_core 1: certify unchanged neighbours before searching (k_nn_certify)
     CertArrays cert = {nullptr, nullptr, nullptr, nullptr, 0, nullptr};
     double last_searched = 0;       // share of (source point, pass) that needed a search in the last align()
-    bool want_leaf_hier = true;     // build the octree-cell hierarchy in set_clouds (false: RING++ front end)
     bool no_cov = false;            // RING++ front end: no covariance buffers
     bool hier_valid[2] = {false, false};
     int big_movers = 1;             // pairs whose last step exceeded motion_switch (counted by k_lm_update): do they need the round-3 kernel?
@@ -2156,8 +2094,7 @@ void free_cloud(mrs_gicp_batch* h, int w)
 }
 
 int blocks_for_points(int n) { return (n + kNNThreads * kPts - 1) / (kNNThreads * kPts); }
-constexpr int kLinChunks = 4;
-constexpr int kLinVariant = 3;    // launch_linearize     // blocks of 1024 points per workgroup of the reduction kernels (ensure_state)
+constexpr int kLinChunks = 4;    // blocks of 1024 points per workgroup of the reduction kernels (ensure_state)
 
 // Source points per lane in the NN scan.  Fewer points per wave = a more compact query set = sharper sub-tile
 // culling; more = every LDS candidate read serves more distance evaluations.  Measured (120k x 120k, MI355X):
@@ -2168,26 +2105,10 @@ void launch_nn_scan(int longest_src, int n_pairs, int num_cu, hipStream_t s, Arg
 {
     const int cus = num_cu > 0 ? num_cu : 256;
     auto wgs = [&](int P) { return (long)n_pairs * ((longest_src + kNNThreads * P - 1) / (kNNThreads * P)); };
-    static const char* const force_p_s = mrs::dev_env("MRS_NN_P");
-    static const int force_p = force_p_s ? atoi(force_p_s) : 0;     // development aid: 1 or 2 source points per lane
-    if (force_p == 2 || (force_p != 1 && wgs(2) >= 3L * cus))
+    if (wgs(2) >= 3L * cus)
         hipLaunchKernelGGL(k_nn_scan<2>, dim3((unsigned)(wgs(2) / n_pairs), n_pairs), dim3(kNNThreads), 0, s, args...);
     else
         hipLaunchKernelGGL(k_nn_scan<1>, dim3((unsigned)(wgs(1) / n_pairs), n_pairs), dim3(kNNThreads), 0, s, args...);
-}
-
-// k_linearize instantiation: 3 (default) = 3 waves per SIMD (142 registers, no spills), normals one point ahead: 0.55 ms per 256 pairs; 1 = 4 waves
-// (128 registers, 3 spilled), normals requested at use: 0.69 ms; 2 = 4 waves + look-ahead (26 spills): 0.95 ms; 4 = 3 waves, no look-ahead: 0.58 ms; 5 = 2 waves.  MRS_DEV=1 MRS_LIN_VARIANT=<n> switches for A/B runs (same sums, same bits).
-template <class... Args>
-void launch_linearize(dim3 grid, hipStream_t s, Args... args)
-{
-    static const char* const v_s = mrs::dev_env("MRS_LIN_VARIANT");
-    static const int v = v_s ? atoi(v_s) : kLinVariant;
-    if (v == 2) hipLaunchKernelGGL((k_linearize<4, true>), grid, dim3(kNNThreads), 0, s, args...);
-    else if (v == 3) hipLaunchKernelGGL((k_linearize<3, true>), grid, dim3(kNNThreads), 0, s, args...);
-    else if (v == 4) hipLaunchKernelGGL((k_linearize<3, false>), grid, dim3(kNNThreads), 0, s, args...);
-    else if (v == 5) hipLaunchKernelGGL((k_linearize<2, true>), grid, dim3(kNNThreads), 0, s, args...);
-    else hipLaunchKernelGGL((k_linearize<4, false>), grid, dim3(kNNThreads), 0, s, args...);
 }
 
 // Octree-cell leaves + tiles + supers of every cloud of side `w` from the sorted keys (set_clouds).  Synchronises (the leaf counts size the arrays).
@@ -2265,26 +2186,6 @@ int build_leaf_hier(mrs_gicp_batch* h, int w, const unsigned long long* d_keys, 
     return MRS_OK;
 }
 
-// k_nn_scan_g, or its instrumented twin under MRS_DEV=1 MRS_NN_PROF=1 (per-launch phase cycles and event counts on stderr; synchronises)
-template <bool WORK, class... Args>
-void launch_nn_scan_g(dim3 grid, hipStream_t s, Args... args)
-{
-    static const bool prof = mrs::dev_env("MRS_NN_PROF") != nullptr;
-    if (!prof) {
-        hipLaunchKernelGGL((k_nn_scan_g<false, WORK>), grid, dim3(kNNThreads), 0, s, args...);
-        return;
-    }
-    unsigned long long z[16] = {0};
-    (void)hipMemcpyToSymbol(HIP_SYMBOL(nnc::g_prof), z, sizeof(z));
-    hipLaunchKernelGGL((k_nn_scan_g<true, WORK>), grid, dim3(kNNThreads), 0, s, args...);
-    (void)hipStreamSynchronize(s);
-    (void)hipMemcpyFromSymbol(z, HIP_SYMBOL(nnc::g_prof), sizeof(z));
-    const double w = (double)(z[0] ? z[0] : 1);
-    fprintf(stderr, "[nn prof] %llu waves%s: cycles/wave total %.0f (max %llu) = setup %.0f + top %.0f + leaf %.0f + drain %.0f; per wave: tiles near %.1f needed %.1f, "
-                    "(group,tile) %.1f, query-vs-leaves tests %.1f, leaves queued %.1f, drains %.2f, batches %.2f, staged points (max group) %.1f\n",
-            z[0], WORK ? " (work list)" : "", z[13] / w, z[14], z[1] / w, z[2] / w, z[3] / w, z[4] / w, z[5] / w, z[6] / w, z[7] / w, z[8] / w, z[9] / w, z[12] / w, z[10] / w, z[11] / w);
-}
-
 // One nearest-neighbour pass for every pair in phase 0 (h->d_state): fills h->d_corr / h->d_seed.
 // mode 0: first pass of an align(), 1: later pass, 2: one plain search with the selected core (linearize hook).
 // search_core 0: the round-3 kernel, every point, every pass.  search_core 1 (round-4 schedule):
@@ -2308,16 +2209,16 @@ int nn_pass(mrs_gicp_batch* h, int mode, hipStream_t s)
         round3(0);
         hipLaunchKernelGGL(k_nn_store_pose, pg, dim3(256), 0, s, (const LmState*)h->d_state, h->n_pairs, h->cert, 0, (const int64_t*)h->d_offs[0], h->prm.motion_switch);
     } else if (mode != 1 || !h->use_certificates) {
-        launch_nn_scan_g<false>(wg, s, (const float4*)h->d_pts[0], (const int64_t*)h->d_offs[0], (const float4*)h->d_pts[1], (const int64_t*)h->d_offs[1],
-                                h->hier(1), (const LmState*)h->d_state, h->prm, h->d_corr, h->d_seed, (const int*)h->d_bbox[1], h->cert);
+        hipLaunchKernelGGL(k_nn_scan_g<false>, wg, dim3(kNNThreads), 0, s, (const float4*)h->d_pts[0], (const int64_t*)h->d_offs[0], (const float4*)h->d_pts[1],
+                           (const int64_t*)h->d_offs[1], h->hier(1), (const LmState*)h->d_state, h->prm, h->d_corr, h->d_seed, (const int*)h->d_bbox[1], h->cert);
         hipLaunchKernelGGL(k_nn_store_pose, pg, dim3(256), 0, s, (const LmState*)h->d_state, h->n_pairs, h->cert, 0, (const int64_t*)h->d_offs[0], h->prm.motion_switch);
     } else {
         if (h->big_movers > 0) round3(1);
         hipLaunchKernelGGL(k_nn_certify, wg, dim3(256), 0, s, (const float4*)h->d_pts[0],
                            (const int64_t*)h->d_offs[0], (const float4*)h->d_pts[1], (const int64_t*)h->d_offs[1], (const LmState*)h->d_state, h->prm,
                            h->d_corr, (const int*)h->d_seed, h->cert);
-        launch_nn_scan_g<true>(wg, s, (const float4*)h->d_pts[0], (const int64_t*)h->d_offs[0], (const float4*)h->d_pts[1], (const int64_t*)h->d_offs[1],
-                               h->hier(1), (const LmState*)h->d_state, h->prm, h->d_corr, h->d_seed, (const int*)h->d_bbox[1], h->cert);
+        hipLaunchKernelGGL(k_nn_scan_g<true>, wg, dim3(kNNThreads), 0, s, (const float4*)h->d_pts[0], (const int64_t*)h->d_offs[0], (const float4*)h->d_pts[1],
+                           (const int64_t*)h->d_offs[1], h->hier(1), (const LmState*)h->d_state, h->prm, h->d_corr, h->d_seed, (const int*)h->d_bbox[1], h->cert);
         hipLaunchKernelGGL(k_nn_store_pose, pg, dim3(256), 0, s, (const LmState*)h->d_state, h->n_pairs, h->cert, 1, (const int64_t*)h->d_offs[0], h->prm.motion_switch);
     }
     MRS_HIP_TRY(hipGetLastError());
@@ -2347,29 +2248,19 @@ void launch_knn_cov(mrs_gicp_batch* h, int w, int c0, int nc, int64_t longest, i
     const dim3 g((unsigned)((longest + kNNThreads - 1) / kNNThreads), nc);
     const int64_t* const offs_c = h->d_offs[w] + c0;
     const int* const tb_c = h->d_tile_base[w] + c0;
-    static const char* const wv_s = mrs::dev_env("MRS_KNN_WAVES");      // development aid: waves per SIMD of the selection kernel
-    const int wv = wv_s ? atoi(wv_s) : 0;
-    if (k <= 16 && wv == 5)
-        hipLaunchKernelGGL((k_knn_cov<16, 5>), g, dim3(kNNThreads), 0, s, h->d_pts[w], offs_c, tb_c, h->d_tlo[w], h->d_thi[w], h->d_mlo[w], h->d_mhi[w], k, d_knn);
-    else if (k <= 16)
+    if (k <= 16)
         hipLaunchKernelGGL(k_knn_cov<16>, g, dim3(kNNThreads), 0, s, h->d_pts[w], offs_c, tb_c, h->d_tlo[w], h->d_thi[w], h->d_mlo[w], h->d_mhi[w], k, d_knn);
     else if (k <= 20)
         hipLaunchKernelGGL(k_knn_cov<20>, g, dim3(kNNThreads), 0, s, h->d_pts[w], offs_c, tb_c, h->d_tlo[w], h->d_thi[w], h->d_mlo[w], h->d_mhi[w], k, d_knn);
-    else if (k <= 30 && wv == 4)
-        hipLaunchKernelGGL((k_knn_cov<30, 4>), g, dim3(kNNThreads), 0, s, h->d_pts[w], offs_c, tb_c, h->d_tlo[w], h->d_thi[w], h->d_mlo[w], h->d_mhi[w], k, d_knn);
     else if (k <= 30)       // RING++'s k: 30 list slots = 30 KB of LDS = five workgroups per compute unit (32: four)
         hipLaunchKernelGGL(k_knn_cov<30>, g, dim3(kNNThreads), 0, s, h->d_pts[w], offs_c, tb_c, h->d_tlo[w], h->d_thi[w], h->d_mlo[w], h->d_mhi[w], k, d_knn);
     else
         hipLaunchKernelGGL(k_knn_cov<32>, g, dim3(kNNThreads), 0, s, h->d_pts[w], offs_c, tb_c, h->d_tlo[w], h->d_thi[w], h->d_mlo[w], h->d_mhi[w], k, d_knn);
 }
 
-// development aids of the selection kernel (MRS_DEV=1): MRS_KNN_DBG=1 counters, MRS_KNN_REC=0 = pass 2 walks the hierarchy again
+// MRS_DEV=1 MRS_KNN_REC=0: pass 2 of the selection walks the hierarchy again (what it does when pass 1 noted too many minis)
 int knn_dev_switches(hipStream_t s)
 {
-    if (mrs::dev_env("MRS_KNN_DBG")) {
-        const int on = 1;
-        MRS_HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(g_knn_dbg_on), &on, sizeof(on)));
-    }
     const char* const e = mrs::dev_env("MRS_KNN_REC");      // read per call (the tests flip it)
     const int off = (e && atoi(e) == 0) ? 1 : 0;
     static int cur = 0;
@@ -2377,32 +2268,6 @@ int knn_dev_switches(hipStream_t s)
         MRS_HIP_TRY(hipStreamSynchronize(s));
         MRS_HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(g_knn_norec), &off, sizeof(off)));
         cur = off;
-    }
-    return MRS_OK;
-}
-
-int knn_dbg_report(hipStream_t s)
-{
-    static const bool knn_dbg = mrs::dev_env("MRS_KNN_DBG") != nullptr;
-    if (!knn_dbg) return MRS_OK;
-    unsigned long long c[8];
-    MRS_HIP_TRY(hipStreamSynchronize(s));
-    MRS_HIP_TRY(hipMemcpyFromSymbol(c, HIP_SYMBOL(g_knn_dbg), sizeof(c)));
-    const double w = (double)(c[6] ? c[6] : 1);
-    fprintf(stderr, "[knn dbg] per query wave: pass 1 groups of 8 candidates %.1f (some lane noted one in %.1f), chain passes after the seed %.1f, pass 2 groups %.1f, "
-                    "entries ranked %.1f; %llu waves; the busiest wave: %llu groups in pass 1, %llu chain passes\n", c[1] / w, c[2] / w, c[3] / w, c[4] / w, c[5] / w, c[6], c[7], c[0]);
-    unsigned long long z[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    MRS_HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(g_knn_dbg), z, sizeof(z)));
-    unsigned long long ck[4];
-    MRS_HIP_TRY(hipMemcpyFromSymbol(ck, HIP_SYMBOL(g_knn_clk), sizeof(ck)));
-    fprintf(stderr, "[knn dbg] per query wave: clocks in the seed %.0f, the pass-1 walk %.0f, pass 2 %.0f; tiles visited in pass 1 %.1f\n", ck[0] / w, ck[1] / w, ck[2] / w, ck[3] / w);
-    MRS_HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(g_knn_clk), z, sizeof(ck)));
-    if (const char* path = getenv("MRS_KNN_TRACE_FILE")) {       // (start, end) of every workgroup of the launch just finished, raw uint64 pairs
-        std::vector<unsigned long long> tr(2 * 65536);
-        MRS_HIP_TRY(hipMemcpyFromSymbol(tr.data(), HIP_SYMBOL(g_knn_trace), tr.size() * sizeof(unsigned long long)));
-        if (FILE* f = fopen(path, "wb")) { fwrite(tr.data(), sizeof(unsigned long long), tr.size(), f); fclose(f); }
-        std::fill(tr.begin(), tr.end(), 0ull);
-        MRS_HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(g_knn_trace), tr.data(), tr.size() * sizeof(unsigned long long)));
     }
     return MRS_OK;
 }
@@ -2577,8 +2442,6 @@ int mrs_gicp_batch_set_params(mrs_gicp_batch* h, const mrs_gicp_params* p)
     MRS_REQUIRE(p->voxel_neighbors == 1 || p->voxel_neighbors == 7 || p->voxel_neighbors == 27, "voxel_neighbors must be 1, 7 or 27");
     h->prm.cert_margin = 0.004f;
     h->prm.motion_switch = 0.02f;
-    { const char* e = mrs::dev_env("MRS_MOTION_SWITCH"); if (e) h->prm.motion_switch = (float)atof(e); }
-    { const char* e = mrs::dev_env("MRS_CERT_MARGIN"); if (e) h->prm.cert_margin = (float)atof(e); }
     h->prm.voxel_res = p->voxel_resolution;
     h->prm.voxel_neighbors = p->voxel_neighbors;
     return MRS_OK;
@@ -2625,9 +2488,9 @@ int mrs_gicp_batch_set_clouds(mrs_gicp_batch* h, int32_t which, const float* d_p
                        h->d_tile_base[which], h->d_tlo[which], h->d_thi[which], h->d_mlo[which], h->d_mhi[which]);
     MRS_HIP_TRY(hipGetLastError());
     // the octree-cell hierarchy serves the round-4 searches: correspondences search the TARGETS (which == 1); the sources need it only
-    // for the round-4 k-NN kernel (setting 3); the RING++ front end (want_leaf_hier = false) not at all
+    // for the round-4 k-NN kernel (setting 3)
     h->hier_valid[which] = false;
-    if (h->want_leaf_hier && (which == 1 || (h->search_core == 1 && h->cold_core == 1))) {
+    if (which == 1 || (h->search_core == 1 && h->cold_core == 1)) {
         if ((st = build_leaf_hier(h, which, keys_out.as<unsigned long long>(), total, s)) != MRS_OK) return st;
         h->hier_valid[which] = true;
     }
@@ -2652,7 +2515,7 @@ int mrs_gicp_batch_set_clouds_from(mrs_gicp_batch* h, int32_t which, mrs_gicp_ba
     MRS_REQUIRE(h->prm.k == store->prm.k, "batch and store use different k_correspondences");
     const int sw = store_which, P = h->n_pairs, U = store->n_pairs;
     for (int i = 0; i < P; ++i) MRS_REQUIRE(h_ids[i] >= 0 && h_ids[i] < U, "cloud id outside the store");
-    const bool need_hier = h->want_leaf_hier && (which == 1 || (h->search_core == 1 && h->cold_core == 1));
+    const bool need_hier = which == 1 || (h->search_core == 1 && h->cold_core == 1);
     MRS_REQUIRE(!need_hier || store->hier_valid[sw], "the store side has no octree-cell hierarchy (store the clouds as targets)");
     MRS_HIP_TRY(hipSetDevice(h->ctx->device));
     hipStream_t s = (hipStream_t)stream;
@@ -2813,7 +2676,6 @@ int mrs_gicp_batch_compute_covariances(mrs_gicp_batch* h, int32_t which, int32_t
                            offs_c, k, (const int*)kn, h->d_cov[which], d_knn_out);
     }
     MRS_HIP_TRY(hipGetLastError());
-    if ((st = knn_dbg_report(s)) != MRS_OK) return st;
     h->cov_valid[which] = true;
     if (which == 1) h->vox_res_built = 0.0;
     return MRS_OK;
@@ -2854,9 +2716,8 @@ static int ensure_state(mrs_gicp_batch* h)
     // for a given cloud size and batch size, the same for every search setting.
     // A small batch (the node's one pair at a time: 39 blocks of 1024 points) cannot afford that: 10 workgroups on 256 compute units; below four
     // workgroups per compute unit every block of 1024 points gets its own workgroup (k_linearize 25.7 -> 11 us per launch for one pair of 39 k points).
-    static const char* const ch_s = mrs::dev_env("MRS_LIN_CHUNKS");
     const int cus = h->ctx->num_cu > 0 ? h->ctx->num_cu : 256;
-    const int chunks = ch_s ? std::max(1, atoi(ch_s)) : ((int64_t)h->n_pairs * blocks_for_points((int)longest) >= (int64_t)4 * kLinChunks * cus ? kLinChunks : 1);
+    const int chunks = (int64_t)h->n_pairs * blocks_for_points((int)longest) >= (int64_t)4 * kLinChunks * cus ? kLinChunks : 1;
     const int mb = (blocks_for_points((int)longest) + chunks - 1) / chunks;
     h->longest_src = (int)longest;
     if (!h->d_state) {
@@ -2991,7 +2852,7 @@ int mrs_gicp_batch_align(mrs_gicp_batch* h, const double* h_guess, double* h_fin
     if (small && window > 1 && h->prm.voxel_res <= 0.0) {
         static_assert(kLmWindowMax * 4 <= mrs::kSidePinnedInts, "the slot's pinned buffer holds a window's counters");
         int* const h_win = side.sl.pinned;
-        const bool alternate = h->n_pairs == 1 && !mrs::dev_env("MRS_GICP_FULL_TICKS");
+        const bool alternate = h->n_pairs == 1;
         const long max_ticks_w = alternate ? 2 * max_ticks : max_ticks;      // a sat-out tick does no work: the bound counts work ticks
         while (next[0] + next[1] > 0 && ticks < max_ticks_w) {
             MRS_HIP_TRY(hipMemsetAsync(h->d_nactive, 0, (size_t)window * 4 * sizeof(int), s));
@@ -3003,7 +2864,7 @@ int mrs_gicp_batch_align(mrs_gicp_batch* h, const double* h_guess, double* h_fin
                 const int trial_only = (alternate && ((ticks + t) & 1)) ? 1 : 0;
                 h->big_movers = 1;                      // the broad search gates itself on the pair's motion (k_nn_scan: gate)
                 if (!trial_only && (st = nn_pass(h, (ticks == 0 && t == 0) ? 0 : 1, s)) != MRS_OK) return st;
-                launch_linearize(grid, s, h->d_pts[0], h->d_offs[0], h->d_cov[0],
+                hipLaunchKernelGGL(k_linearize, grid, dim3(kNNThreads), 0, s, h->d_pts[0], h->d_offs[0], h->d_cov[0],
                                    h->d_pts[1], h->d_offs[1], h->d_cov[1], h->d_state, h->d_corr, h->d_partial, h->max_blocks, trial_only);
                 hipLaunchKernelGGL(k_lm_update, dim3(h->n_pairs), dim3(kLmThreads), 0, s, h->d_state, h->d_partial, h->d_nblocks,
                                    h->max_blocks, h->prm, h->d_nactive + 4 * t, trial_only);
@@ -3026,7 +2887,7 @@ int mrs_gicp_batch_align(mrs_gicp_batch* h, const double* h_guess, double* h_fin
                 h->big_movers = next[2];
                 if ((st = nn_pass(h, nn_ticks == 0 ? 0 : 1, s)) != MRS_OK) return st;
             }
-            launch_linearize(grid, s, h->d_pts[0], h->d_offs[0], h->d_cov[0],
+            hipLaunchKernelGGL(k_linearize, grid, dim3(kNNThreads), 0, s, h->d_pts[0], h->d_offs[0], h->d_cov[0],
                                h->d_pts[1], h->d_offs[1], h->d_cov[1], h->d_state, h->d_corr, h->d_partial, h->max_blocks, 0);
         }
         if (next[0] > 0) ++nn_ticks;
@@ -3085,7 +2946,7 @@ int mrs_gicp_batch_linearize(mrs_gicp_batch* h, const double* h_poses, double* h
                            h->max_blocks);
     } else {
         if ((st = nn_pass(h, 2, s)) != MRS_OK) return st;
-        launch_linearize(dim3(h->max_blocks, h->n_pairs), s, h->d_pts[0], h->d_offs[0],
+        hipLaunchKernelGGL(k_linearize, dim3(h->max_blocks, h->n_pairs), dim3(kNNThreads), 0, s, h->d_pts[0], h->d_offs[0],
                            h->d_cov[0], h->d_pts[1], h->d_offs[1], h->d_cov[1], h->d_state, h->d_corr, h->d_partial,
                            h->max_blocks, 0);
     }
@@ -3172,7 +3033,7 @@ int mrs_gicp_batch_profile(mrs_gicp_batch* h, const double* h_poses, int32_t rep
                        h->d_thi[1], h->d_mlo[1], h->d_mhi[1], h->d_state, h->prm, h->d_corr, h->d_seed, (const int*)h->d_bbox[1], (float*)nullptr, 0);
     };
     auto round4_all = [&]() {
-        hipLaunchKernelGGL((k_nn_scan_g<false, false>), wg, dim3(kNNThreads), 0, s, (const float4*)h->d_pts[0], (const int64_t*)h->d_offs[0],
+        hipLaunchKernelGGL(k_nn_scan_g<false>, wg, dim3(kNNThreads), 0, s, (const float4*)h->d_pts[0], (const int64_t*)h->d_offs[0],
                            (const float4*)h->d_pts[1], (const int64_t*)h->d_offs[1], h->hier(1), (const LmState*)h->d_state, h->prm, h->d_corr, h->d_seed,
                            (const int*)h->d_bbox[1], h->cert);
     };
@@ -3181,7 +3042,7 @@ int mrs_gicp_batch_profile(mrs_gicp_batch* h, const double* h_poses, int32_t rep
                            (const int64_t*)h->d_offs[1], (const LmState*)h->d_state, h->prm, h->d_corr, (const int*)h->d_seed, h->cert);
     };
     auto listed = [&]() {
-        hipLaunchKernelGGL((k_nn_scan_g<false, true>), wg, dim3(kNNThreads), 0, s, (const float4*)h->d_pts[0], (const int64_t*)h->d_offs[0],
+        hipLaunchKernelGGL(k_nn_scan_g<true>, wg, dim3(kNNThreads), 0, s, (const float4*)h->d_pts[0], (const int64_t*)h->d_offs[0],
                            (const float4*)h->d_pts[1], (const int64_t*)h->d_offs[1], h->hier(1), (const LmState*)h->d_state, h->prm, h->d_corr, h->d_seed,
                            (const int*)h->d_bbox[1], h->cert);
     };
@@ -3194,21 +3055,9 @@ int mrs_gicp_batch_profile(mrs_gicp_batch* h, const double* h_poses, int32_t rep
     round3();                                         // seeds + correspondences at the poses
     if ((st = knn_dev_switches(s)) != MRS_OK) return fail(st);
     if ((st = timed(out_ms[2], round3)) != MRS_OK) return fail(st);
-    // MRS_NN_TRACE_FILE: (start, end) of every workgroup of the last k_nn_scan launch (MRS_NN_TRACE_KERNEL=4: of k_nn_scan_g over every point), raw uint64 pairs
-    auto dump_trace = [&](int which) -> int {
-        const char* path = mrs::dev_env("MRS_NN_TRACE_FILE");
-        const char* k = mrs::dev_env("MRS_NN_TRACE_KERNEL");
-        if (!path || (k ? atoi(k) : 3) != which) return MRS_OK;
-        std::vector<unsigned long long> tr(2 * 65536);
-        MRS_HIP_TRY(hipStreamSynchronize(s));
-        MRS_HIP_TRY(hipMemcpyFromSymbol(tr.data(), HIP_SYMBOL(g_nn_trace), tr.size() * sizeof(unsigned long long)));
-        if (FILE* f = fopen(path, "wb")) { fwrite(tr.data(), sizeof(unsigned long long), tr.size(), f); fclose(f); }
-        return MRS_OK;
-    };
-    if ((st = dump_trace(3)) != MRS_OK) return fail(st);
     if ((st = timed(out_ms[0], [&]() {
-             launch_linearize(lin_grid, s, h->d_pts[0], h->d_offs[0], h->d_cov[0], h->d_pts[1], h->d_offs[1], h->d_cov[1],
-                                h->d_state, h->d_corr, h->d_partial, h->max_blocks, 0);
+             hipLaunchKernelGGL(k_linearize, lin_grid, dim3(kNNThreads), 0, s, h->d_pts[0], h->d_offs[0], h->d_cov[0], h->d_pts[1], h->d_offs[1],
+                                h->d_cov[1], h->d_state, h->d_corr, h->d_partial, h->max_blocks, 0);
          })) != MRS_OK) return fail(st);
     {   // correspondences at the poses
         std::vector<int> corr(h->n_seed);
@@ -3218,13 +3067,12 @@ int mrs_gicp_batch_profile(mrs_gicp_batch* h, const double* h_poses, int32_t rep
         out_counts[0] = (int64_t)h->n_seed; out_counts[1] = c;
     }
     if ((st = timed(out_ms[4], round4_all)) != MRS_OK) return fail(st);      // leaves certificates at the poses
-    if ((st = dump_trace(4)) != MRS_OK) return fail(st);
     store_pose();
     if ((st = timed(out_ms[3], certify)) != MRS_OK) return fail(st);
     if ((st = upload(1, 0.0)) != MRS_OK) return fail(st);
     if ((st = timed(out_ms[1], [&]() {
-             launch_linearize(lin_grid, s, h->d_pts[0], h->d_offs[0], h->d_cov[0], h->d_pts[1], h->d_offs[1], h->d_cov[1],
-                                h->d_state, h->d_corr, h->d_partial, h->max_blocks, 0);
+             hipLaunchKernelGGL(k_linearize, lin_grid, dim3(kNNThreads), 0, s, h->d_pts[0], h->d_offs[0], h->d_cov[0], h->d_pts[1], h->d_offs[1],
+                                h->d_cov[1], h->d_state, h->d_corr, h->d_partial, h->max_blocks, 0);
          })) != MRS_OK) return fail(st);
     // a pass after a 1 mm step: certify + search the work lists (the certificates are those of the unmoved poses: t_prev stays)
     if ((st = upload(0, 1e-3)) != MRS_OK) return fail(st);
@@ -3382,38 +3230,28 @@ int mrs_pointfeat_batch(mrs_ctx* ctx, const float* d_points, int32_t stride_floa
             cached = true;
         }
     }
-    {
-        const char* cs = mrs::dev_env("MRS_NN_CORE");
-        h->want_leaf_hier = cs && atoi(cs) == 1;
-        if (h->want_leaf_hier) { h->search_core = 1; h->cold_core = 1; }
-    }
     st = mrs_gicp_batch_set_clouds(h, 0, d_points, stride_floats, h_offsets, stream);
     if (st == MRS_OK) {
         hipStream_t s = (hipStream_t)stream;
         int64_t longest = 0;
         for (int i = 0; i < batch; ++i) longest = std::max(longest, h_offsets[i + 1] - h_offsets[i]);
-        static const char* const core_s = mrs::dev_env("MRS_NN_CORE");      // development aid: 1 = the round-4 k-NN kernel (slower here)
-        const bool core4 = core_s && atoi(core_s) == 1;
         // the selection (k_knn_cov<30>: 5 waves per SIMD, no fp64 state) hands the neighbour indices to k_feat_from_knn through a scratch buffer
         // in blocks of 64 points, slot-major (knn_at); clouds go through in chunks that keep the buffer below 1 GiB (64 scans of 120 k points
         // at k = 30 are 0.92 GB: one chunk)
         const int64_t per_cloud = (int64_t)(knn_ints(longest, 1, k) * sizeof(int));
         const char* const lim_s = mrs::dev_env("MRS_FEAT_CHUNK_MB");        // development aid (the tests): a small limit forces several chunks
         const int64_t limit = lim_s ? std::max<int64_t>(1, atoll(lim_s)) << 20 : (1ll << 30);
-        const int chunk = core4 ? batch : (int)std::max<int64_t>(1, std::min<int64_t>(batch, limit / per_cloud));
+        const int chunk = (int)std::max<int64_t>(1, std::min<int64_t>(batch, limit / per_cloud));
         mrs::Scratch knn;
-        st = knn.alloc(core4 ? knn_ints(h_offsets[batch], batch, k) * sizeof(int) : (size_t)chunk * per_cloud, s);
-        if (st == MRS_OK && !core4) st = knn_dev_switches(s);
+        st = knn.alloc((size_t)chunk * per_cloud, s);
+        if (st == MRS_OK) st = knn_dev_switches(s);
         for (int c0 = 0; st == MRS_OK && c0 < batch; c0 += chunk) {
             const int nc = std::min(chunk, batch - c0);
             int* const kn = knn.as<int>() - (size_t)h_offsets[c0] * k;       // the kernels index by global point number (see compute_covariances)
-            if (core4) st = launch_knn_select(h, 0, k, kn, s);
-            else launch_knn_cov(h, 0, c0, nc, longest, k, kn, s);
-            if (st != MRS_OK) break;
+            launch_knn_cov(h, 0, c0, nc, longest, k, kn, s);
             hipLaunchKernelGGL(k_feat_from_knn, dim3((unsigned)((longest + 255) / 256), nc), dim3(256), 0, s, (const float4*)h->d_pts[0],
                                (const int64_t*)h->d_offs[0] + c0, k, (const int*)kn, d_knn, d_eigens, d_features, d_feat_planes);
         }
-        if (st == MRS_OK && !core4) st = knn_dbg_report(s);
         if (st == MRS_OK && (hipGetLastError() != hipSuccess || hipStreamSynchronize(s) != hipSuccess)) {
             mrs::set_error("point-feature kernels failed: %s", hipGetErrorString(hipGetLastError()));
             st = MRS_ERR_HIP;

@@ -138,23 +138,11 @@ __device__ __forceinline__ float d2_point_box(const float4& lo, const float4& hi
 // groups carried 27 % of all queued leaves, a typical tile was tested for 5-6 groups of which one needed it, and the slowest wave of a
 // launch ran for milliseconds.
 // The whole wave must call it together (ballots, cross-lane moves, wave-private LDS).
-// development counters (MRS_DEV=1 MRS_NN_PROF=1): shader-clock cycles per phase and event counts, summed over the waves of a launch
-struct Prof {
-    unsigned long long cyc_top = 0, cyc_leaf = 0, cyc_drain = 0, tiles_near = 0, tiles_needed = 0, grp_tiles = 0, query_tests = 0, queued = 0,
-                       batches = 0, staged = 0, drains = 0;
-};
-__device__ unsigned long long g_prof[16];
-
-template <bool PROF = false, class Lim, class Visit>
+template <class Lim, class Visit>
 __device__ __forceinline__ void grp_search(const float4* __restrict__ pts, const LeafHier& H, GrpLds& L, float qx, float qy, float qz,
-                                           bool live, Lim lim, Visit visit, Prof* prof = nullptr)
+                                           bool live, Lim lim, Visit visit)
 {
     const int lane = threadIdx.x & 63, g = lane >> 3, c = lane & 7;
-    unsigned long long tk = 0;
-    auto tick = [&](unsigned long long& acc) __attribute__((always_inline)) {
-        if (PROF) { const unsigned long long now = __builtin_readcyclecounter(); acc += now - tk; tk = now; }
-    };
-    if (PROF) tk = __builtin_readcyclecounter();
     const unsigned long long lt_mask = (1ull << lane) - 1ull;
     // the first 64 supers are requested before anything else (they do not depend on the radii, whose first evaluation may wait for a load)
     const int s_first = min(lane, H.nsuper - 1);
@@ -183,10 +171,8 @@ __device__ __forceinline__ void grp_search(const float4* __restrict__ pts, const
 
     auto drain = [&]() __attribute__((always_inline)) {
         if (lqmax == 0) return;
-        if (PROF) { tick(prof->cyc_leaf); ++prof->drains; }
         wave_lds_sync();
         for (int r0 = 0; r0 < lqmax; r0 += 8) {
-            if (PROF) ++prof->batches;
             const int e = r0 + c;
             int start = 0, cnt = 0;
             if (e < mylqn) {
@@ -203,7 +189,6 @@ __device__ __forceinline__ void grp_search(const float4* __restrict__ pts, const
             { const int v = dpp_i<0x112>(inc); if (c >= 2) inc += v; }
             { const int v = dpp_i<0x114>(inc); if (c >= 4) inc += v; }
             const int total = grp_max_i(inc);
-            if (PROF && lane == 63) prof->staged += (unsigned long long)total;
             const int off = inc - cnt;
 #pragma unroll
             for (int u = 0; u < kLeafMax; ++u)
@@ -215,7 +200,6 @@ __device__ __forceinline__ void grp_search(const float4* __restrict__ pts, const
         lqv = 0;
         lqmax = 0; mylqn = 0;
         refresh();
-        if (PROF) tick(prof->cyc_drain);
     };
 
     // one round = up to 64 consecutive leaves (lanes = leaves) against the queries `qm` says need their tile.  `done`: the groups already
@@ -227,7 +211,6 @@ __device__ __forceinline__ void grp_search(const float4* __restrict__ pts, const
             unsigned byte = (unsigned)(qm >> (8 * gg)) & 0xffu;     // the group's queries that need this tile (wave-uniform)
             if (!byte || ((done >> gg) & 1u)) continue;
             unsigned long long lm = 0;                               // leaves of the round any of them needs
-            if (PROF) { ++prof->grp_tiles; prof->query_tests += __popc(byte); }
             while (byte) {
                 const int ql = 8 * gg + (int)__builtin_ctz(byte);
                 byte &= byte - 1;
@@ -239,7 +222,6 @@ __device__ __forceinline__ void grp_search(const float4* __restrict__ pts, const
                 const int n = (int)__popcll(lm);
                 if (base + n > kLQ) return true;
                 if ((lm >> lane) & 1ull) L.lq[gg][base + (int)__popcll(lm & lt_mask)] = entry;
-                if (PROF) prof->queued += n;
                 if (lane == gg) lqv += n;
                 lqmax = max(lqmax, base + n);
                 if (g == gg) mylqn += n;
@@ -272,14 +254,12 @@ __device__ __forceinline__ void grp_search(const float4* __restrict__ pts, const
             if (!full && pend > 1) full = leaf_round(a[1], b[1], pn[1], qmask(1), done1);
             if (!full && pend > 2) full = leaf_round(a[2], b[2], pn[2], qmask(2), done2);
             if (!full) break;
-            if (PROF) tick(prof->cyc_leaf);
             drain();
         }
         pend = 0;
-        if (PROF) tick(prof->cyc_leaf);
     };
     auto push_round = [&](int base, int n, unsigned long long qm) __attribute__((always_inline)) {
-        if (pend == 3) { if (PROF) tick(prof->cyc_top); run_pending(); }
+        if (pend == 3) run_pending();
         if (lane == pend) { vb = base; vn = n; vql = (unsigned)qm; vqh = (unsigned)(qm >> 32); }
         ++pend;
     };
@@ -293,9 +273,7 @@ __device__ __forceinline__ void grp_search(const float4* __restrict__ pts, const
             blo.x = readlane_f(tlo.x, tl); blo.y = readlane_f(tlo.y, tl); blo.z = readlane_f(tlo.z, tl);
             bhi.x = readlane_f(thi.x, tl); bhi.y = readlane_f(thi.y, tl); bhi.z = readlane_f(thi.z, tl);
             const unsigned long long qm = __ballot(d2_point_box(blo, bhi, qx, qy, qz) * 0.9999f <= mylim);
-            if (PROF) ++prof->tiles_near;
             if (!qm) continue;
-            if (PROF) ++prof->tiles_needed;
             const int first = __builtin_amdgcn_readlane(__float_as_int(tlo.w), tl);
             const int nl = __builtin_amdgcn_readlane(__float_as_int(thi.w), tl);
             for (int r0 = 0; r0 < nl; r0 += 64) push_round(first + r0, min(64, nl - r0), qm);
@@ -319,7 +297,6 @@ __device__ __forceinline__ void grp_search(const float4* __restrict__ pts, const
             sm &= sm - 1;
             if (S >= 0) { nlo = H.tlo[min(S * 64 + lane, H.ntile - 1)]; nhi = H.thi[min(S * 64 + lane, H.ntile - 1)]; }
             tile_round(tlo, thi, tin);
-            if (PROF) tick(prof->cyc_top);
         }
     }
     run_pending();

@@ -404,9 +404,7 @@ __global__ __launch_bounds__(NSLOT* kSlotThreads) __attribute__((amdgpu_waves_pe
 // element e always lives in ring slot e % kRing and every LDS offset is an immediate.  The element kRing ahead is requested as
 // soon as an element has been consumed -- across units, so the ring is full while the wave runs the 60-point transform and
 // the |.|-sum; exactly one DMA per element (fillers fetch one 16-byte piece) keeps the `s_waitcnt vmcnt(N)` counts static.
-// SPLIT = false: a wave runs both halves of its candidate in turn and adds them in registers.  SPLIT = true: waves 2 i and
-// 2 i + 1 take the two halves of the same candidate (half the quantisation loss when a wave has only a few candidates); the
-// second to finish reads the partner's per-lane sums from LDS and writes the result -- no barrier, two LDS counters per pair.
+// A wave runs both halves of its candidate in turn and adds them in registers.
 // Arithmetic per column, the transform, the sum over lanes and the order (half 0 + half 1) are those of k_ring_corr_fft:
 // the outputs are bit-identical.
 constexpr int kRing = 8;
@@ -422,18 +420,14 @@ constexpr int kTiledEntryBytes = 58624;
 constexpr int kTiledEntry = kTiledEntryBytes / 8;       // in complex values
 
 
-// POL: cache policy of the DMA load -- 0 default, 1 nt (streaming: the entry is read once), 2 sc1, 3 sc0 sc1, 4 sc1 nt, 5 sc0 sc1 nt
+// NT: cache policy of the DMA load -- false default, true nt (streaming: the entry is read once)
 #define MRS_GLDS(MOD) asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2" MOD "\n\ts_mov_b32 m0, %0" \
                                    : "=&s"(keep) : "v"(voff), "s"(sbase), "s"(lds_dst) : "memory")
-template <int POL>
+template <bool NT>
 __device__ __forceinline__ void glds16(const void* sbase, unsigned voff, unsigned lds_dst)
 {
     unsigned keep;   // M0 = LDS destination of the wave-instruction (lane l lands at M0 + 16 l); written in the statement that reads it
-    if (POL == 1) MRS_GLDS(" nt");
-    else if (POL == 2) MRS_GLDS(" sc1");
-    else if (POL == 3) MRS_GLDS(" sc0 sc1");
-    else if (POL == 4) MRS_GLDS(" sc1 nt");
-    else if (POL == 5) MRS_GLDS(" sc0 sc1 nt");
+    if (NT) MRS_GLDS(" nt");
     else MRS_GLDS("");
 }
 #undef MRS_GLDS
@@ -504,21 +498,20 @@ struct DmaUnit {            // one (candidate, half) as the DMA sees it; wave-un
     bool live;              // false: past the end of this wave's work (fillers only)
 };
 
-template <int WAVES, bool SPLIT, int NT, int RING = kRing, bool QDMA = true, bool TILED = false, bool PRIO = false, bool MC = false, int PF = 2>   // (!SPLIT: candidates are handed out by a per-workgroup LDS ticket)
+// One query: WAVES = 8, NT (the entry is read once).  Several queries: WAVES = 12, default cache policy (see the kernel).
+template <int WAVES, bool NT, bool TILED, bool MC>
 __global__ __launch_bounds__(WAVES * 64) void k_ring_sweep_dma(const float2* __restrict__ Q, const float2* __restrict__ DB, FftCorrP p,
                                                                float* __restrict__ dist, int* __restrict__ angle)
 {
-    // LDS: ring [WAVES][RING][1 KiB] | query [61 * 120 + 8] v2f | SPLIT: partial [WAVES / 2][2 halves][64] v2f, counters
+    // LDS: ring [WAVES][kRing][1 KiB] | query [61 * 120 + 8] v2f | candidate ticket
     extern __shared__ __attribute__((aligned(1024))) unsigned char smem[];
-    v2f* const qs = reinterpret_cast<v2f*>(smem + WAVES * RING * kSlotBytes);
+    v2f* const qs = reinterpret_cast<v2f*>(smem + WAVES * kRing * kSlotBytes);
     constexpr int kQueryVals = kHalf * kD + 8;
-    v2f* const partial = qs + kQueryVals;                                        // SPLIT only
-    unsigned* const counters = reinterpret_cast<unsigned*>(partial + (WAVES / 2) * 2 * 64);   // [WAVES / 2][arrived, done]
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int lane = threadIdx.x & 63;
     const unsigned lds0 = (unsigned)(size_t)(__attribute__((address_space(3))) unsigned char*)smem;
-    const unsigned ring_lds = lds0 + wave * (RING * kSlotBytes);               // wave-uniform LDS byte address of this wave's ring
-    const v2f* const ring = reinterpret_cast<const v2f*>(smem + wave * (RING * kSlotBytes)) + lane;
+    const unsigned ring_lds = lds0 + wave * (kRing * kSlotBytes);              // wave-uniform LDS byte address of this wave's ring
+    const v2f* const ring = reinterpret_cast<const v2f*>(smem + wave * (kRing * kSlotBytes)) + lane;
 
     const size_t plane = TILED ? (size_t)kTiledEntry : (size_t)kHalf * kD;      // float2 values of one channel of an entry
     const size_t entry = (MC ? (size_t)p.channels : (size_t)1) * plane;          // ... from one candidate to the next
@@ -542,13 +535,12 @@ __global__ __launch_bounds__(WAVES * 64) void k_ring_sweep_dma(const float2* __r
     const int ch = MC ? bx % C : 0;
     const int slice = MC ? bx / C : bx;
     const int nslices = MC ? (nbx - ch + C - 1) / C : nbx;
-    const int c0 = SPLIT ? slice * (WAVES / 2) + (wave >> 1) : slice * WAVES + wave;
-    const int cstride = nslices * (SPLIT ? WAVES / 2 : WAVES);
-    const int my_half = SPLIT ? (wave & 1) : 0;
-    // !SPLIT: the workgroup's candidates are the sequence t = 0, 1, 2 ... -> slice * WAVES + t % WAVES + (t / WAVES) * cstride; wave w starts with
+    const int c0 = slice * WAVES + wave;
+    const int cstride = nslices * WAVES;
+    // the workgroup's candidates are the sequence t = 0, 1, 2 ... -> slice * WAVES + t % WAVES + (t / WAVES) * cstride; wave w starts with
     // t = w and draws every further one from a ticket in LDS (a wave that finishes early takes what is left: no wave idles through a last round
     // that only some of them have a candidate for).  Which wave scores a candidate does not touch its result.
-    unsigned* const ticket = reinterpret_cast<unsigned*>(qs + kQueryVals);       // first word behind the query (the SPLIT form's partial sums live there)
+    unsigned* const ticket = reinterpret_cast<unsigned*>(qs + kQueryVals);       // first word behind the query
     auto cand_of = [&](unsigned t) { return slice * WAVES + (int)(t % WAVES) + (int)(t / WAVES) * cstride; };
 
     // per-lane pieces of a DMA: lanes 0-31 row J, lanes 32-63 row 60 - J; 16 B = 2 columns per lane.
@@ -571,7 +563,7 @@ __global__ __launch_bounds__(WAVES * 64) void k_ring_sweep_dma(const float2* __r
     auto issue = [&](const DmaUnit& u, int e) {          // e: element index 0..31 (compile-time after unrolling), strictly in stream order
         if (e == 0) start_unit(u);
         const unsigned voff = (!u.live || e == kElems - 1) ? 0u : run;             // filler: one 16-byte piece for all lanes
-        glds16<NT>(u.base, voff, ring_lds + (e % RING) * kSlotBytes);
+        glds16<NT>(u.base, voff, ring_lds + (e % kRing) * kSlotBytes);
         if (TILED) run += u.half ? 896u : 1024u;
         else run += (unsigned)vdelta;
     };
@@ -584,43 +576,29 @@ __global__ __launch_bounds__(WAVES * 64) void k_ring_sweep_dma(const float2* __r
     };
 
     const float2* const qsrc = Q + ((size_t)qy * C + (size_t)ch) * qentry;           // queries are [nq][C][61][120], row layout
-    if (QDMA) {
+    {
         // the query rides the same engine: 58 pieces of 1 KiB dealt to the waves (the last one 192 B: lanes 0-11), then the unit's
-        // first RING elements behind them -- the barrier below needs only the former (vmcnt(RING)), the latter stay in flight across it
+        // first kRing elements behind them -- the barrier below needs only the former (vmcnt(kRing)), the latter stay in flight across it
         constexpr int kPieces = (kHalf * kD * 8 + kSlotBytes - 1) / kSlotBytes;    // 58
-        const unsigned q_lds = lds0 + WAVES * (RING * kSlotBytes);
+        const unsigned q_lds = lds0 + WAVES * (kRing * kSlotBytes);
         if (threadIdx.x < 8) qs[kHalf * kD + threadIdx.x] = (v2f){0.0f, 0.0f};      // zero tail (read by the dead lanes of row 60)
         for (int pc = wave; pc < kPieces; pc += WAVES)
-            if (pc * kSlotBytes + lane * 16 < kHalf * kD * 8) glds16<0>(qsrc, (unsigned)(pc * kSlotBytes + lane * 16), q_lds + pc * kSlotBytes);
+            if (pc * kSlotBytes + lane * 16 < kHalf * kD * 8) glds16<false>(qsrc, (unsigned)(pc * kSlotBytes + lane * 16), q_lds + pc * kSlotBytes);
     }
-    DmaUnit cur = unit_of(c0, my_half);
+    DmaUnit cur = unit_of(c0, 0);
 #pragma unroll
-    for (int e = 0; e < RING; ++e) issue(cur, e);        // in flight while the query is staged
-    if (QDMA) {
-        wait_vmcnt<RING>();
-        if (SPLIT && threadIdx.x < (WAVES / 2) * 2) counters[threadIdx.x] = 0;
-        if (!SPLIT && threadIdx.x == 0) *ticket = WAVES;
-        asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-    } else {   // query -> LDS through registers (compact rows), zero tail; counters
-        for (int i = threadIdx.x; i < kQueryVals; i += WAVES * 64) {
-            v2f v = {0.0f, 0.0f};
-            if (i < kHalf * kD) { const float2 g = qsrc[i]; v = (v2f){g.x, g.y}; }
-            qs[i] = v;
-        }
-        if (SPLIT && threadIdx.x < (WAVES / 2) * 2) counters[threadIdx.x] = 0;
-        if (!SPLIT && threadIdx.x == 0) *ticket = WAVES;
-        __syncthreads();
-    }
+    for (int e = 0; e < kRing; ++e) issue(cur, e);       // in flight while the query is staged
+    wait_vmcnt<kRing>();
+    if (threadIdx.x == 0) *ticket = WAVES;
+    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
 
-    // PF = LDS look-ahead in elements
+    constexpr int PF = 2;                                // LDS look-ahead in elements
     int c = c0;
-    int round = 0;
-    float accA0 = 0.0f, accA1 = 0.0f;                    // !SPLIT: sums of half 0 while half 1 runs
+    float accA0 = 0.0f, accA1 = 0.0f;                    // sums of half 0 while half 1 runs
     while (cur.live) {
         DmaUnit nxt;
         int c_next = c + cstride;
-        if (SPLIT) nxt = unit_of(c_next, my_half);
-        else if (cur.half == 0) nxt = unit_of(c, 1);
+        if (cur.half == 0) nxt = unit_of(c, 1);
         else {                                           // the candidate after this one: drawn now, its first elements are requested at the end of this unit
             unsigned t = 0;
             if (lane == 0) t = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
@@ -636,20 +614,20 @@ __global__ __launch_bounds__(WAVES * 64) void k_ring_sweep_dma(const float2* __r
         auto read_elem = [&](int e) {
             const int J = e;
             qa[e % (PF + 1)][0] = qcol[J * kD];
-            cb[e % (PF + 1)][0] = ring[(e % RING) * 128];
+            cb[e % (PF + 1)][0] = ring[(e % kRing) * 128];
             if (e < 30) {
                 qa[e % (PF + 1)][1] = qcol[(60 - J) * kD];
-                cb[e % (PF + 1)][1] = ring[(e % RING) * 128 + 64];
+                cb[e % (PF + 1)][1] = ring[(e % kRing) * 128 + 64];
             }
         };
-        if (PRIO) __builtin_amdgcn_s_setprio(1);      // the phase that hands ring slots back to the DMA engine goes first
-        // elements 0 .. PF - 1 of this unit: their DMAs are followed by RING - 1 - e younger ones
-        wait_vmcnt<RING - 1>(); read_elem(0);
-        if (PF > 1) { wait_vmcnt<RING - 2>(); read_elem(1); }
+        __builtin_amdgcn_s_setprio(1);                   // the phase that hands ring slots back to the DMA engine goes first
+        // elements 0 .. PF - 1 of this unit: their DMAs are followed by kRing - 1 - e younger ones
+        wait_vmcnt<kRing - 1>(); read_elem(0);
+        wait_vmcnt<kRing - 2>(); read_elem(1);
 #pragma unroll
         for (int e = 0; e < kElems; ++e) {
             if (e + PF <= 30) {
-                wait_vmcnt<RING - 1 - PF>();            // element e + PF has landed: RING - 1 - PF younger DMAs may be in flight
+                wait_vmcnt<kRing - 1 - PF>();           // element e + PF has landed: kRing - 1 - PF younger DMAs may be in flight
                 read_elem(e + PF);
             }
             if (e < 30) {
@@ -663,51 +641,24 @@ __global__ __launch_bounds__(WAVES * 64) void k_ring_sweep_dma(const float2* __r
                 irfft_pre_pair(30, pm, pm, x[30], unused);
             }
             __builtin_amdgcn_sched_barrier(0);           // the slot's values are in registers before the slot is handed back
-            if (e + RING < kElems) issue(cur, e + RING);
-            else issue(nxt, e + RING - kElems);
+            if (e + kRing < kElems) issue(cur, e + kRing);
+            else issue(nxt, e + kRing - kElems);
         }
-        if (PRIO) __builtin_amdgcn_s_setprio(0);
+        __builtin_amdgcn_s_setprio(0);
         cfft60_inv(x);
         float w0, w1;
         wave_abs_reduce_scatter_masked(x, m, w0, w1);
 
         if (MC) {
-            static_assert(!MC || !SPLIT, "the multi-channel form keeps both halves of a candidate on one wave");
             p.mc_partial[(((size_t)qy * C + ch) * p.ndb + c) * 128 + h * 64 + lane] = make_float2(w0, w1);
             if (h == 1) c = c_next;
-        } else if (!SPLIT) {
-            if (h == 0) { accA0 = w0; accA1 = w1; }
-            else {
-                const float s0 = (accA0 + w0) * kOrtho120, s1 = (accA1 + w1) * kOrtho120;
-                const size_t o = (size_t)qy * p.ndb + c;
-                sweep_epilogue(s0, s1, lane, p.denom, dist + o, angle + o);
-                c = c_next;
-            }
+        } else if (h == 0) {
+            accA0 = w0; accA1 = w1;
         } else {
-            const int pi = wave >> 1;
-            v2f* const mine = partial + (pi * 2 + h) * 64 + lane;
-            const v2f* const theirs = partial + (pi * 2 + (1 - h)) * 64 + lane;
-            unsigned* const arrived = counters + pi * 2;
-            unsigned* const done = arrived + 1;
-            // one slot per pair: the sums of the previous round have been read by whoever finished it second
-            while (__hip_atomic_load(done, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) < (unsigned)round) __builtin_amdgcn_s_sleep(2);
-            *mine = (v2f){w0, w1};
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-            unsigned old = 0;
-            if (lane == 0) old = __hip_atomic_fetch_add(arrived, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_WORKGROUP);
-            old = __builtin_amdgcn_readfirstlane(old);
-            if (old & 1u) {                               // the partner's sums are there: half 0 + half 1, as the two-wave slot adds them
-                const v2f t = *theirs;
-                const float a0 = h == 0 ? w0 : t.x, a1 = h == 0 ? w1 : t.y;
-                const float b0 = h == 0 ? t.x : w0, b1 = h == 0 ? t.y : w1;
-                const float s0 = (a0 + b0) * kOrtho120, s1 = (a1 + b1) * kOrtho120;
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-                if (lane == 0) __hip_atomic_fetch_add(done, 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
-                const size_t o = (size_t)qy * p.ndb + c;
-                sweep_epilogue(s0, s1, lane, p.denom, dist + o, angle + o);
-            }
-            c += cstride;
-            ++round;
+            const float s0 = (accA0 + w0) * kOrtho120, s1 = (accA1 + w1) * kOrtho120;
+            const size_t o = (size_t)qy * p.ndb + c;
+            sweep_epilogue(s0, s1, lane, p.denom, dist + o, angle + o);
+            c = c_next;
         }
         cur = nxt;
     }
@@ -972,14 +923,11 @@ int mrs_ring_half_spectrum_f16(mrs_ctx* ctx, const float* d_norm_sino, int32_t n
 }
 
 extern "C++" {
-constexpr int kSweepDmaDefault = 11008;
-constexpr int kSweepDmaTiledDefault = 11008;
-template <int WAVES, bool SPLIT, int NT, bool TILED, bool PRIO, bool MC = false>
+template <int WAVES, bool NT, bool TILED, bool MC>
 static hipError_t sweep_dma_launch_t(int num_cu, hipStream_t s, const float2* q, const float2* db, const FftCorrP& p, float* dist, int* angle)
 {
-    const size_t lds = (size_t)WAVES * kRing * kSlotBytes + (size_t)(kHalf * kD + 8) * sizeof(v2f) +
-                       (SPLIT ? (size_t)(WAVES / 2) * 2 * 64 * sizeof(v2f) + (WAVES / 2) * 2 * sizeof(unsigned) : 16 /* the ticket */);
-    auto kern = k_ring_sweep_dma<WAVES, SPLIT, NT, kRing, true, TILED, PRIO, MC>;
+    const size_t lds = (size_t)WAVES * kRing * kSlotBytes + (size_t)(kHalf * kD + 8) * sizeof(v2f) + 16 /* the ticket */;
+    auto kern = k_ring_sweep_dma<WAVES, NT, TILED, MC>;
     static std::atomic<unsigned> attr_set{0};          // per instantiation, one bit per device: the attribute call costs microseconds of a 100-us query
     int dev = 0;
     hipError_t e = hipGetDevice(&dev);
@@ -989,9 +937,8 @@ static hipError_t sweep_dma_launch_t(int num_cu, hipStream_t s, const float2* q,
         if (e != hipSuccess) return e;
         attr_set.fetch_or(1u << (dev & 31), std::memory_order_relaxed);
     }
-    const int per_wg = SPLIT ? WAVES / 2 : WAVES;
     const int C = MC ? p.channels : 1;
-    const int need = C * ((p.ndb + per_wg - 1) / per_wg);             // units that have work
+    const int need = C * ((p.ndb + WAVES - 1) / WAVES);               // units that have work
     if (p.nq > 1) {
         // nq workgroups per unit, all of them on the unit's XCD (see the kernel): groups of 8 units x nq queries
         FftCorrP pm = p;
@@ -1005,26 +952,19 @@ static hipError_t sweep_dma_launch_t(int num_cu, hipStream_t s, const float2* q,
     hipLaunchKernelGGL(kern, dim3(blocks, 1), dim3(WAVES * 64), lds, s, q, db, p, dist, angle);
     return hipGetLastError();
 }
-// variant = waves per workgroup (8 / 12) + 100 (the halves of a candidate on two waves) + 1000 (non-temporal DMA loads: the entry is read
-// once) + 10000 (s_setprio 1 while a wave consumes / re-requests ring slots)
-static hipError_t sweep_dma_launch(int variant, int num_cu, hipStream_t s, const float2* q, const float2* db, const FftCorrP& p, float* dist, int* angle, bool tiled = false)
+// One query: 8 waves per workgroup, non-temporal DMA loads (the entry is read once).  Several: 12 waves (three per SIMD), default cache policy
+// (the other queries' workgroups find the entry in L2).
+template <bool TILED, bool MC>
+static hipError_t sweep_dma_launch(int num_cu, hipStream_t s, const float2* q, const float2* db, const FftCorrP& p, float* dist, int* angle)
 {
-    const bool prio = (variant / 10000) % 10 != 0, split = (variant / 100) % 10 != 0, nt = (variant / 1000) % 10 != 0;
-    const int waves = variant % 100;
-#define MRS_DMA_1(W, S, N, T, P) if (tiled == T && waves == W && split == S && nt == (N != 0) && prio == P) return sweep_dma_launch_t<W, S, N, T, P>(num_cu, s, q, db, p, dist, angle);
-#define MRS_DMA_4(N, T, P) MRS_DMA_1(8, false, N, T, P) MRS_DMA_1(8, true, N, T, P) MRS_DMA_1(12, false, N, T, P) MRS_DMA_1(12, true, N, T, P)
-    MRS_DMA_4(0, false, false) MRS_DMA_4(1, false, false) MRS_DMA_4(0, false, true) MRS_DMA_4(1, false, true)
-    MRS_DMA_4(0, true, false) MRS_DMA_4(1, true, false) MRS_DMA_4(0, true, true) MRS_DMA_4(1, true, true)
-#undef MRS_DMA_4
-#undef MRS_DMA_1
-    return hipErrorInvalidValue;
+    return p.nq > 1 ? sweep_dma_launch_t<12, false, TILED, MC>(num_cu, s, q, db, p, dist, angle)
+                    : sweep_dma_launch_t<8, true, TILED, MC>(num_cu, s, q, db, p, dist, angle);
 }
 
 // Several queries per sweep on the LDS-DMA pipeline: at most this many per launch (the queries of a launch share the compute units: 256 / (8 nq)
 // groups of 8 units each)
 constexpr int kSweepDmaMaxQ = 32;
 constexpr int kSweepDmaMaxQMc = 8;       // RING++: the partial sums of a launch are nq x C x ndb x 1 KiB of scratch
-constexpr int kSweepDmaMultiDefault = 10012;   // default cache policy (the other queries' workgroups find the entry in L2), priority, 12 waves
 
 // RING++ (C channels), p.nq queries (<= kSweepDmaMaxQMc): channel-per-workgroup DMA sweep into per-lane partial sums + the finishing kernel
 static int sweep_dma_mc(mrs_ctx* ctx, hipStream_t s, const float2* q, const float2* db, FftCorrP p, float* dist, int* angle, bool tiled)
@@ -1034,19 +974,8 @@ static int sweep_dma_mc(mrs_ctx* ctx, hipStream_t s, const float2* q, const floa
     if (st != MRS_OK) return st;
     p.mc_partial = part.as<float2>();
     const int num_cu = ctx->num_cu > 0 ? ctx->num_cu : 256;
-    if (p.nq > 1) {
-        const char* v = mrs::dev_env("MRS_SWEEP_MQ_MC_WAVES");       // 12 waves (three per SIMD): 23.3-23.5 M pairs/s at 4 queries against 22.7 with 8
-        if (!v || atoi(v) == 12) {
-            if (tiled) MRS_HIP_TRY((sweep_dma_launch_t<12, false, 0, true, true, true>(num_cu, s, q, db, p, dist, angle)));
-            else MRS_HIP_TRY((sweep_dma_launch_t<12, false, 0, false, true, true>(num_cu, s, q, db, p, dist, angle)));
-        } else {
-            if (tiled) MRS_HIP_TRY((sweep_dma_launch_t<8, false, 0, true, true, true>(num_cu, s, q, db, p, dist, angle)));
-            else MRS_HIP_TRY((sweep_dma_launch_t<8, false, 0, false, true, true>(num_cu, s, q, db, p, dist, angle)));
-        }
-    } else {
-        if (tiled) MRS_HIP_TRY((sweep_dma_launch_t<8, false, 1, true, true, true>(num_cu, s, q, db, p, dist, angle)));
-        else MRS_HIP_TRY((sweep_dma_launch_t<8, false, 1, false, true, true>(num_cu, s, q, db, p, dist, angle)));
-    }
+    if (tiled) MRS_HIP_TRY((sweep_dma_launch<true, true>(num_cu, s, q, db, p, dist, angle)));
+    else MRS_HIP_TRY((sweep_dma_launch<false, true>(num_cu, s, q, db, p, dist, angle)));
     hipLaunchKernelGGL(k_ring_mc_finish, dim3((p.ndb + 3) / 4, p.nq), dim3(256), 0, s, p.mc_partial, p.ndb, p.channels, p.denom, dist, angle);
     MRS_HIP_TRY(hipGetLastError());
     return MRS_OK;
@@ -1070,9 +999,8 @@ static int sweep_dma_queries(mrs_ctx* ctx, hipStream_t s, const float2* q, int n
             if (st != MRS_OK) return st;
             continue;
         }
-        int variant = p.nq > 1 ? kSweepDmaMultiDefault : (tiled ? kSweepDmaTiledDefault : kSweepDmaDefault);
-        if (const char* v = mrs::dev_env(p.nq > 1 ? "MRS_SWEEP_MQ_VARIANT" : "MRS_SWEEP_VARIANT")) variant = atoi(v) > 0 ? atoi(v) : variant;
-        MRS_HIP_TRY(sweep_dma_launch(variant, num_cu, s, qq, db, p, dd, aa, tiled));
+        if (tiled) MRS_HIP_TRY((sweep_dma_launch<true, false>(num_cu, s, qq, db, p, dd, aa)));
+        else MRS_HIP_TRY((sweep_dma_launch<false, false>(num_cu, s, qq, db, p, dd, aa)));
     }
     return MRS_OK;
 }
@@ -1128,10 +1056,7 @@ static int corr_fft_launch(mrs_ctx* ctx, const float* d_q, int32_t n_q, const vo
                     // one query, exact entries (the node's loop: main_RING.py:133): the LDS-DMA pipeline, one workgroup per compute unit
                     // ... and, since round 6, a few queries at once (one robot's scan against the other robots' lists: BASELINE configs[3]):
                     // the same pipeline, the queries' workgroups grouped per XCD so that the entry is fetched from HBM once
-                    const char* v1 = mrs::dev_env("MRS_SWEEP_VARIANT");
-                    const char* vq = mrs::dev_env("MRS_SWEEP_MQ_VARIANT");
-                    const bool off = nq == 1 ? (v1 && atoi(v1) == 0) : (vq && atoi(vq) == 0);
-                    if (nq <= kSweepDmaMaxQ && !off && !d_corr && !d_db_first && !d_q_row) {
+                    if (nq <= kSweepDmaMaxQ && !d_corr && !d_db_first && !d_q_row) {
                         const int st = sweep_dma_queries(ctx, s, qq, nq, dd, p, dist_c, angle_c, false);
                         if (st != MRS_OK) return st;
                         launched = true;
@@ -1150,8 +1075,7 @@ static int corr_fft_launch(mrs_ctx* ctx, const float* d_q, int32_t n_q, const vo
                     MRS_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
                     hipLaunchKernelGGL(kern, dim3(blocks, nq), dim3(NSLOT * kSlotThreads), lds, s, qq, dd, p, dist_c, angle_c, corr_c);
                 }
-            } else if (std::is_same<DBT, float2>::value && nq <= kSweepDmaMaxQMc && !d_corr &&
-                       !(mrs::dev_env(nq == 1 ? "MRS_SWEEP_VARIANT" : "MRS_SWEEP_MQ_VARIANT") && atoi(mrs::dev_env(nq == 1 ? "MRS_SWEEP_VARIANT" : "MRS_SWEEP_MQ_VARIANT")) == 0)) {
+            } else if (std::is_same<DBT, float2>::value && nq <= kSweepDmaMaxQMc && !d_corr) {
                 // one query (the node's loop, main_RINGplusplus.py:131-134) or a few: LDS-DMA pipeline, one channel per workgroup
                 const int st = sweep_dma_queries(ctx, s, qq, nq, reinterpret_cast<const float2*>(dd), p, dist_c, angle_c, false);
                 if (st != MRS_OK) return st;

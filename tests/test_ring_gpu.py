@@ -519,8 +519,7 @@ def test_blocked_sweeps_equal_single_sweeps_bit_for_bit(dev):
 def test_several_queries_per_dma_sweep_equal_single_query_sweeps_bit_for_bit(dev):
     """Round 6: mrs_ring_corr_fft_sweep_tiled_q (and the row-layout mrs_ring_corr_fft_sweep[_mc] with 2 .. 32 queries) run the one-query LDS-DMA
     pipeline for Q queries in one launch, the queries' workgroups grouped per XCD.  Every (query, entry) must carry the bits of the
-    one-query sweep and of the register-staged k_ring_corr_fft (MRS_SWEEP_MQ_VARIANT=0 is only reachable under MRS_DEV, so the pairwise
-    kernel is the independent reference here): Q = 2, 4, 5 (groups with idle workgroups), 33 (two launches), databases smaller than one
+    one-query sweep and of the register-staged k_ring_corr_fft (the pairwise kernel is the independent reference here): Q = 2, 4, 5 (groups with idle workgroups), 33 (two launches), databases smaller than one
     round of a workgroup and ragged ones; RING++ with Q = 3 and 9 (two launches)."""
     import torch
     from mr_slam_amd import ring

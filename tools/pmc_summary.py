@@ -53,12 +53,12 @@ for f in files:
         k = m.group(1)
         if k == "k_ring_corr_fft":
             k += "@grid%s" % r["Grid_Size"]
-        if k == "k_ring_sweep_dma":                # row layout / DMA-tiled / multi-channel are different instantiations: <WAVES, SPLIT, NT, RING, QDMA, TILED, PRIO, MC, PF>
+        if k == "k_ring_sweep_dma":                # row layout / DMA-tiled / multi-channel are different instantiations: <WAVES, NT, TILED, MC>
             t = re.search(r"k_ring_sweep_dma<([^>]*)>", r["Kernel_Name"])
             a = [x.strip() for x in t.group(1).split(",")] if t else []
-            if len(a) >= 8:
-                k += "<%s%s, %s waves%s>" % ("tiled" if a[5] in ("true", "1") else "rows", ", 6 channels" if a[7] in ("true", "1") else "", a[0],
-                                             "" if a[2] != "0" else ", several queries")      # NT = 0 (default cache policy) is the several-queries form
+            if len(a) == 4:
+                k += "<%s%s, %s waves%s>" % ("tiled" if a[2] in ("true", "1") else "rows", ", 6 channels" if a[3] in ("true", "1") else "", a[0],
+                                             "" if a[1] in ("true", "1") else ", several queries")      # !NT (default cache policy) is the several-queries form
         if k == "k_knn_cov":                       # k = 15 covariances (16 slots) and the k = 30 point-feature selection (32 slots) are different kernels
             t = re.search(r"k_knn_cov<\s*(\d+)", r["Kernel_Name"])
             if t:
