@@ -577,7 +577,7 @@ int mrs_exchange_fetch_plan_destroy(mrs_fetch_plan* plan);
  * reference's callbacks run on concurrent rospy threads); all device work of a handle runs on the handle's own stream, `stream` is the
  * stream that produced a DEVICE argument (the handle waits for it; for appends it is made to wait until the argument has been consumed). */
 typedef struct mrs_loopdb mrs_loopdb;
-enum mrs_loopdb_kind { MRS_LOOPDB_RING = 0, MRS_LOOPDB_RINGPP = 1, MRS_LOOPDB_DISCO = 2 };
+enum mrs_loopdb_kind { MRS_LOOPDB_RING = 0, MRS_LOOPDB_RINGPP = 1, MRS_LOOPDB_DISCO = 2, MRS_LOOPDB_SC = 3 };
 /* where / what a RING or RING++ descriptor argument is:
  *   HOST / DEVICE : the reference's own object -- RING: pc_TIRING, complex64 [1][120][120] (util.py:198; its first 61 rows are what is
  *                   kept); RING++: pc_TIRING, float32 [C][120][120] magnitudes (util.py:247-250; normalised jointly + transformed along the
@@ -585,7 +585,7 @@ enum mrs_loopdb_kind { MRS_LOOPDB_RING = 0, MRS_LOOPDB_RINGPP = 1, MRS_LOOPDB_DI
  *   DEVICE_SPEC   : half spectra in the product's row layout, complex64 [C][61][120] (mrs_ring_half_spectrum / mrs_ring_spectrum_corr_pairs) */
 enum mrs_loopdb_form { MRS_LOOPDB_FORM_HOST = 0, MRS_LOOPDB_FORM_DEVICE = 1, MRS_LOOPDB_FORM_DEVICE_SPEC = 2 };
 
-/* channels: 1 for RING, C (6 in the reference) for RING++, ignored for DiSCO; capacity_hint: entries to allocate up front (>= 1) */
+/* channels: 1 for RING, C (6 in the reference) for RING++, ignored for DiSCO and SC; capacity_hint: entries to allocate up front (>= 1) */
 int mrs_loopdb_create(mrs_ctx* ctx, int32_t kind, int32_t channels, int32_t capacity_hint, mrs_loopdb** out);
 int mrs_loopdb_destroy(mrs_loopdb* db);
 int mrs_loopdb_size(mrs_loopdb* db, int32_t* out_n);
@@ -615,8 +615,50 @@ int mrs_loopdb_append_disco(mrs_loopdb* db, const float* signature, const float*
  * map (the reference takes it `% num_sector`).  Blocking. */
 int mrs_loopdb_query_disco(mrs_loopdb* db, const float* signature, const float* spectrum, int32_t on_device, int32_t* h_index, float* h_dist2,
                            int32_t* h_flat_argmax, mrs_stream stream);
-/* the entries as they lie on the device (tests, exchange): valid until the next append that grows the capacity */
+/* Scan Context: SC<k>.append(SC_current) / RingkeyPC<k>.append(make_ringkey(SC_current)) of the SC node (RING_ros/main_SC.py; descriptor
+ * = generate_scan_context, main_SC.py:57-69: the Cartesian max-z BEV, float32 [120][120], axis -2 "ring", axis -1 "sector").  The handle
+ * stores the descriptor with its sector keys and column norms, and its ring key (make_ringkey, pr_methods/ScanContext.py:13-21). */
+int mrs_loopdb_append_sc(mrs_loopdb* db, const float* sc, int32_t on_device, mrs_stream stream);
+/* detect_loop_icp_SC's candidate step (main_SC.py:159-167) with num_candidates = k (1 .. 64; the node uses 1, config.py:15 has 10):
+ * the k nearest ring keys (Euclidean, fp64, ascending, ties to the lower index: KDTree(Ringkey_candidates).query(k)), then
+ * dist_align_sc(SC_candidate, SC_current, search_ratio) (pr_methods/ScanContext.py:128-142) for each.  h_index / h_key_dist / h_dist /
+ * h_shift [num_candidates]; *h_count = min(k, n).  The shift is the reference's: in [-S, S), the roll applied to SC_current.  Blocking;
+ * an empty database returns *h_count = 0 and index -1 without device work. */
+int mrs_loopdb_query_sc(mrs_loopdb* db, const float* sc, int32_t on_device, int32_t num_candidates, float search_ratio, int32_t* h_index,
+                        float* h_key_dist, float* h_dist, int32_t* h_shift, int32_t* h_count, mrs_stream stream);
+/* dist_align_sc(entry, sc, search_ratio) against EVERY entry in one launch: h_all_dist / h_all_shift receive the first min(n, all_capacity)
+ * results, *h_best the index of the first smallest dist over all n (-1 when empty), *h_n = n.  Blocking. */
+int mrs_loopdb_query_sc_all(mrs_loopdb* db, const float* sc, int32_t on_device, float search_ratio, int32_t all_capacity, float* h_all_dist,
+                            int32_t* h_all_shift, int32_t* h_best, int32_t* h_n, mrs_stream stream);
+/* the entries as they lie on the device (tests, exchange): valid until the next append that grows the capacity.  SC: d_entries = packed
+ * entries (entry_floats apart: sector keys [128], column norms [128], then the [120][120] descriptor), d_signatures = ring keys [n][120] */
 int mrs_loopdb_device_entries(mrs_loopdb* db, const float** d_entries, const float** d_signatures, int32_t* out_n, int64_t* entry_floats);
+
+/* ------------------------------------------------------------------------------------
+ * Scan Context on device arrays (RING_ros/pr_methods/ScanContext.py).  d_sc* are float32 [n][num_ring][num_sector], row-major like the
+ * reference's descriptors; num_ring, num_sector <= 128 (the node's 120 x 120 Cartesian descriptor, or the paper's 20 x 60 polar one from
+ * mrs_bev_polar_batch); larger geometries return MRS_ERR_UNSUPPORTED.
+ * ---------------------------------------------------------------------------------- */
+
+/* make_ringkey (row means, [n][num_ring]) and make_sectorkey (column means, [n][num_sector]) (ScanContext.py:13-31); either output may be
+ * NULL.  float32 values (the reference stores the float32 means in float64 arrays). */
+int mrs_sc_keys(mrs_ctx* ctx, const float* d_sc, int32_t n, int32_t num_ring, int32_t num_sector, float* d_ring_key, float* d_sector_key,
+                mrs_stream stream);
+/* fast_align_with_sectorkey(key1, key2) (ScanContext.py:86-101) for pairs of float32 keys [n_pairs][len]: min over s of
+ * ||key1 - roll(key2, s)|| (fp64) and the first s attaining it. */
+int mrs_sc_key_align_pairs(mrs_ctx* ctx, const float* d_key1, const float* d_key2, int32_t n_pairs, int32_t len, double* d_norm, int32_t* d_shift,
+                           mrs_stream stream);
+/* dist_direct_sc(sc1, sc2) (ScanContext.py:105-126): 1 - mean column cosine over the columns where both norms are > 0 (1.0 if none). */
+int mrs_sc_dist_direct_pairs(mrs_ctx* ctx, const float* d_sc1, const float* d_sc2, int32_t n_pairs, int32_t num_ring, int32_t num_sector,
+                             float* d_dist, mrs_stream stream);
+/* dist_align_sc(sc1, sc2, search_ratio) (ScanContext.py:128-142): sector-key pre-alignment s*, then the window
+ * [max(-S, s* - r), min(S, s* + r + 1)) with r = round(0.5 search_ratio S), first minimum; d_shift may be negative. */
+int mrs_sc_dist_align_pairs(mrs_ctx* ctx, const float* d_sc1, const float* d_sc2, int32_t n_pairs, int32_t num_ring, int32_t num_sector,
+                            float search_ratio, float* d_dist, int32_t* d_shift, mrs_stream stream);
+/* distance_sc(sc1, sc2) (ScanContext.py:34-69): all num_sector shifts of sc1, mean cosine over the engaged columns (0 if none);
+ * d_dist = 1 - max, d_yaw = argmax + 1 (the reference's convention). */
+int mrs_sc_distance_pairs(mrs_ctx* ctx, const float* d_sc1, const float* d_sc2, int32_t n_pairs, int32_t num_ring, int32_t num_sector, float* d_dist,
+                          int32_t* d_yaw, mrs_stream stream);
 
 /* ------------------------------------------------------------------------------------
  * Mapping-side DiSCO matcher

@@ -81,6 +81,18 @@ struct SectorLut {
 }  // namespace mrs
 
 namespace mrs {
+// Scan Context building blocks (scancontext.hip), shared with the MRS_LOOPDB_SC database of loopdb.hip.  An entry is a header (sector keys,
+// column norms) followed by the [R][S] descriptor; sc_entry_floats(R, S) floats from one entry to the next.
+size_t sc_entry_floats(int R, int S);
+int sc_search_radius(float search_ratio, int S);
+int sc_pack(const float* d_sc, int n, int R, int S, float* d_entries, size_t entry_stride, float* d_ring, float* d_sector, hipStream_t s);
+int sc_nearest(const float* d_q, const float* d_keys, int n, int R, int k, int* d_idx, double* d_d2, hipStream_t s);
+// mode 0: dist_align_sc(F, Q) with the given search radius; 1: distance_sc(Q, F); 2: dist_direct_sc(F, Q)
+int sc_align(mrs_ctx* ctx, const float* d_F, size_t f_stride, const int* d_list, int npairs, const float* d_Q, size_t q_stride, int R, int S,
+             int mode, int radius, float* d_dist, int* d_shift, hipStream_t s);
+}  // namespace mrs
+
+namespace mrs {
 // A second stream + fork / join events + a small pinned buffer, kept in a per-context pool: a registration of one pair (the nodes' shape)
 // borrows one for the duration of mrs_gicp_batch_align.  Creating them per handle cost 0.4 ms per FastGICP object (the nodes construct one
 // per registration, main_RING.py:84); concurrent callers (three rospy callback threads) each get their own slot.

@@ -10,6 +10,8 @@
 // query is ONE sweep launch + one copy of (dist, angle) per entry + the `dist < threshold` filter in index order.
 // All work of a handle runs on the handle's own stream; calls are serialised by a mutex (the reference's callbacks run on
 // concurrent rospy threads, each appending to its own list and reading the other robots').
+// Scan Context (MRS_LOOPDB_SC) replaces the ring-key KDTree + dist_align_sc of main_SC.py:153-172: entries are packed descriptors with their
+// sector keys and column norms (scancontext.hip), the ring keys a dense [n][120] array; a query is a nearest-key sweep + one alignment launch.
 #include "common.hpp"
 #include "fft_codelets.hpp"
 
@@ -23,6 +25,9 @@ constexpr int kA = 120, kD = 120, kHalf = 61;
 constexpr size_t kSpecFloats = (size_t)kHalf * kD * 2;       // one [61][120] complex64 plane
 constexpr size_t kTiledFloats = MRS_RING_TILED_ENTRY_BYTES / 4;
 constexpr int kStageSlots = 4;
+
+// SC top-k query results, one copy to the host: index [kScMaxK] | dist [kScMaxK] | shift [kScMaxK] | squared key distance [kScMaxK] (fp64)
+constexpr int kScDim = 120, kScMaxK = 64, kSmallSc = 5 * kScMaxK;
 
 struct Pinned {
     void* p = nullptr;
@@ -152,12 +157,12 @@ __global__ __launch_bounds__(kPhaseThreads) void k_disco_phase_one(const float2*
 struct mrs_loopdb {
     mrs_ctx* ctx = nullptr;
     int kind = 0, channels = 1;
-    int sig_dim = 0, R = 0, S = 0;            // DiSCO
+    int sig_dim = 0, R = 0, S = 0;            // DiSCO; SC: sig_dim = R = S = 120 (ring keys [cap][120] in d_sigs)
     int n = 0, cap = 0;
     size_t entry_floats = 0;                  // floats from one entry of d_entries to the next
     size_t in_floats = 0;                     // floats of a descriptor in the reference's form (what append / query take)
     float* d_entries = nullptr;               // RING / RING++: [cap + 1][C] DMA-tiled planes (one entry of slack); DiSCO: spectra [cap][R][S] complex64
-    float* d_sigs = nullptr;                  // DiSCO: [cap][dim]
+    float* d_sigs = nullptr;                  // DiSCO: [cap][dim]; SC: ring keys [cap][120]
     float* d_dist = nullptr;                  // [2 cap]: [n] distances, [n] angles
     int32_t* d_angle = nullptr;               // = d_dist + n of the query at hand (one allocation, one copy)
     float* h_dist = nullptr;                  // pinned [2 cap]
@@ -167,7 +172,7 @@ struct mrs_loopdb {
     float* d_query = nullptr;                 // the query in database form (row layout: [C][61][120] complex64)
     float* d_tw = nullptr;                    // DiSCO: exp(+2 pi i k / S), k < S, then exp(+2 pi i k / R), k < R
     unsigned long long* d_best = nullptr;     // DiSCO: packed (distance bits, index)
-    int32_t* d_small = nullptr;               // DiSCO: index, distance bits, argmax
+    int32_t* d_small = nullptr;               // DiSCO: index, distance bits, argmax; SC: the kSmallSc words of a top-k query
     int32_t* h_small = nullptr;               // pinned
     bool phase_attr_set = false;              // DiSCO: the phase kernel's LDS attribute has been set on this handle's device
     Pinned stage[kStageSlots];
@@ -198,13 +203,13 @@ int reserve_locked(mrs_loopdb* db, int want)
     while (cap < want) cap *= 2;
     float *ne = nullptr, *ns = nullptr, *nd = nullptr, *hd = nullptr;
     int32_t *na = nullptr, *ha = nullptr;
-    const size_t slack = db->kind == MRS_LOOPDB_DISCO ? 0 : 1;   // the tiled sweep reads up to 1 KiB past the last entry
+    const size_t slack = (db->kind == MRS_LOOPDB_RING || db->kind == MRS_LOOPDB_RINGPP) ? 1 : 0;   // the tiled sweep reads up to 1 KiB past the last entry
     // every failure path releases what this call has allocated so far (the out-of-memory case must not get worse on retry)
     auto grow = [&]() -> hipError_t {
         hipError_t e = hipMalloc(&ne, ((size_t)cap + slack) * db->entry_floats * sizeof(float));
         if (e != hipSuccess) return e;
         if (slack && (e = hipMemsetAsync(ne + (size_t)cap * db->entry_floats, 0, db->entry_floats * sizeof(float), db->s)) != hipSuccess) return e;
-        if (db->kind == MRS_LOOPDB_DISCO && (e = hipMalloc(&ns, (size_t)cap * db->sig_dim * sizeof(float))) != hipSuccess) return e;
+        if (db->sig_dim > 0 && (e = hipMalloc(&ns, (size_t)cap * db->sig_dim * sizeof(float))) != hipSuccess) return e;
         // distances and angles of a query lie back to back ([n] floats, [n] ints: the angles start at element n, wherever n stands) so that ONE
         // copy brings both to the host; d_dist / h_dist own the 2 x cap elements, d_angle / h_angle are not separate allocations
         if ((e = hipMalloc(&nd, (size_t)2 * cap * sizeof(float))) != hipSuccess) return e;
@@ -294,7 +299,8 @@ int mrs_loopdb_create(mrs_ctx* ctx, int32_t kind, int32_t channels, int32_t capa
 {
     MRS_REQUIRE(ctx && out, "null pointer");
     *out = nullptr;
-    MRS_REQUIRE(kind == MRS_LOOPDB_RING || kind == MRS_LOOPDB_RINGPP || kind == MRS_LOOPDB_DISCO, "unknown kind");
+    MRS_REQUIRE(kind == MRS_LOOPDB_RING || kind == MRS_LOOPDB_RINGPP || kind == MRS_LOOPDB_DISCO || kind == MRS_LOOPDB_SC, "unknown kind");
+    if (kind == MRS_LOOPDB_SC) channels = 1;                   // ignored: one [120][120] descriptor per entry
     MRS_REQUIRE(kind != MRS_LOOPDB_RING || channels == 1, "RING descriptors have one channel");
     MRS_REQUIRE(channels >= 1 && channels <= 16, "channels out of range");
     MRS_HIP_TRY(hipSetDevice(ctx->device));
@@ -302,7 +308,8 @@ int mrs_loopdb_create(mrs_ctx* ctx, int32_t kind, int32_t channels, int32_t capa
     db->ctx = ctx; db->kind = kind; db->channels = channels;
     if (kind == MRS_LOOPDB_RING) { db->entry_floats = kTiledFloats; db->in_floats = (size_t)kA * kD * 2; }
     else if (kind == MRS_LOOPDB_RINGPP) { db->entry_floats = (size_t)channels * kTiledFloats; db->in_floats = (size_t)channels * kA * kD; }
-    else { db->sig_dim = 1024; db->R = kPR; db->S = kPS; db->entry_floats = (size_t)db->R * db->S * 2; db->in_floats = db->entry_floats; }
+    else if (kind == MRS_LOOPDB_DISCO) { db->sig_dim = 1024; db->R = kPR; db->S = kPS; db->entry_floats = (size_t)db->R * db->S * 2; db->in_floats = db->entry_floats; }
+    else { db->sig_dim = db->R = db->S = kScDim; db->entry_floats = mrs::sc_entry_floats(kScDim, kScDim); db->in_floats = (size_t)kScDim * kScDim; }
     auto fail = [&](int st) { mrs_loopdb_destroy(db); return st; };
 #define LDB_TRY(expr) do { if ((expr) != hipSuccess) { mrs::set_error("%s failed (%s:%d)", #expr, __FILE__, __LINE__); return fail(MRS_ERR_HIP); } } while (0)
     LDB_TRY(hipStreamCreateWithFlags(&db->s, hipStreamNonBlocking));
@@ -326,6 +333,10 @@ int mrs_loopdb_create(mrs_ctx* ctx, int32_t kind, int32_t channels, int32_t capa
         LDB_TRY(hipMemset(db->d_best, 0xff, sizeof(unsigned long long)));       // armed; k_disco_phase_one re-arms it after every query
         LDB_TRY(hipMalloc(&db->d_small, 4 * sizeof(int32_t)));
         LDB_TRY(hipHostMalloc(&db->h_small, 4 * sizeof(int32_t), hipHostMallocDefault));
+    }
+    if (kind == MRS_LOOPDB_SC) {
+        LDB_TRY(hipMalloc(&db->d_small, kSmallSc * sizeof(int32_t)));
+        LDB_TRY(hipHostMalloc(&db->h_small, kSmallSc * sizeof(int32_t), hipHostMallocDefault));
     }
 #undef LDB_TRY
     {
@@ -388,7 +399,7 @@ int mrs_loopdb_clear(mrs_loopdb* db)
 int mrs_loopdb_append(mrs_loopdb* db, const void* descriptor, int32_t form, int32_t count, mrs_stream stream)
 {
     MRS_REQUIRE(db && descriptor, "null pointer");
-    MRS_REQUIRE(db->kind != MRS_LOOPDB_DISCO, "DiSCO entries are appended with mrs_loopdb_append_disco");
+    MRS_REQUIRE(db->kind == MRS_LOOPDB_RING || db->kind == MRS_LOOPDB_RINGPP, "not a RING / RING++ database (DiSCO: mrs_loopdb_append_disco, SC: mrs_loopdb_append_sc)");
     MRS_REQUIRE(form == MRS_LOOPDB_FORM_HOST || form == MRS_LOOPDB_FORM_DEVICE || form == MRS_LOOPDB_FORM_DEVICE_SPEC, "unknown form");
     MRS_REQUIRE(count >= 1 && (count == 1 || form == MRS_LOOPDB_FORM_DEVICE_SPEC), "several entries per call only as device half spectra");
     MRS_HIP_TRY(hipSetDevice(db->ctx->device));
@@ -420,7 +431,7 @@ int mrs_loopdb_query(mrs_loopdb* db, const void* descriptor, int32_t form, float
                      mrs_stream stream)
 {
     MRS_REQUIRE(db && descriptor && h_count, "null pointer");
-    MRS_REQUIRE(db->kind != MRS_LOOPDB_DISCO, "DiSCO databases are queried with mrs_loopdb_query_disco");
+    MRS_REQUIRE(db->kind == MRS_LOOPDB_RING || db->kind == MRS_LOOPDB_RINGPP, "not a RING / RING++ database (DiSCO: mrs_loopdb_query_disco, SC: mrs_loopdb_query_sc)");
     MRS_REQUIRE(form == MRS_LOOPDB_FORM_HOST || form == MRS_LOOPDB_FORM_DEVICE || form == MRS_LOOPDB_FORM_DEVICE_SPEC, "unknown form");
     MRS_REQUIRE(max_out >= 0 && (max_out == 0 || (h_index && h_dist && h_angle)), "output arrays");
     MRS_REQUIRE(all_capacity >= 0 && (all_capacity == 0 || h_all_dist || h_all_angle), "all_capacity without an array");
@@ -456,7 +467,7 @@ int mrs_loopdb_query_multi(mrs_loopdb* db, const void* descriptors, int32_t form
                            int32_t* h_all_angle, int32_t* h_n, mrs_stream stream)
 {
     MRS_REQUIRE(db && descriptors && h_all_dist && h_all_angle && h_n, "null pointer");
-    MRS_REQUIRE(db->kind != MRS_LOOPDB_DISCO, "DiSCO databases are queried with mrs_loopdb_query_disco");
+    MRS_REQUIRE(db->kind == MRS_LOOPDB_RING || db->kind == MRS_LOOPDB_RINGPP, "not a RING / RING++ database (DiSCO: mrs_loopdb_query_disco, SC: mrs_loopdb_query_sc)");
     MRS_REQUIRE(form == MRS_LOOPDB_FORM_HOST || form == MRS_LOOPDB_FORM_DEVICE || form == MRS_LOOPDB_FORM_DEVICE_SPEC, "unknown form");
     MRS_REQUIRE(count >= 1 && count <= 1024 && all_capacity >= 0, "count in 1..1024");
     MRS_HIP_TRY(hipSetDevice(db->ctx->device));
@@ -572,6 +583,139 @@ int mrs_loopdb_query_disco(mrs_loopdb* db, const float* signature, const float* 
     *h_index = db->h_small[0];
     memcpy(h_dist2, &db->h_small[1], sizeof(float));
     *h_flat_argmax = db->h_small[2];
+    return MRS_OK;
+}
+
+// ---- Scan Context -------------------------------------------------------------------------------------------------------------------
+
+namespace {
+// the query descriptor -> packed entry at d_query + its ring key at d_tmp, on the handle's stream (lock held)
+int sc_query_prep(mrs_loopdb* db, const float* sc, int32_t on_device, mrs_stream stream)
+{
+    const float* src = sc;
+    if (on_device) {
+        int st = join_in(db, (hipStream_t)stream);
+        if (st != MRS_OK) return st;
+    } else {
+        int st = upload(db, sc, db->in_floats * sizeof(float), db->d_in);
+        if (st != MRS_OK) return st;
+        src = db->d_in;
+    }
+    return mrs::sc_pack(src, 1, kScDim, kScDim, db->d_query, db->entry_floats, db->d_tmp, nullptr, db->s);
+}
+
+// the caller may reuse its device argument once ITS stream has passed this point
+int sc_release_arg(mrs_loopdb* db, int32_t on_device, mrs_stream stream)
+{
+    if (!on_device) return MRS_OK;
+    MRS_HIP_TRY(hipEventRecord(db->ev_out, db->s));
+    MRS_HIP_TRY(hipStreamWaitEvent((hipStream_t)stream, db->ev_out, 0));
+    return MRS_OK;
+}
+}  // namespace
+
+int mrs_loopdb_append_sc(mrs_loopdb* db, const float* sc, int32_t on_device, mrs_stream stream)
+{
+    MRS_REQUIRE(db && sc, "null pointer");
+    MRS_REQUIRE(db->kind == MRS_LOOPDB_SC, "not a Scan Context database");
+    MRS_HIP_TRY(hipSetDevice(db->ctx->device));
+    std::lock_guard<std::mutex> lk(db->mu);
+    int st = reserve_locked(db, db->n + 1);
+    if (st != MRS_OK) return st;
+    const float* src = sc;
+    if (on_device) {
+        st = join_in(db, (hipStream_t)stream);
+        if (st != MRS_OK) return st;
+    } else {
+        st = upload(db, sc, db->in_floats * sizeof(float), db->d_in);
+        if (st != MRS_OK) return st;
+        src = db->d_in;
+    }
+    st = mrs::sc_pack(src, 1, kScDim, kScDim, db->d_entries + (size_t)db->n * db->entry_floats, db->entry_floats,
+                      db->d_sigs + (size_t)db->n * db->sig_dim, nullptr, db->s);
+    if (st != MRS_OK) return st;
+    st = sc_release_arg(db, on_device, stream);
+    if (st != MRS_OK) return st;
+    db->n += 1;
+    return MRS_OK;
+}
+
+int mrs_loopdb_query_sc(mrs_loopdb* db, const float* sc, int32_t on_device, int32_t num_candidates, float search_ratio, int32_t* h_index,
+                        float* h_key_dist, float* h_dist, int32_t* h_shift, int32_t* h_count, mrs_stream stream)
+{
+    MRS_REQUIRE(db && sc && h_index && h_key_dist && h_dist && h_shift && h_count, "null pointer");
+    MRS_REQUIRE(db->kind == MRS_LOOPDB_SC, "not a Scan Context database");
+    MRS_REQUIRE(num_candidates >= 1 && num_candidates <= kScMaxK, "num_candidates in 1..64");
+    MRS_REQUIRE(std::isfinite(search_ratio) && search_ratio >= 0.0f, "search_ratio >= 0");
+    MRS_HIP_TRY(hipSetDevice(db->ctx->device));
+    std::lock_guard<std::mutex> lk(db->mu);
+    const int k = num_candidates;
+    for (int i = 0; i < k; ++i) { h_index[i] = -1; h_key_dist[i] = INFINITY; h_dist[i] = 1.0f; h_shift[i] = 0; }
+    *h_count = 0;
+    const int n = db->n;
+    if (n == 0) return MRS_OK;                             // `if len(Ringkey_candidates) < 1: return`
+    int st = sc_query_prep(db, sc, on_device, stream);
+    if (st != MRS_OK) return st;
+    int32_t* d_idx = db->d_small;
+    float* d_dist = reinterpret_cast<float*>(db->d_small + kScMaxK);
+    int32_t* d_shift = db->d_small + 2 * kScMaxK;
+    double* d_d2 = reinterpret_cast<double*>(db->d_small + 3 * kScMaxK);
+    const int cnt = std::min(k, n);
+    // KDTree(ring keys).query(k) then dist_align_sc(SC_candidate, SC_current, search_ratio) for each candidate (main_SC.py:159-167)
+    st = mrs::sc_nearest(db->d_tmp, db->d_sigs, n, kScDim, k, d_idx, d_d2, db->s);
+    if (st != MRS_OK) return st;
+    st = mrs::sc_align(db->ctx, db->d_entries, db->entry_floats, d_idx, cnt, db->d_query, 0, kScDim, kScDim, 0,
+                       mrs::sc_search_radius(search_ratio, kScDim), d_dist, d_shift, db->s);
+    if (st != MRS_OK) return st;
+    st = sc_release_arg(db, on_device, stream);
+    if (st != MRS_OK) return st;
+    MRS_HIP_TRY(hipMemcpyAsync(db->h_small, db->d_small, kSmallSc * sizeof(int32_t), hipMemcpyDeviceToHost, db->s));
+    MRS_HIP_TRY(hipStreamSynchronize(db->s));
+    const float* hd = reinterpret_cast<const float*>(db->h_small + kScMaxK);
+    const double* hd2 = reinterpret_cast<const double*>(db->h_small + 3 * kScMaxK);
+    for (int i = 0; i < cnt; ++i) {
+        h_index[i] = db->h_small[i];
+        h_key_dist[i] = (float)std::sqrt(hd2[i]);
+        h_dist[i] = hd[i];
+        h_shift[i] = db->h_small[2 * kScMaxK + i];
+    }
+    *h_count = cnt;
+    return MRS_OK;
+}
+
+int mrs_loopdb_query_sc_all(mrs_loopdb* db, const float* sc, int32_t on_device, float search_ratio, int32_t all_capacity, float* h_all_dist,
+                            int32_t* h_all_shift, int32_t* h_best, int32_t* h_n, mrs_stream stream)
+{
+    MRS_REQUIRE(db && sc && h_best && h_n, "null pointer");
+    MRS_REQUIRE(db->kind == MRS_LOOPDB_SC, "not a Scan Context database");
+    MRS_REQUIRE(std::isfinite(search_ratio) && search_ratio >= 0.0f, "search_ratio >= 0");
+    MRS_REQUIRE(all_capacity >= 0 && (all_capacity == 0 || (h_all_dist && h_all_shift)), "all_capacity without arrays");
+    MRS_HIP_TRY(hipSetDevice(db->ctx->device));
+    std::lock_guard<std::mutex> lk(db->mu);
+    const int n = db->n;
+    *h_n = n;
+    *h_best = -1;
+    if (n == 0) return MRS_OK;
+    int st = sc_query_prep(db, sc, on_device, stream);
+    if (st != MRS_OK) return st;
+    db->d_angle = reinterpret_cast<int32_t*>(db->d_dist + n);
+    db->h_angle = reinterpret_cast<int32_t*>(db->h_dist + n);
+    st = mrs::sc_align(db->ctx, db->d_entries, db->entry_floats, nullptr, n, db->d_query, 0, kScDim, kScDim, 0,
+                       mrs::sc_search_radius(search_ratio, kScDim), db->d_dist, db->d_angle, db->s);
+    if (st != MRS_OK) return st;
+    st = sc_release_arg(db, on_device, stream);
+    if (st != MRS_OK) return st;
+    MRS_HIP_TRY(hipMemcpyAsync(db->h_dist, db->d_dist, (size_t)2 * n * sizeof(float), hipMemcpyDeviceToHost, db->s));
+    MRS_HIP_TRY(hipStreamSynchronize(db->s));
+    int best = 0;                                          // first minimum over the entries, as a loop over them would keep it
+    for (int i = 1; i < n; ++i)
+        if (db->h_dist[i] < db->h_dist[best]) best = i;
+    *h_best = best;
+    const size_t m = (size_t)std::min(n, all_capacity);    // never past the caller's arrays
+    if (m > 0) {
+        memcpy(h_all_dist, db->h_dist, m * sizeof(float));
+        memcpy(h_all_shift, db->h_angle, m * sizeof(int32_t));
+    }
     return MRS_OK;
 }
 
