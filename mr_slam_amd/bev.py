@@ -15,12 +15,6 @@ def _cfg(max_length, max_height, n0, n1, num_height, last):
     return BevCfg(int(max_length), int(max_height), int(n0), int(n1), int(num_height), int(last))
 
 
-def _dev(t):
-    if not t.is_cuda:
-        raise _lib.MrsError("expected a device tensor (no CPU fallback)")
-    return t.device.index or 0
-
-
 def pack_scans(scans, device="cuda:0", planes=3):
     """Pack a list of [n_i, planes] (or already-SoA [planes*n_i]) host scans into the ABI's
     ragged layout: one float32 device tensor + int64 offsets (in points)."""
@@ -39,34 +33,30 @@ def pack_scans(scans, device="cuda:0", planes=3):
 
 def polar_indices(xyz_soa, max_length, max_height, num_ring, num_sector, num_height):
     """A1: (ring, sector, height) int32 device tensors for one SoA scan [3n]."""
-    d = _dev(xyz_soa)
+    d = _lib.device_of(xyz_soa)
     n = xyz_soa.numel() // 3
     r, s, h = (torch.empty(n, dtype=torch.int32, device=xyz_soa.device) for _ in range(3))
     cfg = _cfg(max_length, max_height, num_ring, num_sector, num_height, 1)
-    _lib.check(_lib.load().mrs_bev_polar_indices(_lib.ctx(d), _lib.ptr(xyz_soa), n, C.byref(cfg),
-                                                 _lib.ptr(r), _lib.ptr(s), _lib.ptr(h), _lib.current_stream(d)))
+    _lib.load().mrs_bev_polar_indices(_lib.ctx(d), xyz_soa, n, C.byref(cfg), r, s, h, _lib.current_stream(d))
     return r, s, h
 
 
 def cart_indices(xyz_soa, max_length, max_height, num_x, num_y, num_height):
     """A3: (ix, iy, ih) int32 device tensors for one SoA scan [3n]."""
-    d = _dev(xyz_soa)
+    d = _lib.device_of(xyz_soa)
     n = xyz_soa.numel() // 3
     a, b, c = (torch.empty(n, dtype=torch.int32, device=xyz_soa.device) for _ in range(3))
     cfg = _cfg(max_length, max_height, num_x, num_y, num_height, 1)
-    _lib.check(_lib.load().mrs_bev_cart_indices(_lib.ctx(d), _lib.ptr(xyz_soa), n, C.byref(cfg),
-                                                _lib.ptr(a), _lib.ptr(b), _lib.ptr(c), _lib.current_stream(d)))
+    _lib.load().mrs_bev_cart_indices(_lib.ctx(d), xyz_soa, n, C.byref(cfg), a, b, c, _lib.current_stream(d))
     return a, b, c
 
 
 def _batch(fn_name, xyz, offsets, cfg, layout, out_per_scan, out=None):
-    d = _dev(xyz)
+    d = _lib.device_of(xyz)
     batch = offsets.numel() - 1
     if out is None:
         out = torch.empty((batch, out_per_scan), dtype=torch.float32, device=xyz.device)
-    fn = getattr(_lib.load(), fn_name)
-    _lib.check(fn(_lib.ctx(d), _lib.ptr(xyz), _lib.ptr(offsets), batch, C.byref(cfg), layout,
-                  _lib.ptr(out), _lib.current_stream(d)))
+    getattr(_lib.load(), fn_name)(_lib.ctx(d), xyz, offsets, batch, C.byref(cfg), layout, out, _lib.current_stream(d))
     return out
 
 

@@ -36,6 +36,5 @@ class HostTransformer:
 
     def retreive(self):
         out = np.zeros(self._out_size(), dtype=np.float32)
-        fn = getattr(_lib.load(), self._fn)
-        _lib.check(fn(_lib.ctx(0), _lib.ptr(self._point), self._size, C.byref(self._cfg), _lib.ptr(out)))
+        getattr(_lib.load(), self._fn)(_lib.ctx(0), self._point, self._size, C.byref(self._cfg), out)
         return out

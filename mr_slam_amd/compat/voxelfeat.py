@@ -35,6 +35,5 @@ class GPUFeatureExtractor:
         import numpy as np
         from .. import _lib
         out = np.zeros(self._n * 13, dtype=np.float32)
-        _lib.check(_lib.load().mrs_pointfeat_from_neighbors_host(_lib.ctx(0), _lib.ptr(self._p), self._n, self._kk,
-                                                                 _lib.ptr(self._k), _lib.ptr(self._e), _lib.ptr(out)))
+        _lib.load().mrs_pointfeat_from_neighbors_host(_lib.ctx(0), self._p, self._n, self._kk, self._k, self._e, out)
         return out

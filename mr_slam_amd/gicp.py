@@ -42,10 +42,7 @@ class GicpBatch:
         self.n_pairs = int(n_pairs)
         self.device = device
         self._h = C.c_void_p()
-        lib = _lib.load()
-        lib.mrs_gicp_batch_last_nn_passes.restype = C.c_double
-        lib.mrs_gicp_batch_last_searched_fraction.restype = C.c_double
-        _lib.check(lib.mrs_gicp_batch_create(_lib.ctx(device), self.n_pairs, C.byref(self._h)))
+        _lib.load().mrs_gicp_batch_create(_lib.ctx(device), self.n_pairs, C.byref(self._h))
         self.params = default_params()
         self._n = [None, None]
 
@@ -61,12 +58,12 @@ class GicpBatch:
             if not hasattr(self.params, k):
                 raise AttributeError(k)
             setattr(self.params, k, v)
-        _lib.check(_lib.load().mrs_gicp_batch_set_params(self._h, C.byref(self.params)))
+        _lib.load().mrs_gicp_batch_set_params(self._h, C.byref(self.params))
 
     def set_search(self, core):
         """1 (default): octree-cell leaves, per-query culling, certified neighbours; 2: without certificates; 3: round-4 kernel for the cold
         pass too; 0: the round-3 wave-shared traversal (A/B, cross-check)."""
-        _lib.check(_lib.load().mrs_gicp_batch_set_search(self._h, int(core)))
+        _lib.load().mrs_gicp_batch_set_search(self._h, int(core))
 
     def _set(self, which, clouds):
         """clouds: list of [n_i, >=3] arrays (host) or a (device tensor [N, s], offsets) tuple."""
@@ -89,9 +86,7 @@ class GicpBatch:
             pts.copy_(stage[:total], non_blocking=True)
         assert offs.size == self.n_pairs + 1
         pts = pts.contiguous()
-        assert pts.is_cuda and pts.dtype == torch.float32
-        _lib.check(_lib.load().mrs_gicp_batch_set_clouds(self._h, which, _lib.ptr(pts), int(pts.shape[1]),
-                                                         _lib.ptr(offs), _lib.current_stream(self.device)))
+        _lib.load().mrs_gicp_batch_set_clouds(self._h, which, pts, pts.shape[1], offs, _lib.current_stream(self.device))
         self._n[which] = offs
 
     def set_sources(self, clouds):
@@ -111,8 +106,7 @@ class GicpBatch:
     def _set_from(self, which, store, ids, store_which):
         ids = np.ascontiguousarray(ids, dtype=np.int32)
         assert ids.size == self.n_pairs
-        _lib.check(_lib.load().mrs_gicp_batch_set_clouds_from(self._h, which, store._h, int(store_which), _lib.ptr(ids),
-                                                              _lib.current_stream(self.device)))
+        _lib.load().mrs_gicp_batch_set_clouds_from(self._h, which, store._h, int(store_which), ids, _lib.current_stream(self.device))
         so = store._n[store_which]
         offs = np.zeros(self.n_pairs + 1, np.int64)
         offs[1:] = np.cumsum([so[i + 1] - so[i] for i in ids])
@@ -123,15 +117,14 @@ class GicpBatch:
         if want_knn:
             knn = torch.empty((int(self._n[which][-1]), self.params.k_correspondences), dtype=torch.int32,
                               device=f"cuda:{self.device}")
-        _lib.check(_lib.load().mrs_gicp_batch_compute_covariances(self._h, which, _lib.ptr(knn) if want_knn else None,
-                                                                  _lib.current_stream(self.device)))
+        _lib.load().mrs_gicp_batch_compute_covariances(self._h, which, knn, _lib.current_stream(self.device))
         return knn
 
     def covariances(self, which):
         """[N,3,3] float64 regularised covariances (host)."""
         n = int(self._n[which][-1])
         c6 = np.empty((n, 6), np.float64)
-        _lib.check(_lib.load().mrs_gicp_batch_get_covariances(self._h, which, _lib.ptr(c6)))
+        _lib.load().mrs_gicp_batch_get_covariances(self._h, which, c6)
         out = np.empty((n, 3, 3), np.float64)
         out[:, 0, 0], out[:, 0, 1], out[:, 0, 2] = c6[:, 0], c6[:, 1], c6[:, 2]
         out[:, 1, 0], out[:, 1, 1], out[:, 1, 2] = c6[:, 1], c6[:, 3], c6[:, 4]
@@ -148,11 +141,10 @@ class GicpBatch:
         conv = np.empty(P, np.int32)
         its = np.empty(P, np.int32)
         self.hessian = np.empty((P, 36), np.float64)
-        _lib.check(_lib.load().mrs_gicp_batch_align(self._h, _lib.ptr(g) if g is not None else None, _lib.ptr(T),
-                                                    _lib.ptr(conv), _lib.ptr(its), _lib.ptr(self.hessian),
-                                                    _lib.current_stream(self.device)))
-        self.nn_passes = float(_lib.load().mrs_gicp_batch_last_nn_passes(self._h))
-        self.searched_fraction = float(_lib.load().mrs_gicp_batch_last_searched_fraction(self._h))
+        lib = _lib.load()
+        lib.mrs_gicp_batch_align(self._h, g, T, conv, its, self.hessian, _lib.current_stream(self.device))
+        self.nn_passes = lib.mrs_gicp_batch_last_nn_passes(self._h)
+        self.searched_fraction = lib.mrs_gicp_batch_last_searched_fraction(self._h)
         return T.reshape(P, 4, 4), conv.astype(bool), its
 
     def linearize(self, poses, want_corr=False):
@@ -160,9 +152,7 @@ class GicpBatch:
         poses = np.ascontiguousarray(np.asarray(poses, dtype=np.float64).reshape(P, 16))
         H = np.empty((P, 36), np.float64); b = np.empty((P, 6), np.float64); e = np.empty(P, np.float64)
         corr = torch.empty(int(self._n[0][-1]), dtype=torch.int32, device=f"cuda:{self.device}") if want_corr else None
-        _lib.check(_lib.load().mrs_gicp_batch_linearize(self._h, _lib.ptr(poses), _lib.ptr(H), _lib.ptr(b), _lib.ptr(e),
-                                                        _lib.ptr(corr) if want_corr else None,
-                                                        _lib.current_stream(self.device)))
+        _lib.load().mrs_gicp_batch_linearize(self._h, poses, H, b, e, corr, _lib.current_stream(self.device))
         return e, H.reshape(P, 6, 6), b, (corr.cpu().numpy() if want_corr else None)
 
     def profile(self, poses, reps=3):
@@ -171,8 +161,7 @@ class GicpBatch:
         P = self.n_pairs
         poses = np.ascontiguousarray(np.asarray(poses, dtype=np.float64).reshape(P, 16))
         ms = np.zeros(8, np.float32); cnt = np.zeros(3, np.int64)
-        _lib.check(_lib.load().mrs_gicp_batch_profile(self._h, _lib.ptr(poses), int(reps), _lib.ptr(ms), _lib.ptr(cnt),
-                                                      _lib.current_stream(self.device)))
+        _lib.load().mrs_gicp_batch_profile(self._h, poses, int(reps), ms, cnt, _lib.current_stream(self.device))
         names = ("linearize", "linearize_error_only", "search_round3_all", "certify", "search_round4_all", "knn_select", "cov_from_knn",
                  "certify_plus_worklist_1mm")
         return {n: float(v) for n, v in zip(names, ms)}, {"source_points": int(cnt[0]), "correspondences": int(cnt[1]), "worklist_queries_1mm": int(cnt[2])}
@@ -181,6 +170,5 @@ class GicpBatch:
         P = self.n_pairs
         poses = np.ascontiguousarray(np.asarray(poses, dtype=np.float64).reshape(P, 16))
         out = np.empty(P, np.float64)
-        _lib.check(_lib.load().mrs_gicp_batch_fitness(self._h, _lib.ptr(poses), C.c_double(max_range), _lib.ptr(out),
-                                                      _lib.current_stream(self.device)))
+        _lib.load().mrs_gicp_batch_fitness(self._h, poses, max_range, out, _lib.current_stream(self.device))
         return out

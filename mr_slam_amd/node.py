@@ -28,19 +28,21 @@ FORM_HOST, FORM_DEVICE, FORM_DEVICE_SPEC = 0, 1, 2
 
 
 def _as_arg(x, dtype, shape_tail):
-    """descriptor -> (pointer, on_device flag, keep-alive object); accepts torch tensors (host / device) and numpy arrays"""
+    """descriptor -> contiguous tensor (host / device) or numpy array of `dtype`; accepts torch tensors and numpy arrays"""
     if isinstance(x, torch.Tensor):
         t = x.detach()
         if t.dtype != dtype:
             t = t.to(dtype)
         t = t.contiguous()
         assert tuple(t.shape[-len(shape_tail):]) == tuple(shape_tail), (tuple(t.shape), shape_tail)
-        if t.is_complex():
-            t = torch.view_as_real(t)
-        return C.c_void_p(t.data_ptr()), t.is_cuda, t
+        return t
     a = np.ascontiguousarray(x, dtype={torch.complex64: np.complex64, torch.float32: np.float32}[dtype])
     assert tuple(a.shape[-len(shape_tail):]) == tuple(shape_tail), (a.shape, shape_tail)
-    return C.c_void_p(a.ctypes.data), False, a
+    return a
+
+
+def _on_device(x):
+    return isinstance(x, torch.Tensor) and x.is_cuda
 
 
 class LoopDatabase:
@@ -57,8 +59,7 @@ class LoopDatabase:
         self.kind, self.device = kind, int(device)
         self.channels = 1 if kind == "ring" else int(channels or 6)
         self._h = C.c_void_p()
-        lib = _lib.load()
-        _lib.check(lib.mrs_loopdb_create(_lib.ctx(self.device), KIND[kind], self.channels, int(capacity), C.byref(self._h)))
+        _lib.load().mrs_loopdb_create(_lib.ctx(self.device), KIND[kind], self.channels, int(capacity), C.byref(self._h))
 
     def __del__(self):
         try:
@@ -69,35 +70,33 @@ class LoopDatabase:
 
     def __len__(self):
         n = C.c_int32(0)
-        _lib.check(_lib.load().mrs_loopdb_size(self._h, C.byref(n)))
+        _lib.load().mrs_loopdb_size(self._h, C.byref(n))
         return n.value
 
     def _descriptor(self, x):
-        """(pointer, form, keep-alive)"""
+        """(descriptor, form)"""
         C_ = self.channels
         is_spec = (isinstance(x, torch.Tensor) and x.is_cuda and x.is_complex() and tuple(x.shape[-2:]) == (61, 120))
         if is_spec:
-            p, _, keep = _as_arg(x, torch.complex64, (C_, 61, 120) if x.dim() >= 3 else (61, 120))
-            return p, FORM_DEVICE_SPEC, keep
+            return _as_arg(x, torch.complex64, (C_, 61, 120) if x.dim() >= 3 else (61, 120)), FORM_DEVICE_SPEC
         if self.kind == "ring":
-            p, dev, keep = _as_arg(x, torch.complex64, (120, 120))
+            t = _as_arg(x, torch.complex64, (120, 120))
         else:
-            p, dev, keep = _as_arg(x, torch.float32, (C_, 120, 120))
-        return p, (FORM_DEVICE if dev else FORM_HOST), keep
+            t = _as_arg(x, torch.float32, (C_, 120, 120))
+        return t, (FORM_DEVICE if _on_device(t) else FORM_HOST)
 
     def _stream(self, form):
         return _lib.current_stream(self.device) if form != FORM_HOST else None
 
     def append(self, descriptor):
-        p, form, keep = self._descriptor(descriptor)
-        _lib.check(_lib.load().mrs_loopdb_append(self._h, p, form, 1, self._stream(form)))
+        t, form = self._descriptor(descriptor)
+        _lib.load().mrs_loopdb_append(self._h, t, form, 1, self._stream(form))
 
     def extend_spectra(self, spectra):
         """`spectra`: device half spectra [n, C, 61, 120] (or [n, 61, 120] for RING) -- a batch producer's output, appended in one call"""
         assert spectra.is_cuda and spectra.dtype == torch.complex64 and spectra.is_contiguous()
         n = spectra.shape[0]
-        _lib.check(_lib.load().mrs_loopdb_append(self._h, C.c_void_p(torch.view_as_real(spectra).data_ptr()), FORM_DEVICE_SPEC, int(n),
-                                                 _lib.current_stream(self.device)))
+        _lib.load().mrs_loopdb_append(self._h, spectra, FORM_DEVICE_SPEC, n, _lib.current_stream(self.device))
 
     def query(self, descriptor, threshold, want_all=False):
         """-> (idxs int32[m], dists float32[m], angles int32[m]) with dist < threshold, in index order
@@ -105,7 +104,7 @@ class LoopDatabase:
         Thread-safe: the node's callbacks query one twin from concurrent rospy threads (callback1 and callback3 both score against TIRING2) and
         ctypes drops the GIL during the call, so every call owns its output arrays; the entries scored are the n the C side reports (an
         append from another thread between sizing the arrays and the sweep can neither overflow nor truncate them silently)."""
-        p, form, keep = self._descriptor(descriptor)
+        t, form = self._descriptor(descriptor)
         lib = _lib.load()
         cap = max(len(self), 1) + 64                       # room for entries another thread appends before the sweep runs
         while True:
@@ -113,9 +112,8 @@ class LoopDatabase:
             alld = np.empty(cap, np.float32) if want_all else None
             alla = np.empty(cap, np.int32) if want_all else None
             cnt, n = C.c_int32(0), C.c_int32(0)
-            _lib.check(lib.mrs_loopdb_query(self._h, p, form, C.c_float(threshold), int(cap), _lib.ptr(idx), _lib.ptr(dist), _lib.ptr(ang),
-                                            C.byref(cnt), int(cap) if want_all else 0, _lib.ptr(alld) if want_all else None,
-                                            _lib.ptr(alla) if want_all else None, C.byref(n), self._stream(form)))
+            lib.mrs_loopdb_query(self._h, t, form, threshold, cap, idx, dist, ang, C.byref(cnt), cap if want_all else 0, alld, alla,
+                                 C.byref(n), self._stream(form))
             if cnt.value <= cap and n.value <= cap:
                 break
             cap = max(cnt.value, n.value) + 64             # the list grew by more than the slack meanwhile: once more, with room
@@ -144,13 +142,12 @@ class LoopDatabase:
             t = q.to(torch.float32).contiguous()
             assert t.numel() == nq * self.channels * 120 * 120
             form = FORM_DEVICE if t.is_cuda else FORM_HOST
-        ptr = C.c_void_p((torch.view_as_real(t) if t.is_complex() else t).data_ptr())
         lib = _lib.load()
         cap = max(len(self), 1) + 64
         while True:
             alld, alla = np.empty((nq, cap), np.float32), np.empty((nq, cap), np.int32)
             n = C.c_int32(0)
-            _lib.check(lib.mrs_loopdb_query_multi(self._h, ptr, form, nq, int(cap), _lib.ptr(alld), _lib.ptr(alla), C.byref(n), self._stream(form)))
+            lib.mrs_loopdb_query_multi(self._h, t, form, nq, cap, alld, alla, C.byref(n), self._stream(form))
             if n.value <= cap:
                 break
             cap = n.value + 64
@@ -159,7 +156,7 @@ class LoopDatabase:
     def device_entries(self):
         """(device pointer, n, floats per entry) of the stored entries (tests)"""
         p, n, ef = C.c_void_p(), C.c_int32(0), C.c_int64(0)
-        _lib.check(_lib.load().mrs_loopdb_device_entries(self._h, C.byref(p), None, C.byref(n), C.byref(ef)))
+        _lib.load().mrs_loopdb_device_entries(self._h, C.byref(p), None, C.byref(n), C.byref(ef))
         return p.value, n.value, ef.value
 
 
@@ -170,29 +167,29 @@ class DiscoDatabase:
     def __init__(self, device=0, capacity=1024):
         self.device = int(device)
         self._h = C.c_void_p()
-        _lib.check(_lib.load().mrs_loopdb_create(_lib.ctx(self.device), KIND["disco"], 1, int(capacity), C.byref(self._h)))
+        _lib.load().mrs_loopdb_create(_lib.ctx(self.device), KIND["disco"], 1, int(capacity), C.byref(self._h))
 
     __del__ = LoopDatabase.__del__
     __len__ = LoopDatabase.__len__
 
     def _args(self, signature, spectrum):
-        ps, dev_s, k1 = _as_arg(torch.as_tensor(signature).reshape(-1), torch.float32, (1024,))
-        pf, dev_f, k2 = _as_arg(spectrum, torch.complex64, (40, 120))
-        if dev_s != dev_f:       # one side on the host: bring the signature (4 KB) where the spectrum is
-            ps, dev_s, k1 = _as_arg(k1.to(k2.device) if isinstance(k1, torch.Tensor) else torch.from_numpy(k1).to(k2.device), torch.float32, (1024,))
-        return ps, pf, int(dev_s), (k1, k2)
+        sig = _as_arg(torch.as_tensor(signature).reshape(-1), torch.float32, (1024,))
+        spec = _as_arg(spectrum, torch.complex64, (40, 120))
+        if _on_device(sig) != _on_device(spec):       # one side on the host: bring the signature (4 KB) where the spectrum is
+            sig = sig.to(spec.device)
+        return sig, spec, int(_on_device(spec))
 
     def append(self, signature, spectrum):
-        ps, pf, dev, keep = self._args(signature, spectrum)
-        _lib.check(_lib.load().mrs_loopdb_append_disco(self._h, ps, pf, dev, _lib.current_stream(self.device) if dev else None))
+        sig, spec, dev = self._args(signature, spectrum)
+        _lib.load().mrs_loopdb_append_disco(self._h, sig, spec, dev, _lib.current_stream(self.device) if dev else None)
 
     def query(self, signature, spectrum, num_sector=120):
         """-> (index, squared distance, yaw bin) of the nearest stored signature; index -1 for an empty database"""
-        ps, pf, dev, keep = self._args(signature, spectrum)
-        idx, d2, arg = C.c_int32(-1), C.c_float(0), C.c_int32(0)
-        _lib.check(_lib.load().mrs_loopdb_query_disco(self._h, ps, pf, dev, C.byref(idx), C.byref(d2), C.byref(arg),
-                                                      _lib.current_stream(self.device) if dev else None))
-        return idx.value, d2.value, arg.value % num_sector
+        sig, spec, dev = self._args(signature, spectrum)
+        idx, d2, arg = C.c_int32(-1), (C.c_float * 1)(), C.c_int32(0)
+        _lib.load().mrs_loopdb_query_disco(self._h, sig, spec, dev, C.byref(idx), d2, C.byref(arg),
+                                           _lib.current_stream(self.device) if dev else None)
+        return idx.value, d2[0], arg.value % num_sector
 
 
 class DescriptorList(list):

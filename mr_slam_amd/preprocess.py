@@ -11,14 +11,14 @@ from . import _lib
 def voxel_down_sample(points, voxel_size):
     """open3d voxel_down_sample (main_RING.py:257-259).  points: device tensor [n, s>=3] float32/float64.
     Returns a float64 device tensor [m,3] of voxel centroids (sorted by voxel index)."""
-    assert points.is_cuda and points.dtype in (torch.float32, torch.float64)
-    d = points.device.index or 0
+    assert points.dtype in (torch.float32, torch.float64)
+    d = _lib.device_of(points)
     p = points.contiguous()
     n = p.shape[0]
     out = torch.empty((n, 3), dtype=torch.float64, device=p.device)
     cnt = C.c_int32(0)
-    _lib.check(_lib.load().mrs_voxel_downsample(_lib.ctx(d), _lib.ptr(p), int(p.dtype == torch.float64), int(p.shape[1]),
-                                                n, C.c_double(voxel_size), _lib.ptr(out), C.byref(cnt), _lib.current_stream(d)))
+    _lib.load().mrs_voxel_downsample(_lib.ctx(d), p, p.dtype == torch.float64, p.shape[1], n, voxel_size, out, C.byref(cnt),
+                                     _lib.current_stream(d))
     return out[: cnt.value]
 
 
@@ -26,17 +26,16 @@ def voxel_down_sample_batch(points, raw_offsets, voxel_size):
     """voxel_down_sample for a batch of clouds in one set of launches (hash grid; each scan's voxels in order of first occurrence).
     points: device tensor [N, s>=3] float32/float64, raw_offsets: host int64 [B+1] starting at 0.
     Returns (centroids float64 device [M,3], offsets int64 device [B+1])."""
-    assert points.is_cuda and points.dtype in (torch.float32, torch.float64)
-    d = points.device.index or 0
+    assert points.dtype in (torch.float32, torch.float64)
+    d = _lib.device_of(points)
     p = points.contiguous()
     h_off = np.ascontiguousarray(raw_offsets, dtype=np.int64)
     d_off = torch.from_numpy(h_off).to(p.device)
     B = h_off.size - 1
     out = torch.empty((int(h_off[-1]), 3), dtype=torch.float64, device=p.device)
     offs = torch.empty(B + 1, dtype=torch.int64, device=p.device)
-    _lib.check(_lib.load().mrs_voxel_downsample_batch(_lib.ctx(d), _lib.ptr(p), int(p.dtype == torch.float64), int(p.shape[1]), _lib.ptr(d_off),
-                                                      _lib.ptr(h_off), B, C.c_double(voxel_size), _lib.ptr(out), _lib.ptr(offs),
-                                                      _lib.current_stream(d)))
+    _lib.load().mrs_voxel_downsample_batch(_lib.ctx(d), p, p.dtype == torch.float64, p.shape[1], d_off, h_off, B, voxel_size, out, offs,
+                                           _lib.current_stream(d))
     return out[: int(offs[-1])], offs
 
 
@@ -44,14 +43,14 @@ def approx_voxel_grid(points, leaf_size):
     """pcl::ApproximateVoxelGrid as pygicp.downsample(points, leaf) applies it (main_RING.py:84-85; row G1): points device
     tensor [n, s>=3] float32/float64 -> float64 device tensor [m,3] (float-precision centroids in the filter's flush
     order, bit-identical to the sequential filter)."""
-    assert points.is_cuda and points.dtype in (torch.float32, torch.float64)
-    d = points.device.index or 0
+    assert points.dtype in (torch.float32, torch.float64)
+    d = _lib.device_of(points)
     p = points.contiguous()
     n = p.shape[0]
     out = torch.empty((n, 3), dtype=torch.float64, device=p.device)
     cnt = C.c_int32(0)
-    _lib.check(_lib.load().mrs_voxel_downsample_approx(_lib.ctx(d), _lib.ptr(p), int(p.dtype == torch.float64), int(p.shape[1]),
-                                                       n, C.c_double(leaf_size), _lib.ptr(out), C.byref(cnt), _lib.current_stream(d)))
+    _lib.load().mrs_voxel_downsample_approx(_lib.ctx(d), p, p.dtype == torch.float64, p.shape[1], n, leaf_size, out, C.byref(cnt),
+                                            _lib.current_stream(d))
     return out[: cnt.value]
 
 
@@ -59,17 +58,15 @@ def load_pc_infer_batch(points, raw_offsets):
     """util.py:91-112 for a batch: points device tensor [N, s>=3] (float32/float64) of raw clouds,
     raw_offsets host int64 [B+1].  Returns (xyz_soa float32 device [3*N] (upper bound, ragged SoA),
     offsets int64 device [B+1]) ready for bev.cart_bev / polar_bev."""
-    assert points.is_cuda and points.dtype in (torch.float32, torch.float64)
-    d = points.device.index or 0
+    assert points.dtype in (torch.float32, torch.float64)
+    d = _lib.device_of(points)
     p = points.contiguous()
     h_off = np.ascontiguousarray(raw_offsets, dtype=np.int64)
     d_off = torch.from_numpy(h_off).to(p.device)
     B = h_off.size - 1
     out = torch.empty(3 * max(1, int(h_off[-1])), dtype=torch.float32, device=p.device)
     offs = torch.empty(B + 1, dtype=torch.int64, device=p.device)
-    _lib.check(_lib.load().mrs_crop_scale_batch(_lib.ctx(d), _lib.ptr(p), int(p.dtype == torch.float64), int(p.shape[1]),
-                                                _lib.ptr(d_off), _lib.ptr(h_off), B, _lib.ptr(out), _lib.ptr(offs),
-                                                _lib.current_stream(d)))
+    _lib.load().mrs_crop_scale_batch(_lib.ctx(d), p, p.dtype == torch.float64, p.shape[1], d_off, h_off, B, out, offs, _lib.current_stream(d))
     return out, offs
 
 

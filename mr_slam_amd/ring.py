@@ -19,12 +19,6 @@ MAX_LENGTH = 1
 MAX_HEIGHT = 1
 
 
-def _dev(t):
-    if not t.is_cuda:
-        raise _lib.MrsError("expected a device tensor (no CPU fallback)")
-    return t.device.index or 0
-
-
 class RadonPlan:
     """Parallel-beam geometry bound to one device (C ABI mrs_radon_plan_*)."""
 
@@ -33,8 +27,7 @@ class RadonPlan:
         self.n_angles, self.det, self.h, self.w = int(ang.size), int(det_count), int(height), int(width)
         self.device = device
         self._h = C.c_void_p()
-        _lib.check(_lib.load().mrs_radon_plan_create(_lib.ctx(device), _lib.ptr(ang), self.n_angles, self.det,
-                                                     C.c_float(det_spacing), self.h, self.w, C.byref(self._h)))
+        _lib.load().mrs_radon_plan_create(_lib.ctx(device), ang, self.n_angles, self.det, det_spacing, self.h, self.w, C.byref(self._h))
 
     def __del__(self):
         try:
@@ -47,25 +40,23 @@ class RadonPlan:
         """Sinograms whose fused normalisation met std == 0 (blank / constant image) since the last reset: the reference
         raises there (fn.normalize, util.py:197), the kernel writes zeros and counts."""
         n = C.c_int32(0)
-        _lib.check(_lib.load().mrs_radon_plan_degenerate_count(self._h, int(bool(reset)), C.byref(n)))
+        _lib.load().mrs_radon_plan_degenerate_count(self._h, bool(reset), C.byref(n))
         return n.value
 
     OPT_FUSED_STAGGER_US, OPT_FUSED_PREFETCH, OPT_FUSED_GRID, OPT_FUSED_VARIANT, OPT_FUSED_SKIP = 1, 2, 3, 4, 5
 
     def set_option(self, option, value):
         """Tuning knobs of the fused descriptor kernel (mrs_radon_plan_set_option); results do not depend on them."""
-        _lib.check(_lib.load().mrs_radon_plan_set_option(self._h, int(option), int(value)))
+        _lib.load().mrs_radon_plan_set_option(self._h, int(option), int(value))
 
     def forward(self, img, raw=True, normalized=False):
         """img float32 [B,H,W] (device, contiguous) -> (sino [B,A,D] | None, sino_norm | None)."""
-        d = _dev(img)
+        d = _lib.device_of(img)
         assert img.dtype == torch.float32 and img.is_contiguous() and img.shape[-2:] == (self.h, self.w)
         B = img.numel() // (self.h * self.w)
         sino = torch.empty((B, self.n_angles, self.det), dtype=torch.float32, device=img.device) if raw else None
         norm = torch.empty((B, self.n_angles, self.det), dtype=torch.float32, device=img.device) if normalized else None
-        _lib.check(_lib.load().mrs_radon_forward(self._h, _lib.ptr(img), B,
-                                                 _lib.ptr(sino) if raw else None,
-                                                 _lib.ptr(norm) if normalized else None, _lib.current_stream(d)))
+        _lib.load().mrs_radon_forward(self._h, img, B, sino, norm, _lib.current_stream(d))
         return sino, norm
 
 
@@ -88,34 +79,31 @@ def ring_plan(device=0, num_ring=NUM_RING, num_sector=NUM_SECTOR):
 def normalize(x, group_len=None):
     """fn.normalize(t, mean=t.mean(), std=t.std()) per group of `group_len` floats
     (default: per leading-dim entry)."""
-    d = _dev(x)
+    d = _lib.device_of(x)
     x = x.contiguous()
     gl = int(group_len or x[0].numel())
     out = torch.empty_like(x)
-    _lib.check(_lib.load().mrs_normalize_groups(_lib.ctx(d), _lib.ptr(x), _lib.ptr(out), x.numel() // gl, gl,
-                                                _lib.current_stream(d)))
+    _lib.load().mrs_normalize_groups(_lib.ctx(d), x, out, x.numel() // gl, gl, _lib.current_stream(d))
     return out
 
 
 def fft_angle(x):
     """torch.fft.fft2(x, dim=-2, norm='ortho') of real [..., A, D] (util.py:198) -> complex64."""
-    d = _dev(x)
+    d = _lib.device_of(x)
     x = x.contiguous()
     A, D = x.shape[-2:]
     out = torch.empty(x.shape + (2,), dtype=torch.float32, device=x.device)
-    _lib.check(_lib.load().mrs_fft_angle_r2c(_lib.ctx(d), _lib.ptr(x), x.numel() // (A * D), A, D, _lib.ptr(out),
-                                             _lib.current_stream(d)))
+    _lib.load().mrs_fft_angle_r2c(_lib.ctx(d), x, x.numel() // (A * D), A, D, out, _lib.current_stream(d))
     return torch.view_as_complex(out)
 
 
 def forward_row_fft(x):
     """util.py:295-300 (magnitude only): |fft along the detector axis|, ortho."""
-    d = _dev(x)
+    d = _lib.device_of(x)
     x = x.contiguous()
     A, D = x.shape[-2:]
     out = torch.empty_like(x)
-    _lib.check(_lib.load().mrs_fft_row_magnitude(_lib.ctx(d), _lib.ptr(x), x.numel() // (A * D), A, D,
-                                                 _lib.ptr(out), _lib.current_stream(d)))
+    _lib.load().mrs_fft_row_magnitude(_lib.ctx(d), x, x.numel() // (A * D), A, D, out, _lib.current_stream(d))
     return out
 
 
@@ -129,7 +117,7 @@ def ring_descriptors(xyz, offsets, num_ring=NUM_RING, num_sector=NUM_SECTOR, wan
     """Batched generate_RING front half (util.py:174-197): Cartesian BEV -> Radon -> normalise.
     Returns (bev | None, sinogram [B,A,D], normalised sinogram [B,A,D]).  fused: True / False picks the single-launch
     kernel / the two-call sequence (same bits), None decides by FUSED_MIN_BATCH."""
-    d = _dev(xyz)
+    d = _lib.device_of(xyz)
     auto = fused is None
     if auto:
         fused = FUSED_MIN_BATCH is not None and offsets.numel() - 1 >= FUSED_MIN_BATCH
@@ -151,7 +139,7 @@ def ring_descriptors_fused(xyz, offsets, num_ring=NUM_RING, num_sector=NUM_SECTO
     """The same in ONE launch (C ABI mrs_ring_descriptors_batch): a persistent workgroup per compute unit rasterises two scans
     straight into the Radon kernel's LDS tile and marches the rays; the BEV image reaches HBM only if want_bev.
     Bit-identical to ring_descriptors(fused=False)."""
-    d = _dev(xyz)
+    d = _lib.device_of(xyz)
     assert xyz.dtype == torch.float32 and xyz.is_contiguous() and offsets.dtype == torch.int64
     B = offsets.numel() - 1
     plan = ring_plan(d, num_ring, num_sector)
@@ -163,9 +151,7 @@ def ring_descriptors_fused(xyz, offsets, num_ring=NUM_RING, num_sector=NUM_SECTO
         norm = out_norm if out_norm is not None else torch.empty((B, plan.n_angles, plan.det), dtype=torch.float32, device=dev)
         assert norm.is_contiguous() and norm.numel() == B * plan.n_angles * plan.det
     cfg = _lib.BevCfg(MAX_LENGTH, MAX_HEIGHT, num_ring, num_sector, 1, 1)
-    _lib.check(_lib.load().mrs_ring_descriptors_batch(plan._h, _lib.ptr(xyz), _lib.ptr(offsets), B, C.byref(cfg),
-                                                      _lib.ptr(img) if want_bev else None, _lib.ptr(sino) if raw else None,
-                                                      _lib.ptr(norm) if normalized else None, _lib.current_stream(d)))
+    _lib.load().mrs_ring_descriptors_batch(plan._h, xyz, offsets, B, C.byref(cfg), img, sino, norm, _lib.current_stream(d))
     return img, sino, norm
 
 
@@ -263,7 +249,7 @@ def generate_RING(pc, device="cuda:0"):
 def corr_sweep(query, db, want_corr=False):
     """C1/C2 sweep: query [Q,C,A,D], db [N,C,A,D] normalised real descriptors (device).
     Returns (dist [Q,N] float32, angle [Q,N] int32[, corr [Q,N,A]])."""
-    d = _dev(query)
+    d = _lib.device_of(query)
     query, db = query.contiguous(), db.contiguous()
     Q, Cc, A, D = query.shape
     N = db.shape[0]
@@ -271,22 +257,19 @@ def corr_sweep(query, db, want_corr=False):
     dist = torch.empty((Q, N), dtype=torch.float32, device=query.device)
     ang = torch.empty((Q, N), dtype=torch.int32, device=query.device)
     corr = torch.empty((Q, N, A), dtype=torch.float32, device=query.device) if want_corr else None
-    _lib.check(_lib.load().mrs_ring_corr_sweep(_lib.ctx(d), _lib.ptr(query), Q, _lib.ptr(db), N, Cc, A, D,
-                                               _lib.ptr(dist), _lib.ptr(ang),
-                                               _lib.ptr(corr) if want_corr else None, _lib.current_stream(d)))
+    _lib.load().mrs_ring_corr_sweep(_lib.ctx(d), query, Q, db, N, Cc, A, D, dist, ang, corr, _lib.current_stream(d))
     return (dist, ang, corr) if want_corr else (dist, ang)
 
 
 def corr_pairs(a, b, out=None):
     """Pairwise C1/C2: a, b [P,C,A,D] normalised real descriptors -> (dist [P], angle [P])."""
-    d = _dev(a)
+    d = _lib.device_of(a)
     a, b = a.contiguous(), b.contiguous()
     P, Cc, A, D = a.shape
     assert b.shape == a.shape
     dist, ang = out if out is not None else (torch.empty(P, dtype=torch.float32, device=a.device),
                                              torch.empty(P, dtype=torch.int32, device=a.device))
-    _lib.check(_lib.load().mrs_ring_corr_pairs(_lib.ctx(d), _lib.ptr(a), _lib.ptr(b), P, Cc, A, D, _lib.ptr(dist),
-                                               _lib.ptr(ang), None, _lib.current_stream(d)))
+    _lib.load().mrs_ring_corr_pairs(_lib.ctx(d), a, b, P, Cc, A, D, dist, ang, None, _lib.current_stream(d))
     return dist, ang
 
 
@@ -324,12 +307,10 @@ def fast_corr(a, b, device="cuda:0", want_corr=False):
         return h[0], h[1:2].view(np.int32)[0]
     fa, fb = _full_of(ta), _full_of(tb)
     Cc, A, D = fa.shape
-    d = _dev(fa)
+    d = _lib.device_of(fa)
     corr = torch.empty(A, dtype=torch.float32, device=dv) if want_corr else None
-    _lib.check(_lib.load().mrs_ring_corr_spectra(_lib.ctx(d), _lib.ptr(torch.view_as_real(fa)),
-                                                 _lib.ptr(torch.view_as_real(fb)), 1, Cc, A, D, C.c_void_p(out.data_ptr()),
-                                                 C.c_void_p(out.data_ptr() + 4), _lib.ptr(corr) if want_corr else None,
-                                                 _lib.current_stream(d)))
+    _lib.load().mrs_ring_corr_spectra(_lib.ctx(d), fa, fb, 1, Cc, A, D, C.c_void_p(out.data_ptr()), C.c_void_p(out.data_ptr() + 4), corr,
+                                      _lib.current_stream(d))
     h = out.cpu().numpy()
     res = (h[0], h[1:2].view(np.int32)[0])
     return res + (corr.cpu().numpy(),) if want_corr else res
@@ -377,14 +358,12 @@ def solve_translation(query, positive, rot_angle, device="cuda:0", want_shifts=F
     q = torch.as_tensor(query, dtype=torch.float32).to(device).contiguous()
     p = torch.as_tensor(positive, dtype=torch.float32).to(device).contiguous()
     Cc, H, W = q.shape
-    d = _dev(q)
+    d = _lib.device_of(q)
     angles = torch.from_numpy(np.linspace(0, 2 * np.pi, H).astype(np.float32)).to(q.device)
     rot = torch.tensor([float(rot_angle)], dtype=torch.float32, device=q.device)
     res = torch.empty(3, dtype=torch.float32, device=q.device)
     sh = torch.empty(H, dtype=torch.float32, device=q.device) if (want_shifts or not least_squares) else None
-    _lib.check(_lib.load().mrs_ring_solve_translation(_lib.ctx(d), _lib.ptr(q), _lib.ptr(p), 1, Cc, H, W,
-                                                      _lib.ptr(angles), _lib.ptr(rot), _lib.ptr(res),
-                                                      _lib.ptr(sh) if sh is not None else None, _lib.current_stream(d)))
+    _lib.load().mrs_ring_solve_translation(_lib.ctx(d), q, p, 1, Cc, H, W, angles, rot, res, sh, _lib.current_stream(d))
     if not least_squares:
         b = sh.cpu()
         ang = torch.FloatTensor(np.linspace(0, 2 * np.pi, H).astype(np.float32)) + rot_angle
@@ -405,7 +384,7 @@ def solve_translation(query, positive, rot_angle, device="cuda:0", want_shifts=F
 def rotate_bev(bev_img, angle):
     """util.py:67-70: rotate a [C,H,W] (or [N,C,H,W] with one angle per N) BEV by `angle` radians
     (torchvision rotate defaults: nearest, about the centre, zero fill)."""
-    d = _dev(bev_img)
+    d = _lib.device_of(bev_img)
     x = bev_img.contiguous()
     single = x.dim() == 3
     if single:
@@ -414,8 +393,7 @@ def rotate_bev(bev_img, angle):
     ang = torch.as_tensor(np.atleast_1d(np.asarray(angle, dtype=np.float64)) * 180.0 / np.pi, dtype=torch.float32).to(x.device)
     assert ang.numel() == N
     out = torch.empty_like(x)
-    _lib.check(_lib.load().mrs_rotate_nearest(_lib.ctx(d), _lib.ptr(x), N * Cc, Cc, H, W, _lib.ptr(ang), _lib.ptr(out),
-                                              _lib.current_stream(d)))
+    _lib.load().mrs_rotate_nearest(_lib.ctx(d), x, N * Cc, Cc, H, W, ang, out, _lib.current_stream(d))
     return out[0] if single else out
 
 
@@ -425,15 +403,13 @@ def solve_translation_bev(a, b, want_corr=False, num_ring=NUM_RING, num_sector=N
     single = a.dim() == 3
     if single:
         a, b = a[None], b[None]
-    d = _dev(a)
+    d = _lib.device_of(a)
     a, b = a.contiguous(), b.contiguous()
     P, Cc, H, W = a.shape
     arg = torch.empty(P, dtype=torch.int32, device=a.device)
     mx = torch.empty(P, dtype=torch.float32, device=a.device)
     corr = torch.empty((P, H, W), dtype=torch.float32, device=a.device) if want_corr else None
-    _lib.check(_lib.load().mrs_bev_translation(_lib.ctx(d), _lib.ptr(a), _lib.ptr(b), P, Cc, H, W, _lib.ptr(arg),
-                                               _lib.ptr(mx), _lib.ptr(corr) if want_corr else None,
-                                               _lib.current_stream(d)))
+    _lib.load().mrs_bev_translation(_lib.ctx(d), a, b, P, Cc, H, W, arg, mx, corr, _lib.current_stream(d))
     arg = arg.cpu().numpy()
     idx_x, idx_y = arg // W, arg % W
     x = idx_x - num_sector // 2
@@ -449,7 +425,7 @@ def ringpp_descriptors(points, offsets, k=30, num_ring=NUM_RING, num_sector=NUM_
     |FFT along the detector axis|.  points: float32 device tensor [N, s>=3] of pre-processed clouds,
     offsets: host int64 [B+1].  Returns (bev [B,6,R,S], ring [B,6,A,D], tiring [B,6,A,D])."""
     from . import pointfeat
-    d = _dev(points)
+    d = _lib.device_of(points)
     planes = pointfeat.point_features(points, offsets, k, want=("planes",))["planes"]
     offs_dev = torch.as_tensor(np.asarray(offsets, dtype=np.int64)).to(points.device)
     fb = bev.feat_bev(planes, offs_dev, 9, MAX_LENGTH, MAX_HEIGHT, num_ring, num_sector, 1, layout=OUT_COMPACT)
@@ -473,34 +449,33 @@ def generate_RINGplusplus(pc, device="cuda:0"):
 def half_spectrum(norm):
     """Half TIRING (first 61 angle-frequency rows, ortho) of normalised sinograms [..., 120, 120]:
     the database format of the FFT-domain sweep."""
-    d = _dev(norm)
+    d = _lib.device_of(norm)
     x = norm.contiguous()
     A, D = x.shape[-2:]
     n = x.numel() // (A * D)
     out = torch.empty(x.shape[:-2] + (A // 2 + 1, D, 2), dtype=torch.float32, device=x.device)
-    _lib.check(_lib.load().mrs_ring_half_spectrum(_lib.ctx(d), _lib.ptr(x), n, A, D, _lib.ptr(out), _lib.current_stream(d)))
+    _lib.load().mrs_ring_half_spectrum(_lib.ctx(d), x, n, A, D, out, _lib.current_stream(d))
     return torch.view_as_complex(out)
 
 
 def half_spectrum_f16(norm, want_f32=True):
     """half_spectrum plus its fp16 replica [..., 61, 120, 2] float16 (the multi-GPU exchange format).
     Returns (spec complex64 | None, spec16 float16)."""
-    d = _dev(norm)
+    d = _lib.device_of(norm)
     x = norm.contiguous()
     A, D = x.shape[-2:]
     n = x.numel() // (A * D)
     shape = x.shape[:-2] + (A // 2 + 1, D, 2)
     out = torch.empty(shape, dtype=torch.float32, device=x.device) if want_f32 else None
     out16 = torch.empty(shape, dtype=torch.float16, device=x.device)
-    _lib.check(_lib.load().mrs_ring_half_spectrum_f16(_lib.ctx(d), _lib.ptr(x), n, A, D, _lib.ptr(out) if want_f32 else None,
-                                                      _lib.ptr(out16), _lib.current_stream(d)))
+    _lib.load().mrs_ring_half_spectrum_f16(_lib.ctx(d), x, n, A, D, out, out16, _lib.current_stream(d))
     return (torch.view_as_complex(out) if want_f32 else None), out16
 
 
 def spectrum_corr_pairs(norm, cand_spec, want_f32=True, want_f16=False, out=None):
     """half_spectrum(norm) and corr_pairs_fft(that, cand_spec) in one launch.  norm float32 [P,120,120], cand_spec
     complex64 [P,61,120].  Returns (spec | None, spec16 | None, dist [P], angle [P])."""
-    d = _dev(norm)
+    d = _lib.device_of(norm)
     x, c = norm.contiguous(), cand_spec.contiguous()
     P = x.shape[0]
     assert x.shape[-2:] == (120, 120) and c.shape == (P, 61, 120)
@@ -508,9 +483,7 @@ def spectrum_corr_pairs(norm, cand_spec, want_f32=True, want_f16=False, out=None
     spec16 = torch.empty((P, 61, 120, 2), dtype=torch.float16, device=x.device) if want_f16 else None
     dist, ang = out if out is not None else (torch.empty(P, dtype=torch.float32, device=x.device),
                                              torch.empty(P, dtype=torch.int32, device=x.device))
-    _lib.check(_lib.load().mrs_ring_spectrum_corr_pairs(_lib.ctx(d), _lib.ptr(x), _lib.ptr(torch.view_as_real(c)), P, 120, 120,
-                                                        _lib.ptr(spec) if want_f32 else None, _lib.ptr(spec16) if want_f16 else None,
-                                                        _lib.ptr(dist), _lib.ptr(ang), _lib.current_stream(d)))
+    _lib.load().mrs_ring_spectrum_corr_pairs(_lib.ctx(d), x, c, P, 120, 120, spec, spec16, dist, ang, _lib.current_stream(d))
     return (torch.view_as_complex(spec) if want_f32 else None), spec16, dist, ang
 
 
@@ -518,31 +491,29 @@ def spectrum_corr_pairs_db(norm, db_spec, cand_index, want_f32=True, want_f16=Fa
     """spectrum_corr_pairs with the candidate of pair i = row cand_index[i] (int32 device tensor) of a database of half
     spectra: complex64 [N,61,120] or the fp16 replica format [N,61,120,2] float16.  spec_out (optional): complex64
     [P,61,120] tensor that receives the new half spectra (e.g. the database slot they belong to)."""
-    d = _dev(norm)
+    d = _lib.device_of(norm)
     x, db, idx = norm.contiguous(), db_spec.contiguous(), cand_index.contiguous()
     P = x.shape[0]
-    assert x.shape[-2:] == (120, 120) and idx.dtype == torch.int32 and idx.numel() == P
+    assert x.shape[-2:] == (120, 120) and idx.numel() == P
     f16 = db.dtype == torch.float16
     assert (f16 and db.shape[1:] == (61, 120, 2)) or (db.dtype == torch.complex64 and db.shape[1:] == (61, 120))
     if spec_out is not None:
         assert spec_out.dtype == torch.complex64 and spec_out.shape == (P, 61, 120) and spec_out.is_contiguous()
-        spec, want_f32 = torch.view_as_real(spec_out), True
+        spec = spec_out
     else:
-        spec = torch.empty((P, 61, 120, 2), dtype=torch.float32, device=x.device) if want_f32 else None
+        spec = torch.empty((P, 61, 120), dtype=torch.complex64, device=x.device) if want_f32 else None
     spec16 = torch.empty((P, 61, 120, 2), dtype=torch.float16, device=x.device) if want_f16 else None
     dist, ang = out if out is not None else (torch.empty(P, dtype=torch.float32, device=x.device),
                                              torch.empty(P, dtype=torch.int32, device=x.device))
-    _lib.check(_lib.load().mrs_ring_spectrum_corr_pairs_db(_lib.ctx(d), _lib.ptr(x), _lib.ptr(db if f16 else torch.view_as_real(db)),
-                                                           int(f16), int(db.shape[0]), _lib.ptr(idx), P, 120, 120,
-                                                           _lib.ptr(spec) if want_f32 else None, _lib.ptr(spec16) if want_f16 else None,
-                                                           _lib.ptr(dist), _lib.ptr(ang), _lib.current_stream(d)))
-    return (torch.view_as_complex(spec) if want_f32 else None), spec16, dist, ang
+    _lib.load().mrs_ring_spectrum_corr_pairs_db(_lib.ctx(d), x, db, f16, db.shape[0], idx, P, 120, 120, spec, spec16, dist, ang,
+                                                _lib.current_stream(d))
+    return spec, spec16, dist, ang
 
 
 def corr_sweep_fft(query_spec, db_spec, want_corr=False):
     """C1 sweep on half spectra: query_spec [Q,61,120] complex64, db_spec [N,61,120] complex64 or its fp16
     replica [N,61,120,2] float16 (device)."""
-    d = _dev(query_spec)
+    d = _lib.device_of(query_spec)
     q, db = query_spec.contiguous(), db_spec.contiguous()
     Q, N = q.shape[0], db.shape[0]
     dist = torch.empty((Q, N), dtype=torch.float32, device=q.device)
@@ -550,19 +521,13 @@ def corr_sweep_fft(query_spec, db_spec, want_corr=False):
     corr = torch.empty((Q, N, 120), dtype=torch.float32, device=q.device) if want_corr else None
     if db.dtype == torch.float16:
         assert db.shape[1:] == (61, 120, 2)
-        fn, dbp = _lib.load().mrs_ring_corr_fft_sweep_f16, _lib.ptr(db)
+        _lib.load().mrs_ring_corr_fft_sweep_f16(_lib.ctx(d), q, Q, db, N, dist, ang, corr, _lib.current_stream(d))
     elif db.dim() == 4:        # RING++: [N, C, 61, 120]
         assert db.dtype == torch.complex64 and q.dim() == 4 and q.shape[1] == db.shape[1]
-        _lib.check(_lib.load().mrs_ring_corr_fft_sweep_mc(_lib.ctx(d), _lib.ptr(torch.view_as_real(q)), Q,
-                                                          _lib.ptr(torch.view_as_real(db)), N, int(db.shape[1]), _lib.ptr(dist),
-                                                          _lib.ptr(ang), _lib.ptr(corr) if want_corr else None,
-                                                          _lib.current_stream(d)))
-        return (dist, ang, corr) if want_corr else (dist, ang)
+        _lib.load().mrs_ring_corr_fft_sweep_mc(_lib.ctx(d), q, Q, db, N, db.shape[1], dist, ang, corr, _lib.current_stream(d))
     else:
         assert db.dtype == torch.complex64
-        fn, dbp = _lib.load().mrs_ring_corr_fft_sweep, _lib.ptr(torch.view_as_real(db))
-    _lib.check(fn(_lib.ctx(d), _lib.ptr(torch.view_as_real(q)), Q, dbp, N, _lib.ptr(dist), _lib.ptr(ang),
-                  _lib.ptr(corr) if want_corr else None, _lib.current_stream(d)))
+        _lib.load().mrs_ring_corr_fft_sweep(_lib.ctx(d), q, Q, db, N, dist, ang, corr, _lib.current_stream(d))
     return (dist, ang, corr) if want_corr else (dist, ang)
 
 
@@ -572,20 +537,20 @@ TILED_ENTRY_FLOATS = 58624 // 4     # MRS_RING_TILED_ENTRY_BYTES: one DMA-tiled 
 def spec_to_tiled(spec):
     """[n,61,120] (RING) or [n,C,61,120] (RING++) complex64 half spectra -> the DMA-tiled database format of the one-query sweep: float32
     [n + 1, C * 14656], n entries of C planes of 58 624 B and one entry of zero slack behind them (include/mrslam_hip.h: mrs_ring_spec_to_tiled)."""
-    d = _dev(spec)
+    d = _lib.device_of(spec)
     x = spec.contiguous()
     assert x.dtype == torch.complex64 and x.shape[-2:] == (61, 120) and x.dim() in (3, 4)
     n = x.shape[0]
     planes = x.numel() // (61 * 120)
     out = torch.zeros((n + 1, (planes // n) * TILED_ENTRY_FLOATS), dtype=torch.float32, device=x.device)
-    _lib.check(_lib.load().mrs_ring_spec_to_tiled(_lib.ctx(d), _lib.ptr(torch.view_as_real(x)), planes, _lib.ptr(out), _lib.current_stream(d)))
+    _lib.load().mrs_ring_spec_to_tiled(_lib.ctx(d), x, planes, out, _lib.current_stream(d))
     return out
 
 
 def corr_sweep_fft_tiled(query_spec, tiled, n_db=None):
     """One query ([C,61,120] / [1,C,61,120] / [61,120] complex64, row layout) against a DMA-tiled database (spec_to_tiled): (dist [n], angle [n]),
     bit-identical to corr_sweep_fft(query, db)[...][0]."""
-    d = _dev(query_spec)
+    d = _lib.device_of(query_spec)
     q = query_spec.contiguous()
     channels = tiled.shape[1] // TILED_ENTRY_FLOATS
     assert q.dtype == torch.complex64 and q.numel() == channels * 61 * 120 and tiled.dtype == torch.float32 and tiled.is_contiguous()
@@ -593,15 +558,14 @@ def corr_sweep_fft_tiled(query_spec, tiled, n_db=None):
     assert 0 < n < tiled.shape[0], "the tiled array needs one entry of slack behind the last one"
     dist = torch.empty(n, dtype=torch.float32, device=q.device)
     ang = torch.empty(n, dtype=torch.int32, device=q.device)
-    _lib.check(_lib.load().mrs_ring_corr_fft_sweep_tiled(_lib.ctx(d), _lib.ptr(torch.view_as_real(q)), _lib.ptr(tiled), n, int(channels), _lib.ptr(dist), _lib.ptr(ang),
-                                                         _lib.current_stream(d)))
+    _lib.load().mrs_ring_corr_fft_sweep_tiled(_lib.ctx(d), q, tiled, n, channels, dist, ang, _lib.current_stream(d))
     return dist, ang
 
 
 def corr_sweep_fft_tiled_q(query_specs, tiled, n_db=None):
     """Q queries ([Q,C,61,120] / [Q,61,120] complex64, row layout) against a DMA-tiled database in one call (mrs_ring_corr_fft_sweep_tiled_q: the
     one-query LDS-DMA pipeline, the queries' workgroups grouped per XCD): (dist [Q,n], angle [Q,n]), bit-identical to corr_sweep_fft(queries, db)."""
-    d = _dev(query_specs)
+    d = _lib.device_of(query_specs)
     q = query_specs.contiguous()
     channels = tiled.shape[1] // TILED_ENTRY_FLOATS
     assert q.dtype == torch.complex64 and q.numel() % (channels * 61 * 120) == 0 and tiled.dtype == torch.float32 and tiled.is_contiguous()
@@ -610,8 +574,7 @@ def corr_sweep_fft_tiled_q(query_specs, tiled, n_db=None):
     assert 0 < n < tiled.shape[0], "the tiled array needs one entry of slack behind the last one"
     dist = torch.empty((nq, n), dtype=torch.float32, device=q.device)
     ang = torch.empty((nq, n), dtype=torch.int32, device=q.device)
-    _lib.check(_lib.load().mrs_ring_corr_fft_sweep_tiled_q(_lib.ctx(d), _lib.ptr(torch.view_as_real(q)), int(nq), _lib.ptr(tiled), n, int(channels),
-                                                           _lib.ptr(dist), _lib.ptr(ang), _lib.current_stream(d)))
+    _lib.load().mrs_ring_corr_fft_sweep_tiled_q(_lib.ctx(d), q, nq, tiled, n, channels, dist, ang, _lib.current_stream(d))
     return dist, ang
 
 
@@ -619,7 +582,7 @@ def corr_sweep_fft_blocks(spec_pool, query_rows, db_first, n_db, out=None, check
     """Several C1 sweeps in one launch: query q = entry query_rows[q] of spec_pool ([E,61,120] complex64) against the n_db entries that start
     at entry db_first[q] (int64 device tensors).  Returns (dist [Q,n_db], angle [Q,n_db]); bit-identical to corr_sweep_fft per query.
     The kernel trusts the indices (they live on the device): check=True verifies them against the pool first (one host synchronisation)."""
-    d = _dev(spec_pool)
+    d = _lib.device_of(spec_pool)
     if check:
         E = spec_pool.shape[0]
         assert int(query_rows.min()) >= 0 and int(query_rows.max()) < E and int(db_first.min()) >= 0 and int(db_first.max()) + int(n_db) <= E, \
@@ -630,25 +593,20 @@ def corr_sweep_fft_blocks(spec_pool, query_rows, db_first, n_db, out=None, check
     Q = qr.numel()
     dist, ang = out if out is not None else (torch.empty((Q, n_db), dtype=torch.float32, device=spec_pool.device),
                                              torch.empty((Q, n_db), dtype=torch.int32, device=spec_pool.device))
-    _lib.check(_lib.load().mrs_ring_corr_fft_sweep_blocks(_lib.ctx(d), _lib.ptr(torch.view_as_real(spec_pool)), _lib.ptr(qr), Q, _lib.ptr(df), int(n_db),
-                                                          _lib.ptr(dist), _lib.ptr(ang), _lib.current_stream(d)))
+    _lib.load().mrs_ring_corr_fft_sweep_blocks(_lib.ctx(d), spec_pool, qr, Q, df, int(n_db), dist, ang, _lib.current_stream(d))
     return dist, ang
 
 
 def corr_pairs_fft(a_spec, b_spec, out=None):
     """Pairwise C1/C2 on half spectra [P,61,120] (or RING++ [P,C,61,120]) complex64 -> (dist [P], angle [P])."""
-    d = _dev(a_spec)
+    d = _lib.device_of(a_spec)
     a, b = a_spec.contiguous(), b_spec.contiguous()
     P = a.shape[0]
     dist, ang = out if out is not None else (torch.empty(P, dtype=torch.float32, device=a.device),
                                              torch.empty(P, dtype=torch.int32, device=a.device))
     if a.dim() == 4:
         assert a.shape == b.shape
-        _lib.check(_lib.load().mrs_ring_corr_fft_pairs_mc(_lib.ctx(d), _lib.ptr(torch.view_as_real(a)),
-                                                          _lib.ptr(torch.view_as_real(b)), P, int(a.shape[1]), _lib.ptr(dist),
-                                                          _lib.ptr(ang), None, _lib.current_stream(d)))
-        return dist, ang
-    _lib.check(_lib.load().mrs_ring_corr_fft_pairs(_lib.ctx(d), _lib.ptr(torch.view_as_real(a)),
-                                                   _lib.ptr(torch.view_as_real(b)), P, _lib.ptr(dist), _lib.ptr(ang),
-                                                   None, _lib.current_stream(d)))
+        _lib.load().mrs_ring_corr_fft_pairs_mc(_lib.ctx(d), a, b, P, a.shape[1], dist, ang, None, _lib.current_stream(d))
+    else:
+        _lib.load().mrs_ring_corr_fft_pairs(_lib.ctx(d), a, b, P, dist, ang, None, _lib.current_stream(d))
     return dist, ang

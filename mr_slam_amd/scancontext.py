@@ -18,15 +18,9 @@ KIND_SC = 3
 MAX_CANDIDATES = 64
 
 
-def _dev(t):
-    if not isinstance(t, torch.Tensor) or not t.is_cuda:
-        raise _lib.MrsError("expected a device tensor (no CPU fallback)")
-    return t.device.index or 0
-
-
 def _batch(sc):
     """[R, S] / [1, R, S] (one descriptor) or [n, R, S] / [n, 1, R, S] float32 device tensor -> ([n, R, S] contiguous, one descriptor?)"""
-    _dev(sc)
+    _lib.device_of(sc)
     t = sc.detach().to(torch.float32)
     R, S = t.shape[-2:]
     return t.reshape(-1, R, S).contiguous(), t.dim() <= 3 and t.numel() == R * S
@@ -50,10 +44,10 @@ def keys(sc):
     """(ring keys [n, R], sector keys [n, S]) float32 of a batch of descriptors (make_ringkey / make_sectorkey)"""
     t, _ = _batch(sc)
     n, R, S = t.shape
-    d = _dev(t)
+    d = _lib.device_of(t)
     ring = torch.empty((n, R), dtype=torch.float32, device=t.device)
     sector = torch.empty((n, S), dtype=torch.float32, device=t.device)
-    _lib.check(_lib.load().mrs_sc_keys(_lib.ctx(d), _lib.ptr(t), n, R, S, _lib.ptr(ring), _lib.ptr(sector), _lib.current_stream(d)))
+    _lib.load().mrs_sc_keys(_lib.ctx(d), t, n, R, S, ring, sector, _lib.current_stream(d))
     return ring, sector
 
 
@@ -73,16 +67,15 @@ def make_sectorkey(sc):
 
 def fast_align_with_sectorkey(key1, key2):
     """ScanContext.py:86-101 for device keys [len] or [n, len]: (min ||key1 - roll(key2, s)|| (fp64), first s) over s < len"""
-    _dev(key1)
+    _lib.device_of(key1)
     a = key1.detach().to(torch.float32).reshape(-1, key1.shape[-1]).contiguous()
     b = key2.detach().to(torch.float32).reshape(-1, key2.shape[-1]).contiguous()
     assert a.shape == b.shape, (a.shape, b.shape)
     n, L = a.shape
-    d = _dev(a)
+    d = _lib.device_of(a)
     norm = torch.empty(n, dtype=torch.float64, device=a.device)
     shift = torch.empty(n, dtype=torch.int32, device=a.device)
-    _lib.check(_lib.load().mrs_sc_key_align_pairs(_lib.ctx(d), _lib.ptr(a), _lib.ptr(b), n, L, _lib.ptr(norm), _lib.ptr(shift),
-                                                  _lib.current_stream(d)))
+    _lib.load().mrs_sc_key_align_pairs(_lib.ctx(d), a, b, n, L, norm, shift, _lib.current_stream(d))
     return (norm[0], shift[0]) if key1.dim() == 1 else (norm, shift)
 
 
@@ -94,14 +87,11 @@ def _pairs(fn, sc1, sc2, *extra, with_shift=True):
         single = False
     assert a.shape == b.shape, (a.shape, b.shape)
     n, R, S = a.shape
-    d = _dev(a)
+    d = _lib.device_of(a)
     dist = torch.empty(n, dtype=torch.float32, device=a.device)
     shift = torch.empty(n, dtype=torch.int32, device=a.device) if with_shift else None
-    args = [_lib.ctx(d), _lib.ptr(a), _lib.ptr(b), n, R, S] + list(extra) + [_lib.ptr(dist)]
-    if with_shift:
-        args.append(_lib.ptr(shift))
-    args.append(_lib.current_stream(d))
-    _lib.check(getattr(_lib.load(), fn)(*args))
+    outs = (dist, shift) if with_shift else (dist,)
+    getattr(_lib.load(), fn)(_lib.ctx(d), a, b, n, R, S, *extra, *outs, _lib.current_stream(d))
     if single:
         return (dist[0], shift[0]) if with_shift else dist[0]
     return (dist, shift) if with_shift else dist
@@ -114,7 +104,7 @@ def dist_direct_sc(sc1, sc2):
 
 def dist_align_sc(sc1, sc2, search_ratio=0.1):
     """ScanContext.py:128-142: (dist, shift); the shift rolls sc2 and may be negative.  Batched over a leading axis."""
-    return _pairs("mrs_sc_dist_align_pairs", sc1, sc2, C.c_float(search_ratio))
+    return _pairs("mrs_sc_dist_align_pairs", sc1, sc2, search_ratio)
 
 
 def distance_sc(sc1, sc2):
@@ -130,7 +120,7 @@ class ScanContextDatabase:
     def __init__(self, device=0, capacity=1024):
         self.device = int(device)
         self._h = C.c_void_p()
-        _lib.check(_lib.load().mrs_loopdb_create(_lib.ctx(self.device), KIND_SC, 1, int(capacity), C.byref(self._h)))
+        _lib.load().mrs_loopdb_create(_lib.ctx(self.device), KIND_SC, 1, int(capacity), C.byref(self._h))
 
     def __del__(self):
         try:
@@ -141,54 +131,51 @@ class ScanContextDatabase:
 
     def __len__(self):
         n = C.c_int32(0)
-        _lib.check(_lib.load().mrs_loopdb_size(self._h, C.byref(n)))
+        _lib.load().mrs_loopdb_size(self._h, C.byref(n))
         return n.value
 
     def _arg(self, sc):
-        """(pointer, on_device, keep-alive, stream) of one [120, 120] descriptor (torch host / device tensor or numpy array)"""
+        """(descriptor, on_device, stream) of one [120, 120] descriptor (torch host / device tensor or numpy array)"""
         if isinstance(sc, torch.Tensor):
             t = sc.detach().to(torch.float32).contiguous()
             assert t.numel() == NUM_RING * NUM_SECTOR, tuple(t.shape)
             if t.is_cuda:
-                return C.c_void_p(t.data_ptr()), 1, t, _lib.current_stream(t.device.index or 0)
-            return C.c_void_p(t.data_ptr()), 0, t, None
+                return t, 1, _lib.current_stream(t.device.index or 0)
+            return t, 0, None
         a = np.ascontiguousarray(sc, dtype=np.float32)
         assert a.size == NUM_RING * NUM_SECTOR, a.shape
-        return C.c_void_p(a.ctypes.data), 0, a, None
+        return a, 0, None
 
     def append(self, sc):
-        p, dev, keep, stream = self._arg(sc)
-        _lib.check(_lib.load().mrs_loopdb_append_sc(self._h, p, dev, stream))
+        _lib.load().mrs_loopdb_append_sc(self._h, *self._arg(sc))
 
     def query(self, sc, num_candidates=1, search_ratio=0.1):
         """-> (indices, ring-key distances, dists, shifts) as numpy arrays of length min(num_candidates, len(self)), nearest key first"""
         k = int(num_candidates)
         if not 1 <= k <= MAX_CANDIDATES:
             raise ValueError("num_candidates in 1..%d" % MAX_CANDIDATES)
-        p, dev, keep, stream = self._arg(sc)
+        t, dev, stream = self._arg(sc)
         idx, kd = np.full(k, -1, np.int32), np.zeros(k, np.float32)
         dist, shift = np.zeros(k, np.float32), np.zeros(k, np.int32)
         cnt = C.c_int32(0)
-        _lib.check(_lib.load().mrs_loopdb_query_sc(self._h, p, dev, k, C.c_float(search_ratio), _lib.ptr(idx), _lib.ptr(kd), _lib.ptr(dist),
-                                                   _lib.ptr(shift), C.byref(cnt), stream))
+        _lib.load().mrs_loopdb_query_sc(self._h, t, dev, k, search_ratio, idx, kd, dist, shift, C.byref(cnt), stream)
         c = cnt.value
         return idx[:c], kd[:c], dist[:c], shift[:c]
 
     def query_all(self, sc, search_ratio=0.1):
         """-> (dists [n], shifts [n], index of the first smallest dist or -1): dist_align_sc(entry, sc) for every entry"""
-        p, dev, keep, stream = self._arg(sc)
+        t, dev, stream = self._arg(sc)
         lib = _lib.load()
         while True:
             cap = len(self)
             dist, shift = np.zeros(max(cap, 1), np.float32), np.zeros(max(cap, 1), np.int32)
             best, n = C.c_int32(-1), C.c_int32(0)
-            _lib.check(lib.mrs_loopdb_query_sc_all(self._h, p, dev, C.c_float(search_ratio), int(cap), _lib.ptr(dist), _lib.ptr(shift),
-                                                   C.byref(best), C.byref(n), stream))
+            lib.mrs_loopdb_query_sc_all(self._h, t, dev, search_ratio, cap, dist, shift, C.byref(best), C.byref(n), stream)
             if n.value <= cap:        # another thread may have appended since len(): ask again with larger arrays
                 return dist[:n.value], shift[:n.value], best.value
 
     def device_entries(self):
         """(packed entries [n, entry_floats], ring keys [n, 120]) as device tensors viewing the handle's memory (valid until it grows)"""
         pe, ps, n, ef = C.c_void_p(), C.c_void_p(), C.c_int32(0), C.c_int64(0)
-        _lib.check(_lib.load().mrs_loopdb_device_entries(self._h, C.byref(pe), C.byref(ps), C.byref(n), C.byref(ef)))
+        _lib.load().mrs_loopdb_device_entries(self._h, C.byref(pe), C.byref(ps), C.byref(n), C.byref(ef))
         return pe.value, ps.value, n.value, ef.value

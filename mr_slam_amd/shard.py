@@ -13,8 +13,12 @@ the CPU tests).  The reference has no collective at all; what shards here:
                             come back) and fetch_rows (only the candidate rows asked for travel).
 No kernel contains an exchange step.
 """
+import ctypes as C
+
 import torch
 import torch.distributed as dist
+
+from . import _lib
 
 
 def shard_bounds(n_items, rank, world):
@@ -329,9 +333,6 @@ class Exchange:
       fetch_rows(local_db, rows)    -> local_db-shaped rows by GLOBAL index (rank r owns rows [r * n, (r + 1) * n)), in request order"""
 
     def __init__(self, device=0, group=None):
-        import ctypes as C
-        from . import _lib
-        self._C, self._lib_mod = C, _lib
         lib = _lib.load()
         if not lib.mrs_exchange_available():
             raise _lib.MrsError("RCCL entry points not found (librccl.so.1): the C-ABI exchange is unavailable")
@@ -339,45 +340,37 @@ class Exchange:
         self.world, self.rank = _world(group), _rank(group)
         ident = (C.c_uint8 * 128)()
         if self.rank == 0:
-            _lib.check(lib.mrs_exchange_unique_id(ident))
+            lib.mrs_exchange_unique_id(ident)
         if self.world > 1:
             box = [bytes(ident)]
             dist.broadcast_object_list(box, src=0, group=group)
             ident = (C.c_uint8 * 128).from_buffer_copy(box[0])
         self._h = C.c_void_p()
-        _lib.check(lib.mrs_exchange_create(_lib.ctx(self.device), self.world, self.rank, ident, C.byref(self._h)))
+        lib.mrs_exchange_create(_lib.ctx(self.device), self.world, self.rank, ident, C.byref(self._h))
 
     def __del__(self):
         try:
             if getattr(self, "_h", None):
-                self._lib_mod.load().mrs_exchange_destroy(self._h)
+                _lib.load().mrs_exchange_destroy(self._h)
         except Exception:
             pass
 
-    @staticmethod
-    def _bytes(t):
-        return torch.view_as_real(t) if t.is_complex() else t
-
     def allgather(self, local):
-        _lib = self._lib_mod
         x = local.contiguous()
-        assert x.is_cuda and x.shape[0] > 0
+        assert x.shape[0] > 0
         out = torch.empty((self.world * x.shape[0],) + tuple(x.shape[1:]), dtype=x.dtype, device=x.device)
         entry = x[0].numel() * x.element_size()
-        _lib.check(_lib.load().mrs_exchange_allgather(self._h, _lib.ptr(self._bytes(x)), self._C.c_int64(x.shape[0]), self._C.c_int64(entry),
-                                                      _lib.ptr(self._bytes(out)), _lib.current_stream(self.device)))
+        _lib.load().mrs_exchange_allgather(self._h, x, x.shape[0], entry, out, _lib.current_stream(self.device))
         return out
 
     def allgather_into(self, out, local, stream=None):
         """ONE ncclAllGather of `local` (contiguous, the same size on every rank) into `out` (world x local, rank order), enqueued on `stream`
         (a torch stream; default: the current one): stream-ordered, nothing blocks the host"""
-        _lib = self._lib_mod
-        assert local.is_cuda and out.is_cuda and local.is_contiguous() and out.is_contiguous()
+        assert local.is_contiguous() and out.is_contiguous()
         nbytes = local.numel() * local.element_size()
         assert out.numel() * out.element_size() == self.world * nbytes
-        st = self._C.c_void_p(stream.cuda_stream) if stream is not None else _lib.current_stream(self.device)
-        _lib.check(_lib.load().mrs_exchange_allgather(self._h, self._C.c_void_p(local.data_ptr()), self._C.c_int64(1), self._C.c_int64(nbytes),
-                                                      self._C.c_void_p(out.data_ptr()), st))
+        st = C.c_void_p(stream.cuda_stream) if stream is not None else _lib.current_stream(self.device)
+        _lib.load().mrs_exchange_allgather(self._h, local, 1, nbytes, out, st)
         return out
 
     def fetch_plan(self, global_rows, rows_per_rank):
@@ -385,14 +378,12 @@ class Exchange:
         return PlannedFetch(self, global_rows, rows_per_rank)
 
     def fetch_rows(self, local_db, global_rows):
-        _lib = self._lib_mod
         db = local_db.contiguous()
         rows = global_rows.to(torch.int64).reshape(-1).contiguous()
-        assert db.is_cuda and rows.is_cuda and rows.numel() > 0
+        assert rows.numel() > 0
         entry = db[0].numel() * db.element_size()
         out = torch.empty((rows.numel(),) + tuple(db.shape[1:]), dtype=db.dtype, device=db.device)
-        _lib.check(_lib.load().mrs_exchange_fetch_rows(self._h, _lib.ptr(self._bytes(db)), self._C.c_int64(db.shape[0]), self._C.c_int64(entry),
-                                                       _lib.ptr(rows), int(rows.numel()), _lib.ptr(self._bytes(out)), _lib.current_stream(self.device)))
+        _lib.load().mrs_exchange_fetch_rows(self._h, db, db.shape[0], entry, rows, rows.numel(), out, _lib.current_stream(self.device))
         return out
 
 
@@ -409,23 +400,21 @@ class PlannedFetch:
             torch.cuda.current_stream().wait_event(self.event)       # stream-side wait, like a torch.distributed Work on a CUDA stream
 
     def __init__(self, exchange, global_rows, rows_per_rank):
-        import ctypes as C
-        self.x, self._C = exchange, C
-        _lib = exchange._lib_mod
+        self.x = exchange
         rows = global_rows.to(torch.int64).reshape(-1).contiguous()
-        assert rows.is_cuda and rows.numel() > 0
+        assert rows.numel() > 0
         self.n, self.rows_per_rank = int(rows.numel()), int(rows_per_rank)
         self._h = C.c_void_p()
-        _lib.check(_lib.load().mrs_exchange_fetch_plan_create(exchange._h, C.c_int64(self.rows_per_rank), _lib.ptr(rows), self.n,
-                                                              _lib.current_stream(exchange.device), C.byref(self._h)))
+        _lib.load().mrs_exchange_fetch_plan_create(exchange._h, self.rows_per_rank, rows, self.n, _lib.current_stream(exchange.device),
+                                                   C.byref(self._h))
         sent, recv = C.c_int64(0), C.c_int64(0)
-        _lib.check(_lib.load().mrs_exchange_fetch_plan_counts(self._h, C.byref(sent), C.byref(recv)))
+        _lib.load().mrs_exchange_fetch_plan_counts(self._h, C.byref(sent), C.byref(recv))
         self.rows_from_peers, self.rows_to_peers = int(recv.value), int(sent.value)
 
     def __del__(self):
         try:
             if getattr(self, "_h", None):
-                self.x._lib_mod.load().mrs_exchange_fetch_plan_destroy(self._h)
+                _lib.load().mrs_exchange_fetch_plan_destroy(self._h)
         except Exception:
             pass
 
@@ -435,19 +424,16 @@ class PlannedFetch:
     def fetch(self, local_db, async_op=False, stream=None):
         """rows in request order; async_op: (work, finish) -- the fetch runs on `stream` (a torch stream the caller keeps for communication;
         it first waits for what the current stream has enqueued so far), work.wait() makes the then-current stream wait for it"""
-        _lib = self.x._lib_mod
         db = local_db.contiguous()
-        assert db.is_cuda and db.shape[0] == self.rows_per_rank
-        real = torch.view_as_real(db) if db.is_complex() else db
-        entry = real[0].numel() * real.element_size()
+        assert db.shape[0] == self.rows_per_rank
+        entry = db[0].numel() * db.element_size()
         out = torch.empty((self.n,) + tuple(db.shape[1:]), dtype=db.dtype, device=db.device)
-        oreal = torch.view_as_real(out) if out.is_complex() else out
         cur = torch.cuda.current_stream()
         st = stream if stream is not None else cur
         if st is not cur:
             ready = torch.cuda.Event(); ready.record(cur)
             st.wait_event(ready)
-        _lib.check(_lib.load().mrs_exchange_fetch_planned(self._h, _lib.ptr(real), self._C.c_int64(entry), _lib.ptr(oreal), self._C.c_void_p(st.cuda_stream)))
+        _lib.load().mrs_exchange_fetch_planned(self._h, db, entry, out, C.c_void_p(st.cuda_stream))
         if not async_op:
             if st is not cur:
                 done = torch.cuda.Event(); done.record(st); cur.wait_event(done)

@@ -122,7 +122,7 @@ def test_fused_persistent_rounds_and_tuning_knobs(dev, opts):
         plan.set_option(plan.OPT_FUSED_VARIANT, 1)
 
 
-def test_fused_rejects_what_it_cannot_do(dev):
+def test_fused_rejects_what_it_cannot_do_with_mrs_error(dev):
     import ctypes as C
     import torch
     from mr_slam_amd import _lib, bev, ring, synth
@@ -131,8 +131,9 @@ def test_fused_rejects_what_it_cannot_do(dev):
     out = torch.empty((1, 120, 120), dtype=torch.float32, device=dev)
     lib = _lib.load()
     for cfg in (_lib.BevCfg(1, 1, 120, 120, 2, 1), _lib.BevCfg(1, 1, 100, 120, 1, 1)):      # two height layers; grid != the plan's image
-        st = lib.mrs_ring_descriptors_batch(plan._h, _lib.ptr(xyz), _lib.ptr(offs), 1, C.byref(cfg), None, None, _lib.ptr(out), None)
-        assert st != 0 and b"unsupported" in lib.mrs_status_str(st)
+        with pytest.raises(_lib.MrsError) as e:
+            lib.mrs_ring_descriptors_batch(plan._h, xyz, offs, 1, C.byref(cfg), None, None, out, None)
+        assert "unsupported" in str(e.value)
     with pytest.raises(_lib.MrsError):
         plan.set_option(plan.OPT_FUSED_PREFETCH, 3)
     with pytest.raises(_lib.MrsError):

@@ -191,7 +191,7 @@ def test_database_query_all_and_host_device_bits(g, big_db):
     assert np.array_equal(d_all.view(np.uint32), d3.view(np.uint32)) and np.array_equal(s_all, s3)
 
 
-def test_empty_database_and_wrong_kind_calls(g):
+def test_empty_database_and_wrong_kind_calls_raise(g):
     from mr_slam_amd import _lib
     from mr_slam_amd.node import LoopDatabase, DiscoDatabase
     from mr_slam_amd.scancontext import ScanContextDatabase
@@ -206,24 +206,26 @@ def test_empty_database_and_wrong_kind_calls(g):
     i32 = np.zeros(64, np.int32)
     f32 = np.zeros(64, np.float32)
     cnt = C.c_int32(0)
+
+    def rejected(fn, *args):
+        with pytest.raises(_lib.MrsError) as e:
+            fn(*args)
+        assert e.value.status == 1
+
     # RING / RING++ / DiSCO entry points on an SC handle
-    assert lib.mrs_loopdb_append(h, _lib.ptr(buf), 0, 1, None) == 1
-    assert lib.mrs_loopdb_query(h, _lib.ptr(buf), 0, C.c_float(1.0), 4, _lib.ptr(i32), _lib.ptr(f32), _lib.ptr(i32), C.byref(cnt), 0, None,
-                                None, None, None) == 1
-    assert lib.mrs_loopdb_query_multi(h, _lib.ptr(buf), 0, 1, 4, _lib.ptr(f32), _lib.ptr(i32), C.byref(cnt), None) == 1
-    assert lib.mrs_loopdb_append_disco(h, _lib.ptr(buf), _lib.ptr(buf), 0, None) == 1
-    assert lib.mrs_loopdb_query_disco(h, _lib.ptr(buf), _lib.ptr(buf), 0, _lib.ptr(i32), _lib.ptr(f32), _lib.ptr(i32), None) == 1
+    rejected(lib.mrs_loopdb_append, h, buf, 0, 1, None)
+    rejected(lib.mrs_loopdb_query, h, buf, 0, 1.0, 4, i32, f32, i32, C.byref(cnt), 0, None, None, None, None)
+    rejected(lib.mrs_loopdb_query_multi, h, buf, 0, 1, 4, f32, i32, C.byref(cnt), None)
+    rejected(lib.mrs_loopdb_append_disco, h, buf, buf, 0, None)
+    rejected(lib.mrs_loopdb_query_disco, h, buf, buf, 0, i32, f32, i32, None)
     assert len(db) == 0
     # SC entry points on RING and DiSCO handles
     for other in (LoopDatabase("ring", None, 0, 4), DiscoDatabase(0, 4)):
-        assert lib.mrs_loopdb_append_sc(other._h, _lib.ptr(buf), 0, None) == 1
-        assert lib.mrs_loopdb_query_sc(other._h, _lib.ptr(buf), 0, 1, C.c_float(0.1), _lib.ptr(i32), _lib.ptr(f32), _lib.ptr(f32), _lib.ptr(i32),
-                                       C.byref(cnt), None) == 1
-        assert lib.mrs_loopdb_query_sc_all(other._h, _lib.ptr(buf), 0, C.c_float(0.1), 4, _lib.ptr(f32), _lib.ptr(i32), C.byref(cnt),
-                                           C.byref(cnt), None) == 1
+        rejected(lib.mrs_loopdb_append_sc, other._h, buf, 0, None)
+        rejected(lib.mrs_loopdb_query_sc, other._h, buf, 0, 1, 0.1, i32, f32, f32, i32, C.byref(cnt), None)
+        rejected(lib.mrs_loopdb_query_sc_all, other._h, buf, 0, 0.1, 4, f32, i32, C.byref(cnt), C.byref(cnt), None)
         assert len(other) == 0
-    assert lib.mrs_loopdb_query_sc(h, _lib.ptr(buf), 0, 65, C.c_float(0.1), _lib.ptr(i32), _lib.ptr(f32), _lib.ptr(f32), _lib.ptr(i32),
-                                   C.byref(cnt), None) == 1
+    rejected(lib.mrs_loopdb_query_sc, h, buf, 0, 65, 0.1, i32, f32, f32, i32, C.byref(cnt), None)
 
 
 def test_database_threads(g):

@@ -26,7 +26,7 @@ import ctypes as C
 from mr_slam_amd import _lib
 L=_lib.load(); ctx=_lib.ctx(0)
 def k_full():
-    L.mrs_ring_corr_spectra(ctx, _lib.ptr(torch.view_as_real(a)), _lib.ptr(torch.view_as_real(b)), 1, 1, 120, 120, C.c_void_p(out.data_ptr()), C.c_void_p(out.data_ptr()+4), None, _lib.current_stream(0))
+    L.mrs_ring_corr_spectra(ctx, a, b, 1, 1, 120, 120, C.c_void_p(out.data_ptr()), C.c_void_p(out.data_ptr()+4), None, _lib.current_stream(0))
 def k_half():
     ring.corr_pairs_fft(ha, hb, out=(out[0:1], out[1:2].view(torch.int32)))
 print("full kernel events us", ev(k_full), "wall launch-only us", wall(k_full))
