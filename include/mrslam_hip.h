@@ -157,6 +157,11 @@ int mrs_radon_forward(mrs_radon_plan* plan, const float* d_img, int32_t batch, f
  * dist = 1) and count the event so that the host mirror can raise the same error.  Synchronises the device. */
 int mrs_radon_plan_degenerate_count(mrs_radon_plan* plan, int32_t reset, int32_t* out_count);
 
+/* Read-only: the ray each lane slot of the two-image kernels marches (slot s = k * 1024 + lane, -1 = idle; every ray once), as the plan
+ * dealt them when it was built.  Host memory, no GPU work.  *n_slots = number of slots (0: the plan has no slot tables); at most
+ * `capacity` entries are written to h_slot_rays. */
+int mrs_radon_plan_slot_rays(mrs_radon_plan* plan, int32_t* h_slot_rays, int32_t capacity, int32_t* n_slots);
+
 /* A3/A4 + R1 + R2a in one launch: the front half of generate_RING (RING_ros/util.py:174-197: voxelocc.GPUTransformer
  * transform() + retreive(), channel 2 -> ParallelBeam.forward -> fn.normalize) for a batch of scans.  One persistent workgroup
  * per compute unit rasterises two scans straight into the Radon kernel's LDS tile and marches the rays; the BEV image goes to

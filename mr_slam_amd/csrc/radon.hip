@@ -23,6 +23,7 @@
 
 #include "common.hpp"
 #include "radon_device.hpp"
+#include "radon_deal.hpp"
 
 namespace {
 
@@ -416,26 +417,22 @@ int mrs_radon_plan_create(mrs_ctx* ctx, const float* h_angles, int32_t n_angles,
         delete pl;
         return MRS_ERR_HIP;
     }
-    // slot tables (two-image kernels): rays sorted by (orientation, step count, ray id), 64 consecutive slots per wave and round
+    // slot tables (two-image kernels): rays dealt to lane slots by orientation, length and LDS bank (radon_deal.hpp)
     const int per_lane = (int)((rays + kRadonWG - 1) / kRadonWG);
     if (pl->two_in_lds && per_lane <= 16) {
-        std::vector<int> order(rays);
-        for (size_t i = 0; i < rays; ++i) order[i] = (int)i;
-        std::stable_sort(order.begin(), order.end(), [&](int a, int b) {
-            const int ya = meta[a] >> 16, yb = meta[b] >> 16, na = meta[a] & 0xffff, nb = meta[b] & 0xffff;
-            return ya != yb ? ya > yb : na > nb;
-        });
+        const radon_deal::RayTable rt = {meta, base, q, vm, (int)rays, stride};
+        pl->h_slot_ray = radon_deal::deal_rays(rt, kRadonWG, per_lane);
         const size_t slots = (size_t)per_lane * kRadonWG;
         std::vector<int4> h_slot(slots, make_int4(0, 0, 0, 0));
         std::vector<float> h_nrm(slots, 0.0f);
-        std::vector<int> h_ray(slots, -1);
-        for (size_t i = 0; i < rays; ++i) {
-            const int r = order[i];
+        const std::vector<int>& h_ray = pl->h_slot_ray;
+        for (size_t i = 0; i < slots; ++i) {
+            const int r = h_ray[i];
+            if (r < 0) continue;
             int qb, vb;
             memcpy(&qb, &q[r], 4); memcpy(&vb, &vm[r], 4);
             h_slot[i] = make_int4(meta[r], base[r], qb, vb);
             h_nrm[i] = nrm[r];
-            h_ray[i] = r;
         }
         if (hipMalloc(&pl->d_slot, slots * sizeof(int4)) != hipSuccess || hipMalloc(&pl->d_slot_nrm, slots * sizeof(float)) != hipSuccess ||
             hipMalloc(&pl->d_slot_ray, slots * sizeof(int)) != hipSuccess ||
@@ -462,6 +459,16 @@ int mrs_radon_plan_destroy(mrs_radon_plan* plan)
     if (plan->d_meta) (void)hipFree(plan->d_meta);
     if (plan->d_degenerate) (void)hipFree(plan->d_degenerate);
     delete plan;
+    return MRS_OK;
+}
+
+int mrs_radon_plan_slot_rays(mrs_radon_plan* plan, int32_t* h_slot_rays, int32_t capacity, int32_t* n_slots)
+{
+    MRS_REQUIRE(plan && n_slots, "null pointer");
+    MRS_REQUIRE(capacity >= 0 && (h_slot_rays || capacity == 0), "capacity without a buffer");
+    const int32_t n = (int32_t)plan->h_slot_ray.size();
+    *n_slots = n;
+    if (h_slot_rays && n) memcpy(h_slot_rays, plan->h_slot_ray.data(), sizeof(int32_t) * (size_t)std::min(n, capacity));
     return MRS_OK;
 }
 

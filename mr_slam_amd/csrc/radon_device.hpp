@@ -1,6 +1,8 @@
 // radon_device.hpp -- the parts of the Radon kernels shared by radon.hip and fused.hip: plan object, ray table view,
 // the two-image sample loop (march2 / trace_ray2) and the fused normalisation.  See radon.hip for the design notes.
 #pragma once
+#include <vector>
+
 #include "common.hpp"
 
 struct mrs_radon_plan {
@@ -18,13 +20,14 @@ struct mrs_radon_plan {
     int fused_skip = 0;         // measurement aid (MRS_RADON_OPT_FUSED_SKIP): 1 = the slot-table kernel without its rasteriser, 2 = without its ray march
     int fused_variant = 2;      // 2 (default): slot tables (rays sorted by orientation and length) + rolled ray loop, raw sums in registers, sinogram written once;
                                 // 1: the same with the raw sums parked in the output buffer (re-read, rewritten); 0: the table in ray order, 15 rays unrolled
-    // slot tables of the two-image kernels: lane slot s = k * 1024 + lane carries ray slot_ray[s] (-1: idle).  Rays are sorted by
-    // (orientation, step count), so that the 64 lanes of a wave march rays of (almost) the same length: a wave executes the longest
-    // of its rays, and in (angle, detector) order 16 % of the lane-steps were idle
+    // slot tables of the two-image kernels: lane slot s = k * 1024 + lane carries ray slot_ray[s] (-1: idle).  The 64 lanes of a wave march
+    // rays of one orientation and (almost) the same length: a wave executes the longest of its rays, and in (angle, detector) order 16 %
+    // of the lane-steps were idle.  Which 32 of them share a lane group is chosen against the LDS bank model of radon_deal.hpp
     int4* d_slot = nullptr;     // {n_steps | ydom << 16, LDS byte offset of the first texel line (single-image units), q bits, vm bits}
     float* d_slot_nrm = nullptr;
     int* d_slot_ray = nullptr;
     int slot_per_lane = 0;
+    std::vector<int> h_slot_ray;   // host copy of d_slot_ray (mrs_radon_plan_slot_rays)
 };
 
 namespace {

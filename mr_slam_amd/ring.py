@@ -43,6 +43,15 @@ class RadonPlan:
         _lib.load().mrs_radon_plan_degenerate_count(self._h, bool(reset), C.byref(n))
         return n.value
 
+    def slot_rays(self):
+        """int32 [slots]: the ray each lane slot (k * 1024 + lane) of the two-image kernels marches, -1 = idle (mrs_radon_plan_slot_rays);
+        empty when the plan has no slot tables."""
+        n = C.c_int32(0)
+        _lib.load().mrs_radon_plan_slot_rays(self._h, None, 0, C.byref(n))
+        out = np.full(max(n.value, 1), -1, dtype=np.int32)
+        _lib.load().mrs_radon_plan_slot_rays(self._h, out, n.value, C.byref(n))
+        return out[:n.value]
+
     OPT_FUSED_STAGGER_US, OPT_FUSED_PREFETCH, OPT_FUSED_GRID, OPT_FUSED_VARIANT, OPT_FUSED_SKIP = 1, 2, 3, 4, 5
 
     def set_option(self, option, value):

@@ -2,10 +2,15 @@
 Per wave and sample step: 2 ds_read_b64 (cells of 8 bytes; 64 banks of 4 B; lane groups {0-31}, {32-63}; distinct cells with equal
 (cell index mod 32) inside a group serialise) and ~24 VALU cycles (tools/ubench/valu.hip: v_fract, v_cvt, v_lshl_add, 2 v_pk_fma at 4,
 v_add, v_sub at 2).  A wave executes max(n_steps) of its lanes per orientation.  Prints per workgroup round (one pair of images):
-VALU SIMD-cycles / 4 SIMDs, LDS-array cycles, lane efficiency, conflict share."""
+VALU SIMD-cycles / 4 SIMDs, LDS-array cycles, lane efficiency, conflict share.
+
+  python tools/radon_order_sim.py                  closed-form orders + the order radon_deal.hpp deals (compiled here with g++, no GPU)
+  python tools/radon_order_sim.py --from-library   the order the built library really holds (mrs_radon_plan_slot_rays; needs a GPU context)
+  python tools/radon_order_sim.py --table T.npy    a slot table saved earlier (int32 [slots], -1 = idle)"""
+import os
 import sys
 import numpy as np
-sys.path.insert(0, __import__("os").path.dirname(__file__))
+sys.path.insert(0, os.path.dirname(__file__))
 from radon_lds_sim import ray_table, PAD, STRIDE
 
 VALU_PER_STEP = 24.0
@@ -85,8 +90,46 @@ def chunks_to_waves(order, nw=16, balance=False, t=None):
     return waves
 
 
+def table_to_waves(table, wg=1024):
+    """slot table (slot s = k * wg + wave * 64 + lane) -> per hardware wave its list of 64-ray rounds"""
+    tab = np.asarray(table).reshape(-1, wg // 64, 64)
+    return [[tab[k, w] for k in range(tab.shape[0]) if (tab[k, w] >= 0).any()] for w in range(tab.shape[1])]
+
+
+def dealt_on_cpu(t, stride=STRIDE, wg=1024):
+    """the slot table of mr_slam_amd/csrc/radon_deal.hpp for ray table t: the library's own routine, compiled with the host compiler"""
+    import ctypes as C
+    import subprocess
+    import tempfile
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    with tempfile.TemporaryDirectory() as d:
+        so = os.path.join(d, "radon_deal.so")
+        subprocess.run(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-I" + os.path.join(root, "mr_slam_amd", "csrc"),
+                        os.path.join(root, "tests", "cpp", "radon_deal_capi.cpp"), "-o", so], check=True)
+        lib = C.CDLL(so)
+        rays = t["n"].size
+        meta = (t["n"] | (t["ydom"].astype(np.int64) << 16)).astype(np.int32)
+        base = (4 * np.where(t["ydom"], (t["major"] + PAD) * stride, t["major"] + PAD)).astype(np.int32)
+        q, vm = t["q"].astype(np.float32), t["vm"].astype(np.float32)
+        per_lane = (rays + wg - 1) // wg
+        out = np.full(per_lane * wg, -1, dtype=np.int32)
+        ptr = lambda a: a.ctypes.data_as(C.c_void_p)
+        lib.deal_rays_c(ptr(meta), ptr(base), ptr(q), ptr(vm), rays, stride, wg, per_lane, ptr(out))
+    return out
+
+
 if __name__ == "__main__":
     t = ray_table()
+    if "--from-library" in sys.argv:
+        sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+        from mr_slam_amd import ring
+        table = ring.ring_plan(0).slot_rays()
+        valu, lds = evaluate(t, table_to_waves(table), "library (mrs_radon_plan_slot_rays)")
+        sys.exit(0)
+    if "--table" in sys.argv:
+        table = np.load(sys.argv[sys.argv.index("--table") + 1])
+        evaluate(t, table_to_waves(table), "saved slot table")
+        sys.exit(0)
     R = t["n"].size
     n, yd = t["n"], t["ydom"]
     evaluate(t, chunks_to_waves(np.arange(R)), "natural (angle, det)")
@@ -102,3 +145,4 @@ if __name__ == "__main__":
     b = (n + 23) // 24
     o = np.lexsort((np.arange(R), b, yd))
     evaluate(t, chunks_to_waves(o, balance=True, t=t), "bucket24 + LPT")
+    evaluate(t, table_to_waves(dealt_on_cpu(t)), "radon_deal.hpp (searched)")
