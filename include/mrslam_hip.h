@@ -183,6 +183,9 @@ enum mrs_radon_option {
                                            once; 1: the same with the raw sums parked in the output buffer; 0: (angle, detector) order */
 };
 int mrs_radon_plan_set_option(mrs_radon_plan* plan, int32_t option, int32_t value);
+/* The value an option has now (what the plan was created with, or the last value set).  Defaults: stagger 70, prefetch 2, grid 0,
+ * variant 2, skip 0. */
+int mrs_radon_plan_get_option(mrs_radon_plan* plan, int32_t option, int32_t* value);
 
 /* (x - mean) / std over n_groups consecutive groups of group_len floats (unbiased std):
  * torchvision fn.normalize(t, mean=t.mean(), std=t.std()) as RING_ros/util.py:197,339-340,429-430

@@ -389,6 +389,21 @@ int mrs_radon_plan_set_option(mrs_radon_plan* plan, int32_t option, int32_t valu
     }
 }
 
+int mrs_radon_plan_get_option(mrs_radon_plan* plan, int32_t option, int32_t* value)
+{
+    MRS_REQUIRE(plan && value, "null pointer");
+    switch (option) {
+        case MRS_RADON_OPT_FUSED_STAGGER_US: *value = plan->fused_stagger_us; return MRS_OK;
+        case MRS_RADON_OPT_FUSED_PREFETCH: *value = plan->fused_prefetch; return MRS_OK;
+        case MRS_RADON_OPT_FUSED_GRID: *value = plan->fused_grid; return MRS_OK;
+        case MRS_RADON_OPT_FUSED_VARIANT: *value = plan->fused_variant; return MRS_OK;
+        case MRS_RADON_OPT_FUSED_SKIP: *value = plan->fused_skip; return MRS_OK;
+        default:
+            mrs::set_error("unknown plan option %d", (int)option);
+            return MRS_ERR_ARG;
+    }
+}
+
 int mrs_ring_descriptors_batch(mrs_radon_plan* plan, const float* d_xyz, const int64_t* d_offsets, int32_t batch,
                                const mrs_bev_cfg* cfg, float* d_bev, float* d_sino, float* d_sino_norm, mrs_stream stream)
 {

@@ -422,23 +422,19 @@ int mrs_radon_plan_create(mrs_ctx* ctx, const float* h_angles, int32_t n_angles,
     if (pl->two_in_lds && per_lane <= 16) {
         const radon_deal::RayTable rt = {meta, base, q, vm, (int)rays, stride};
         pl->h_slot_ray = radon_deal::deal_rays(rt, kRadonWG, per_lane);
-        const size_t slots = (size_t)per_lane * kRadonWG;
-        std::vector<int4> h_slot(slots, make_int4(0, 0, 0, 0));
-        std::vector<float> h_nrm(slots, 0.0f);
-        const std::vector<int>& h_ray = pl->h_slot_ray;
-        for (size_t i = 0; i < slots; ++i) {
-            const int r = h_ray[i];
-            if (r < 0) continue;
-            int qb, vb;
-            memcpy(&qb, &q[r], 4); memcpy(&vb, &vm[r], 4);
-            h_slot[i] = make_int4(meta[r], base[r], qb, vb);
-            h_nrm[i] = nrm[r];
+        // the fused kernel walks 15 or 16 slots per lane whatever per_lane is: device tables padded with idle entries (radon_deal::slot_images)
+        const radon_deal::SlotImages im = radon_deal::slot_images(rt, nrm, pl->h_slot_ray, kRadonWG, per_lane);
+        const size_t slots = im.ray.size();
+        if (slots != (size_t)radon_deal::walked_per_lane(per_lane) * kRadonWG) {
+            mrs::set_error("slot table of %zu entries for %d rays per lane", pl->h_slot_ray.size(), per_lane);
+            mrs_radon_plan_destroy(pl);
+            return MRS_ERR_ARG;
         }
         if (hipMalloc(&pl->d_slot, slots * sizeof(int4)) != hipSuccess || hipMalloc(&pl->d_slot_nrm, slots * sizeof(float)) != hipSuccess ||
             hipMalloc(&pl->d_slot_ray, slots * sizeof(int)) != hipSuccess ||
-            hipMemcpy(pl->d_slot, h_slot.data(), slots * sizeof(int4), hipMemcpyHostToDevice) != hipSuccess ||
-            hipMemcpy(pl->d_slot_nrm, h_nrm.data(), slots * sizeof(float), hipMemcpyHostToDevice) != hipSuccess ||
-            hipMemcpy(pl->d_slot_ray, h_ray.data(), slots * sizeof(int), hipMemcpyHostToDevice) != hipSuccess) {
+            hipMemcpy(pl->d_slot, im.slot.data(), slots * sizeof(int4), hipMemcpyHostToDevice) != hipSuccess ||
+            hipMemcpy(pl->d_slot_nrm, im.nrm.data(), slots * sizeof(float), hipMemcpyHostToDevice) != hipSuccess ||
+            hipMemcpy(pl->d_slot_ray, im.ray.data(), slots * sizeof(int), hipMemcpyHostToDevice) != hipSuccess) {
             mrs::set_error("could not upload the slot tables");
             mrs_radon_plan_destroy(pl);
             return MRS_ERR_HIP;

@@ -420,4 +420,41 @@ inline std::vector<int> deal_rays(const RayTable& t, int wg, int per_lane)
     return table;
 }
 
+// ---- device images of the slot table -------------------------------------------------------------------------------------------------
+// The slot-table kernels (k_bev_radon3, fused.hip) are instantiated for 15 or 16 rays per lane and walk ALL of those lane slots, whatever
+// the plan's own ceil(rays / wg) is: the tables they read are padded to that length with idle entries (ray -1, norm 0, a zero slot), which
+// the kernels' `ray >= 0` test skips.
+inline int walked_per_lane(int per_lane) { return per_lane <= 15 ? 15 : 16; }
+
+struct SlotEntry { int meta, base, q_bits, vm_bits; };   // the int4 the kernel loads: {n_steps | ydom << 16, byte offset, q bits, vm bits}
+static_assert(sizeof(SlotEntry) == 16, "SlotEntry is uploaded as int4");
+
+struct SlotImages {
+    std::vector<SlotEntry> slot;
+    std::vector<float> nrm;
+    std::vector<int> ray;
+};
+
+// slot_ray: deal_rays' table [per_lane * wg]; nrm: step length per ray.  Every image has walked_per_lane(per_lane) * wg entries; a table
+// of any other length than per_lane * wg is an error: the images come back empty.
+inline SlotImages slot_images(const RayTable& t, const float* nrm, const std::vector<int>& slot_ray, int wg, int per_lane)
+{
+    const size_t dealt = (size_t)per_lane * wg, padded = (size_t)walked_per_lane(per_lane) * wg;
+    SlotImages im;
+    if (slot_ray.size() != dealt) return im;
+    im.slot.assign(padded, SlotEntry{0, 0, 0, 0});
+    im.nrm.assign(padded, 0.0f);
+    im.ray.assign(padded, -1);
+    for (size_t i = 0; i < dealt; ++i) {
+        const int r = slot_ray[i];
+        if (r < 0) continue;
+        int qb, vb;
+        memcpy(&qb, &t.q[r], 4); memcpy(&vb, &t.vm[r], 4);
+        im.slot[i] = SlotEntry{t.meta[r], t.base[r], qb, vb};
+        im.nrm[i] = nrm[r];
+        im.ray[i] = r;
+    }
+    return im;
+}
+
 }  // namespace radon_deal

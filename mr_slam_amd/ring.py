@@ -58,6 +58,12 @@ class RadonPlan:
         """Tuning knobs of the fused descriptor kernel (mrs_radon_plan_set_option); results do not depend on them."""
         _lib.load().mrs_radon_plan_set_option(self._h, int(option), int(value))
 
+    def get_option(self, option):
+        """The option's current value (mrs_radon_plan_get_option)."""
+        v = C.c_int32(0)
+        _lib.load().mrs_radon_plan_get_option(self._h, int(option), C.byref(v))
+        return v.value
+
     def forward(self, img, raw=True, normalized=False):
         """img float32 [B,H,W] (device, contiguous) -> (sino [B,A,D] | None, sino_norm | None)."""
         d = _lib.device_of(img)

@@ -51,11 +51,44 @@ def deal(tmp_path_factory):
         got = lib.deal_rays_c(ptr(meta), ptr(base), ptr(q), ptr(vm), rays, stride, WG, per_lane, ptr(out))
         assert got == out.size
         return out.reshape(per_lane, WG // 64, 64)
+
+    def images(t, stride, tab, nrm, drop=0):
+        """slot table of run() -> the padded device images (int4 slots [n, 4], norms [n], rays [n]) of radon_deal::slot_images; drop > 0: hand
+        over a table that many entries short and return what the routine answers"""
+        import radon_lds_sim as sim
+        rays = t["n"].size
+        meta = (t["n"] | (t["ydom"].astype(np.int64) << 16)).astype(np.int32)
+        base = (4 * np.where(t["ydom"], (t["major"] + sim.PAD) * stride, t["major"] + sim.PAD)).astype(np.int32)
+        q, vm = t["q"].astype(np.float32), t["vm"].astype(np.float32)
+        per_lane = tab.shape[0]
+        flat = np.ascontiguousarray(tab.reshape(-1), dtype=np.int32)
+        cap = 32 * WG                                          # guard cells behind the images: the routine must not write past its length
+        slot = np.full((cap + 1, 4), -7, dtype=np.int32)
+        out_nrm, out_ray = np.full(cap + 1, -7.0, dtype=np.float32), np.full(cap + 1, -7, dtype=np.int32)
+        ptr = lambda a: a.ctypes.data_as(C.c_void_p)
+        n = lib.slot_images_c(ptr(meta), ptr(base), ptr(q), ptr(vm), ptr(np.ascontiguousarray(nrm, dtype=np.float32)), rays, stride, WG, per_lane,
+                              ptr(flat), flat.size - drop, cap, ptr(slot), ptr(out_nrm), ptr(out_ray))
+        if drop:
+            assert (slot == -7).all() and (out_ray == -7).all(), "a refused table was written out all the same"
+            return n
+        assert 0 < n <= cap, n
+        assert (slot[n:] == -7).all() and (out_nrm[n:] == -7.0).all() and (out_ray[n:] == -7).all()
+        return slot[:n], out_nrm[:n], out_ray[:n], (meta, base, q, vm)
+    lib.slot_images_c.restype = C.c_int
+    run.images = images
     return run
 
 
+# ring.ring_plan(num_ring, num_sector) builds A = H = num_ring, D = W = num_sector: the grids tests/test_fused_gpu.py runs the fused kernel on,
+# and the 64 x 64 image under the default rays whose raw sums do not fit the tile (the fall-back of OPT_FUSED_VARIANT 2)
 GEOMETRIES = {"default": dict(A=120, D=120, H=120, W=120), "90x100_on_100x120": dict(A=90, D=100, H=100, W=120),
-              "under_1024_rays": dict(A=30, D=30, H=120, W=120)}
+              "under_1024_rays": dict(A=30, D=30, H=120, W=120),
+              "ring100x128": dict(A=100, D=128, H=100, W=128), "ring128x100": dict(A=128, D=100, H=128, W=100),
+              "ring128x128": dict(A=128, D=128, H=128, W=128), "ring127x127": dict(A=127, D=127, H=127, W=127),
+              "ring30x30": dict(A=30, D=30, H=30, W=30), "default_rays_on_64x64": dict(A=120, D=120, H=64, W=64)}
+# lane slots per lane that the fused kernel's instantiation walks: k_bev_radon3<15, ...> for up to 15 rays per lane, <16, ...> for 16
+# (mrs_ring_descriptors_batch, fused.hip), whatever ceil(rays / 1024) is
+WALKED = {name: (16 if -(-g["A"] * g["D"] // WG) == 16 else 15) for name, g in GEOMETRIES.items()}
 
 
 @pytest.mark.parametrize("name", list(GEOMETRIES))
@@ -81,6 +114,46 @@ def test_every_ray_once_orientations_apart_deterministic(deal, name):
             mixed += int(live.size > 0 and t["ydom"][live].min() != t["ydom"][live].max())
     assert mixed <= 1, "%d wave-rounds mix the two orientations" % mixed
     assert np.array_equal(tab, deal(t, stride)), "two calls gave different tables"
+
+
+@pytest.mark.parametrize("name", list(GEOMETRIES))
+def test_device_slot_tables_cover_every_slot_the_kernel_walks(deal, name):
+    """The slot-table kernel reads table entry lane + k * 1024 for EVERY k below its template's rays per lane (15 or 16), also when the plan
+    deals fewer rounds (13 for 100 x 128, 1 for 30 x 30): the device images must be that long, the entries behind the dealt ones idle
+    (ray -1, norm 0, zero slot: the kernel's `ray >= 0` test skips them), the dealt ones unchanged."""
+    import radon_lds_sim as sim
+    g = GEOMETRIES[name]
+    t = sim.ray_table(**g)
+    stride = (g["W"] + 2 * sim.PAD) | 1
+    tab = deal(t, stride)
+    rays, per_lane = t["n"].size, tab.shape[0]
+    assert per_lane == -(-rays // WG) <= 16
+    nrm = (1.0 + np.arange(rays) / rays).astype(np.float32)            # any non-zero norms: a pad entry cannot be mistaken for a ray's
+    slot, got_nrm, got_ray, (meta, base, q, vm) = deal.images(t, stride, tab, nrm)
+    walked = WALKED[name]
+    assert walked in (15, 16) and walked >= per_lane
+    assert slot.shape == (walked * WG, 4) and got_nrm.shape == (walked * WG,) and got_ray.shape == (walked * WG,), \
+        "the kernel walks %d slots per lane, the device tables hold %d" % (walked, got_ray.size // WG)
+    dealt = per_lane * WG
+    assert np.array_equal(got_ray[:dealt], tab.ravel()), "the dealt part differs from the slot table"
+    assert (got_ray[dealt:] == -1).all() and (got_nrm[dealt:] == 0.0).all() and (slot[dealt:] == 0).all(), "a pad entry is not idle"
+    live = got_ray >= 0
+    assert np.array_equal(np.sort(got_ray[live]), np.arange(rays)), "a ray is missing or dealt twice"
+    r = got_ray[live]
+    want = np.stack([meta[r], base[r], q[r].view(np.int32), vm[r].view(np.int32)], axis=1)
+    assert np.array_equal(slot[live], want) and np.array_equal(got_nrm[live], nrm[r])
+    assert (slot[~live] == 0).all() and (got_nrm[~live] == 0.0).all()
+
+
+def test_slot_table_of_the_wrong_length_is_refused(deal):
+    """a table shorter than per_lane * 1024 is an error (no images), not something to pad over"""
+    import radon_lds_sim as sim
+    g = GEOMETRIES["ring30x30"]
+    t = sim.ray_table(**g)
+    stride = (g["W"] + 2 * sim.PAD) | 1
+    tab = deal(t, stride)
+    nrm = np.ones(t["n"].size, dtype=np.float32)
+    assert deal.images(t, stride, tab, nrm, drop=1) == 0 and deal.images(t, stride, tab, nrm, drop=WG) == 0
 
 
 def test_model_cost_of_the_default_plan(deal):
@@ -119,6 +192,7 @@ def fused_digests(dev="cuda:0"):
     xyz, offs = bev.pack_scans(fused_scans(), dev)
     plan = ring.ring_plan(0)
     out = {}
+    before = plan.get_option(plan.OPT_FUSED_VARIANT)
     try:
         for variant in (0, 1, 2):
             plan.set_option(plan.OPT_FUSED_VARIANT, variant)
@@ -127,7 +201,7 @@ def fused_digests(dev="cuda:0"):
             out[str(variant)] = {"raw": hashlib.sha256(raw.cpu().numpy().tobytes()).hexdigest(),
                                  "norm": hashlib.sha256(norm.cpu().numpy().tobytes()).hexdigest()}
     finally:
-        plan.set_option(plan.OPT_FUSED_VARIANT, 2)
+        plan.set_option(plan.OPT_FUSED_VARIANT, before)
     return out
 
 

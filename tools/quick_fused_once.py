@@ -28,6 +28,7 @@ for nscan in (CH * B, CH * B - 1):
     def fused(out, raw=False):
         return ring.ring_descriptors_fused(flat, offs, raw=raw, normalized=True, out_norm=out)
 
+    was = plan.get_option(plan.OPT_FUSED_VARIANT)
     plan.set_option(plan.OPT_FUSED_VARIANT, 1)
     _, raw_ref, ref = fused(None, raw=True)
     ref, raw_ref = ref.clone(), raw_ref.clone()
@@ -41,4 +42,4 @@ for nscan in (CH * B, CH * B - 1):
             same = bool(torch.equal(ref.view(torch.int32), got.view(torch.int32))) and (raw_got is None or bool(torch.equal(raw_got, raw_ref)))
             ms = bench.ev_ms(lambda: fused(buf), reps=5, warm=1)
             print({"scans": nscan, "variant": v, "bit_identical": same, "ms_per_1024": round(ms / nscan * 1024, 4)}, flush=True)
-    plan.set_option(plan.OPT_FUSED_VARIANT, 1)
+    plan.set_option(plan.OPT_FUSED_VARIANT, was)
