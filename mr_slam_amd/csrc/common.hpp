@@ -69,6 +69,50 @@ struct Scratch {
     T* as() const { return static_cast<T*>(p); }
 };
 
+// Owner of one plain hipMalloc allocation of T (move-only; freed by the destructor -- the owner's device must be current by then).
+// For buffers that live as long as a handle; per-call temporaries use Scratch.
+template <class T>
+class DeviceBuffer {
+public:
+    DeviceBuffer() = default;
+    DeviceBuffer(const DeviceBuffer&) = delete;
+    DeviceBuffer& operator=(const DeviceBuffer&) = delete;
+    DeviceBuffer(DeviceBuffer&& o) noexcept : p_(o.p_), cap_(o.cap_) { o.p_ = nullptr; o.cap_ = 0; }
+    DeviceBuffer& operator=(DeviceBuffer&& o) noexcept
+    {
+        if (this != &o) { reset(); p_ = o.p_; cap_ = o.cap_; o.p_ = nullptr; o.cap_ = 0; }
+        return *this;
+    }
+    ~DeviceBuffer() { reset(); }
+    void reset()
+    {
+        if (p_) (void)hipFree(p_);
+        p_ = nullptr; cap_ = 0;
+    }
+    // Grow-only: the allocation is kept when it holds `need` elements; otherwise it is freed and one of `cap` >= need elements takes its place
+    // (contents are not carried over).  MRS_OK / MRS_ERR_HIP; the buffer is empty after a failure.
+    int reserve(size_t need, size_t cap)
+    {
+        if (need <= cap_) return MRS_OK;
+        reset();
+        const hipError_t e = hipMalloc(&p_, cap * sizeof(T));
+        if (e != hipSuccess) {
+            p_ = nullptr;
+            set_error("device allocation of %zu bytes failed: %s", cap * sizeof(T), hipGetErrorString(e));
+            return MRS_ERR_HIP;
+        }
+        cap_ = cap;
+        return MRS_OK;
+    }
+    T* get() const { return p_; }
+    size_t capacity() const { return cap_; }      // elements
+    explicit operator bool() const { return p_ != nullptr; }
+
+private:
+    T* p_ = nullptr;
+    size_t cap_ = 0;
+};
+
 // Device lookup table that reproduces the reference's sector() step function exactly
 // (built on the host with the host libm, see bev.hip).
 struct SectorLut {

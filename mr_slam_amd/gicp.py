@@ -1,4 +1,4 @@
-"""Batched GICP over the C ABI (rows G2-G6).  Host logic only; the kernels live in csrc/gicp.hip."""
+"""Batched GICP over the C ABI (rows G2-G6).  Host logic only; the kernels live in csrc/gicp_device.hpp, their host side in csrc/gicp.hip."""
 import ctypes as C
 
 import numpy as np

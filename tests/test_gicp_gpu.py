@@ -535,3 +535,95 @@ def test_submap_store_pairs_equal_per_pair_clouds_bit_for_bit(dev):
     b.set_targets([allc[i] for i in [3, 2, 1, 0, 0]])
     T3, _, _ = b.align()
     assert np.array_equal(T2, T3)
+
+
+# ---- a handle that is fed again: grow-only buffers, and an error return inside align() ----
+_REUSE_PRM = dict(k_correspondences=15, max_correspondence_distance=5.0)
+_REUSE_SIZES = (3000, 9000, 3100, 12000)    # small, large (3x: past the 1/8 slack, 3 -> 9 tiles of 1024), small again, larger still (the store round)
+_reuse_cache = {}
+
+
+def _reuse_round(r):
+    """Round r of the re-use tests: 9 (source, target) pairs of about _REUSE_SIZES[r] points, every cloud of another size (none a multiple of
+    the 1024-point tile).  Built like _pair, from two ray-cast scans that are thinned to the size wanted (a ray cast per cloud would cost a
+    second each)."""
+    from mr_slam_amd import synth
+    if "bases" not in _reuse_cache:
+        _reuse_cache["bases"] = [synth.lidar_scan(900 + j, 14000, metric=True).astype(np.float64) for j in range(2)]
+    if r not in _reuse_cache:
+        rng = np.random.default_rng(40 + r)
+        srcs, tgts = [], []
+        for i in range(9):
+            full = _reuse_cache["bases"][(i + r) % 2]
+            n = _REUSE_SIZES[r] + 137 * i
+            base = full[np.floor(np.arange(n) * (full.shape[0] / n)).astype(np.int64)]
+            R = Rot.from_rotvec((0.02, -0.03, 0.05 + 0.01 * i)).as_matrix()
+            srcs.append((base + rng.normal(0, 0.01, base.shape)).astype(np.float32))
+            tgts.append((base @ R.T + np.array([0.5 - 0.05 * i, -0.4, 0.1]) + rng.normal(0, 0.01, base.shape)).astype(np.float32))
+        _reuse_cache[r] = (srcs, tgts)
+    return _reuse_cache[r]
+
+
+def _new_batch(n_pairs, search):
+    from mr_slam_amd import gicp
+    b = gicp.GicpBatch(n_pairs)
+    b.set_params(**_REUSE_PRM)
+    b.set_search(search)
+    return b
+
+
+def _align_all(b):
+    T, conv, its = b.align()
+    return T, conv, its, b.covariances(0), b.covariances(1), b.fitness(T, 1.0)
+
+
+def _assert_same(got, want, what):
+    for name, g, w in zip(("transforms", "converged", "iterations", "covariances(0)", "covariances(1)", "fitness"), got, want):
+        assert np.array_equal(g, w), (what, name)
+
+
+@pytest.mark.parametrize("search", [1, 3])
+@pytest.mark.parametrize("n_pairs", [1, 9])
+def test_reused_handle_equals_fresh_handles_bit_for_bit(dev, n_pairs, search):
+    """One GicpBatch fed small clouds, then large ones (every buffer is re-allocated), then small ones again (they run in the spare capacity)
+    gives in every round what a fresh GicpBatch gives for the same clouds: transforms, converged, iterations, both sides' covariances and the
+    fitness, bit for bit.  One pair is the windowed LM schedule with the borrowed side stream, nine (> kLmWindowPairs, clouds of unequal
+    sizes) the per-tick one; search setting 3 builds the octree-cell hierarchy of the sources as well.  In a last round the targets come from a
+    store whose clouds are larger than anything the handle held: the hierarchy grows through the copy path."""
+    reused = _new_batch(n_pairs, search)
+    for r in range(3):
+        srcs, tgts = (c[:n_pairs] for c in _reuse_round(r))
+        reused.set_sources(srcs); reused.set_targets(tgts)
+        fresh = _new_batch(n_pairs, search)
+        fresh.set_sources(srcs); fresh.set_targets(tgts)
+        _assert_same(_align_all(reused), _align_all(fresh), "round %d" % r)
+    srcs, tgts = (c[:n_pairs] for c in _reuse_round(3))
+    store = _new_batch(n_pairs, search)
+    store.set_targets(tgts)
+    store.compute_covariances(1)
+    ids = list(range(n_pairs))[::-1]
+    reused.set_sources(srcs); reused.set_targets_from(store, ids)
+    fresh = _new_batch(n_pairs, search)
+    fresh.set_sources(srcs); fresh.set_targets([tgts[i] for i in ids])
+    _assert_same(_align_all(reused), _align_all(fresh), "store round")
+
+
+def test_error_return_inside_align_leaves_handle_and_side_slot_usable(dev):
+    """align() that fails an argument check AFTER it has started the target covariances on the borrowed side stream (search setting 3 chosen
+    after the sources were set: they have no hierarchy) raises; the same handle, set back to the default search, and a second fresh handle
+    that borrows the returned side slot in the same thread both give a fresh default handle's result bit for bit."""
+    from mr_slam_amd import _lib
+    srcs, tgts = (c[:1] for c in _reuse_round(0))
+    want_b = _new_batch(1, 1)
+    want_b.set_sources(srcs); want_b.set_targets(tgts)
+    want = _align_all(want_b)
+    b = _new_batch(1, 1)
+    b.set_sources(srcs); b.set_targets(tgts)
+    b.set_search(3)
+    with pytest.raises(_lib.MrsError):
+        b.align()
+    b.set_search(1)
+    _assert_same(_align_all(b), want, "same handle after the error")
+    c = _new_batch(1, 1)
+    c.set_sources(srcs); c.set_targets(tgts)
+    _assert_same(_align_all(c), want, "second handle on the returned slot")
