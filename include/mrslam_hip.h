@@ -585,7 +585,7 @@ int mrs_exchange_fetch_plan_destroy(mrs_fetch_plan* plan);
  * reference's callbacks run on concurrent rospy threads); all device work of a handle runs on the handle's own stream, `stream` is the
  * stream that produced a DEVICE argument (the handle waits for it; for appends it is made to wait until the argument has been consumed). */
 typedef struct mrs_loopdb mrs_loopdb;
-enum mrs_loopdb_kind { MRS_LOOPDB_RING = 0, MRS_LOOPDB_RINGPP = 1, MRS_LOOPDB_DISCO = 2, MRS_LOOPDB_SC = 3 };
+enum mrs_loopdb_kind { MRS_LOOPDB_RING = 0, MRS_LOOPDB_RINGPP = 1, MRS_LOOPDB_DISCO = 2, MRS_LOOPDB_SC = 3, MRS_LOOPDB_M2DP = 4 };
 /* where / what a RING or RING++ descriptor argument is:
  *   HOST / DEVICE : the reference's own object -- RING: pc_TIRING, complex64 [1][120][120] (util.py:198; its first 61 rows are what is
  *                   kept); RING++: pc_TIRING, float32 [C][120][120] magnitudes (util.py:247-250; normalised jointly + transformed along the
@@ -593,7 +593,7 @@ enum mrs_loopdb_kind { MRS_LOOPDB_RING = 0, MRS_LOOPDB_RINGPP = 1, MRS_LOOPDB_DI
  *   DEVICE_SPEC   : half spectra in the product's row layout, complex64 [C][61][120] (mrs_ring_half_spectrum / mrs_ring_spectrum_corr_pairs) */
 enum mrs_loopdb_form { MRS_LOOPDB_FORM_HOST = 0, MRS_LOOPDB_FORM_DEVICE = 1, MRS_LOOPDB_FORM_DEVICE_SPEC = 2 };
 
-/* channels: 1 for RING, C (6 in the reference) for RING++, ignored for DiSCO and SC; capacity_hint: entries to allocate up front (>= 1) */
+/* channels: 1 for RING, C (6 in the reference) for RING++, ignored for DiSCO, SC and M2DP; capacity_hint: entries to allocate up front (>= 1) */
 int mrs_loopdb_create(mrs_ctx* ctx, int32_t kind, int32_t channels, int32_t capacity_hint, mrs_loopdb** out);
 int mrs_loopdb_destroy(mrs_loopdb* db);
 int mrs_loopdb_size(mrs_loopdb* db, int32_t* out_n);
@@ -638,6 +638,15 @@ int mrs_loopdb_query_sc(mrs_loopdb* db, const float* sc, int32_t on_device, int3
  * results, *h_best the index of the first smallest dist over all n (-1 when empty), *h_n = n.  Blocking. */
 int mrs_loopdb_query_sc_all(mrs_loopdb* db, const float* sc, int32_t on_device, float search_ratio, int32_t all_capacity, float* h_all_dist,
                             int32_t* h_all_shift, int32_t* h_best, int32_t* h_n, mrs_stream stream);
+/* M2DP (MRS_LOOPDB_M2DP): the list of 192-d descriptors a node would keep per robot and search by Euclidean distance (the M2DP paper's
+ * matching rule; the reference ships the descriptor, RING_ros/pr_methods/M2DP.py, without a node of its own).  desc = double [192] as
+ * mrs_m2dp_batch writes it, host (on_device = 0) or device; entries are stored as float32 [192]. */
+int mrs_loopdb_append_m2dp(mrs_loopdb* db, const double* desc, int32_t on_device, mrs_stream stream);
+/* The k nearest entries by squared L2 distance over the float32-rounded descriptors (mrs_signature_knn with dim = 192: ascending, ties to
+ * the lower index), 1 <= k <= 32: h_index / h_dist2 [k], *h_count = min(k, n); the slots past it hold -1 / +inf.  Blocking; an empty
+ * database returns *h_count = 0 and index -1 without device work. */
+int mrs_loopdb_query_m2dp(mrs_loopdb* db, const double* desc, int32_t on_device, int32_t k, int32_t* h_index, float* h_dist2, int32_t* h_count,
+                          mrs_stream stream);
 /* the entries as they lie on the device (tests, exchange): valid until the next append that grows the capacity.  SC: d_entries = packed
  * entries (entry_floats apart: sector keys [128], column norms [128], then the [120][120] descriptor), d_signatures = ring keys [n][120] */
 int mrs_loopdb_device_entries(mrs_loopdb* db, const float** d_entries, const float** d_signatures, int32_t* out_n, int64_t* entry_floats);
@@ -667,6 +676,32 @@ int mrs_sc_dist_align_pairs(mrs_ctx* ctx, const float* d_sc1, const float* d_sc2
  * d_dist = 1 - max, d_yaw = argmax + 1 (the reference's convention). */
 int mrs_sc_distance_pairs(mrs_ctx* ctx, const float* d_sc1, const float* d_sc2, int32_t n_pairs, int32_t num_ring, int32_t num_sector, float* d_dist,
                           int32_t* d_yaw, mrs_stream stream);
+
+/* ------------------------------------------------------------------------------------
+ * M2DP on device arrays (RING_ros/pr_methods/M2DP.py:43-124)
+ * ---------------------------------------------------------------------------------- */
+
+/* points per workgroup of the signature-matrix kernel (tests probe both sides of it) */
+#define MRS_M2DP_TILE_POINTS 1024
+
+/* M2DP(cloud) for a batch of clouds in one set of launches, replacing the reference's Python loop over 64 planes with np.histogram2d
+ * inside (GetSignatureMatrix, M2DP.py:43-82) and its sklearn PCA / np.linalg.svd calls (M2DP.py:99-123).  d_points [total][stride] float
+ * (is_double = 0; widened to double first) or double (1), xyz first; d_offsets / h_offsets int64 [batch + 1], device and host copies of the
+ * same offsets (the convention of mrs_voxel_downsample_batch).  d_desc double [batch][192] = concat(u0 [64], v0 [128]) of the signature
+ * matrix, with the sign that makes sum(u0) >= 0 (both vectors non-negative; LAPACK's sign is arbitrary); d_A double [batch][64][128]
+ * (optional) = the signature matrix, row 16 * azimuth_index + elevation_index, column 16 * rho_bin + theta_bin, counts / n.  Clouds of
+ * fewer than 3 points give zeros (M2DP.py:100-109).  All arithmetic is fp64 and the counts are integers: the result does not depend on
+ * the batch a cloud is in.  Enqueued on `stream`. */
+int mrs_m2dp_batch(mrs_ctx* ctx, const void* d_points, int32_t is_double, int32_t stride, const int64_t* d_offsets, const int64_t* h_offsets,
+                   int32_t batch, double* d_desc, double* d_A, mrs_stream stream);
+/* The PCA stage of mrs_m2dp_batch alone (PCA().fit_transform, M2DP.py:105, and maxRho, M2DP.py:117-118): d_pca double [batch][16] =
+ * mean [3], components [3][3] (rows, descending eigenvalue, largest-magnitude coefficient positive), maxRho, covariance eigenvalues [3];
+ * zeros for clouds of fewer than 3 points. */
+int mrs_m2dp_pca_batch(mrs_ctx* ctx, const void* d_points, int32_t is_double, int32_t stride, const int64_t* d_offsets,
+                       const int64_t* h_offsets, int32_t batch, double* d_pca, mrs_stream stream);
+/* One cloud, host arrays in and out (the reference's calling convention): h_points [n][stride], n >= 0; h_desc double [192],
+ * h_A double [64][128] (optional).  Blocking. */
+int mrs_m2dp_host(mrs_ctx* ctx, const void* h_points, int32_t is_double, int32_t stride, int32_t n, double* h_desc, double* h_A);
 
 /* ------------------------------------------------------------------------------------
  * Mapping-side DiSCO matcher

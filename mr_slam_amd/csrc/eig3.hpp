@@ -191,4 +191,31 @@ MRS_HD void sym3_eigvals(const double* c, double* w)
     w[2] = (g.sep_is_smallest ? g.w_sep : lo) * m;
 }
 
+// all three eigenpairs of the symmetric 3x3 `c`: eigenvalues w[3] DESCENDING, unit eigenvectors as the ROWS of v[9] (row k belongs to w[k]).
+// The separated vector of stage 1, then the two of the 2x2 restriction in the (U, V) basis, in the cancellation-free form (d + r, m01) /
+// (m01, r - d); accurate to ~eps ||A|| / gap like the stages themselves.  The zero matrix and multiples of the identity give a fixed
+// orthonormal basis.  For the PCA axes of the M2DP descriptor (m2dp.hip).
+MRS_HD void sym3_eigvecs_desc(const double* c, double* w, double* v)
+{
+#if defined(__clang__)
+#pragma clang fp contract(fast)
+#endif
+    Sym3 s;
+    const double m = eig3_scale(c, s);
+    Eig3Stages g;
+    eig3_stages(s, g);
+    const double mid = 0.5 * (g.m00 + g.m11), d = 0.5 * (g.m00 - g.m11), r = sqrt(d * d + g.m01 * g.m01);
+    const bool pos = d >= 0.0;
+    double x = pos ? d + r : g.m01, y = pos ? g.m01 : r - d;      // eigenvector of mid + r in the (U, V) basis
+    const bool flat = !(x * x + y * y > 0.0);                     // the 2x2 is a multiple of the identity: U and V themselves
+    x = flat ? 1.0 : x; y = flat ? 0.0 : y;
+    const double inv = 1.0 / sqrt(x * x + y * y);
+    x *= inv; y *= inv;
+    double hi[3], lo[3];
+    for (int k = 0; k < 3; ++k) { hi[k] = x * g.U[k] + y * g.V[k]; lo[k] = x * g.V[k] - y * g.U[k]; }
+    const int ie = g.sep_is_smallest ? 2 : 0, ih = g.sep_is_smallest ? 0 : 1, il = g.sep_is_smallest ? 1 : 2;
+    w[ie] = g.w_sep * m; w[ih] = (mid + r) * m; w[il] = (mid - r) * m;
+    for (int k = 0; k < 3; ++k) { v[3 * ie + k] = g.e[k]; v[3 * ih + k] = hi[k]; v[3 * il + k] = lo[k]; }
+}
+
 }  // namespace mrs

@@ -12,6 +12,7 @@
 // concurrent rospy threads, each appending to its own list and reading the other robots').
 // Scan Context (MRS_LOOPDB_SC) replaces the ring-key KDTree + dist_align_sc of main_SC.py:153-172: entries are packed descriptors with their
 // sector keys and column norms (scancontext.hip), the ring keys a dense [n][120] array; a query is a nearest-key sweep + one alignment launch.
+// M2DP (MRS_LOOPDB_M2DP) keeps the 192-d descriptors of m2dp.hip as float32 rows; a query is mrs_signature_knn over them.
 #include "common.hpp"
 #include "fft_codelets.hpp"
 
@@ -28,6 +29,9 @@ constexpr int kStageSlots = 4;
 
 // SC top-k query results, one copy to the host: index [kScMaxK] | dist [kScMaxK] | shift [kScMaxK] | squared key distance [kScMaxK] (fp64)
 constexpr int kScDim = 120, kScMaxK = 64, kSmallSc = 5 * kScMaxK;
+
+// M2DP top-k query results, one copy to the host: index [kM2dpMaxK] | squared distance [kM2dpMaxK]
+constexpr int kM2dpDim = 192, kM2dpMaxK = 32, kSmallM2dp = 2 * kM2dpMaxK;
 
 struct Pinned {
     void* p = nullptr;
@@ -150,6 +154,12 @@ __global__ __launch_bounds__(kPhaseThreads) void k_disco_phase_one(const float2*
         __threadfence_system();
         *best = ~0ull;
     }
+}
+
+// an M2DP descriptor as the builder writes it (fp64) -> the float32 row the database keeps
+__global__ void k_m2dp_to_float(const double* __restrict__ src, float* __restrict__ dst)
+{
+    if (threadIdx.x < kM2dpDim) dst[threadIdx.x] = (float)src[threadIdx.x];
 }
 
 }  // namespace
@@ -299,8 +309,9 @@ int mrs_loopdb_create(mrs_ctx* ctx, int32_t kind, int32_t channels, int32_t capa
 {
     MRS_REQUIRE(ctx && out, "null pointer");
     *out = nullptr;
-    MRS_REQUIRE(kind == MRS_LOOPDB_RING || kind == MRS_LOOPDB_RINGPP || kind == MRS_LOOPDB_DISCO || kind == MRS_LOOPDB_SC, "unknown kind");
-    if (kind == MRS_LOOPDB_SC) channels = 1;                   // ignored: one [120][120] descriptor per entry
+    MRS_REQUIRE(kind == MRS_LOOPDB_RING || kind == MRS_LOOPDB_RINGPP || kind == MRS_LOOPDB_DISCO || kind == MRS_LOOPDB_SC ||
+                kind == MRS_LOOPDB_M2DP, "unknown kind");
+    if (kind == MRS_LOOPDB_SC || kind == MRS_LOOPDB_M2DP) channels = 1;      // ignored: one descriptor per entry
     MRS_REQUIRE(kind != MRS_LOOPDB_RING || channels == 1, "RING descriptors have one channel");
     MRS_REQUIRE(channels >= 1 && channels <= 16, "channels out of range");
     MRS_HIP_TRY(hipSetDevice(ctx->device));
@@ -309,6 +320,7 @@ int mrs_loopdb_create(mrs_ctx* ctx, int32_t kind, int32_t channels, int32_t capa
     if (kind == MRS_LOOPDB_RING) { db->entry_floats = kTiledFloats; db->in_floats = (size_t)kA * kD * 2; }
     else if (kind == MRS_LOOPDB_RINGPP) { db->entry_floats = (size_t)channels * kTiledFloats; db->in_floats = (size_t)channels * kA * kD; }
     else if (kind == MRS_LOOPDB_DISCO) { db->sig_dim = 1024; db->R = kPR; db->S = kPS; db->entry_floats = (size_t)db->R * db->S * 2; db->in_floats = db->entry_floats; }
+    else if (kind == MRS_LOOPDB_M2DP) { db->entry_floats = kM2dpDim; db->in_floats = 2 * (size_t)kM2dpDim; }      // arguments are 192 doubles
     else { db->sig_dim = db->R = db->S = kScDim; db->entry_floats = mrs::sc_entry_floats(kScDim, kScDim); db->in_floats = (size_t)kScDim * kScDim; }
     auto fail = [&](int st) { mrs_loopdb_destroy(db); return st; };
 #define LDB_TRY(expr) do { if ((expr) != hipSuccess) { mrs::set_error("%s failed (%s:%d)", #expr, __FILE__, __LINE__); return fail(MRS_ERR_HIP); } } while (0)
@@ -337,6 +349,10 @@ int mrs_loopdb_create(mrs_ctx* ctx, int32_t kind, int32_t channels, int32_t capa
     if (kind == MRS_LOOPDB_SC) {
         LDB_TRY(hipMalloc(&db->d_small, kSmallSc * sizeof(int32_t)));
         LDB_TRY(hipHostMalloc(&db->h_small, kSmallSc * sizeof(int32_t), hipHostMallocDefault));
+    }
+    if (kind == MRS_LOOPDB_M2DP) {
+        LDB_TRY(hipMalloc(&db->d_small, kSmallM2dp * sizeof(int32_t)));
+        LDB_TRY(hipHostMalloc(&db->h_small, kSmallM2dp * sizeof(int32_t), hipHostMallocDefault));
     }
 #undef LDB_TRY
     {
@@ -399,7 +415,7 @@ int mrs_loopdb_clear(mrs_loopdb* db)
 int mrs_loopdb_append(mrs_loopdb* db, const void* descriptor, int32_t form, int32_t count, mrs_stream stream)
 {
     MRS_REQUIRE(db && descriptor, "null pointer");
-    MRS_REQUIRE(db->kind == MRS_LOOPDB_RING || db->kind == MRS_LOOPDB_RINGPP, "not a RING / RING++ database (DiSCO: mrs_loopdb_append_disco, SC: mrs_loopdb_append_sc)");
+    MRS_REQUIRE(db->kind == MRS_LOOPDB_RING || db->kind == MRS_LOOPDB_RINGPP, "not a RING / RING++ database (DiSCO: mrs_loopdb_append_disco, SC: mrs_loopdb_append_sc, M2DP: mrs_loopdb_append_m2dp)");
     MRS_REQUIRE(form == MRS_LOOPDB_FORM_HOST || form == MRS_LOOPDB_FORM_DEVICE || form == MRS_LOOPDB_FORM_DEVICE_SPEC, "unknown form");
     MRS_REQUIRE(count >= 1 && (count == 1 || form == MRS_LOOPDB_FORM_DEVICE_SPEC), "several entries per call only as device half spectra");
     MRS_HIP_TRY(hipSetDevice(db->ctx->device));
@@ -431,7 +447,7 @@ int mrs_loopdb_query(mrs_loopdb* db, const void* descriptor, int32_t form, float
                      mrs_stream stream)
 {
     MRS_REQUIRE(db && descriptor && h_count, "null pointer");
-    MRS_REQUIRE(db->kind == MRS_LOOPDB_RING || db->kind == MRS_LOOPDB_RINGPP, "not a RING / RING++ database (DiSCO: mrs_loopdb_query_disco, SC: mrs_loopdb_query_sc)");
+    MRS_REQUIRE(db->kind == MRS_LOOPDB_RING || db->kind == MRS_LOOPDB_RINGPP, "not a RING / RING++ database (DiSCO: mrs_loopdb_query_disco, SC: mrs_loopdb_query_sc, M2DP: mrs_loopdb_query_m2dp)");
     MRS_REQUIRE(form == MRS_LOOPDB_FORM_HOST || form == MRS_LOOPDB_FORM_DEVICE || form == MRS_LOOPDB_FORM_DEVICE_SPEC, "unknown form");
     MRS_REQUIRE(max_out >= 0 && (max_out == 0 || (h_index && h_dist && h_angle)), "output arrays");
     MRS_REQUIRE(all_capacity >= 0 && (all_capacity == 0 || h_all_dist || h_all_angle), "all_capacity without an array");
@@ -467,7 +483,7 @@ int mrs_loopdb_query_multi(mrs_loopdb* db, const void* descriptors, int32_t form
                            int32_t* h_all_angle, int32_t* h_n, mrs_stream stream)
 {
     MRS_REQUIRE(db && descriptors && h_all_dist && h_all_angle && h_n, "null pointer");
-    MRS_REQUIRE(db->kind == MRS_LOOPDB_RING || db->kind == MRS_LOOPDB_RINGPP, "not a RING / RING++ database (DiSCO: mrs_loopdb_query_disco, SC: mrs_loopdb_query_sc)");
+    MRS_REQUIRE(db->kind == MRS_LOOPDB_RING || db->kind == MRS_LOOPDB_RINGPP, "not a RING / RING++ database (DiSCO: mrs_loopdb_query_disco, SC: mrs_loopdb_query_sc, M2DP: mrs_loopdb_query_m2dp)");
     MRS_REQUIRE(form == MRS_LOOPDB_FORM_HOST || form == MRS_LOOPDB_FORM_DEVICE || form == MRS_LOOPDB_FORM_DEVICE_SPEC, "unknown form");
     MRS_REQUIRE(count >= 1 && count <= 1024 && all_capacity >= 0, "count in 1..1024");
     MRS_HIP_TRY(hipSetDevice(db->ctx->device));
@@ -716,6 +732,69 @@ int mrs_loopdb_query_sc_all(mrs_loopdb* db, const float* sc, int32_t on_device, 
         memcpy(h_all_dist, db->h_dist, m * sizeof(float));
         memcpy(h_all_shift, db->h_angle, m * sizeof(int32_t));
     }
+    return MRS_OK;
+}
+
+// ---- M2DP ---------------------------------------------------------------------------------------------------------------------------
+
+namespace {
+// the descriptor argument (192 doubles, host or device) -> float32 [192] at `dst`, on the handle's stream (lock held)
+int m2dp_to_row(mrs_loopdb* db, const double* desc, int32_t on_device, mrs_stream stream, float* dst)
+{
+    const double* src = desc;
+    if (on_device) {
+        int st = join_in(db, (hipStream_t)stream);
+        if (st != MRS_OK) return st;
+    } else {
+        int st = upload(db, desc, kM2dpDim * sizeof(double), db->d_in);
+        if (st != MRS_OK) return st;
+        src = reinterpret_cast<const double*>(db->d_in);
+    }
+    hipLaunchKernelGGL(k_m2dp_to_float, dim3(1), dim3(256), 0, db->s, src, dst);
+    MRS_HIP_TRY(hipGetLastError());
+    return sc_release_arg(db, on_device, stream);
+}
+}  // namespace
+
+int mrs_loopdb_append_m2dp(mrs_loopdb* db, const double* desc, int32_t on_device, mrs_stream stream)
+{
+    MRS_REQUIRE(db && desc, "null pointer");
+    MRS_REQUIRE(db->kind == MRS_LOOPDB_M2DP, "not an M2DP database");
+    MRS_HIP_TRY(hipSetDevice(db->ctx->device));
+    std::lock_guard<std::mutex> lk(db->mu);
+    int st = reserve_locked(db, db->n + 1);
+    if (st != MRS_OK) return st;
+    st = m2dp_to_row(db, desc, on_device, stream, db->d_entries + (size_t)db->n * db->entry_floats);
+    if (st != MRS_OK) return st;
+    db->n += 1;
+    return MRS_OK;
+}
+
+int mrs_loopdb_query_m2dp(mrs_loopdb* db, const double* desc, int32_t on_device, int32_t k, int32_t* h_index, float* h_dist2, int32_t* h_count,
+                          mrs_stream stream)
+{
+    MRS_REQUIRE(db && desc && h_index && h_dist2 && h_count, "null pointer");
+    MRS_REQUIRE(db->kind == MRS_LOOPDB_M2DP, "not an M2DP database");
+    MRS_REQUIRE(k >= 1 && k <= kM2dpMaxK, "k in 1..32");
+    MRS_HIP_TRY(hipSetDevice(db->ctx->device));
+    std::lock_guard<std::mutex> lk(db->mu);
+    for (int i = 0; i < k; ++i) { h_index[i] = -1; h_dist2[i] = INFINITY; }
+    *h_count = 0;
+    const int n = db->n;
+    if (n == 0) return MRS_OK;
+    int st = m2dp_to_row(db, desc, on_device, stream, db->d_query);
+    if (st != MRS_OK) return st;
+    st = mrs_signature_knn(db->ctx, db->d_query, 1, db->d_entries, n, kM2dpDim, k, db->d_small, reinterpret_cast<float*>(db->d_small + kM2dpMaxK),
+                           db->s);
+    if (st != MRS_OK) return st;
+    MRS_HIP_TRY(hipMemcpyAsync(db->h_small, db->d_small, kSmallM2dp * sizeof(int32_t), hipMemcpyDeviceToHost, db->s));
+    MRS_HIP_TRY(hipStreamSynchronize(db->s));
+    const int cnt = std::min(k, n);
+    for (int i = 0; i < cnt; ++i) {
+        h_index[i] = db->h_small[i];
+        memcpy(&h_dist2[i], &db->h_small[kM2dpMaxK + i], sizeof(float));
+    }
+    *h_count = cnt;
     return MRS_OK;
 }
 
