@@ -531,6 +531,55 @@ int mrs_crop_scale_batch(mrs_ctx* ctx, const void* d_points, int32_t is_double, 
                          float* d_xyz_soa, int64_t* d_out_offsets, mrs_stream stream);
 
 /* ------------------------------------------------------------------------------------
+ * GICP submap assembly from a resident keyframe store
+ * ---------------------------------------------------------------------------------- */
+
+/* GlobalManager::mergeNearestKeyframes (Mapping/src/global_manager/src/global_manager.cpp:1894-1939; called twice per loop candidate by
+ * ICPCheck, :1968-1969) concatenates the 2 * submap_size + 1 keyframes around the loop keyframe, each moved into the loop keyframe's frame
+ * by currPose.inverse() * nearPose, keeps x and y in [-60, 60] (pcl::PassThrough) and runs pcl::VoxelGrid with leaf icp_filter_size -- on the
+ * host, on whole clouds, once per candidate.  A mrs_keyframes keeps one robot's keyframes on the device (an arena of float4 x, y, z,
+ * intensity; poses on the host) and builds the submaps of a whole batch of candidates in one chain of launches, in the layout
+ * mrs_gicp_batch_set_clouds takes (stride_floats = 4).  DESIGN.md section 4.11 states the arithmetic (float32, one rounding per operation,
+ * no fused multiply-add; exact pcl::VoxelGrid cells and output order, 64-bit keys) and the deviations from the reference.  Thread-safe (one
+ * lock per handle); the device work of a handle runs on the handle's own stream, `stream` is the stream that produced a DEVICE argument or
+ * uses d_out (the handle waits for it).  "Bad argument" below is MRS_ERR_ARG, checked before any launch. */
+typedef struct mrs_keyframes mrs_keyframes;
+/* capacity_hint_points: points to allocate up front (the arena doubles when it runs out; earlier keyframes keep their ids and bits) */
+int mrs_keyframes_create(mrs_ctx* ctx, int64_t capacity_hint_points, mrs_keyframes** out);
+int mrs_keyframes_destroy(mrs_keyframes* kf);
+/* *out_n = keyframes stored, *out_points (optional) = their points */
+int mrs_keyframes_size(mrs_keyframes* kf, int32_t* out_n, int64_t* out_points);
+/* `keyframes.push_back(cloud)` + `trajectory.push_back(pose)`: points [n][stride] float (is_double = 0) or double (1), xyz first, stride 3, 4
+ * or 8 (pygicp's Nx3, pcl::PointXYZ, pcl::PointXYZI), in HOST (on_device = 0; staged through pinned memory, blocking) or DEVICE memory;
+ * intensity_col = the column that holds the intensity (4 in a pcl::PointXYZI, 3 in a packed x y z i row) or -1 for none (stored as 0).
+ * h_pose16: row-major float32 4x4 rigid transform.  *out_id = the new keyframe's id (0, 1, 2 ...).  One copy (float [n][4] with the
+ * intensity in column 3) or one conversion kernel. */
+int mrs_keyframes_append(mrs_keyframes* kf, const void* points, int32_t on_device, int32_t is_double, int32_t stride, int32_t intensity_col,
+                         int64_t n, const float* h_pose16, int32_t* out_id, mrs_stream stream);
+/* the pose graph re-optimises trajectories (global_manager.cpp:636-664): the pose of keyframe `id` replaced, its points untouched */
+int mrs_keyframes_set_pose(mrs_keyframes* kf, int32_t id, const float* h_pose16);
+/* h_pose16 <- the pose of keyframe `id`, *out_points (optional) <- its point count */
+int mrs_keyframes_get_pose(mrs_keyframes* kf, int32_t id, float* h_pose16, int64_t* out_points);
+
+/* n_submaps submaps from explicit segments: segment i puts keyframe h_seg_keyframe[i], moved by the row-major float32 4x4 h_seg_T16 + 16 i,
+ * into submap h_seg_submap[i]; segments are listed in ascending submap order (a submap may have none).  Every point is transformed
+ * (x' = ((T00 x + T01 y) + T02 z) + T03 ...), dropped unless x', y', z' are finite and -crop <= x', y' <= crop, and the survivors of a
+ * submap go through the voxel grid: cell = floorf(v * (1.0f / leaf)), key = (i - min.x) + (j - min.y) div.x + (k - min.z) div.x div.y in 64
+ * bits, one output point per occupied voxel in ascending key order = the mean of x', y', z', intensity over the voxel's points.
+ * d_out float[capacity_points][4] (device) receives the submaps one after the other, h_offsets int64[n_submaps + 1] (host) their extents.
+ * capacity_points must be at least the sum of the segments' point counts (otherwise: bad argument, nothing written).  Bad argument too:
+ * leaf <= 0 or not finite, crop < 0 or not finite, a keyframe id out of range, and (after the launches) a grid whose keys need more than
+ * 63 bits.  Results are the same bits from run to run and do not depend on the batch a submap is in.  One host synchronisation, at the end. */
+int mrs_submap_assemble(mrs_keyframes* kf, int32_t n_submaps, int32_t n_segments, const int32_t* h_seg_submap, const int32_t* h_seg_keyframe,
+                        const float* h_seg_T16, float crop, float leaf, float* d_out, int64_t capacity_points, int64_t* h_offsets,
+                        mrs_stream stream);
+/* mergeNearestKeyframes for n_submaps loop keyframes at once: submap b = the keyframes h_loop_ids[b] + i, i = -submap_size .. submap_size,
+ * with 0 < id < size (the reference's `keyNear <= 0` skip is kept: keyframe 0 is never merged; its `keyNear == size()` read past the vector
+ * is not), each moved by inverse(pose[loop id]) * pose[id], computed on the host in float32 term by term.  Then as mrs_submap_assemble. */
+int mrs_submap_merge_nearest(mrs_keyframes* kf, int32_t n_submaps, const int32_t* h_loop_ids, int32_t submap_size, float crop, float leaf,
+                             float* d_out, int64_t capacity_points, int64_t* h_offsets, mrs_stream stream);
+
+/* ------------------------------------------------------------------------------------
  * Multi-GPU exchange of the descriptor database over RCCL / xGMI
  * ---------------------------------------------------------------------------------- */
 

@@ -1,0 +1,126 @@
+"""GICP submaps assembled on the GPU from a resident keyframe store (row G0).  Host logic only; the kernels live in csrc/submap.hip.
+
+Replaces GlobalManager::mergeNearestKeyframes (Mapping/src/global_manager/src/global_manager.cpp:1894-1939): the keyframes around a loop
+keyframe moved into its frame, pass-through on x and y, exact voxel grid.  What assemble / merge_nearest return is the (points, offsets)
+tuple GicpBatch.set_sources / set_targets take, so a submap goes from the store to the registration without leaving the device.
+"""
+import ctypes as C
+
+import numpy as np
+import torch
+
+from . import _lib
+
+F = np.float32
+
+
+def nearest_keyframe_ids(loop_id, submap_size, n_keyframes):
+    """The keyframes mergeNearestKeyframes merges around loop_id (global_manager.cpp:1901-1905): loop_id + i for i = -submap_size ..
+    submap_size, in that order, kept where 0 < id < n_keyframes.  The reference's `keyNear <= 0` skip is kept on purpose (keyframe 0 is
+    never merged, a centre of 0 yields only its later neighbours); its `keyNear > size()` test lets id == size() through and reads past
+    the vector: that id is dropped here."""
+    return [loop_id + i for i in range(-submap_size, submap_size + 1) if 0 < loop_id + i < n_keyframes]
+
+
+def relative_transform(center_pose, near_pose):
+    """currPose.inverse() * nearPose (global_manager.cpp:1908-1911) for rigid row-major 4x4 poses, in float32, every product and sum
+    rounded once in the written order (what mrs_submap_merge_nearest computes on the host): Ri = Rc^T,
+    ti[i] = -((Ri[i,0] tc[0] + Ri[i,1] tc[1]) + Ri[i,2] tc[2]), T[i,j] = (Ri[i,0] Pk[0,j] + Ri[i,1] Pk[1,j]) + Ri[i,2] Pk[2,j],
+    T[i,3] = ((Ri[i,0] Pk[0,3] + Ri[i,1] Pk[1,3]) + Ri[i,2] Pk[2,3]) + ti[i].  -> float32 [4, 4]"""
+    Pc, Pk = np.asarray(center_pose, F).reshape(4, 4), np.asarray(near_pose, F).reshape(4, 4)
+    Ri, tc = Pc[:3, :3].T, Pc[:3, 3]
+    T = np.zeros((4, 4), F)
+    T[3, 3] = 1
+    for i in range(3):
+        ti = -((Ri[i, 0] * tc[0] + Ri[i, 1] * tc[1]) + Ri[i, 2] * tc[2])
+        T[i, :3] = (Ri[i, 0] * Pk[0, :3] + Ri[i, 1] * Pk[1, :3]) + Ri[i, 2] * Pk[2, :3]
+        T[i, 3] = ((Ri[i, 0] * Pk[0, 3] + Ri[i, 1] * Pk[1, 3]) + Ri[i, 2] * Pk[2, 3]) + ti
+    return T
+
+
+class KeyframeStore:
+    """One robot's keyframes (thisRobotHandle->keyframes / ->trajectory) resident on one GPU."""
+
+    def __init__(self, device=0, capacity_hint=1 << 20):
+        self.device = device
+        self._h = C.c_void_p()
+        self._counts = []
+        _lib.load().mrs_keyframes_create(_lib.ctx(device), int(capacity_hint), C.byref(self._h))
+
+    def __del__(self):
+        try:
+            if getattr(self, "_h", None):
+                _lib.load().mrs_keyframes_destroy(self._h)
+        except Exception:
+            pass
+
+    def __len__(self):
+        return len(self._counts)
+
+    def append(self, points, pose, intensity_col=None):
+        """points: [n, 3 | 4 | 8] float32 or float64, a host array or a device tensor; the intensity is column 3 of a 4-column cloud and
+        column 4 of an 8-column one (pcl::PointXYZI) unless intensity_col says otherwise, and 0 for 3 columns.  pose: 4x4.  -> the id"""
+        on_device = isinstance(points, torch.Tensor) and points.is_cuda
+        if on_device:
+            if points.dtype not in (torch.float32, torch.float64):
+                points = points.to(torch.float32)
+            points = points.contiguous()
+            is_double = points.dtype == torch.float64
+        else:
+            points = np.asarray(points)
+            if points.dtype not in (np.float32, np.float64):
+                points = points.astype(F)
+            points = np.ascontiguousarray(points)
+            is_double = points.dtype == np.float64
+        if points.ndim != 2 or points.shape[1] not in (3, 4, 8):
+            raise ValueError("points must be [n, 3], [n, 4] or [n, 8]")
+        n, stride = int(points.shape[0]), int(points.shape[1])
+        if intensity_col is None:
+            intensity_col = {3: -1, 4: 3, 8: 4}[stride]
+        pose = np.ascontiguousarray(np.asarray(pose, F).reshape(16))
+        kid = C.c_int32(-1)
+        _lib.load().mrs_keyframes_append(self._h, points if n else None, int(on_device), int(is_double), stride, int(intensity_col), n, pose,
+                                         C.byref(kid), _lib.current_stream(self.device))
+        self._counts.append(n)
+        return kid.value
+
+    def set_pose(self, kid, pose):
+        _lib.load().mrs_keyframes_set_pose(self._h, int(kid), np.ascontiguousarray(np.asarray(pose, F).reshape(16)))
+
+    def pose(self, kid):
+        out = np.empty(16, F)
+        _lib.load().mrs_keyframes_get_pose(self._h, int(kid), out, None)
+        return out.reshape(4, 4)
+
+    def _out(self, capacity):
+        return torch.empty((max(int(capacity), 1), 4), dtype=torch.float32, device=f"cuda:{self.device}")
+
+    @staticmethod
+    def _trim(out, m):
+        """The first m rows of the capacity-sized output buffer.  The buffer holds one row per SEGMENT point (about three times the
+        voxels at leaf 0.2), and a view would keep all of it alive for as long as the caller holds the result, so when less than half
+        of it is used the rows are copied out (16 B per voxel, on the device) and the buffer is released."""
+        return out[:m].clone() if 2 * m < out.shape[0] else out[:m]
+
+    def assemble(self, segments, crop=60.0, leaf=0.2):
+        """segments: one list per submap of (keyframe id, T 4x4) pairs.  -> (points float32 device [M, 4], offsets int64 host [B + 1])"""
+        sub = np.array([b for b, segs in enumerate(segments) for _ in segs], np.int32)
+        kfs = np.array([k for segs in segments for k, _ in segs], np.int32)
+        Ts = np.ascontiguousarray(np.array([np.asarray(T, F).reshape(16) for segs in segments for _, T in segs], F).reshape(-1, 16))
+        capacity = sum(self._counts[k] for k in kfs if 0 <= k < len(self._counts))
+        out, offs = self._out(capacity), np.zeros(len(segments) + 1, np.int64)
+        _lib.load().mrs_submap_assemble(self._h, len(segments), int(sub.size), sub if sub.size else None, kfs if sub.size else None,
+                                        Ts if sub.size else None, float(crop), float(leaf), out, capacity, offs,
+                                        _lib.current_stream(self.device))
+        return self._trim(out, int(offs[-1])), offs
+
+    def merge_nearest(self, loop_ids, submap_size, crop=60.0, leaf=0.2):
+        """mergeNearestKeyframes for every loop keyframe of loop_ids in one set of launches.  -> (points float32 device [M, 4], offsets
+        int64 host [B + 1])"""
+        ids = np.ascontiguousarray(loop_ids, dtype=np.int32).reshape(-1)
+        n = len(self._counts)
+        capacity = sum(self._counts[k] for c in ids for k in nearest_keyframe_ids(int(c), int(submap_size), n))
+        out, offs = self._out(capacity), np.zeros(ids.size + 1, np.int64)
+        _lib.load().mrs_submap_merge_nearest(self._h, int(ids.size), ids if ids.size else None, int(submap_size), float(crop), float(leaf),
+                                             out, capacity, offs, _lib.current_stream(self.device))
+        return self._trim(out, int(offs[-1])), offs
