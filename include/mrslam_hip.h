@@ -580,6 +580,31 @@ int mrs_submap_merge_nearest(mrs_keyframes* kf, int32_t n_submaps, const int32_t
                              float* d_out, int64_t capacity_points, int64_t* h_offsets, mrs_stream stream);
 
 /* ------------------------------------------------------------------------------------
+ * The merged multi-robot map composed from the keyframe stores
+ * ---------------------------------------------------------------------------------- */
+
+/* GlobalManager::composeGlobalMap (Mapping/src/global_manager/src/global_manager.cpp:2090-2210) / savingGlobalMap (:143-170): every robot's
+ * keyframes moved by their optimised poses, concatenated, one pcl::VoxelGrid with leaf globalmap_voxel_leaf_size_ over the whole thing.
+ * ONE voxel grid for the whole call (the point arithmetic, cells, keys and output order are section 4.11's).  The
+ * input is, in this order: the optional previous map d_prev, float[n_prev][4] on the device, taken as it is (the incremental branch,
+ * :2170-2189: an old centroid counts as one point), then segment 0, 1, ...: keyframe h_seg_keyframe[i] of stores[h_seg_store[i]] moved by
+ * the row-major float32 4x4 h_seg_T16 + 16 i; segments of different stores may interleave, and a store may be listed more than once.  A
+ * point is dropped only if x', y' or z' is not finite; there is no crop.  d_out float[capacity_points][4] (device) receives one point per
+ * occupied voxel in ascending key order, the mean of x', y', z', intensity, summed in float64 in an order fixed by the input alone and
+ * rounded to float32 once: the same bits from call to call.  *out_points = the number of voxels.
+ * Bad argument (MRS_ERR_ARG), checked before any launch, nothing written: a null pointer where one is needed, n_stores outside
+ * 1 .. MRS_MAP_MAX_STORES, stores on different devices, a store index or keyframe id out of range, a transform or leaf that is not finite,
+ * leaf <= 0, capacity_points < n_prev + the segments' point counts, more than 2^31 - 1 input points, d_prev overlapping d_out.  MRS_ERR_ARG
+ * too, after the first launches, when the grid's keys need more than 63 bits.
+ * Thread-safe: every distinct store is locked once, in address order.  The device work runs on the first store's stream, which waits for
+ * the other stores' streams and for `stream` (the stream that produced d_prev and uses d_out).  Two host synchronisations: one for the
+ * key width, one at the end. */
+#define MRS_MAP_MAX_STORES 16
+int mrs_map_compose(int32_t n_stores, mrs_keyframes* const* stores, int32_t n_segments, const int32_t* h_seg_store,
+                    const int32_t* h_seg_keyframe, const float* h_seg_T16, const float* d_prev, int64_t n_prev, float leaf, float* d_out,
+                    int64_t capacity_points, int64_t* out_points, mrs_stream stream);
+
+/* ------------------------------------------------------------------------------------
  * Multi-GPU exchange of the descriptor database over RCCL / xGMI
  * ---------------------------------------------------------------------------------- */
 
