@@ -356,6 +356,49 @@ int mrs_gicp_batch_set_search(mrs_gicp_batch* h, int32_t core);
 /* share of (source point, nearest-neighbour pass) of the last align() that needed a search (1.0 without certificates) */
 double mrs_gicp_batch_last_searched_fraction(const mrs_gicp_batch* h);
 
+/* Point-to-point ICP (row G9): pcl::IterativeClosestPoint<PointXYZI, PointXYZI> as GlobalManager::performLoopClosure
+ * (global_manager.cpp:890-906) and the PCL_ICP branch of select_registration_method (:2427-2434) drive it, batched over the pairs of a
+ * mrs_gicp_batch: same handle, same clouds (set_clouds / set_clouds_host / set_clouds_from), same exact searches; no covariances are
+ * computed.  PCL is not part of the reference tree: DESIGN.md section 4.13 is the definition (TransformationEstimationSVD + DefaultConvergenceCriteria
+ * with max_iterations_similar_transforms = 0; the pose accumulates in fp64), parity with PCL is unpinned.  Names and defaults are PCL's. */
+typedef struct mrs_icp_params {
+    int32_t max_iterations;             /* setMaximumIterations (10; Mapping: icp_iters)                        */
+    int32_t force_iterations;           /* > 0: exactly this many iterations, stopping rules disabled (timing,
+                                           fixed-length parity); converged = 0, state NOT_CONVERGED             */
+    double max_correspondence_distance; /* setMaxCorrespondenceDistance (sqrt(DBL_MAX); Mapping: 2.0 and 100)   */
+    double transformation_epsilon;      /* setTransformationEpsilon (0; Mapping: 1e-3): bound on the SQUARED
+                                           translation of an increment, and 1 - it on the cosine of its angle  */
+    double rotation_epsilon;            /* setTransformationRotationEpsilon (0 = derive from the above)         */
+    double euclidean_fitness_epsilon;   /* setEuclideanFitnessEpsilon (-DBL_MAX = never; Mapping: 1e-3):
+                                           relative change of the mean squared correspondence distance         */
+} mrs_icp_params;
+
+void mrs_icp_default_params(mrs_icp_params* p);
+
+/* align(output, guess) of every pair.  h_guess / h_final as in mrs_gicp_batch_align; h_converged, h_iterations and h_state
+ * (int32[n_pairs], each optional): hasConverged(), iterations run, and the ConvergenceState that ended the pair: 0 NOT_CONVERGED,
+ * 1 ITERATIONS, 2 TRANSFORM, 3 ABS_MSE, 4 REL_MSE, 5 NO_CORRESPONDENCES (fewer than 3 correspondences: converged = 0, the pose stays).
+ * getFitnessScore is mrs_gicp_batch_fitness.  Synchronises `stream`.  The handle's GICP parameters are not used: in particular a
+ * voxel_resolution > 0 is ignored (ICP always searches the target points; the voxelised mode has no ICP counterpart).  An alignment leaves nothing behind that a later
+ * mrs_gicp_batch_align or mrs_gicp_batch_align_icp on the same handle depends on. */
+int mrs_gicp_batch_align_icp(mrs_gicp_batch* h, const mrs_icp_params* p, const double* h_guess, double* h_final, int32_t* h_converged,
+                             int32_t* h_iterations, int32_t* h_state, mrs_stream stream);
+
+/* One iteration's correspondences, sums and rigid fit at given poses (kernel-level parity hook, the twin of mrs_gicp_batch_linearize):
+ * h_sums double[n_pairs][17] = n, sum a (3), sum b (3), sum a b^T (9, row-major), sum |b - a|^2 with a = pose * source point and b its
+ * nearest target point; h_delta double[n_pairs][16] the fitted increment (identity below 3 correspondences); d_corr (optional)
+ * int32[total source points] correspondences or -1. */
+int mrs_gicp_batch_icp_step(mrs_gicp_batch* h, const mrs_icp_params* p, const double* h_poses, double* h_sums, double* h_delta,
+                            int32_t* d_corr, mrs_stream stream);
+
+/* Measurement hook of tools/bench_icp.py (no reference counterpart): the three stages of one ICP iteration launched alone between HIP
+ * events on `stream`, `reps` times each, at the given poses (double[n_pairs][16]).  out_ms float[3]: 0 the search of every source point
+ * (the handle's search setting, warm), 1 k_icp_sums, 2 k_icp_update.  out_counts int64[2]: source points, correspondences at the poses.
+ * The batch's correspondences and warm-start seeds are overwritten, and the repeated launches of k_icp_update keep composing the same
+ * increment into the poses: the alignment state the call leaves behind is meaningless (the next align / align_icp starts over anyway). */
+int mrs_gicp_batch_icp_profile(mrs_gicp_batch* h, const mrs_icp_params* p, const double* h_poses, int32_t reps, float* out_ms,
+                               int64_t* out_counts, mrs_stream stream);
+
 /* ------------------------------------------------------------------------------------
  * rocFFT-backed 2-D correlations: DiSCO (rows D1, D2) and RING++ BEV translation (row C4)
  * ---------------------------------------------------------------------------------- */

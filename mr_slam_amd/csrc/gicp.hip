@@ -1,5 +1,6 @@
 // gicp.hip -- host side of the batched GICP refinement: the handle (owning device buffers), the launch helpers and the C entry points.
 // The kernels and the design notes are in gicp_device.hpp, included here and nowhere else (one translation unit).
+// Point-to-point ICP (row G9) runs on the same handle: its kernels are in icp_device.hpp, its entry points at the end of the align section.
 #include <hipcub/hipcub.hpp>
 
 #include <cstdlib>
@@ -7,6 +8,7 @@
 
 #include "common.hpp"
 #include "gicp_device.hpp"
+#include "icp_device.hpp"
 
 // Small batches (<= kLmWindowPairs pairs: ONE registration at a time is how the nodes call it, main_RING.py:81-104, global_manager.cpp:2016-2021)
 // run the LM schedule in windows of kLmWindow ticks without a host round trip in between: every kernel of a tick gates itself on the pair's
@@ -199,7 +201,7 @@ int build_leaf_hier(mrs_gicp_batch* h, int w, const unsigned long long* d_keys, 
 // culling; more = every LDS candidate read serves more distance evaluations.  Measured (120k x 120k, MI355X):
 // 2 beats 4 at every batch size (23.5k vs 21.4k it/s at 256 pairs, 14.3k vs 11.1k at 16) and 1 only wins when a
 // single pair would otherwise leave most CUs idle.
-void launch_nn_scan(mrs_gicp_batch* h, float* lb_out, int gate, hipStream_t s)
+void launch_nn_scan(mrs_gicp_batch* h, const GicpParams& prm, float* lb_out, int gate, hipStream_t s)
 {
     const GicpCloud &S = h->side[0], &T = h->side[1];
     const int P = h->n_pairs, longest_src = (int)S.longest;
@@ -207,7 +209,7 @@ void launch_nn_scan(mrs_gicp_batch* h, float* lb_out, int gate, hipStream_t s)
     auto wgs = [&](int pts) { return (long)P * ((longest_src + kNNThreads * pts - 1) / (kNNThreads * pts)); };
     auto launch = [&](auto kernel, int pts) {
         hipLaunchKernelGGL(kernel, dim3((unsigned)(wgs(pts) / P), P), dim3(kNNThreads), 0, s, S.pts.get(), S.d_offs.get(), T.pts.get(), T.d_offs.get(),
-                           T.tile_base.get(), T.tlo.get(), T.thi.get(), T.mlo.get(), T.mhi.get(), h->lm.state.get(), h->prm, h->lm.corr.get(),
+                           T.tile_base.get(), T.tlo.get(), T.thi.get(), T.mlo.get(), T.mhi.get(), h->lm.state.get(), prm, h->lm.corr.get(),
                            h->lm.seed.get(), T.bbox.get(), lb_out, gate);
     };
     if (wgs(2) >= 3L * cus)
@@ -220,12 +222,12 @@ void launch_nn_scan(mrs_gicp_batch* h, float* lb_out, int gate, hipStream_t s)
 dim3 cert_grid(const mrs_gicp_batch* h) { return dim3((unsigned)(((int)h->side[0].longest + kCertBlock - 1) / kCertBlock), h->n_pairs); }
 
 // work_lists: only the queries that k_nn_certify left on the work lists (else every point)
-void launch_nn_scan_g(mrs_gicp_batch* h, bool work_lists, hipStream_t s)
+void launch_nn_scan_g(mrs_gicp_batch* h, const GicpParams& prm, bool work_lists, hipStream_t s)
 {
     const GicpCloud &S = h->side[0], &T = h->side[1];
     auto launch = [&](auto kernel) {
         hipLaunchKernelGGL(kernel, cert_grid(h), dim3(kNNThreads), 0, s, S.pts.get(), S.d_offs.get(), T.pts.get(), T.d_offs.get(), T.hier(),
-                           h->lm.state.get(), h->prm, h->lm.corr.get(), h->lm.seed.get(), T.bbox.get(), h->cert.view());
+                           h->lm.state.get(), prm, h->lm.corr.get(), h->lm.seed.get(), T.bbox.get(), h->cert.view());
     };
     if (!work_lists)
         launch(k_nn_scan_g<false>);
@@ -233,11 +235,11 @@ void launch_nn_scan_g(mrs_gicp_batch* h, bool work_lists, hipStream_t s)
         launch(k_nn_scan_g<true>);
 }
 
-void launch_nn_certify(mrs_gicp_batch* h, hipStream_t s)
+void launch_nn_certify(mrs_gicp_batch* h, const GicpParams& prm, hipStream_t s)
 {
     const GicpCloud &S = h->side[0], &T = h->side[1];
     hipLaunchKernelGGL(k_nn_certify, cert_grid(h), dim3(256), 0, s, S.pts.get(), S.d_offs.get(), T.pts.get(), T.d_offs.get(), h->lm.state.get(),
-                       h->prm, h->lm.corr.get(), h->lm.seed.get(), h->cert.view());
+                       prm, h->lm.corr.get(), h->lm.seed.get(), h->cert.view());
 }
 
 void launch_nn_store_pose(mrs_gicp_batch* h, int worklists, hipStream_t s)
@@ -296,29 +298,30 @@ void launch_knn_cov(mrs_gicp_batch* h, int w, int c0, int nc, int k, int* d_knn,
     });
 }
 
-// One nearest-neighbour pass for every pair in phase 0 (h->lm.state): fills h->lm.corr / h->lm.seed.
+// One nearest-neighbour pass for every pair in phase 0 (h->lm.state): fills h->lm.corr / h->lm.seed.  prm: the searches' parameters (the
+// correspondence distance above all): the handle's own for GICP, a copy with ICP's distance for ICP.
 // mode 0: first pass of an align(), 1: later pass, 2: one plain search with the selected core (linearize hook).
 // search_core 0: the round-3 kernel, every point, every pass.  search_core 1 (round-4 schedule):
 //   * first pass, and every pair whose last step moved it by more than prm.motion_switch: the round-3 kernel -- a search whose radius
 //     is decimetres is a broad search, and brute force over fat minis is at its best there (measured: 17 against 26 ms for 5 cold
 //     passes of 64 pairs); it leaves no certificates;
 //   * the other pairs: certify the previous pass's neighbours, search what could not be certified (k_nn_scan_g leaves certificates).
-int nn_pass(mrs_gicp_batch* h, int mode, hipStream_t s)
+int nn_pass(mrs_gicp_batch* h, const GicpParams& prm, int mode, hipStream_t s)
 {
     MRS_REQUIRE(h->search_core == 0 || h->side[1].hier_valid, "target hierarchy missing: set the target clouds after choosing the search setting");
     float* const lb = h->search_core == 1 ? h->cert.lb.get() : nullptr;
     if (h->search_core == 0) {
-        launch_nn_scan(h, lb, 0, s);
+        launch_nn_scan(h, prm, lb, 0, s);
     } else if (mode == 0 && h->cold_core == 0) {
-        launch_nn_scan(h, lb, 0, s);
+        launch_nn_scan(h, prm, lb, 0, s);
         launch_nn_store_pose(h, 0, s);
     } else if (mode != 1 || !h->use_certificates) {
-        launch_nn_scan_g(h, false, s);
+        launch_nn_scan_g(h, prm, false, s);
         launch_nn_store_pose(h, 0, s);
     } else {
-        if (h->big_movers > 0) launch_nn_scan(h, lb, 1, s);
-        launch_nn_certify(h, s);
-        launch_nn_scan_g(h, true, s);
+        if (h->big_movers > 0) launch_nn_scan(h, prm, lb, 1, s);
+        launch_nn_certify(h, prm, s);
+        launch_nn_scan_g(h, prm, true, s);
         launch_nn_store_pose(h, 1, s);
     }
     MRS_HIP_TRY(hipGetLastError());
@@ -737,6 +740,21 @@ int mrs_gicp_batch_get_covariances(mrs_gicp_batch* h, int32_t which, double* h_c
     return MRS_OK;
 }
 
+// what the last alignment's searches did: mrs_gicp_batch_last_nn_passes / _last_searched_fraction
+static int record_search_stats(mrs_gicp_batch* h, long nn_ticks)
+{
+    h->last_nn_passes = (double)nn_ticks;
+    h->last_searched = 1.0;
+    if (h->search_core == 1 && h->cert.searched && h->prm.voxel_res <= 0.0 && nn_ticks > 0) {
+        std::vector<unsigned long long> stat((size_t)h->n_pairs * kStatStride);
+        MRS_HIP_TRY(hipMemcpy(stat.data(), h->cert.searched.get(), stat.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+        unsigned long long q[2] = {0, 0};
+        for (int p = 0; p < h->n_pairs; ++p) { q[0] += stat[(size_t)p * kStatStride]; q[1] += stat[(size_t)p * kStatStride + 1]; }
+        if (q[1]) h->last_searched = (double)q[0] / (double)q[1];
+    }
+    return MRS_OK;
+}
+
 static int ensure_state(mrs_gicp_batch* h)
 {
     const GicpCloud& S = h->side[0];
@@ -888,7 +906,7 @@ int mrs_gicp_batch_align(mrs_gicp_batch* h, const double* h_guess, double* h_fin
                 // tick out -- k_linearize / k_lm_update leave it alone -- and takes the next one: same transitions, same bits.
                 const int trial_only = (alternate && ((ticks + t) & 1)) ? 1 : 0;
                 h->big_movers = 1;                      // the broad search gates itself on the pair's motion (k_nn_scan: gate)
-                if (!trial_only && (st = nn_pass(h, (ticks == 0 && t == 0) ? 0 : 1, s)) != MRS_OK) return st;
+                if (!trial_only && (st = nn_pass(h, h->prm, (ticks == 0 && t == 0) ? 0 : 1, s)) != MRS_OK) return st;
                 launch_linearize(h, trial_only, s);
                 hipLaunchKernelGGL(k_lm_update, dim3(h->n_pairs), dim3(kLmThreads), 0, s, L.state.get(), L.partial.get(), L.nblocks.get(),
                                    L.max_blocks, h->prm, L.nactive.get() + 4 * t, trial_only);
@@ -908,7 +926,7 @@ int mrs_gicp_batch_align(mrs_gicp_batch* h, const double* h_guess, double* h_fin
         } else {
             if (next[0] > 0) {   // only linearisations search; LM trials score the cached correspondences
                 h->big_movers = next[2];
-                if ((st = nn_pass(h, nn_ticks == 0 ? 0 : 1, s)) != MRS_OK) return st;
+                if ((st = nn_pass(h, h->prm, nn_ticks == 0 ? 0 : 1, s)) != MRS_OK) return st;
             }
             launch_linearize(h, 0, s);
         }
@@ -920,15 +938,7 @@ int mrs_gicp_batch_align(mrs_gicp_batch* h, const double* h_guess, double* h_fin
         MRS_HIP_TRY(hipStreamSynchronize(s));
         ++ticks;
     }
-    h->last_nn_passes = (double)nn_ticks;
-    h->last_searched = 1.0;
-    if (h->search_core == 1 && h->cert.searched && h->prm.voxel_res <= 0.0 && nn_ticks > 0) {
-        std::vector<unsigned long long> stat((size_t)h->n_pairs * kStatStride);
-        MRS_HIP_TRY(hipMemcpy(stat.data(), h->cert.searched.get(), stat.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-        unsigned long long q[2] = {0, 0};
-        for (int p = 0; p < h->n_pairs; ++p) { q[0] += stat[(size_t)p * kStatStride]; q[1] += stat[(size_t)p * kStatStride + 1]; }
-        if (q[1]) h->last_searched = (double)q[0] / (double)q[1];
-    }
+    if ((st = record_search_stats(h, nn_ticks)) != MRS_OK) return st;
     MRS_HIP_TRY(hipMemcpy(init.data(), L.state.get(), init.size() * sizeof(LmState), hipMemcpyDeviceToHost));
     for (int p = 0; p < h->n_pairs; ++p) {
         const LmState& S = init[p];
@@ -938,6 +948,186 @@ int mrs_gicp_batch_align(mrs_gicp_batch* h, const double* h_guess, double* h_fin
         if (h_hessian) memcpy(h_hessian + (size_t)p * 36, S.final_H, sizeof(S.final_H));
     }
     side.completed = true;
+    return MRS_OK;
+}
+
+/* ---- point-to-point ICP (row G9; kernels: icp_device.hpp) ---- */
+
+void mrs_icp_default_params(mrs_icp_params* p)
+{
+    if (!p) return;
+    p->max_iterations = 10;                             // pcl::Registration; Mapping sets icp_iters (global_manager.cpp:892, :2431)
+    p->force_iterations = 0;
+    p->max_correspondence_distance = sqrt(DBL_MAX);     // Mapping: 2.0 (:891) and 100 (:2430)
+    p->transformation_epsilon = 0.0;                    // Mapping: 1e-3 (:893, :2432)
+    p->rotation_epsilon = 0.0;
+    p->euclidean_fitness_epsilon = -DBL_MAX;            // never fires; Mapping: 1e-3 (:894, :2433)
+}
+
+namespace {
+
+int icp_check_params(const mrs_icp_params* p)
+{
+    MRS_REQUIRE(p->max_iterations > 0, "max_iterations must be positive");
+    MRS_REQUIRE(p->force_iterations >= 0, "force_iterations must be >= 0");
+    MRS_REQUIRE(p->max_correspondence_distance > 0, "max_correspondence_distance must be positive");
+    return MRS_OK;
+}
+
+IcpParams icp_device_params(const mrs_gicp_batch* h, const mrs_icp_params* p)
+{
+    IcpParams d;
+    d.crit.trans_eps = p->transformation_epsilon;
+    d.crit.rot_thr = mrs::icp_rotation_threshold(p->rotation_epsilon, p->transformation_epsilon);
+    d.crit.fit_eps = p->euclidean_fitness_epsilon;
+    d.crit.max_iter = p->max_iterations;
+    d.crit.force_iters = p->force_iterations;
+    d.motion_switch = h->prm.motion_switch;
+    d.pad = 0;
+    return d;
+}
+
+// The searches' parameters of an ICP call: the handle's (search margins, motion switch) with ICP's own correspondence distance.
+GicpParams icp_search_params(const mrs_gicp_batch* h, const mrs_icp_params* p)
+{
+    GicpParams sp = h->prm;
+    sp.max_corr2 = p->max_correspondence_distance >= 1e150 ? INFINITY : p->max_correspondence_distance * p->max_correspondence_distance;
+    return sp;
+}
+
+void launch_icp_tick(mrs_gicp_batch* h, const IcpParams& dp, int* n_next, hipStream_t s)
+{
+    const GicpCloud &S = h->side[0], &T = h->side[1];
+    GicpLmBuffers& L = h->lm;
+    hipLaunchKernelGGL(k_icp_sums, dim3(L.max_blocks, h->n_pairs), dim3(kNNThreads), 0, s, S.pts.get(), S.d_offs.get(), T.pts.get(), T.d_offs.get(),
+                       L.state.get(), L.corr.get(), L.partial.get(), L.max_blocks);
+    hipLaunchKernelGGL(k_icp_update, dim3(h->n_pairs), dim3(kLmThreads), 0, s, L.state.get(), L.partial.get(), L.nblocks.get(), L.max_blocks, dp,
+                       n_next);
+}
+
+}  // namespace
+
+/* The tick loop of mrs_gicp_batch_align with one kind of tick: search, sums, update.  No covariances, no voxel map. */
+int mrs_gicp_batch_align_icp(mrs_gicp_batch* h, const mrs_icp_params* p, const double* h_guess, double* h_final, int32_t* h_converged,
+                             int32_t* h_iterations, int32_t* h_state, mrs_stream stream)
+{
+    MRS_REQUIRE(h && p && h_final, "null pointer");
+    MRS_REQUIRE(h->clouds_set(), "set source and target clouds first");
+    MRS_REQUIRE(!h->no_cov, "a covariance-free container holds no correspondence buffers");
+    int st = icp_check_params(p);
+    if (st != MRS_OK) return st;
+    MRS_HIP_TRY(hipSetDevice(h->ctx->device));
+    hipStream_t s = (hipStream_t)stream;
+    if ((st = ensure_state(h)) != MRS_OK) return st;
+    const IcpParams dp = icp_device_params(h, p);
+    const GicpParams sp = icp_search_params(h, p);
+    GicpLmBuffers& L = h->lm;
+    const int P = h->n_pairs;
+    std::vector<LmState> init(P);
+    for (int q = 0; q < P; ++q) {
+        LmState& S = init[q];
+        memset(&S, 0, sizeof(S));
+        for (int i = 0; i < 16; ++i) {
+            const double g = h_guess ? h_guess[(size_t)q * 16 + i] : (i % 5 == 0 ? 1.0 : 0.0);
+            S.x[i] = S.xi[i] = (double)(float)g;     // pcl::Registration::align takes a Matrix4f guess
+        }
+        S.y0 = DBL_MAX; S.active = 1;
+    }
+    MRS_HIP_TRY(hipMemcpyAsync(L.state.get(), init.data(), init.size() * sizeof(LmState), hipMemcpyHostToDevice, s));
+    if (h->cert.searched) MRS_HIP_TRY(hipMemsetAsync(h->cert.searched.get(), 0, (size_t)P * kStatStride * sizeof(unsigned long long), s));
+    const long max_ticks = p->force_iterations > 0 ? p->force_iterations : p->max_iterations;     // one iteration per tick
+    long ticks = 0, nn_ticks = 0;
+    int next[4] = {P, 0, P, 0};
+    int window = kLmWindow;
+    if (const char* v = mrs::dev_env("MRS_GICP_WINDOW")) window = std::max(0, std::min(kLmWindowMax, atoi(v)));
+    if (P <= kLmWindowPairs && window > 1) {
+        // the pinned buffer of a context slot receives a window's counters (its stream and events are not used here)
+        struct Side {
+            mrs_ctx* ctx; hipStream_t s; mrs::SideSlot sl; bool completed;
+            ~Side()
+            {
+                if (!completed && sl.pinned) (void)hipStreamSynchronize(s);
+                mrs::side_release(ctx, sl);
+            }
+        } side{h->ctx, s, {}, false};
+        if ((st = mrs::side_acquire(h->ctx, &side.sl)) != MRS_OK) return st;
+        int* const h_win = side.sl.pinned;
+        while (next[0] > 0 && ticks < max_ticks) {
+            MRS_HIP_TRY(hipMemsetAsync(L.nactive.get(), 0, (size_t)window * 4 * sizeof(int), s));
+            for (int t = 0; t < window; ++t) {
+                h->big_movers = 1;                      // the broad search gates itself on the pair's motion (k_nn_scan: gate)
+                if ((st = nn_pass(h, sp, (ticks == 0 && t == 0) ? 0 : 1, s)) != MRS_OK) return st;
+                launch_icp_tick(h, dp, L.nactive.get() + 4 * t, s);
+            }
+            MRS_HIP_TRY(hipGetLastError());
+            MRS_HIP_TRY(hipMemcpyAsync(h_win, L.nactive.get(), (size_t)window * 4 * sizeof(int), hipMemcpyDeviceToHost, s));
+            MRS_HIP_TRY(hipStreamSynchronize(s));
+            for (int t = 0; t < window; ++t) nn_ticks += h_win[4 * t + 3];
+            for (int i = 0; i < 3; ++i) next[i] = h_win[4 * (window - 1) + i];
+            ticks += window;
+        }
+        side.completed = true;
+    }
+    while (next[0] > 0 && ticks < max_ticks) {
+        MRS_HIP_TRY(hipMemsetAsync(L.nactive.get(), 0, 4 * sizeof(int), s));
+        h->big_movers = next[2];
+        if ((st = nn_pass(h, sp, nn_ticks == 0 ? 0 : 1, s)) != MRS_OK) return st;
+        launch_icp_tick(h, dp, L.nactive.get(), s);
+        ++nn_ticks;
+        MRS_HIP_TRY(hipGetLastError());
+        MRS_HIP_TRY(hipMemcpyAsync(next, L.nactive.get(), 3 * sizeof(int), hipMemcpyDeviceToHost, s));
+        MRS_HIP_TRY(hipStreamSynchronize(s));
+        ++ticks;
+    }
+    if ((st = record_search_stats(h, nn_ticks)) != MRS_OK) return st;
+    MRS_HIP_TRY(hipMemcpy(init.data(), L.state.get(), init.size() * sizeof(LmState), hipMemcpyDeviceToHost));
+    for (int q = 0; q < P; ++q) {
+        const LmState& S = init[q];
+        for (int i = 0; i < 16; ++i) h_final[(size_t)q * 16 + i] = (double)(float)S.x[i];  // final_transformation_ is float
+        if (h_converged) h_converged[q] = S.converged;
+        if (h_iterations) h_iterations[q] = S.outer;
+        if (h_state) h_state[q] = S.inner;
+    }
+    return MRS_OK;
+}
+
+int mrs_gicp_batch_icp_step(mrs_gicp_batch* h, const mrs_icp_params* p, const double* h_poses, double* h_sums, double* h_delta,
+                            int32_t* d_corr, mrs_stream stream)
+{
+    MRS_REQUIRE(h && p && h_poses && h_sums && h_delta, "null pointer");
+    MRS_REQUIRE(h->clouds_set(), "set source and target clouds first");
+    MRS_REQUIRE(!h->no_cov, "a covariance-free container holds no correspondence buffers");
+    int st = icp_check_params(p);
+    if (st != MRS_OK) return st;
+    MRS_HIP_TRY(hipSetDevice(h->ctx->device));
+    hipStream_t s = (hipStream_t)stream;
+    const GicpCloud &S = h->side[0], &T = h->side[1];
+    GicpLmBuffers& L = h->lm;
+    if ((st = ensure_state(h)) != MRS_OK) return st;
+    IcpParams dp = icp_device_params(h, p);
+    dp.crit.max_iter = 1;           // one iteration, then the pair stops whatever the criteria say
+    dp.crit.force_iters = 0;
+    const GicpParams sp = icp_search_params(h, p);
+    std::vector<LmState> init(h->n_pairs);
+    for (int q = 0; q < h->n_pairs; ++q) {
+        memset(&init[q], 0, sizeof(LmState));
+        for (int i = 0; i < 16; ++i) init[q].x[i] = init[q].xi[i] = h_poses[(size_t)q * 16 + i];
+        init[q].y0 = DBL_MAX; init[q].active = 1;
+    }
+    MRS_HIP_TRY(hipMemcpyAsync(L.state.get(), init.data(), init.size() * sizeof(LmState), hipMemcpyHostToDevice, s));
+    MRS_HIP_TRY(hipMemsetAsync(L.nactive.get(), 0, 4 * sizeof(int), s));
+    if ((st = nn_pass(h, sp, 2, s)) != MRS_OK) return st;
+    launch_icp_tick(h, dp, L.nactive.get(), s);
+    if (d_corr)
+        hipLaunchKernelGGL(k_corr_to_original, dim3(64, h->n_pairs), dim3(256), 0, s, S.pts.get(), S.d_offs.get(), T.pts.get(), T.d_offs.get(),
+                           L.corr.get(), d_corr);
+    MRS_HIP_TRY(hipGetLastError());
+    MRS_HIP_TRY(hipMemcpyAsync(init.data(), L.state.get(), init.size() * sizeof(LmState), hipMemcpyDeviceToHost, s));
+    MRS_HIP_TRY(hipStreamSynchronize(s));
+    for (int q = 0; q < h->n_pairs; ++q) {
+        memcpy(h_sums + (size_t)q * kIcpTerms, init[q].H, kIcpTerms * sizeof(double));
+        memcpy(h_delta + (size_t)q * 16, init[q].delta, 16 * sizeof(double));
+    }
     return MRS_OK;
 }
 
@@ -968,7 +1158,7 @@ int mrs_gicp_batch_linearize(mrs_gicp_batch* h, const double* h_poses, double* h
         MRS_REQUIRE(d_corr == nullptr, "per-point correspondences are not defined for the voxelised variant");
         launch_linearize_voxel(h, s);
     } else {
-        if ((st = nn_pass(h, 2, s)) != MRS_OK) return st;
+        if ((st = nn_pass(h, h->prm, 2, s)) != MRS_OK) return st;
         launch_linearize(h, 0, s);
     }
     if (d_corr)
@@ -989,6 +1179,74 @@ int mrs_gicp_batch_linearize(mrs_gicp_batch* h, const double* h_poses, double* h
         for (int r = 0; r < 6; ++r) h_b[(size_t)p * 6 + r] = sum[21 + r];
         h_err[p] = sum[27];
     }
+    return MRS_OK;
+}
+
+/* Measurement hook of tools/bench_icp.py: the three stages of one ICP iteration launched ALONE between HIP events on `stream`, at the given
+ * poses, `reps` times each (the average goes to out_ms): [0] the search of every source point (the handle's search setting, warm),
+ * [1] k_icp_sums, [2] k_icp_update.  out_counts: [0] source points, [1] correspondences at the poses.  Overwrites the batch's correspondences
+ * and warm-start seeds. */
+int mrs_gicp_batch_icp_profile(mrs_gicp_batch* h, const mrs_icp_params* p, const double* h_poses, int32_t reps, float* out_ms, int64_t* out_counts,
+                               mrs_stream stream)
+{
+    MRS_REQUIRE(h && p && h_poses && out_ms && out_counts, "null pointer");
+    MRS_REQUIRE(h->clouds_set(), "set source and target clouds first");
+    MRS_REQUIRE(!h->no_cov, "a covariance-free container holds no correspondence buffers");
+    MRS_REQUIRE(reps >= 1, "reps must be >= 1");
+    int st = icp_check_params(p);
+    if (st != MRS_OK) return st;
+    MRS_HIP_TRY(hipSetDevice(h->ctx->device));
+    hipStream_t s = (hipStream_t)stream;
+    GicpLmBuffers& L = h->lm;
+    if ((st = ensure_state(h)) != MRS_OK) return st;
+    IcpParams dp = icp_device_params(h, p);
+    dp.crit.max_iter = INT32_MAX;       // the update kernel is timed on pairs that stay active: no rule may end them
+    dp.crit.force_iters = INT32_MAX;
+    const GicpParams sp = icp_search_params(h, p);
+    std::vector<LmState> init(h->n_pairs);
+    for (int q = 0; q < h->n_pairs; ++q) {
+        memset(&init[q], 0, sizeof(LmState));
+        for (int i = 0; i < 16; ++i) init[q].x[i] = init[q].xi[i] = h_poses[(size_t)q * 16 + i];
+        init[q].y0 = DBL_MAX; init[q].active = 1;
+    }
+    MRS_HIP_TRY(hipMemcpyAsync(L.state.get(), init.data(), init.size() * sizeof(LmState), hipMemcpyHostToDevice, s));
+    MRS_HIP_TRY(hipStreamSynchronize(s));
+    struct Events {
+        hipEvent_t e0 = nullptr, e1 = nullptr;
+        ~Events() { if (e0) (void)hipEventDestroy(e0); if (e1) (void)hipEventDestroy(e1); }
+    } ev;
+    MRS_HIP_TRY(hipEventCreate(&ev.e0)); MRS_HIP_TRY(hipEventCreate(&ev.e1));
+    auto timed = [&](float& ms, auto&& launch) -> int {
+        launch();                                     // warm
+        MRS_HIP_TRY(hipEventRecord(ev.e0, s));
+        for (int r = 0; r < reps; ++r) launch();
+        MRS_HIP_TRY(hipEventRecord(ev.e1, s));
+        MRS_HIP_TRY(hipEventSynchronize(ev.e1));
+        MRS_HIP_TRY(hipGetLastError());
+        MRS_HIP_TRY(hipEventElapsedTime(&ms, ev.e0, ev.e1));
+        ms /= (float)reps;
+        return MRS_OK;
+    };
+    const GicpCloud &S = h->side[0], &T = h->side[1];
+    int nn_st = MRS_OK;
+    if ((st = timed(out_ms[0], [&]() { const int r = nn_pass(h, sp, 2, s); if (r != MRS_OK) nn_st = r; })) != MRS_OK) return st;
+    if (nn_st != MRS_OK) return nn_st;
+    if ((st = timed(out_ms[1], [&]() {
+             hipLaunchKernelGGL(k_icp_sums, dim3(L.max_blocks, h->n_pairs), dim3(kNNThreads), 0, s, S.pts.get(), S.d_offs.get(), T.pts.get(),
+                                T.d_offs.get(), L.state.get(), L.corr.get(), L.partial.get(), L.max_blocks);
+         })) != MRS_OK) return st;
+    {
+        std::vector<int> corr(L.n_seed);
+        MRS_HIP_TRY(hipMemcpy(corr.data(), L.corr.get(), corr.size() * sizeof(int), hipMemcpyDeviceToHost));
+        int64_t c = 0;
+        for (int v : corr) c += v >= 0;
+        out_counts[0] = (int64_t)L.n_seed; out_counts[1] = c;
+    }
+    MRS_HIP_TRY(hipMemsetAsync(L.nactive.get(), 0, 4 * sizeof(int), s));
+    if ((st = timed(out_ms[2], [&]() {
+             hipLaunchKernelGGL(k_icp_update, dim3(h->n_pairs), dim3(kLmThreads), 0, s, L.state.get(), L.partial.get(), L.nblocks.get(), L.max_blocks,
+                                dp, L.nactive.get());
+         })) != MRS_OK) return st;
     return MRS_OK;
 }
 
@@ -1050,7 +1308,7 @@ int mrs_gicp_batch_profile(mrs_gicp_batch* h, const double* h_poses, int32_t rep
         return MRS_OK;
     };
     h->search_core = 1; h->cold_core = 0; h->use_certificates = true;      // restored by `guard`
-    auto round3 = [&]() { launch_nn_scan(h, nullptr, 0, s); };
+    auto round3 = [&]() { launch_nn_scan(h, h->prm, nullptr, 0, s); };
     auto linearize = [&]() { launch_linearize(h, 0, s); };
     if ((st = upload(0, 0.0)) != MRS_OK) return st;
     round3();                                         // seeds + correspondences at the poses
@@ -1064,9 +1322,9 @@ int mrs_gicp_batch_profile(mrs_gicp_batch* h, const double* h_poses, int32_t rep
         for (int v : corr) c += v >= 0;
         out_counts[0] = (int64_t)L.n_seed; out_counts[1] = c;
     }
-    if ((st = timed(out_ms[4], [&]() { launch_nn_scan_g(h, false, s); })) != MRS_OK) return st;      // leaves certificates at the poses
+    if ((st = timed(out_ms[4], [&]() { launch_nn_scan_g(h, h->prm, false, s); })) != MRS_OK) return st;      // leaves certificates at the poses
     launch_nn_store_pose(h, 0, s);
-    if ((st = timed(out_ms[3], [&]() { launch_nn_certify(h, s); })) != MRS_OK) return st;
+    if ((st = timed(out_ms[3], [&]() { launch_nn_certify(h, h->prm, s); })) != MRS_OK) return st;
     if ((st = upload(1, 0.0)) != MRS_OK) return st;
     if ((st = timed(out_ms[1], linearize)) != MRS_OK) return st;
     // a pass after a 1 mm step: certify + search the work lists (the certificates are those of the unmoved poses: t_prev stays)
@@ -1079,8 +1337,8 @@ int mrs_gicp_batch_profile(mrs_gicp_batch* h, const double* h_poses, int32_t rep
         for (int r = 0; r < reps + 1; ++r) {
             MRS_HIP_TRY(hipMemcpyAsync(h->cert.lb.get(), lb_save.p, L.n_seed * sizeof(float), hipMemcpyDeviceToDevice, s));
             MRS_HIP_TRY(hipEventRecord(e0, s));
-            launch_nn_certify(h, s);
-            launch_nn_scan_g(h, true, s);
+            launch_nn_certify(h, h->prm, s);
+            launch_nn_scan_g(h, h->prm, true, s);
             MRS_HIP_TRY(hipEventRecord(e1, s));
             MRS_HIP_TRY(hipEventSynchronize(e1));
             float ms = 0.0f;

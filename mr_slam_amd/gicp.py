@@ -22,6 +22,26 @@ def default_params():
     return p
 
 
+class IcpParams(C.Structure):
+    _fields_ = [("max_iterations", C.c_int32), ("force_iterations", C.c_int32),
+                ("max_correspondence_distance", C.c_double), ("transformation_epsilon", C.c_double),
+                ("rotation_epsilon", C.c_double), ("euclidean_fitness_epsilon", C.c_double)]
+
+
+ICP_STATES = ("NOT_CONVERGED", "ITERATIONS", "TRANSFORM", "ABS_MSE", "REL_MSE", "NO_CORRESPONDENCES")    # PCL's ConvergenceState
+
+
+def default_icp_params(**kw):
+    """pcl::IterativeClosestPoint's defaults, with the given fields replaced"""
+    p = IcpParams()
+    _lib.load().mrs_icp_default_params(C.byref(p))
+    for k, v in kw.items():
+        if not hasattr(p, k):
+            raise AttributeError(k)
+        setattr(p, k, v)
+    return p
+
+
 _tls = __import__("threading").local()
 
 
@@ -154,6 +174,45 @@ class GicpBatch:
         corr = torch.empty(int(self._n[0][-1]), dtype=torch.int32, device=f"cuda:{self.device}") if want_corr else None
         _lib.load().mrs_gicp_batch_linearize(self._h, poses, H, b, e, corr, _lib.current_stream(self.device))
         return e, H.reshape(P, 6, 6), b, (corr.cpu().numpy() if want_corr else None)
+
+    def align_icp(self, guesses=None, **params):
+        """Point-to-point ICP (row G9, pcl::IterativeClosestPoint) on the batch's clouds; params: the fields of IcpParams (PCL's defaults
+        otherwise).  Returns (T [P,4,4] float64, converged [P] bool, iterations [P] int32, state [P] int32: index into ICP_STATES)."""
+        P = self.n_pairs
+        g = None
+        if guesses is not None:
+            g = np.ascontiguousarray(np.asarray(guesses, dtype=np.float64).reshape(P, 16))
+        T = np.empty((P, 16), np.float64)
+        conv = np.empty(P, np.int32)
+        its = np.empty(P, np.int32)
+        state = np.empty(P, np.int32)
+        lib = _lib.load()
+        lib.mrs_gicp_batch_align_icp(self._h, C.byref(default_icp_params(**params)), g, T, conv, its, state, _lib.current_stream(self.device))
+        self.nn_passes = lib.mrs_gicp_batch_last_nn_passes(self._h)
+        self.searched_fraction = lib.mrs_gicp_batch_last_searched_fraction(self._h)
+        return T.reshape(P, 4, 4), conv.astype(bool), its, state
+
+    def icp_step(self, poses, want_corr=False, **params):
+        """One ICP iteration's correspondences, 17 sums and fitted increment at `poses` (mrs_gicp_batch_icp_step).
+        Returns (sums [P,17], delta [P,4,4], corr or None)."""
+        P = self.n_pairs
+        poses = np.ascontiguousarray(np.asarray(poses, dtype=np.float64).reshape(P, 16))
+        sums = np.empty((P, 17), np.float64); delta = np.empty((P, 16), np.float64)
+        corr = torch.empty(int(self._n[0][-1]), dtype=torch.int32, device=f"cuda:{self.device}") if want_corr else None
+        _lib.load().mrs_gicp_batch_icp_step(self._h, C.byref(default_icp_params(**params)), poses, sums, delta, corr,
+                                            _lib.current_stream(self.device))
+        return sums, delta.reshape(P, 4, 4), (corr.cpu().numpy() if want_corr else None)
+
+    def icp_profile(self, poses, reps=3, **params):
+        """HIP-event duration of the three stages of one ICP iteration, each launched alone at `poses` (mrs_gicp_batch_icp_profile).
+        Returns (dict of ms, dict of counts)."""
+        P = self.n_pairs
+        poses = np.ascontiguousarray(np.asarray(poses, dtype=np.float64).reshape(P, 16))
+        ms = np.zeros(3, np.float32); cnt = np.zeros(2, np.int64)
+        _lib.load().mrs_gicp_batch_icp_profile(self._h, C.byref(default_icp_params(**params)), poses, int(reps), ms, cnt,
+                                               _lib.current_stream(self.device))
+        return ({n: float(v) for n, v in zip(("search", "icp_sums", "icp_update"), ms)},
+                {"source_points": int(cnt[0]), "correspondences": int(cnt[1])})
 
     def profile(self, poses, reps=3):
         """HIP-event duration of every kernel of one outer iteration, launched alone at `poses` (mrs_gicp_batch_profile).
