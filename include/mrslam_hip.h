@@ -858,7 +858,10 @@ typedef struct mrs_elev_map mrs_elev_map;
 int mrs_elev_create(mrs_ctx* ctx, int32_t length, float resolution, float mahalanobis_threshold, float obstacle_threshold,
                     mrs_elev_map** out);
 int mrs_elev_destroy(mrs_elev_map* m);
-/* Move(current_Position[3], resolution, length, Central_coordinate[2], Start_indice[2], alignedPositionShift[2]) */
+/* Move(current_Position[3], resolution, length, Central_coordinate[2], Start_indice[2], alignedPositionShift[2]).
+ * A shift of a whole map length or more clears the map, in either direction (the reference is undefined for -length and
+ * below).  Move, Map_optmove and Map_closeloop return MRS_ERR_ARG and change nothing when a position is not finite or lies
+ * 2^30 cells or more from the map centre. */
 int mrs_elev_move(mrs_elev_map* m, const float* h_position3, float* h_central2, int32_t* h_start2, float* h_aligned_shift2);
 /* Process_points(map_index, point_x/y/z (read only: the reference never copies its device copy back), point_var, point_x/y/z_ts, transform, point_num, thresholds,
  * sensor model, sensorJacobian, rotationVariance, C_SB_transpose, P_mul_C_BM_transpose, B_r_BS_skew) */

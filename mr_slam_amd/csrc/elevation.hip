@@ -350,6 +350,17 @@ float position_to_range(float p, float shift, float res)  // :992-998
     return (pi + si) * res;
 }
 
+// A target position the three moving entry points can turn into a cell shift: finite, and less than 2^30 cells from the
+// map centre (the float-to-int casts below are undefined beyond int range; the reference has no such check).
+bool shift_in_range(const mrs_elev_map* m, const float* p2)
+{
+    for (int i = 0; i < 2; ++i) {
+        const float cells = (p2[i] - m->central[i]) / m->res;
+        if (!std::isfinite(p2[i]) || !(std::fabs(cells) < 1073741824.0f)) return false;
+    }
+    return true;
+}
+
 // stable bucket sort of point indices by cell
 int bucket(const int* d_idx, int n, int cells, hipStream_t s, mrs::Scratch& keys_out, mrs::Scratch& vals_out)
 {
@@ -411,6 +422,7 @@ int mrs_elev_destroy(mrs_elev_map* m)
 int mrs_elev_move(mrs_elev_map* m, const float* h_position3, float* h_central2, int32_t* h_start2, float* h_aligned_shift2)
 {
     MRS_REQUIRE(m && h_position3 && h_central2 && h_start2 && h_aligned_shift2, "null pointer");
+    MRS_REQUIRE(std::isfinite(h_position3[2]) && shift_in_range(m, h_position3), "position not finite or 2^30 cells or more away");
     MRS_HIP_TRY(hipSetDevice(m->ctx->device));
     m->sensor_z = h_position3[2];
     const float pshift[2] = {h_position3[0] - m->central[0], h_position3[1] - m->central[1]};
@@ -426,7 +438,10 @@ int mrs_elev_move(mrs_elev_map* m, const float* h_position3, float* h_central2, 
     };
     for (int i = 0; i < 2; ++i) {
         if (ishift[i] != 0) {
-            if (ishift[i] >= L) {
+            // A jump of a whole map length or more, in either direction, clears everything.  This departs from the reference,
+            // whose `indexShift >= length` (:1031) sends a shift <= -L into the partial clear with a region longer than the
+            // map: undefined there (it writes past every layer).
+            if (std::abs(ishift[i]) >= L) {
                 hipLaunchKernelGGL(k_elev_fill, dim3(nb(cells)), dim3(256), 0, nullptr, m->lowest, m->elevation, m->variance,
                                    m->intensity, m->traver, m->cr, m->cg, m->cb, cells, 1);
             } else {
@@ -569,6 +584,7 @@ int mrs_elev_raytracing(mrs_elev_map* m)
 int mrs_elev_map_optmove(mrs_elev_map* m, const float* h_opt_p2, float height_update, float* h_aligned2)
 {
     MRS_REQUIRE(m && h_opt_p2 && h_aligned2, "null pointer");
+    MRS_REQUIRE(shift_in_range(m, h_opt_p2), "position not finite or 2^30 cells or more away");
     MRS_HIP_TRY(hipSetDevice(m->ctx->device));
     for (int i = 0; i < 2; ++i) {
         const float ps = h_opt_p2[i] - m->central[i];
@@ -585,6 +601,7 @@ int mrs_elev_map_optmove(mrs_elev_map* m, const float* h_opt_p2, float height_up
 int mrs_elev_map_closeloop(mrs_elev_map* m, const float* h_update_position2, float height_update)
 {
     MRS_REQUIRE(m && h_update_position2, "null pointer");
+    MRS_REQUIRE(shift_in_range(m, h_update_position2), "position not finite or 2^30 cells or more away");
     MRS_HIP_TRY(hipSetDevice(m->ctx->device));
     for (int i = 0; i < 2; ++i) {
         const float ps = h_update_position2[i] - m->central[i];

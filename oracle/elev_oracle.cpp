@@ -20,6 +20,10 @@
  *   - the `map_lowest` update in G_pointsprocess (atomicMin followed by a non-atomic "+3 sigma" bump):
  *     read as  lowest = (h <= lowest) ? h + 3*var : lowest, points in input order;
  *   - G_fuse is already sequential per cell (each cell thread walks all points in order).
+ * One departure from the reference: Move treats a shift of |cells| >= L as clear-all for either sign; the reference tests
+ * `indexShift >= length` only, and a shift <= -L then clears a region longer than the map (out of bounds, undefined).  The
+ * three moving functions also refuse positions that are not finite or 2^30 cells or more away (the casts are undefined there).
+ * orc_elev_set / orc_elev_set_frame load a state read from the product, so that a test can run one stage on identical inputs.
  * Quirks reproduced on purpose: the point filter keeps only points with y <= -1 outside the 1.5 m box
  * (:394-397), Raytracing returns before its final test for cells on the robot's row/column (:770-804),
  * `robot_index` is an int (:730,:742-751), d_min_elevation only uses x indices (:690-704).
@@ -38,6 +42,7 @@ struct ElevMap {
     float central[2] = {0, 0};
     int start[2] = {0, 0};
     float sensor_z = 0;
+    std::vector<float> margin;   // last raytracing: |oe - 3 sqrt(var) - restrict_e| of every cell that reached the test, else inf
 };
 
 int points_to_index(const ElevMap& m, float px, float py, bool storage)
@@ -66,6 +71,16 @@ float position_to_range(float p, float shift, float res)
 {
     const int pi = (int)std::round(p / res), si = (int)std::round(shift / res);
     return (pi + si) * res;
+}
+
+// finite and less than 2^30 cells from the map centre: what the float-to-int casts of the moving functions can take
+bool shift_in_range(const ElevMap& m, const float* p2)
+{
+    for (int i = 0; i < 2; ++i) {
+        const float cells = (p2[i] - m.central[i]) / m.res;
+        if (!std::isfinite(p2[i]) || !(std::fabs(cells) < 1073741824.0f)) return false;
+    }
+    return true;
 }
 
 void clear_region(ElevMap& m, int start, int shift, bool row)
@@ -145,9 +160,11 @@ void* orc_elev_create(int length, float resolution, float mahal_thr, float obsta
 }
 void orc_elev_destroy(void* h) { delete static_cast<ElevMap*>(h); }
 
-void orc_elev_move(void* h, const float* pos3, float* central, int* start, float* aligned_shift)
+/* the three moving functions return 0, or 1 (nothing touched) for a position that is not finite or 2^30 cells or more away */
+int orc_elev_move(void* h, const float* pos3, float* central, int* start, float* aligned_shift)
 {
     ElevMap& m = *static_cast<ElevMap*>(h);
+    if (!std::isfinite(pos3[2]) || !shift_in_range(m, pos3)) return 1;
     m.sensor_z = pos3[2];
     float pshift[2] = {pos3[0] - m.central[0], pos3[1] - m.central[1]};
     int ishift[2];
@@ -157,7 +174,9 @@ void orc_elev_move(void* h, const float* pos3, float* central, int* start, float
     }
     for (int i = 0; i < 2; ++i) {
         if (ishift[i] != 0) {
-            if (ishift[i] >= m.L) {
+            // |shift| >= L clears everything, whatever its sign.  This departs from the reference: its `indexShift >= length`
+            // (:1031) lets a shift <= -L into the partial clear below with nc >= L, which writes past the layers (undefined).
+            if (std::abs(ishift[i]) >= m.L) {
                 for (size_t c = 0; c < m.elevation.size(); ++c) {
                     m.intensity[c] = 0; m.elevation[c] = -10; m.variance[c] = -10; m.traver[c] = -10;
                     m.cr[c] = m.cg[c] = m.cb[c] = 0;
@@ -181,6 +200,7 @@ void orc_elev_move(void* h, const float* pos3, float* central, int* start, float
     }
     central[0] = m.central[0]; central[1] = m.central[1];
     start[0] = m.start[0]; start[1] = m.start[1];
+    return 0;
 }
 
 /* T: row-major 4x4; 3-vectors and row-major 3x3 matrices as plain floats */
@@ -318,6 +338,7 @@ void orc_elev_raytracing(void* h)
         return low + (m.sensor_z - low) / x2 * x1;
     };
     std::vector<float> elev = m.elevation;  // cells only write their own entry: a snapshot is equivalent
+    m.margin.assign((size_t)L * L, INFINITY);
     for (int i = 0; i < L * L; ++i) {
         if (!(m.traver[i] < m.obstacle_thr && m.elevation[i] != -10)) continue;
         const int cx = i / L, cy = i % L;
@@ -346,15 +367,17 @@ void orc_elev_raytracing(void* h)
             else if (dnx < dny) { cur[0] += ix; bx += (float)ix; later = dnx; dnx = bx / dir[0]; }
             else { cur[0] += ix; cur[1] += iy; bx += (float)ix; by += (float)iy; later = dnx; dnx = bx / dir[0]; dny = by / dir[1]; }
         }
+        m.margin[i] = std::fabs(oe - 3 * std::sqrt(m.variance[i]) - restrict_e);
         if (oe - 3 * std::sqrt(m.variance[i]) > restrict_e) elev[i] = -10;
     }
     m.elevation = elev;
     for (auto& x : m.lowest) x = 10;
 }
 
-void orc_elev_map_optmove(void* h, const float* opt_p, float height_update, float* aligned)
+int orc_elev_map_optmove(void* h, const float* opt_p, float height_update, float* aligned)
 {
     ElevMap& m = *static_cast<ElevMap*>(h);
+    if (!shift_in_range(m, opt_p)) return 1;
     for (int i = 0; i < 2; ++i) {
         const float ps = opt_p[i] - m.central[i];
         const int is = static_cast<int>(ps / m.res + 0.5 * (ps > 0 ? 1 : -1));
@@ -362,17 +385,20 @@ void orc_elev_map_optmove(void* h, const float* opt_p, float height_update, floa
     }
     m.central[0] = aligned[0]; m.central[1] = aligned[1];
     for (auto& e : m.elevation) if (e != -10) e += height_update;
+    return 0;
 }
 
-void orc_elev_map_closeloop(void* h, const float* update_pos, float height_update)
+int orc_elev_map_closeloop(void* h, const float* update_pos, float height_update)
 {
     ElevMap& m = *static_cast<ElevMap*>(h);
+    if (!shift_in_range(m, update_pos)) return 1;
     for (int i = 0; i < 2; ++i) {
         const float ps = update_pos[i] - m.central[i];
         const int is = static_cast<int>(ps / m.res + 0.5 * (ps > 0 ? 1 : -1));
         m.central[i] = position_to_range(m.central[i], (float)is * m.res, m.res);
     }
     for (auto& e : m.elevation) if (e != -10) e += height_update;
+    return 0;
 }
 
 /* state readback for the tests: which = 0 lowest, 1 elevation, 2 variance, 3 intensity, 4 traver */
@@ -386,6 +412,29 @@ void orc_elev_get_frame(void* h, float* central, int* start)
 {
     ElevMap& m = *static_cast<ElevMap*>(h);
     central[0] = m.central[0]; central[1] = m.central[1]; start[0] = m.start[0]; start[1] = m.start[1];
+}
+
+/* state injection (checker side only: the stage tests load a state read from the product into a fresh restatement).
+ * which = 0..4 as in orc_elev_get (float data), 5 / 6 / 7 = colour R / G / B (int data) */
+void orc_elev_set(void* h, int which, const void* data)
+{
+    ElevMap& m = *static_cast<ElevMap*>(h);
+    std::vector<float>* v[5] = {&m.lowest, &m.elevation, &m.variance, &m.intensity, &m.traver};
+    std::vector<int>* c[3] = {&m.cr, &m.cg, &m.cb};
+    if (which >= 0 && which < 5) std::memcpy(v[which]->data(), data, v[which]->size() * sizeof(float));
+    else if (which >= 5 && which < 8) std::memcpy(c[which - 5]->data(), data, c[which - 5]->size() * sizeof(int));
+}
+void orc_elev_set_frame(void* h, const float* central, const int* start, float sensor_z)
+{
+    ElevMap& m = *static_cast<ElevMap*>(h);
+    m.central[0] = central[0]; m.central[1] = central[1]; m.start[0] = start[0]; m.start[1] = start[1];
+    m.sensor_z = sensor_z;
+}
+/* decision margin of the last orc_elev_raytracing, |oe - 3 sqrt(var) - restrict_e| per cell (inf where no decision was taken) */
+void orc_elev_get_margin(void* h, float* out)
+{
+    ElevMap& m = *static_cast<ElevMap*>(h);
+    for (size_t i = 0; i < (size_t)m.L * m.L; ++i) out[i] = i < m.margin.size() ? m.margin[i] : INFINITY;
 }
 
 }  // extern "C"

@@ -396,7 +396,8 @@ class ElevMap:
 
     def move(self, pos3):
         p = _f32(pos3); c = np.zeros(2, np.float32); s = np.zeros(2, np.int32); a = np.zeros(2, np.float32)
-        self._l.orc_elev_move(self._h, _p(p), _p(c), _p(s), _p(a))
+        if self._l.orc_elev_move(self._h, _p(p), _p(c), _p(s), _p(a)):
+            raise ValueError("position not finite or 2^30 cells or more away")
         return c, s, a
 
     def process_points(self, x, y, z, T, lower, upper, min_r, beam_a, beam_c, sj, rv, csb, pmul, bskew):
@@ -433,11 +434,13 @@ class ElevMap:
 
     def map_optmove(self, p, dh):
         a = np.zeros(2, np.float32)
-        self._l.orc_elev_map_optmove(self._h, _p(_f32(p)), C.c_float(dh), _p(a))
+        if self._l.orc_elev_map_optmove(self._h, _p(_f32(p)), C.c_float(dh), _p(a)):
+            raise ValueError("position not finite or 2^30 cells or more away")
         return a
 
     def map_closeloop(self, p, dh):
-        self._l.orc_elev_map_closeloop(self._h, _p(_f32(p)), C.c_float(dh))
+        if self._l.orc_elev_map_closeloop(self._h, _p(_f32(p)), C.c_float(dh)):
+            raise ValueError("position not finite or 2^30 cells or more away")
 
     def layer(self, which):
         out = np.empty(self.L * self.L, np.float32)
@@ -448,6 +451,21 @@ class ElevMap:
         c = np.zeros(2, np.float32); s = np.zeros(2, np.int32)
         self._l.orc_elev_get_frame(self._h, _p(c), _p(s))
         return c, s
+
+    def set(self, which, data):
+        """state injection: which = 0 lowest, 1 elevation, 2 variance, 3 intensity, 4 traver (float32), 5 / 6 / 7 colour R / G / B (int32)"""
+        a = np.ascontiguousarray(data, np.float32 if which < 5 else np.int32).reshape(-1)
+        assert 0 <= which < 8 and a.size == self.L * self.L
+        self._l.orc_elev_set(self._h, int(which), _p(a))
+
+    def set_frame(self, central, start, sensor_z):
+        self._l.orc_elev_set_frame(self._h, _p(_f32(central)), _p(np.ascontiguousarray(start, np.int32)), C.c_float(sensor_z))
+
+    def raytracing_margin(self):
+        """|oe - 3 sqrt(var) - restrict_e| of the last raytracing() per cell, inf where the ray walk took no decision"""
+        out = np.empty(self.L * self.L, np.float32)
+        self._l.orc_elev_get_margin(self._h, _p(out))
+        return out
 
 
 class RefElevMap:

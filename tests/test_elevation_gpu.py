@@ -29,11 +29,11 @@ def test_session_matches_sequential_restatement(dev, oracle, L):
     seen_cells = 0
     for (kg, g), (kw, w) in zip(got, want):
         assert kg == kw
-        if kg in ("move", "frame"):
-            for a, b in zip(g, w):
-                np.testing.assert_allclose(a, b, rtol=0, atol=1e-6)
+        if kg in ("move", "frame"):                            # frames and the fuse-only layers: + - * / sqrt under
+            for a, b in zip(g, w):                             # -ffp-contract=off, bit-identical on an MI355X
+                np.testing.assert_array_equal(a, b)
         elif kg == "optmove":
-            np.testing.assert_allclose(g, w, atol=1e-6)
+            np.testing.assert_array_equal(g, w)
         elif kg == "points":
             np.testing.assert_array_equal(g["map_index"], w["map_index"])
             assert (g["map_index"] >= 0).sum() > 500
@@ -42,7 +42,7 @@ def test_session_matches_sequential_restatement(dev, oracle, L):
             np.testing.assert_allclose(g["var"], w["var"], rtol=1e-6, atol=1e-12)
         elif kg == "feature":
             for k in ("elevation", "var", "intensity"):
-                np.testing.assert_allclose(g[k], w[k], rtol=2e-6, atol=1e-7)
+                np.testing.assert_array_equal(g[k], w[k], err_msg=k)
             for k in ("colorR", "colorG", "colorB"):
                 np.testing.assert_array_equal(g[k], w[k])
             np.testing.assert_allclose(g["rough"], w["rough"], rtol=1e-4, atol=1e-5)
@@ -77,7 +77,7 @@ def test_session_matches_the_reference_source_built_for_the_host(dev, oracle):
             seen = w["elevation"] != -10                       # elsewhere the reference's rough / slope / traver are uninitialised
             np.testing.assert_array_equal(g["elevation"] != -10, seen)
             for k in ("elevation", "var", "intensity"):
-                np.testing.assert_allclose(g[k], w[k], rtol=2e-6, atol=1e-7)
+                np.testing.assert_array_equal(g[k], w[k], err_msg=k)
             for k in ("colorR", "colorG", "colorB"):
                 np.testing.assert_array_equal(g[k], w[k])
             np.testing.assert_allclose(g["rough"][seen], w["rough"][seen], rtol=1e-4, atol=1e-5)
@@ -85,4 +85,4 @@ def test_session_matches_the_reference_source_built_for_the_host(dev, oracle):
             assert ok.mean() > 0.995
         elif kg in ("move", "frame"):
             for a, b in zip(g, w):
-                np.testing.assert_allclose(a, b, rtol=0, atol=1e-6)
+                np.testing.assert_array_equal(a, b)
