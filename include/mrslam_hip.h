@@ -623,6 +623,45 @@ int mrs_submap_merge_nearest(mrs_keyframes* kf, int32_t n_submaps, const int32_t
                              float* d_out, int64_t capacity_points, int64_t* h_offsets, mrs_stream stream);
 
 /* ------------------------------------------------------------------------------------
+ * Keyframe intake: raw clouds filtered on the device and registered in the store
+ * ---------------------------------------------------------------------------------- */
+
+/* The front of GlobalManager::mapUpdate (Mapping/src/global_manager/src/global_manager.cpp:1684-1709, :1735, :1797): pcl::fromROSMsg, an
+ * exact pcl::VoxelGrid with leaf submap_voxel_leaf_size_, pcl::PassThrough on z in [-1, 30], intensity = robotid * 30, emplace_back -- for
+ * n_clouds >= 0 raw clouds in one chain of launches.  DESIGN.md section 4.14 is the contract; the cells, keys, output order and means are
+ * section 4.11's.
+ * `data` is one byte blob in HOST (on_device = 0; staged through the handle's pinned buffer) or DEVICE memory (4-byte aligned).  Cloud c is
+ * the points h_offsets[c] .. h_offsets[c + 1] (int64 [n_clouds + 1], ascending, h_offsets[0] = 0); point i starts at byte i * point_step;
+ * off_x, off_y, off_z are the byte offsets of three float32 fields and off_intensity that of a fourth, or -1 for none (taken as 0): what a
+ * sensor_msgs/PointCloud2 describes.  pcl::toROSMsg of a pcl::PointXYZI cloud is point_step 32 with offsets 0, 4, 8, 16; the store's own
+ * float[n][4] is 16 with 0, 4, 8, 12.
+ * Per cloud, independently of the others: a point is dropped unless x, y, z are finite; the rest go through the voxel grid (cell =
+ * floorf(v * (1.0f / leaf)), 64-bit keys, one point per occupied voxel in ascending key order = the mean of x, y, z, intensity, summed in
+ * float64 in input order and rounded to float32 once); a voxel is kept iff z_lo <= mean z <= z_hi (both ends inclusive, +-inf switches a
+ * side off); if set_intensity is 1 every survivor's intensity becomes `intensity` (the caller passes robotid * 30).  The survivors become
+ * keyframe out_ids[c] (int32 [n_clouds], consecutive, in input order) with the row-major float32 4x4 pose h_pose16s + 16 c; out_counts[c]
+ * (int64 [n_clouds]) is their number.  A cloud with no point or no survivor is a keyframe with 0 points and gets its id.  Only the
+ * survivors are stored: mrs_keyframes_size's point total grows by the sum of out_counts.  Results are the same bits from run to run and
+ * do not depend on the other clouds of the call.
+ * Bad argument (MRS_ERR_ARG), checked before any launch, store unchanged: a null pointer where one is needed; point_step < 12 or not a
+ * multiple of 4; an offset that is negative (other than off_intensity = -1), not a multiple of 4 or beyond point_step - 4; off_x, off_y,
+ * off_z not ascending; leaf <= 0 or not finite; z_lo or z_hi NaN, or z_lo > z_hi; set_intensity other than 0 / 1; intensity not finite
+ * when set_intensity is 1; a pose that is not finite; h_offsets not ascending from 0; more than 2^31 - 1 points in the call.  MRS_ERR_ARG
+ * too, after the first launches and with the store still unchanged: a cloud whose grid needs keys of more than 63 bits, and a call whose
+ * (cloud, key) pairs do not fit 64 bits together (bits of the widest grid + bits of n_clouds: split the call; one cloud always fits).
+ * Thread-safe (the handle's lock); the device work runs on the handle's stream, which waits for `stream` (the stream that produced a
+ * device blob).  Two host synchronisations: one for the key widths, one for the counts. */
+int mrs_keyframes_ingest(mrs_keyframes* kf, int32_t n_clouds, const void* data, int32_t on_device, const int64_t* h_offsets, int32_t point_step,
+                         int32_t off_x, int32_t off_y, int32_t off_z, int32_t off_intensity, float leaf, float z_lo, float z_hi,
+                         int32_t set_intensity, float intensity, const float* h_pose16s, int32_t* out_ids, int64_t* out_counts,
+                         mrs_stream stream);
+/* `keyframe_pub.publish(*keyframe)` (global_manager.cpp:1800-1802) and savingKeyframes (:218-272): the points of keyframe `id` copied as
+ * float[n][4] (x, y, z, intensity) into `out`, in HOST (on_device = 0; blocking) or DEVICE memory (ordered after and before the work of
+ * `stream`); *out_points = n.  Bad argument: id out of range, capacity_points (the room in `out`, in points) below n. */
+int mrs_keyframes_get_points(mrs_keyframes* kf, int32_t id, float* out, int32_t on_device, int64_t capacity_points, int64_t* out_points,
+                             mrs_stream stream);
+
+/* ------------------------------------------------------------------------------------
  * The merged multi-robot map composed from the keyframe stores
  * ---------------------------------------------------------------------------------- */
 

@@ -29,7 +29,6 @@ namespace {
 using namespace mrs::kfdev;
 
 constexpr int kThreads = 256, kPerThread = 4, kTile = kThreads * kPerThread, kWaves = kThreads / 64;
-constexpr float kFltMax = 3.402823466e38f;
 constexpr int kLdsSegments = 1024;       // k_mc_means keeps the segment lookup of a call with at most this many segments in LDS (12 KiB)
 constexpr int kBoundsBlocks = 1024;      // workgroups of k_mc_bounds at most: 4 per compute unit, 7 atomics each on the same words
 
@@ -79,8 +78,7 @@ __device__ __forceinline__ Acc acc_up(const Acc& a, int o)
 }
 __device__ __forceinline__ float4 acc_mean(const Acc& a)
 {
-    const double m = (double)a.n;
-    return make_float4((float)(a.x / m), (float)(a.y / m), (float)(a.z / m), (float)(a.w / m));
+    return mean_of(a.x, a.y, a.z, a.w, (double)a.n);
 }
 
 // a segment's point moved (section 4.11's arithmetic; the previous map is not moved) and whether it is kept: x', y', z' finite
@@ -88,7 +86,7 @@ __device__ __forceinline__ bool moved(const float4 p, const MapSegment& sg, floa
 {
     if (sg.raw) {
         x = p.x; y = p.y; z = p.z;
-        return fabsf(x) <= kFltMax && fabsf(y) <= kFltMax && fabsf(z) <= kFltMax;
+        return finite3(x, y, z);
     }
     return move_and_crop(p, sg.T, kFltMax, x, y, z);
 }
@@ -113,7 +111,7 @@ __global__ __launch_bounds__(kThreads) void k_mc_bounds(const float4* const* __r
             if (i < sg.count) {
                 float x, y, z;
                 if (moved(src[i], sg, x, y, z)) {
-                    const unsigned c[3] = {order_bits(floorf(x * inv)), order_bits(floorf(y * inv)), order_bits(floorf(z * inv))};
+                    const unsigned c[3] = {order_bits(cell_of(x, inv)), order_bits(cell_of(y, inv)), order_bits(cell_of(z, inv))};
 #pragma unroll
                     for (int a = 0; a < 3; ++a) { lo[a] = min(lo[a], c[a]); hi[a] = max(hi[a], c[a]); }
                     ++kept;
@@ -121,15 +119,9 @@ __global__ __launch_bounds__(kThreads) void k_mc_bounds(const float4* const* __r
             }
         }
     }
+    wave_minmax3(lo, hi);
 #pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-#pragma unroll
-        for (int a = 0; a < 3; ++a) {
-            lo[a] = min(lo[a], (unsigned)__shfl_xor((int)lo[a], o, 64));
-            hi[a] = max(hi[a], (unsigned)__shfl_xor((int)hi[a], o, 64));
-        }
-        kept += (unsigned)__shfl_xor((int)kept, o, 64);
-    }
+    for (int o = 32; o > 0; o >>= 1) kept += (unsigned)__shfl_xor((int)kept, o, 64);
     const int wave = threadIdx.x >> 6;
     if ((threadIdx.x & 63) == 0) {
         for (int a = 0; a < 3; ++a) { red[wave][a] = lo[a]; red[wave][3 + a] = hi[a]; }
@@ -150,24 +142,7 @@ __global__ __launch_bounds__(kThreads) void k_mc_bounds(const float4* const* __r
 __global__ void k_mc_grid(Info* __restrict__ info)
 {
     if (blockIdx.x != 0 || threadIdx.x != 0 || info->kept == 0) return;
-    long long div[3];
-    bool ok = true;
-    for (int a = 0; a < 3; ++a) {
-        const float lo = order_float(info->bounds[a]), hi = order_float(info->bounds[3 + a]);
-        if (!(fabsf(lo) < 4.6e18f && fabsf(hi) < 4.6e18f)) { ok = false; break; }       // a cell beyond +-2^62 (or v * inv overflowed to inf)
-        info->mn[a] = (long long)lo;
-        div[a] = (long long)hi - info->mn[a] + 1;
-    }
-    const long long kMax = 0x7fffffffffffffffll;
-    if (ok && div[1] > kMax / div[0]) ok = false;
-    if (ok) {
-        info->mul_y = div[0];
-        info->mul_z = div[0] * div[1];
-        if (div[2] > kMax / info->mul_z) ok = false;                                    // div.x * div.y * div.z must stay below 2^63
-    }
-    if (!ok) { info->overflow = 1; return; }
-    const unsigned long long last = (unsigned long long)(info->mul_z * div[2]) - 1ull;   // the largest key the grid can hold
-    info->bits = last == 0ull ? 1 : 64 - __clzll((long long)last);
+    if (!grid_from_bounds(info->bounds, info->mn, info->mul_y, info->mul_z, info->bits)) info->overflow = 1;
 }
 
 // ---- pass 2: voxel keys ---------------------------------------------------------------------------------------------------------------------
@@ -189,8 +164,7 @@ __global__ __launch_bounds__(kThreads) void k_mc_keys(const float4* const* __res
             float x, y, z;
             unsigned long long key = dropped;
             if (moved(src[i], sg, x, y, z)) {
-                const long long cx = (long long)floorf(x * inv) - mx, cy = (long long)floorf(y * inv) - my, cz = (long long)floorf(z * inv) - mz;
-                key = (unsigned long long)(cx + cy * mul_y + cz * mul_z);
+                key = voxel_key(x, y, z, inv, mx, my, mz, mul_y, mul_z);
             }
             const long long pos = sg.base + i;
             keys[pos] = key;

@@ -26,7 +26,6 @@ namespace {
 using namespace mrs::kfdev;
 
 constexpr int kThreads = 256, kPerThread = 4, kTile = kThreads * kPerThread;      // points of one workgroup of k_cells / k_keys
-constexpr long long kMaxArenaPoints = 1ll << 34;                                // 256 GiB of float4: no size computed from a point count can wrap
 constexpr unsigned long long kDropped = ~0ull;                                  // key of a point the pass-through dropped (valid keys < 2^63)
 
 struct Segment {          // one keyframe of one submap, as the kernels see it
@@ -77,18 +76,13 @@ __global__ __launch_bounds__(kThreads) void k_cells(const float4* __restrict__ a
         if (i < sg.count) {
             float x, y, z;
             if (move_and_crop(src[i], sg.T, crop, x, y, z)) {
-                const unsigned c[3] = {order_bits(floorf(x * inv)), order_bits(floorf(y * inv)), order_bits(floorf(z * inv))};
+                const unsigned c[3] = {order_bits(cell_of(x, inv)), order_bits(cell_of(y, inv)), order_bits(cell_of(z, inv))};
 #pragma unroll
                 for (int a = 0; a < 3; ++a) { lo[a] = min(lo[a], c[a]); hi[a] = max(hi[a], c[a]); }
             }
         }
     }
-#pragma unroll
-    for (int a = 0; a < 3; ++a)
-        for (int o = 32; o > 0; o >>= 1) {
-            lo[a] = min(lo[a], (unsigned)__shfl_xor((int)lo[a], o, 64));
-            hi[a] = max(hi[a], (unsigned)__shfl_xor((int)hi[a], o, 64));
-        }
+    wave_minmax3(lo, hi);
     const int wave = threadIdx.x >> 6;
     if ((threadIdx.x & 63) == 0)
         for (int a = 0; a < 3; ++a) { red[wave][a] = lo[a]; red[wave][3 + a] = hi[a]; }
@@ -112,21 +106,8 @@ __global__ void k_grid(const unsigned* __restrict__ bounds, int n_submaps, Grid*
     const unsigned* bb = bounds + (size_t)b * 6;
     if (bb[0] <= bb[3]) {                        // something was kept (all three components are set together)
         g.kept = 1;
-        long long div[3];
-        bool ok = true;
-        for (int a = 0; a < 3; ++a) {
-            const float lo = order_float(bb[a]), hi = order_float(bb[3 + a]);
-            if (!(fabsf(lo) < 4.6e18f && fabsf(hi) < 4.6e18f)) { ok = false; break; }       // a cell beyond +-2^62 (or x * inv overflowed to inf)
-            g.mn[a] = (long long)lo;
-            div[a] = (long long)hi - g.mn[a] + 1;
-        }
-        const long long kMax = 0x7fffffffffffffffll;
-        if (ok && div[1] > kMax / div[0]) ok = false;
-        if (ok) {
-            g.mul_y = div[0];
-            g.mul_z = div[0] * div[1];
-            if (div[2] > kMax / g.mul_z) ok = false;                                        // div.x * div.y * div.z must stay below 2^63
-        }
+        int bits;
+        const bool ok = grid_from_bounds(bb, g.mn, g.mul_y, g.mul_z, bits);
         if (!ok) { g.kept = 0; atomicOr(overflow, 1); }
     }
     grids[b] = g;
@@ -152,9 +133,7 @@ __global__ __launch_bounds__(kThreads) void k_keys(const float4* __restrict__ ar
             float x, y, z;
             unsigned long long key = kDropped;
             if (move_and_crop(src[i], sg.T, crop, x, y, z) && gr.kept) {
-                const long long cx = (long long)floorf(x * inv) - gr.mn[0], cy = (long long)floorf(y * inv) - gr.mn[1],
-                                cz = (long long)floorf(z * inv) - gr.mn[2];
-                key = (unsigned long long)(cx + cy * gr.mul_y + cz * gr.mul_z);
+                key = voxel_key(x, y, z, inv, gr.mn[0], gr.mn[1], gr.mn[2], gr.mul_y, gr.mul_z);
             }
             const long long pos = sg.base + i;
             keys[pos] = key;
@@ -219,8 +198,7 @@ __global__ __launch_bounds__(kThreads) void k_means(const float4* __restrict__ a
             sx += (double)x; sy += (double)y; sz += (double)z; si += (double)pt.w;
             ++m;
         }
-        const double dm = (double)m;
-        out[slot[p]] = make_float4((float)(sx / dm), (float)(sy / dm), (float)(sz / dm), (float)(si / dm));
+        out[slot[p]] = mean_of(sx, sy, sz, si, (double)m);
     }
 }
 
@@ -234,30 +212,6 @@ __global__ void k_offsets(const int* __restrict__ head, const int* __restrict__ 
     const int n_in = sub_base[n_submaps];
     const int pos = sub_base[b];
     out[b] = pos < n_in ? slot[pos] : slot[n_in - 1] + head[n_in - 1];
-}
-
-// room for `want` points: a new arena (doubling), what is there copied on the device, the old one freed after the copy; lock held
-int arena_reserve(mrs_keyframes* kf, long long want)
-{
-    MRS_REQUIRE(want >= 0 && want <= kMaxArenaPoints, "more than 2^34 points in one keyframe store");
-    if ((size_t)want <= kf->arena.capacity()) return MRS_OK;
-    size_t cap = std::max(kf->arena.capacity(), (size_t)1024);
-    while (cap < (size_t)want) cap *= 2;
-    mrs::DeviceBuffer<float4> grown;
-    int st = grown.reserve(cap, cap);
-    if (st != MRS_OK) return st;
-    const long long used = kf->offsets.back();
-    if (used > 0) MRS_HIP_TRY(hipMemcpyAsync(grown.get(), kf->arena.get(), (size_t)used * sizeof(float4), hipMemcpyDeviceToDevice, kf->s));
-    MRS_HIP_TRY(hipStreamSynchronize(kf->s));
-    kf->arena = std::move(grown);
-    return MRS_OK;
-}
-
-bool rigid_finite(const float* P)
-{
-    for (int i = 0; i < 16; ++i)
-        if (!std::isfinite(P[i])) return false;
-    return true;
 }
 
 // inverse(centre) * near, float32, term by term (every product and sum rounded once, in this order)

@@ -12,6 +12,8 @@ import torch
 from . import _lib
 
 F = np.float32
+# (point_step, off_x, off_y, off_z, off_intensity) in bytes of a float32 [n, columns] cloud: xyz, the store's x y z i, pcl::PointXYZI
+LAYOUTS = {3: (12, 0, 4, 8, -1), 4: (16, 0, 4, 8, 12), 8: (32, 0, 4, 8, 16)}
 
 
 def nearest_keyframe_ids(loop_id, submap_size, n_keyframes):
@@ -83,6 +85,80 @@ class KeyframeStore:
                                          C.byref(kid), _lib.current_stream(self.device))
         self._counts.append(n)
         return kid.value
+
+    @staticmethod
+    def _blob(cloud, layout):
+        """-> (contiguous host array or device tensor, on_device, points, (point_step, off_x, off_y, off_z, off_intensity))"""
+        on_device = isinstance(cloud, torch.Tensor) and cloud.is_cuda
+        if isinstance(cloud, (bytes, bytearray, memoryview)):
+            cloud = np.frombuffer(cloud, np.uint8)
+        if layout is None:
+            if not on_device:
+                cloud = np.asarray(cloud)
+            if cloud.ndim != 2 or cloud.shape[1] not in LAYOUTS or str(cloud.dtype).replace("torch.", "") != "float32":
+                raise ValueError("a cloud without a layout must be float32 [n, 3], [n, 4] or [n, 8]")
+            layout = LAYOUTS[int(cloud.shape[1])]
+        elif len(layout) != 5:
+            raise ValueError("layout is (point_step, off_x, off_y, off_z, off_intensity)")
+        cloud = cloud.contiguous() if on_device else np.ascontiguousarray(cloud)
+        nbytes = cloud.numel() * cloud.element_size() if on_device else cloud.nbytes
+        step = int(layout[0])
+        if step <= 0 or nbytes % step:
+            raise ValueError("the blob's size is not a multiple of point_step")
+        return cloud, on_device, nbytes // step, tuple(int(v) for v in layout)
+
+    def ingest_batch(self, clouds, poses, leaf=0.3, z_limits=(-1.0, 30.0), intensity=None, layout=None, offsets=None):
+        """GlobalManager::mapUpdate's intake (global_manager.cpp:1684-1709) for several raw clouds in one chain of launches: exact voxel grid
+        with `leaf`, pass-through on z in z_limits (inclusive), every survivor's intensity set to `intensity` (robotid * 30; None keeps the
+        voxel means), the result registered as a keyframe with its pose.  clouds: a list of float32 [n, 3 | 4 | 8] host arrays or device
+        tensors of one shape (as append takes them), or of bytes / uint8 blobs with layout = (point_step, off_x, off_y, off_z,
+        off_intensity) in bytes (off_intensity -1: none); with `offsets` (int64 [len(poses) + 1], in points) `clouds` is ONE such array or
+        blob that holds all of them.  poses: 4x4 each.  -> (ids list, counts int64 [n]: the points each keyframe kept)"""
+        poses = np.ascontiguousarray(np.asarray(poses, F).reshape(-1, 16))
+        n = int(poses.shape[0])
+        if offsets is None:
+            parts = [self._blob(c, layout) for c in clouds]
+            if len(parts) != n:
+                raise ValueError("one pose per cloud")
+            if len({(p[1], p[3]) for p in parts}) > 1:
+                raise ValueError("the clouds of one call share one layout and one placement")
+            offsets = np.concatenate([[0], np.cumsum([p[2] for p in parts])]).astype(np.int64)
+            on_device, lay = (parts[0][1], parts[0][3]) if parts else (False, LAYOUTS[4])
+            if n == 1:
+                data = parts[0][0]
+            elif on_device:
+                data = torch.cat([p[0].reshape(-1).view(torch.uint8) for p in parts])
+            else:
+                data = np.concatenate([p[0].reshape(-1).view(np.uint8) for p in parts]) if parts else np.zeros(0, np.uint8)
+        else:
+            data, on_device, total, lay = self._blob(clouds, layout)
+            offsets = np.ascontiguousarray(offsets, dtype=np.int64).reshape(-1)
+            if offsets.size != n + 1 or (n and int(offsets[-1]) != total):
+                raise ValueError("offsets must be [len(poses) + 1] and end at the blob's point count")
+        ids, counts = np.full(n, -1, np.int32), np.zeros(n, np.int64)
+        lo, hi = z_limits
+        _lib.load().mrs_keyframes_ingest(self._h, n, data if int(offsets[-1]) else None, int(on_device), offsets, lay[0], lay[1], lay[2], lay[3],
+                                         lay[4], float(leaf), float(lo), float(hi), int(intensity is not None),
+                                         float(0.0 if intensity is None else intensity), poses if n else None, ids if n else None,
+                                         counts if n else None, _lib.current_stream(self.device))
+        self._counts.extend(int(c) for c in counts)
+        return ids.tolist(), counts
+
+    def ingest(self, cloud, pose, leaf=0.3, z_limits=(-1.0, 30.0), intensity=None, layout=None):
+        """One raw cloud filtered and registered (see ingest_batch).  -> the id"""
+        return self.ingest_batch([cloud], [pose], leaf, z_limits, intensity, layout)[0][0]
+
+    def points(self, kid):
+        """A copy of keyframe kid's points -> float32 device tensor [n, 4] (x, y, z, intensity)"""
+        kid = int(kid)
+        if not 0 <= kid < len(self._counts):
+            raise IndexError("keyframe id out of range")
+        n = self._counts[kid]
+        out = torch.empty((n, 4), dtype=torch.float32, device=f"cuda:{self.device}")
+        got = C.c_int64(-1)
+        _lib.load().mrs_keyframes_get_points(self._h, kid, out if n else None, 1, n, C.byref(got), _lib.current_stream(self.device))
+        assert got.value == n
+        return out
 
     def set_pose(self, kid, pose):
         _lib.load().mrs_keyframes_set_pose(self._h, int(kid), np.ascontiguousarray(np.asarray(pose, F).reshape(16)))
