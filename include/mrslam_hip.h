@@ -311,6 +311,14 @@ int mrs_gicp_batch_set_clouds_from(mrs_gicp_batch* h, int32_t which, mrs_gicp_ba
 int mrs_gicp_batch_compute_covariances(mrs_gicp_batch* h, int32_t which, int32_t* d_knn_out, mrs_stream stream);
 /* h_cov6: double[total_points][6] = xx xy xz yy yz zz of the regularised 3x3 block */
 int mrs_gicp_batch_get_covariances(mrs_gicp_batch* h, int32_t which, double* h_cov6);
+/* Read-out of the voxel map that the voxelised variant (voxel_resolution > 0) registers against: upstream's GaussianVoxelMap of the targets
+ * (fast_gicp's CUDA voxel map: voxel coordinate floor(x / resolution - 0.5) in float arithmetic, mean of the points, mean of
+ * their regularised covariances).  Builds the map if it is not current (and the covariances it needs, like linearize does); needs both
+ * sides' clouds.  h_n_voxels: int32[1], the number of voxels of all pairs together.  The arrays (each optional; all NULL: the count only)
+ * hold one entry per voxel in ascending (pair, x, y, z): h_pair int32[n], h_coord int32[n][3] signed voxel coordinate, h_mean float[n][3],
+ * h_count int32[n] points in the voxel, h_cov6 double[n][6] = xx xy xz yy yz zz.  Synchronises `stream`. */
+int mrs_gicp_batch_get_voxel_map(mrs_gicp_batch* h, int32_t* h_n_voxels, int32_t* h_pair, int32_t* h_coord, float* h_mean, int32_t* h_count,
+                                 double* h_cov6, mrs_stream stream);
 
 /* align(output, guess): h_guess double[n_pairs][16] row-major 4x4 (NULL = identity; narrowed to
  * float like the reference's Eigen::Matrix4f guess), h_final double[n_pairs][16] =

@@ -407,6 +407,7 @@ static int prepare_side(mrs_gicp_batch* h, int32_t which, const int64_t* h_offse
     S.max_tiles = longest_tiles;
     S.cov_valid = false;
     S.hier_valid = false;
+    if (which == 1) h->vox.res_built = 0.0;   // new targets: their voxel map is built again (set_clouds_from delivers covariances, so compute_covariances does not run)
     if (which == 0) h->lm.n_seed = (size_t)total;
     if (h->lm.seed) MRS_HIP_TRY(hipMemsetAsync(h->lm.seed.get(), 0xff, h->lm.n_seed * sizeof(int), s));  // -1: no warm start across clouds
     MRS_HIP_TRY(hipMemcpyAsync(S.d_offs.get(), h_offsets, (P + 1) * sizeof(int64_t), hipMemcpyHostToDevice, s));
@@ -824,6 +825,39 @@ static int build_voxel_map(mrs_gicp_batch* h, hipStream_t s)
     MRS_HIP_TRY(hipGetLastError());
     MRS_HIP_TRY(hipStreamSynchronize(s));
     V.res_built = h->prm.voxel_res;
+    return MRS_OK;
+}
+
+int mrs_gicp_batch_get_voxel_map(mrs_gicp_batch* h, int32_t* h_n_voxels, int32_t* h_pair, int32_t* h_coord, float* h_mean, int32_t* h_count,
+                                 double* h_cov6, mrs_stream stream)
+{
+    MRS_REQUIRE(h && h_n_voxels, "null pointer");
+    MRS_REQUIRE(h->clouds_set(), "set source and target clouds first");
+    MRS_REQUIRE(h->prm.voxel_res > 0.0, "voxel_resolution is 0: plain GICP has no voxel map");
+    MRS_HIP_TRY(hipSetDevice(h->ctx->device));
+    hipStream_t s = (hipStream_t)stream;
+    int st;
+    for (int w = 0; w < 2; ++w)     // like linearize
+        if (!h->side[w].cov_valid) { st = mrs_gicp_batch_compute_covariances(h, w, nullptr, stream); if (st != MRS_OK) return st; }
+    if ((st = build_voxel_map(h, s)) != MRS_OK) return st;
+    const GicpVoxelMap& V = h->vox;
+    *h_n_voxels = V.n;
+    if (!h_pair && !h_coord && !h_mean && !h_count && !h_cov6) return MRS_OK;
+    const size_t n = (size_t)V.n;
+    std::vector<unsigned long long> keys(n);
+    std::vector<float4> mean(n);
+    MRS_HIP_TRY(hipMemcpyAsync(keys.data(), V.keys.get(), n * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+    MRS_HIP_TRY(hipMemcpyAsync(mean.data(), V.mean.get(), n * sizeof(float4), hipMemcpyDeviceToHost, s));
+    if (h_cov6) MRS_HIP_TRY(hipMemcpyAsync(h_cov6, V.cov.get(), n * 6 * sizeof(double), hipMemcpyDeviceToHost, s));
+    MRS_HIP_TRY(hipStreamSynchronize(s));
+    for (size_t v = 0; v < n; ++v) {
+        const unsigned long long k = keys[v];   // voxel_key: pair | x | y | z, the coordinates offset by 32768
+        if (h_pair) h_pair[v] = (int32_t)(k >> 48);
+        if (h_coord)
+            for (int a = 0; a < 3; ++a) h_coord[3 * v + a] = (int32_t)((k >> (32 - 16 * a)) & 0xffff) - 32768;
+        if (h_mean) { h_mean[3 * v] = mean[v].x; h_mean[3 * v + 1] = mean[v].y; h_mean[3 * v + 2] = mean[v].z; }
+        if (h_count) h_count[v] = (int32_t)mean[v].w;
+    }
     return MRS_OK;
 }
 

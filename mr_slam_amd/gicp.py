@@ -151,6 +151,18 @@ class GicpBatch:
         out[:, 2, 0], out[:, 2, 1], out[:, 2, 2] = c6[:, 2], c6[:, 4], c6[:, 5]
         return out
 
+    def voxel_map(self):
+        """The targets' voxel map of the voxelised variant (voxel_resolution > 0), built if need be: (pair [V] int32, coord [V,3] int32,
+        mean [V,3] float32, count [V] int32, cov [V,3,3] float64), voxels in ascending (pair, x, y, z)."""
+        lib, stream = _lib.load(), _lib.current_stream(self.device)
+        n = np.zeros(1, np.int32)
+        lib.mrs_gicp_batch_get_voxel_map(self._h, n, None, None, None, None, None, stream)
+        V = int(n[0])
+        pair = np.empty(V, np.int32); coord = np.empty((V, 3), np.int32); mean = np.empty((V, 3), np.float32)
+        count = np.empty(V, np.int32); c6 = np.empty((V, 6), np.float64)
+        lib.mrs_gicp_batch_get_voxel_map(self._h, n, pair, coord, mean, count, c6, stream)
+        return pair, coord, mean, count, c6[:, [0, 1, 2, 1, 3, 4, 2, 4, 5]].reshape(V, 3, 3)
+
     def align(self, guesses=None):
         """Returns (T [P,4,4] float64, converged [P] bool, iterations [P] int32)."""
         P = self.n_pairs
