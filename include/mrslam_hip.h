@@ -407,6 +407,51 @@ int mrs_gicp_batch_icp_step(mrs_gicp_batch* h, const mrs_icp_params* p, const do
 int mrs_gicp_batch_icp_profile(mrs_gicp_batch* h, const mrs_icp_params* p, const double* h_poses, int32_t reps, float* out_ms,
                                int64_t* out_counts, mrs_stream stream);
 
+/* PCL-style GICP (row G11): pcl::GeneralizedIterativeClosestPoint<PointXYZI, PointXYZI> as the PCL_GICP branch of
+ * GlobalManager::select_registration_method drives it (global_manager.cpp:2419-2426), batched over the pairs of a mrs_gicp_batch: same handle,
+ * same clouds, same exact searches, and the handle's own k-NN covariances (k_correspondences of mrs_gicp_params; computed lazily, cached, shared
+ * with mrs_gicp_batch_align).  PCL's optimiser: per outer iteration the Mahalanobis matrices are frozen and a BFGS over (t, roll, pitch, yaw)
+ * minimises the mean Mahalanobis error -- here on 74 sums over the correspondences, of which the error is an exact quadratic form, so the
+ * points are read once per outer iteration.  PCL is not part of the reference tree: DESIGN.md section 4.15 is the definition (line search,
+ * pivot and the six named deviations included), parity with PCL is unpinned.  Names and defaults are PCL's. */
+typedef struct mrs_pclgicp_params {
+    int32_t max_iterations;             /* setMaximumIterations (200; Mapping: icp_iters)                                     */
+    int32_t max_inner_iterations;       /* setMaximumOptimizerIterations (20): iterations of the inner BFGS                    */
+    int32_t force_iterations;           /* > 0: exactly this many outer iterations, stopping rule disabled (timing,
+                                           fixed-length parity); converged = 0, state NOT_CONVERGED                            */
+    double max_correspondence_distance; /* setMaxCorrespondenceDistance (5.0; Mapping: 100)                                    */
+    double rotation_epsilon;            /* setRotationEpsilon (2e-3): scale of the rotation entries of the pose change         */
+    double transformation_epsilon;      /* setTransformationEpsilon (5e-4; Mapping: 1e-3): scale of its translation entries    */
+    double gradient_tolerance;          /* the inner BFGS stops below this gradient norm (1e-2)                                */
+} mrs_pclgicp_params;
+
+void mrs_pclgicp_default_params(mrs_pclgicp_params* p);
+
+/* align(output, guess) of every pair.  h_guess / h_final as in mrs_gicp_batch_align; h_converged, h_iterations and h_state (int32[n_pairs],
+ * each optional): hasConverged(), outer iterations run, and the state that ended the pair in mrs_gicp_batch_align_icp's numbering: 0
+ * NOT_CONVERGED, 1 ITERATIONS, 2 TRANSFORM (the largest entry of |X_new - X|, rotation entries over rotation_epsilon and translation
+ * entries over transformation_epsilon, fell below 1), 5 NO_CORRESPONDENCES (fewer than 4: converged = 0, the pose stays).  getFitnessScore is
+ * mrs_gicp_batch_fitness.  Synchronises `stream`.  The handle's GICP parameters are not touched and, k_correspondences apart, not used: a
+ * voxel_resolution > 0 is ignored.  An alignment leaves nothing behind that a later mrs_gicp_batch_align, _align_icp or _align_pcl on the
+ * same handle depends on, apart from the valid covariance cache. */
+int mrs_gicp_batch_align_pcl(mrs_gicp_batch* h, const mrs_pclgicp_params* p, const double* h_guess, double* h_final, int32_t* h_converged,
+                             int32_t* h_iterations, int32_t* h_state, mrs_stream stream);
+
+/* One outer iteration at given poses (kernel-level parity hook, the twin of mrs_gicp_batch_icp_step): h_sums double[n_pairs][74] in the
+ * layout of DESIGN.md section 4.15 (n, sum M, sum M q, sum q'Mq, sum p_a M, sum p_a M q, sum p_a p_b M; zeros below 4 correspondences);
+ * h_next double[n_pairs][16] the next pose (the given one below 4 correspondences); h_inner int32[n_pairs][2] the inner minimisation's
+ * iterations and ending (0 GRADIENT, 1 LIMIT, 2 NO_PROGRESS); d_corr (optional) int32[total source points] correspondences or -1. */
+int mrs_gicp_batch_pcl_step(mrs_gicp_batch* h, const mrs_pclgicp_params* p, const double* h_poses, double* h_sums, double* h_next,
+                            int32_t* h_inner, int32_t* d_corr, mrs_stream stream);
+
+/* Measurement hook of tools/bench_pclgicp.py (no reference counterpart): the three stages of one outer iteration launched alone between HIP
+ * events on `stream`, `reps` times each, at the given poses (double[n_pairs][16]).  out_ms float[3]: 0 the search of every source point
+ * (the handle's search setting, warm), 1 k_pclgicp_sums, 2 k_pclgicp_update (every launch from the given poses: a device-to-device copy of the states is part of the time).  out_counts int64[2]:
+ * source points, correspondences at the poses.  The batch's correspondences and warm-start seeds are overwritten: the alignment state the
+ * call leaves behind is meaningless (the next alignment starts over anyway). */
+int mrs_gicp_batch_pcl_profile(mrs_gicp_batch* h, const mrs_pclgicp_params* p, const double* h_poses, int32_t reps, float* out_ms,
+                               int64_t* out_counts, mrs_stream stream);
+
 /* ------------------------------------------------------------------------------------
  * rocFFT-backed 2-D correlations: DiSCO (rows D1, D2) and RING++ BEV translation (row C4)
  * ---------------------------------------------------------------------------------- */

@@ -1,6 +1,7 @@
 // gicp.hip -- host side of the batched GICP refinement: the handle (owning device buffers), the launch helpers and the C entry points.
 // The kernels and the design notes are in gicp_device.hpp, included here and nowhere else (one translation unit).
 // Point-to-point ICP (row G9) runs on the same handle: its kernels are in icp_device.hpp, its entry points at the end of the align section.
+// So does PCL-style GICP (row G11): pclgicp_device.hpp, entry points after ICP's.
 #include <hipcub/hipcub.hpp>
 
 #include <cstdlib>
@@ -9,6 +10,7 @@
 #include "common.hpp"
 #include "gicp_device.hpp"
 #include "icp_device.hpp"
+#include "pclgicp_device.hpp"
 
 // Small batches (<= kLmWindowPairs pairs: ONE registration at a time is how the nodes call it, main_RING.py:81-104, global_manager.cpp:2016-2021)
 // run the LM schedule in windows of kLmWindow ticks without a host round trip in between: every kernel of a tick gates itself on the pair's
@@ -861,6 +863,42 @@ int mrs_gicp_batch_get_voxel_map(mrs_gicp_batch* h, int32_t* h_n_voxels, int32_t
     return MRS_OK;
 }
 
+// The context slot (second stream, two events, pinned buffer) an alignment of a small batch holds for the duration of the call.  It goes back
+// idle: on the normal way out it is (the last window was synchronised); on any other way out work may still run on its stream, or a window's
+// counters may still be on their way into its pinned buffer from `s`, so both streams are drained first.
+struct AlignSide {
+    mrs_ctx* ctx; hipStream_t s; mrs::SideSlot sl; bool completed;
+    ~AlignSide()
+    {
+        if (!completed && sl.stream) {
+            (void)hipStreamSynchronize(sl.stream);
+            (void)hipStreamSynchronize(s);
+        }
+        mrs::side_release(ctx, sl);
+    }
+};
+
+// The covariances an alignment needs and the handle does not hold yet (mrs_gicp_batch_align, mrs_gicp_batch_align_pcl), enqueued on `s`.
+static int covariances_first(mrs_gicp_batch* h, bool small, const mrs::SideSlot& sl, hipStream_t s)
+{
+    int st;
+    if (small && !h->side[0].cov_valid && !h->side[1].cov_valid && !mrs::dev_env("MRS_GICP_SERIAL_COV")) {
+        // both clouds are new (every registration of the nodes): a cloud of 30-40 k points fills 150 of the 256 compute units with one wave per
+        // SIMD, so the two k-NN + covariance passes run side by side on two streams instead of back to back
+        MRS_HIP_TRY(hipEventRecord(sl.fork, s));
+        MRS_HIP_TRY(hipStreamWaitEvent(sl.stream, sl.fork, 0));
+        st = mrs_gicp_batch_compute_covariances(h, 1, nullptr, (mrs_stream)sl.stream);
+        if (st != MRS_OK) return st;
+        MRS_HIP_TRY(hipEventRecord(sl.join, sl.stream));
+        st = mrs_gicp_batch_compute_covariances(h, 0, nullptr, (mrs_stream)s);
+        if (st != MRS_OK) return st;
+        MRS_HIP_TRY(hipStreamWaitEvent(s, sl.join, 0));
+    }
+    for (int w = 0; w < 2; ++w)
+        if (!h->side[w].cov_valid) { st = mrs_gicp_batch_compute_covariances(h, w, nullptr, (mrs_stream)s); if (st != MRS_OK) return st; }
+    return MRS_OK;
+}
+
 int mrs_gicp_batch_align(mrs_gicp_batch* h, const double* h_guess, double* h_final, int32_t* h_converged,
                          int32_t* h_iterations, double* h_hessian, mrs_stream stream)
 {
@@ -874,35 +912,10 @@ int mrs_gicp_batch_align(mrs_gicp_batch* h, const double* h_guess, double* h_fin
     st = ensure_state(h);
     if (st != MRS_OK) return st;
     const bool small = h->n_pairs <= kLmWindowPairs;
-    // a second stream, two events and a pinned buffer from the context's pool for the duration of this call (small batches only).  The slot
-    // goes back idle: on the normal way out it is (the last window was synchronised); on any other way out work may still run on its stream,
-    // or a window's counters may still be on their way into its pinned buffer from `s`, so both streams are drained first.
-    struct Side {
-        mrs_ctx* ctx; hipStream_t s; mrs::SideSlot sl; bool completed;
-        ~Side()
-        {
-            if (!completed && sl.stream) {
-                (void)hipStreamSynchronize(sl.stream);
-                (void)hipStreamSynchronize(s);
-            }
-            mrs::side_release(ctx, sl);
-        }
-    } side{h->ctx, s, {}, false};
+    // a second stream, two events and a pinned buffer from the context's pool for the duration of this call (small batches only)
+    AlignSide side{h->ctx, s, {}, false};
     if (small && (st = mrs::side_acquire(h->ctx, &side.sl)) != MRS_OK) return st;
-    if (small && !h->side[0].cov_valid && !h->side[1].cov_valid && !mrs::dev_env("MRS_GICP_SERIAL_COV")) {
-        // both clouds are new (every registration of the nodes): a cloud of 30-40 k points fills 150 of the 256 compute units with one wave per
-        // SIMD, so the two k-NN + covariance passes run side by side on two streams instead of back to back
-        MRS_HIP_TRY(hipEventRecord(side.sl.fork, s));
-        MRS_HIP_TRY(hipStreamWaitEvent(side.sl.stream, side.sl.fork, 0));
-        st = mrs_gicp_batch_compute_covariances(h, 1, nullptr, (mrs_stream)side.sl.stream);
-        if (st != MRS_OK) return st;
-        MRS_HIP_TRY(hipEventRecord(side.sl.join, side.sl.stream));
-        st = mrs_gicp_batch_compute_covariances(h, 0, nullptr, stream);
-        if (st != MRS_OK) return st;
-        MRS_HIP_TRY(hipStreamWaitEvent(s, side.sl.join, 0));
-    }
-    for (int w = 0; w < 2; ++w)
-        if (!h->side[w].cov_valid) { st = mrs_gicp_batch_compute_covariances(h, w, nullptr, stream); if (st != MRS_OK) return st; }
+    if ((st = covariances_first(h, small, side.sl, s)) != MRS_OK) return st;
     if (h->prm.voxel_res > 0.0) {
         st = build_voxel_map(h, s);
         if (st != MRS_OK) return st;
@@ -1162,6 +1175,283 @@ int mrs_gicp_batch_icp_step(mrs_gicp_batch* h, const mrs_icp_params* p, const do
         memcpy(h_sums + (size_t)q * kIcpTerms, init[q].H, kIcpTerms * sizeof(double));
         memcpy(h_delta + (size_t)q * 16, init[q].delta, 16 * sizeof(double));
     }
+    return MRS_OK;
+}
+
+/* ---- PCL-style GICP (row G11; kernels: pclgicp_device.hpp) ---- */
+
+void mrs_pclgicp_default_params(mrs_pclgicp_params* p)
+{
+    if (!p) return;
+    p->max_iterations = 200;                    // pcl::GeneralizedIterativeClosestPoint; Mapping sets icp_iters (global_manager.cpp:2423)
+    p->max_inner_iterations = 20;               // setMaximumOptimizerIterations
+    p->force_iterations = 0;
+    p->max_correspondence_distance = 5.0;       // Mapping: 100 (:2422)
+    p->rotation_epsilon = 2e-3;
+    p->transformation_epsilon = 5e-4;           // Mapping: 1e-3 (:2424)
+    p->gradient_tolerance = 1e-2;
+}
+
+namespace {
+
+int pcl_check_params(const mrs_pclgicp_params* p)
+{
+    MRS_REQUIRE(p->max_iterations > 0, "max_iterations must be positive");
+    MRS_REQUIRE(p->max_inner_iterations > 0, "max_inner_iterations must be positive");
+    MRS_REQUIRE(p->force_iterations >= 0, "force_iterations must be >= 0");
+    MRS_REQUIRE(p->max_correspondence_distance > 0, "max_correspondence_distance must be positive");
+    MRS_REQUIRE(p->rotation_epsilon > 0, "rotation_epsilon must be positive");
+    MRS_REQUIRE(p->transformation_epsilon > 0, "transformation_epsilon must be positive");
+    MRS_REQUIRE(p->gradient_tolerance > 0, "gradient_tolerance must be positive");
+    return MRS_OK;
+}
+
+PclGicpParams pcl_device_params(const mrs_gicp_batch* h, const mrs_pclgicp_params* p)
+{
+    PclGicpParams d;
+    d.crit.rot_eps = p->rotation_epsilon;
+    d.crit.trans_eps = p->transformation_epsilon;
+    d.crit.grad_tol = p->gradient_tolerance;
+    d.crit.max_iter = p->max_iterations;
+    d.crit.max_inner = p->max_inner_iterations;
+    d.crit.force_iters = p->force_iterations;
+    d.crit.pad = 0;
+    d.motion_switch = h->prm.motion_switch;
+    d.pad = 0;
+    return d;
+}
+
+// The searches' parameters of a PCL-GICP call: the handle's (search margins, motion switch) with the call's own correspondence distance.
+GicpParams pcl_search_params(const mrs_gicp_batch* h, const mrs_pclgicp_params* p)
+{
+    GicpParams sp = h->prm;
+    sp.max_corr2 = p->max_correspondence_distance >= 1e150 ? INFINITY : p->max_correspondence_distance * p->max_correspondence_distance;
+    sp.voxel_res = 0.0;
+    return sp;
+}
+
+// state, block counts and a partial buffer of 74 terms per workgroup plus the totals' row per pair
+int pcl_ensure_state(mrs_gicp_batch* h)
+{
+    int st = ensure_state(h);
+    if (st != MRS_OK) return st;
+    const size_t need = (size_t)h->n_pairs * (h->lm.max_blocks + 1) * kPclTerms;
+    return h->lm.partial.reserve(need, need);
+}
+
+void launch_pcl_sums(mrs_gicp_batch* h, hipStream_t s)
+{
+    const GicpCloud &S = h->side[0], &T = h->side[1];
+    GicpLmBuffers& L = h->lm;
+    // one launch over all 74 terms: it has no scratch at 2 waves per SIMD, so the two-range form is not needed
+    hipLaunchKernelGGL((k_pclgicp_sums<0, kPclTerms>), dim3(L.max_blocks, h->n_pairs), dim3(kNNThreads), 0, s, S.pts.get(), S.d_offs.get(),
+                       S.cov.get(), T.pts.get(), T.d_offs.get(), T.cov.get(), T.bbox.get(), L.state.get(), L.corr.get(), L.partial.get(), L.max_blocks);
+}
+
+void launch_pcl_update(mrs_gicp_batch* h, const PclGicpParams& dp, int* n_next, hipStream_t s)
+{
+    GicpLmBuffers& L = h->lm;
+    hipLaunchKernelGGL(k_pclgicp_update, dim3(h->n_pairs), dim3(kLmThreads), 0, s, L.state.get(), L.partial.get(), L.nblocks.get(), L.max_blocks,
+                       h->side[1].bbox.get(), dp, n_next);
+}
+
+void pcl_init_states(std::vector<LmState>& init, const double* h_poses, bool narrow)
+{
+    for (size_t q = 0; q < init.size(); ++q) {
+        LmState& S = init[q];
+        memset(&S, 0, sizeof(S));
+        for (int i = 0; i < 16; ++i) {
+            const double g = h_poses ? h_poses[q * 16 + i] : (i % 5 == 0 ? 1.0 : 0.0);
+            S.x[i] = S.xi[i] = narrow ? (double)(float)g : g;     // pcl::Registration::align takes a Matrix4f guess
+        }
+        S.active = 1;
+    }
+}
+
+}  // namespace
+
+/* The tick loop of mrs_gicp_batch_align_icp (one kind of tick: search, sums, update) behind the covariances of mrs_gicp_batch_align. */
+int mrs_gicp_batch_align_pcl(mrs_gicp_batch* h, const mrs_pclgicp_params* p, const double* h_guess, double* h_final, int32_t* h_converged,
+                             int32_t* h_iterations, int32_t* h_state, mrs_stream stream)
+{
+    MRS_REQUIRE(h && p && h_final, "null pointer");
+    MRS_REQUIRE(h->clouds_set(), "set source and target clouds first");
+    MRS_REQUIRE(!h->no_cov, "a covariance-free container holds no covariances");
+    int st = pcl_check_params(p);
+    if (st != MRS_OK) return st;
+    MRS_HIP_TRY(hipSetDevice(h->ctx->device));
+    hipStream_t s = (hipStream_t)stream;
+    if ((st = pcl_ensure_state(h)) != MRS_OK) return st;
+    const PclGicpParams dp = pcl_device_params(h, p);
+    const GicpParams sp = pcl_search_params(h, p);
+    GicpLmBuffers& L = h->lm;
+    const int P = h->n_pairs;
+    const bool small = P <= kLmWindowPairs;
+    AlignSide side{h->ctx, s, {}, false};
+    if (small && (st = mrs::side_acquire(h->ctx, &side.sl)) != MRS_OK) return st;
+    if ((st = covariances_first(h, small, side.sl, s)) != MRS_OK) return st;
+    std::vector<LmState> init(P);
+    pcl_init_states(init, h_guess, true);
+    MRS_HIP_TRY(hipMemcpyAsync(L.state.get(), init.data(), init.size() * sizeof(LmState), hipMemcpyHostToDevice, s));
+    if (h->cert.searched) MRS_HIP_TRY(hipMemsetAsync(h->cert.searched.get(), 0, (size_t)P * kStatStride * sizeof(unsigned long long), s));
+    const long max_ticks = p->force_iterations > 0 ? p->force_iterations : p->max_iterations;     // one iteration per tick
+    long ticks = 0, nn_ticks = 0;
+    int next[4] = {P, 0, P, 0};
+    int window = kLmWindow;
+    if (const char* v = mrs::dev_env("MRS_GICP_WINDOW")) window = std::max(0, std::min(kLmWindowMax, atoi(v)));
+    if (small && window > 1) {
+        int* const h_win = side.sl.pinned;
+        while (next[0] > 0 && ticks < max_ticks) {
+            MRS_HIP_TRY(hipMemsetAsync(L.nactive.get(), 0, (size_t)window * 4 * sizeof(int), s));
+            for (int t = 0; t < window; ++t) {
+                h->big_movers = 1;                      // the broad search gates itself on the pair's motion (k_nn_scan: gate)
+                if ((st = nn_pass(h, sp, (ticks == 0 && t == 0) ? 0 : 1, s)) != MRS_OK) return st;
+                launch_pcl_sums(h, s);
+                launch_pcl_update(h, dp, L.nactive.get() + 4 * t, s);
+            }
+            MRS_HIP_TRY(hipGetLastError());
+            MRS_HIP_TRY(hipMemcpyAsync(h_win, L.nactive.get(), (size_t)window * 4 * sizeof(int), hipMemcpyDeviceToHost, s));
+            MRS_HIP_TRY(hipStreamSynchronize(s));
+            for (int t = 0; t < window; ++t) nn_ticks += h_win[4 * t + 3];
+            for (int i = 0; i < 3; ++i) next[i] = h_win[4 * (window - 1) + i];
+            ticks += window;
+        }
+    }
+    while (next[0] > 0 && ticks < max_ticks) {
+        MRS_HIP_TRY(hipMemsetAsync(L.nactive.get(), 0, 4 * sizeof(int), s));
+        h->big_movers = next[2];
+        if ((st = nn_pass(h, sp, nn_ticks == 0 ? 0 : 1, s)) != MRS_OK) return st;
+        launch_pcl_sums(h, s);
+        launch_pcl_update(h, dp, L.nactive.get(), s);
+        ++nn_ticks;
+        MRS_HIP_TRY(hipGetLastError());
+        MRS_HIP_TRY(hipMemcpyAsync(next, L.nactive.get(), 3 * sizeof(int), hipMemcpyDeviceToHost, s));
+        MRS_HIP_TRY(hipStreamSynchronize(s));
+        ++ticks;
+    }
+    MRS_HIP_TRY(hipStreamSynchronize(s));
+    side.completed = true;
+    if ((st = record_search_stats(h, nn_ticks)) != MRS_OK) return st;
+    MRS_HIP_TRY(hipMemcpy(init.data(), L.state.get(), init.size() * sizeof(LmState), hipMemcpyDeviceToHost));
+    for (int q = 0; q < P; ++q) {
+        const LmState& S = init[q];
+        for (int i = 0; i < 16; ++i) h_final[(size_t)q * 16 + i] = (double)(float)S.x[i];  // final_transformation_ is float
+        if (h_converged) h_converged[q] = S.converged;
+        if (h_iterations) h_iterations[q] = S.outer;
+        if (h_state) h_state[q] = S.inner;
+    }
+    return MRS_OK;
+}
+
+int mrs_gicp_batch_pcl_step(mrs_gicp_batch* h, const mrs_pclgicp_params* p, const double* h_poses, double* h_sums, double* h_next,
+                            int32_t* h_inner, int32_t* d_corr, mrs_stream stream)
+{
+    MRS_REQUIRE(h && p && h_poses && h_sums && h_next && h_inner, "null pointer");
+    MRS_REQUIRE(h->clouds_set(), "set source and target clouds first");
+    MRS_REQUIRE(!h->no_cov, "a covariance-free container holds no covariances");
+    int st = pcl_check_params(p);
+    if (st != MRS_OK) return st;
+    MRS_HIP_TRY(hipSetDevice(h->ctx->device));
+    hipStream_t s = (hipStream_t)stream;
+    const GicpCloud &S = h->side[0], &T = h->side[1];
+    GicpLmBuffers& L = h->lm;
+    if ((st = pcl_ensure_state(h)) != MRS_OK) return st;
+    for (int w = 0; w < 2; ++w)
+        if (!h->side[w].cov_valid) { st = mrs_gicp_batch_compute_covariances(h, w, nullptr, stream); if (st != MRS_OK) return st; }
+    PclGicpParams dp = pcl_device_params(h, p);
+    dp.crit.max_iter = 1;           // one iteration, then the pair stops whatever the rule says
+    dp.crit.force_iters = 0;
+    const GicpParams sp = pcl_search_params(h, p);
+    const int P = h->n_pairs;
+    std::vector<LmState> init(P);
+    pcl_init_states(init, h_poses, false);
+    MRS_HIP_TRY(hipMemcpyAsync(L.state.get(), init.data(), init.size() * sizeof(LmState), hipMemcpyHostToDevice, s));
+    MRS_HIP_TRY(hipMemsetAsync(L.nactive.get(), 0, 4 * sizeof(int), s));
+    if ((st = nn_pass(h, sp, 2, s)) != MRS_OK) return st;
+    launch_pcl_sums(h, s);
+    launch_pcl_update(h, dp, L.nactive.get(), s);
+    if (d_corr)
+        hipLaunchKernelGGL(k_corr_to_original, dim3(64, P), dim3(256), 0, s, S.pts.get(), S.d_offs.get(), T.pts.get(), T.d_offs.get(),
+                           L.corr.get(), d_corr);
+    MRS_HIP_TRY(hipGetLastError());
+    MRS_HIP_TRY(hipMemcpyAsync(init.data(), L.state.get(), init.size() * sizeof(LmState), hipMemcpyDeviceToHost, s));
+    for (int q = 0; q < P; ++q)
+        MRS_HIP_TRY(hipMemcpyAsync(h_sums + (size_t)q * kPclTerms, L.partial.get() + ((size_t)q * (L.max_blocks + 1) + L.max_blocks) * kPclTerms,
+                                   kPclTerms * sizeof(double), hipMemcpyDeviceToHost, s));
+    MRS_HIP_TRY(hipStreamSynchronize(s));
+    for (int q = 0; q < P; ++q) {
+        memcpy(h_next + (size_t)q * 16, init[q].x, 16 * sizeof(double));
+        h_inner[2 * q] = init[q].trials;
+        h_inner[2 * q + 1] = init[q].failed;
+    }
+    return MRS_OK;
+}
+
+/* Measurement hook of tools/bench_pclgicp.py: the three stages of one iteration launched ALONE between HIP events on `stream`, at the given
+ * poses, `reps` times each (the average goes to out_ms): [0] the search of every source point (the handle's search setting, warm),
+ * [1] k_pclgicp_sums, [2] k_pclgicp_update.  out_counts: [0] source points, [1] correspondences at the poses.  Overwrites the batch's
+ * correspondences and warm-start seeds. */
+int mrs_gicp_batch_pcl_profile(mrs_gicp_batch* h, const mrs_pclgicp_params* p, const double* h_poses, int32_t reps, float* out_ms,
+                               int64_t* out_counts, mrs_stream stream)
+{
+    MRS_REQUIRE(h && p && h_poses && out_ms && out_counts, "null pointer");
+    MRS_REQUIRE(h->clouds_set(), "set source and target clouds first");
+    MRS_REQUIRE(!h->no_cov, "a covariance-free container holds no covariances");
+    MRS_REQUIRE(reps >= 1, "reps must be >= 1");
+    int st = pcl_check_params(p);
+    if (st != MRS_OK) return st;
+    MRS_HIP_TRY(hipSetDevice(h->ctx->device));
+    hipStream_t s = (hipStream_t)stream;
+    GicpLmBuffers& L = h->lm;
+    if ((st = pcl_ensure_state(h)) != MRS_OK) return st;
+    for (int w = 0; w < 2; ++w)
+        if (!h->side[w].cov_valid) { st = mrs_gicp_batch_compute_covariances(h, w, nullptr, stream); if (st != MRS_OK) return st; }
+    PclGicpParams dp = pcl_device_params(h, p);
+    dp.crit.max_iter = INT32_MAX;       // the update kernel is timed on pairs that stay active: no rule may end them
+    dp.crit.force_iters = INT32_MAX;
+    const GicpParams sp = pcl_search_params(h, p);
+    std::vector<LmState> init(h->n_pairs);
+    pcl_init_states(init, h_poses, false);
+    MRS_HIP_TRY(hipMemcpyAsync(L.state.get(), init.data(), init.size() * sizeof(LmState), hipMemcpyHostToDevice, s));
+    MRS_HIP_TRY(hipStreamSynchronize(s));
+    struct Events {
+        hipEvent_t e0 = nullptr, e1 = nullptr;
+        ~Events() { if (e0) (void)hipEventDestroy(e0); if (e1) (void)hipEventDestroy(e1); }
+    } ev;
+    MRS_HIP_TRY(hipEventCreate(&ev.e0)); MRS_HIP_TRY(hipEventCreate(&ev.e1));
+    auto timed = [&](float& ms, auto&& launch) -> int {
+        launch();                                     // warm
+        MRS_HIP_TRY(hipEventRecord(ev.e0, s));
+        for (int r = 0; r < reps; ++r) launch();
+        MRS_HIP_TRY(hipEventRecord(ev.e1, s));
+        MRS_HIP_TRY(hipEventSynchronize(ev.e1));
+        MRS_HIP_TRY(hipGetLastError());
+        MRS_HIP_TRY(hipEventElapsedTime(&ms, ev.e0, ev.e1));
+        ms /= (float)reps;
+        return MRS_OK;
+    };
+    int nn_st = MRS_OK;
+    if ((st = timed(out_ms[0], [&]() { const int r = nn_pass(h, sp, 2, s); if (r != MRS_OK) nn_st = r; })) != MRS_OK) return st;
+    if (nn_st != MRS_OK) return nn_st;
+    if ((st = timed(out_ms[1], [&]() { launch_pcl_sums(h, s); })) != MRS_OK) return st;
+    {
+        std::vector<int> corr(L.n_seed);
+        MRS_HIP_TRY(hipMemcpy(corr.data(), L.corr.get(), corr.size() * sizeof(int), hipMemcpyDeviceToHost));
+        int64_t c = 0;
+        for (int v : corr) c += v >= 0;
+        out_counts[0] = (int64_t)L.n_seed; out_counts[1] = c;
+    }
+    MRS_HIP_TRY(hipMemsetAsync(L.nactive.get(), 0, 4 * sizeof(int), s));
+    // every launch starts from the given poses (a device-to-device copy of the states, part of the time): the inner minimisation timed is
+    // that of the sums at hand, not of a pose already at their minimum
+    mrs::Scratch start;
+    if ((st = start.alloc(init.size() * sizeof(LmState), s)) != MRS_OK) return st;
+    MRS_HIP_TRY(hipMemcpyAsync(start.p, init.data(), init.size() * sizeof(LmState), hipMemcpyHostToDevice, s));
+    MRS_HIP_TRY(hipStreamSynchronize(s));
+    if ((st = timed(out_ms[2], [&]() {
+             (void)hipMemcpyAsync(L.state.get(), start.p, init.size() * sizeof(LmState), hipMemcpyDeviceToDevice, s);
+             launch_pcl_update(h, dp, L.nactive.get(), s);
+         })) != MRS_OK) return st;
     return MRS_OK;
 }
 

@@ -42,6 +42,26 @@ def default_icp_params(**kw):
     return p
 
 
+class PclGicpParams(C.Structure):
+    _fields_ = [("max_iterations", C.c_int32), ("max_inner_iterations", C.c_int32), ("force_iterations", C.c_int32),
+                ("max_correspondence_distance", C.c_double), ("rotation_epsilon", C.c_double),
+                ("transformation_epsilon", C.c_double), ("gradient_tolerance", C.c_double)]
+
+
+PCL_INNER_ENDS = ("GRADIENT", "LIMIT", "NO_PROGRESS")    # how the inner BFGS of a PCL-style GICP iteration ended
+
+
+def default_pclgicp_params(**kw):
+    """pcl::GeneralizedIterativeClosestPoint's defaults, with the given fields replaced"""
+    p = PclGicpParams()
+    _lib.load().mrs_pclgicp_default_params(C.byref(p))
+    for k, v in kw.items():
+        if not hasattr(p, k):
+            raise AttributeError(k)
+        setattr(p, k, v)
+    return p
+
+
 _tls = __import__("threading").local()
 
 
@@ -224,6 +244,46 @@ class GicpBatch:
         _lib.load().mrs_gicp_batch_icp_profile(self._h, C.byref(default_icp_params(**params)), poses, int(reps), ms, cnt,
                                                _lib.current_stream(self.device))
         return ({n: float(v) for n, v in zip(("search", "icp_sums", "icp_update"), ms)},
+                {"source_points": int(cnt[0]), "correspondences": int(cnt[1])})
+
+    def align_pcl(self, guesses=None, **params):
+        """PCL-style GICP (row G11, pcl::GeneralizedIterativeClosestPoint) on the batch's clouds and covariances; params: the fields of
+        PclGicpParams (PCL's defaults otherwise).  Returns (T [P,4,4] float64, converged [P] bool, iterations [P] int32, state [P] int32:
+        index into ICP_STATES)."""
+        P = self.n_pairs
+        g = None
+        if guesses is not None:
+            g = np.ascontiguousarray(np.asarray(guesses, dtype=np.float64).reshape(P, 16))
+        T = np.empty((P, 16), np.float64)
+        conv = np.empty(P, np.int32)
+        its = np.empty(P, np.int32)
+        state = np.empty(P, np.int32)
+        lib = _lib.load()
+        lib.mrs_gicp_batch_align_pcl(self._h, C.byref(default_pclgicp_params(**params)), g, T, conv, its, state, _lib.current_stream(self.device))
+        self.nn_passes = lib.mrs_gicp_batch_last_nn_passes(self._h)
+        self.searched_fraction = lib.mrs_gicp_batch_last_searched_fraction(self._h)
+        return T.reshape(P, 4, 4), conv.astype(bool), its, state
+
+    def pcl_step(self, poses, want_corr=False, **params):
+        """One outer iteration of PCL-style GICP at `poses` (mrs_gicp_batch_pcl_step): correspondences, the 74 sums, the inner BFGS.
+        Returns (sums [P,74], next pose [P,4,4], inner [P,2] int32: iterations and index into PCL_INNER_ENDS, corr or None)."""
+        P = self.n_pairs
+        poses = np.ascontiguousarray(np.asarray(poses, dtype=np.float64).reshape(P, 16))
+        sums = np.empty((P, 74), np.float64); nxt = np.empty((P, 16), np.float64); inner = np.empty((P, 2), np.int32)
+        corr = torch.empty(int(self._n[0][-1]), dtype=torch.int32, device=f"cuda:{self.device}") if want_corr else None
+        _lib.load().mrs_gicp_batch_pcl_step(self._h, C.byref(default_pclgicp_params(**params)), poses, sums, nxt, inner, corr,
+                                            _lib.current_stream(self.device))
+        return sums, nxt.reshape(P, 4, 4), inner, (corr.cpu().numpy() if want_corr else None)
+
+    def pcl_profile(self, poses, reps=3, **params):
+        """HIP-event duration of the three stages of one PCL-style GICP iteration, each launched alone at `poses`
+        (mrs_gicp_batch_pcl_profile).  Returns (dict of ms, dict of counts)."""
+        P = self.n_pairs
+        poses = np.ascontiguousarray(np.asarray(poses, dtype=np.float64).reshape(P, 16))
+        ms = np.zeros(3, np.float32); cnt = np.zeros(2, np.int64)
+        _lib.load().mrs_gicp_batch_pcl_profile(self._h, C.byref(default_pclgicp_params(**params)), poses, int(reps), ms, cnt,
+                                               _lib.current_stream(self.device))
+        return ({n: float(v) for n, v in zip(("search", "pclgicp_sums", "pclgicp_update"), ms)},
                 {"source_points": int(cnt[0]), "correspondences": int(cnt[1])})
 
     def profile(self, poses, reps=3):
