@@ -142,14 +142,18 @@ __global__ __launch_bounds__(kWG) void k_ring_corr(const float* __restrict__ Q, 
 // ---- small DFTs along one axis of [n_img][A][D] tiles held in LDS (N <= 256) ---------------
 // twiddle table: tw[k] = (cos(2 pi k / N), sin(2 pi k / N)), computed on the host in double.
 
+// The float2 twiddle table follows the float tile in LDS: the tile length is rounded up to an even
+// number of floats so that the table is 8-byte aligned for odd sizes too (kernels and launchers agree).
+__host__ __device__ constexpr size_t even_floats(size_t n) { return (n + 1) & ~(size_t)1; }
+
 // R2 (util.py:198): X[k][d] = N^-1/2 * sum_j x[j][d] * exp(-2 pi i j k / N), along the angle axis.
 // out is interleaved complex64 [img][A][D].  One workgroup per image.
 __global__ __launch_bounds__(kWG) void k_dft_angle_r2c(const float* __restrict__ x, int A, int D,
                                                        const float2* __restrict__ tw_g, float2* __restrict__ out)
 {
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    float* tile = smem;                                   // [A][D]
-    float2* tw = reinterpret_cast<float2*>(tile + A * D);  // [A]
+    float* tile = smem;                                              // [A][D]
+    float2* tw = reinterpret_cast<float2*>(tile + even_floats(A * D));  // [A], 8-byte aligned for every A, D
     const float* src = x + (size_t)blockIdx.x * A * D;
     for (int i = threadIdx.x; i < A * D; i += kWG) tile[i] = src[i];
     for (int i = threadIdx.x; i < A; i += kWG) tw[i] = tw_g[i];
@@ -179,8 +183,8 @@ __global__ __launch_bounds__(kWG) void k_dft_row_mag(const float* __restrict__ x
                                                      const float2* __restrict__ tw_g, float* __restrict__ out)
 {
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    float* tile = smem;                                       // [A][D+1] padded
-    float2* tw = reinterpret_cast<float2*>(tile + A * (D + 1));
+    float* tile = smem;                                                    // [A][D+1] padded
+    float2* tw = reinterpret_cast<float2*>(tile + even_floats(A * (D + 1)));  // [D], 8-byte aligned for every A, D
     const float* src = x + (size_t)blockIdx.x * A * D;
     for (int i = threadIdx.x; i < A * D; i += kWG) {
         const int r = i / D, c = i - r * D;
@@ -460,7 +464,7 @@ int mrs_fft_angle_r2c(mrs_ctx* ctx, const float* d_x, int32_t n_img, int32_t n_a
 {
     MRS_REQUIRE(ctx && d_x && d_out, "null pointer");
     MRS_REQUIRE(n_img > 0 && n_angles > 0 && det > 0, "sizes must be positive");
-    const size_t lds = ((size_t)n_angles * det + 2 * (size_t)n_angles) * sizeof(float);
+    const size_t lds = (even_floats((size_t)n_angles * det) + 2 * (size_t)n_angles) * sizeof(float);
     if (lds > ctx->lds_bytes) { mrs::set_error("fft_angle_r2c: tile does not fit LDS"); return MRS_ERR_UNSUPPORTED; }
     MRS_HIP_TRY(hipSetDevice(ctx->device));
     const float2* tw;
@@ -479,7 +483,7 @@ int mrs_fft_row_magnitude(mrs_ctx* ctx, const float* d_x, int32_t n_img, int32_t
 {
     MRS_REQUIRE(ctx && d_x && d_out, "null pointer");
     MRS_REQUIRE(n_img > 0 && n_angles > 0 && det > 0, "sizes must be positive");
-    const size_t lds = ((size_t)n_angles * (det + 1) + 2 * (size_t)det) * sizeof(float);
+    const size_t lds = (even_floats((size_t)n_angles * (det + 1)) + 2 * (size_t)det) * sizeof(float);
     if (lds > ctx->lds_bytes) { mrs::set_error("fft_row_magnitude: tile does not fit LDS"); return MRS_ERR_UNSUPPORTED; }
     MRS_HIP_TRY(hipSetDevice(ctx->device));
     const float2* tw;
