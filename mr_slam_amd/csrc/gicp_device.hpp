@@ -1531,7 +1531,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void k
         const double rad = sqrt(hd * hd + cv[1] * cv[1]);
         float e[5] = {(float)w[0], (float)w[1], (float)w[2], (float)(hm + rad), (float)(hm - rad)};
         float f[13];
-        point_features(e, nz, k, f);
+        point_features(e, nz, cnt, f);     // cnt = min(k, n): a cloud with fewer than k points gives what k = n gives (no phantom neighbours at z = 0)
         const size_t gi = (size_t)(o + oi);
         if (knn_out)
             for (int s = 0; s < k; ++s) knn_out[gi * k + s] = nb[s << 6] >= 0 ? __float_as_int(pts[nb[s << 6]].w) : -1;

@@ -39,12 +39,21 @@ def _pose_err(A, B):
 def test_knn_and_covariances_match_oracle(dev, oracle):
     from mr_slam_amd import gicp
     src, tgt, _ = _pair(1, 7000)
-    for k in (20, 15):
+    wants = {}
+    # the default search at the oracle's and Mapping's k; then both selection kernels (3: k_knn_select, which has no list size of 30; 0:
+    # k_knn_cov) at k = 3 (the smallest), 7, 17 (partial last chunks of neighbour_moments' 5 slots), 31 and 32 (the 32-slot lists)
+    for k, core in [(20, None), (15, None)] + [(k, c) for k in (3, 7, 17, 31, 32) for c in (3, 0)]:
         b = gicp.GicpBatch(2)
+        if core is not None:
+            b.set_search(core)
         b.set_params(k_correspondences=k)
         b.set_sources([src, tgt[:3001]])
         knn = b.compute_covariances(0, want_knn=True).cpu().numpy()
-        want = np.concatenate([oracle.knn(src, k), oracle.knn(tgt[:3001], k)])
+        if k not in wants:
+            g = oracle.Gicp(k=k)
+            g.set_source(src); g.set_target(tgt[:3001])
+            wants[k] = (np.concatenate([oracle.knn(src, k), oracle.knn(tgt[:3001], k)]), np.concatenate([g.covariances(0), g.covariances(1)]))
+        want, want_cov = wants[k]
         same = (np.sort(knn, 1) == np.sort(want, 1)).all(1)
         # exactness: wherever the index sets differ the DISTANCES are identical (exact float ties), i.e. the multiset of
         # the k smallest squared distances (the search's own float operation chain) agrees for every point
@@ -55,13 +64,10 @@ def test_knn_and_covariances_match_oracle(dev, oracle):
             assert np.array_equal(np.sort(dg, 1), np.sort(dw, 1))
             assert (np.diff(dg, axis=1) >= 0).all()            # ascending distance, as the header promises
         assert same.mean() > 0.99                                # ties are rare on noisy clouds
-        g = oracle.Gicp(k=k)
-        g.set_source(src); g.set_target(tgt[:3001])
-        want_cov = np.concatenate([g.covariances(0), g.covariances(1)])
         got = b.covariances(0)
         # identical neighbour sets -> identical covariances (to rounding of the 3x3 eigenvector); a point whose set
         # differs by an exact tie legitimately has another (equally valid) covariance
-        assert np.abs(got - want_cov).reshape(-1, 9).max(1)[same].max() < 1e-9
+        assert np.abs(got - want_cov).reshape(-1, 9).max(1)[same].max() < 1e-9, (k, core)
 
 
 def test_linearize_matches_oracle(dev, oracle):
@@ -362,7 +368,7 @@ def _knn_d2(oracle, cloud, knn):
     return np.stack([oracle.pair_d2(cloud, I, cloud, knn[:, j]) for j in range(knn.shape[1])], 1)
 
 
-@pytest.mark.parametrize("k", [15, 20, 30])
+@pytest.mark.parametrize("k", [15, 20, 30, 3, 7, 17, 31, 32])
 def test_knn_exact_on_adversarial_clouds(dev, oracle, k):
     """Both k-NN kernels (round 4: octree-cell leaves, per-query culling; round 3: the default) against the restatement's exact kd-tree
     search: same multiset of float distances, ascending, every index valid and distinct -- on a lidar scan, uniform points, a lattice
