@@ -36,9 +36,10 @@ namespace {
 //   * eps_fast (bev_cart.hpp): the distance from a bin edge below which a point leaves the fp32 path is 3.4x the worst-case error
 //     of the fma quotient instead of the stand-alone kernel's 17x, so that 1.3 % instead of 6 % of the wave-points drag their
 //     wave through the exact (fp64 division) path.  Same bits: tools/ab_fused.py compares billions of points per run.
+// The scan is shared by `G` lanes, of which this is lane `t`: the whole workgroup, or the half of it that rasterise_pair (below) gives a scan.
 template <int PF>
 __device__ __forceinline__ void rasterise_scan(int* icells, int which, const float* __restrict__ px, const float* __restrict__ py,
-                                               const float* __restrict__ pz, int n, const CartP& p, int stride)
+                                               const float* __restrict__ pz, int n, const CartP& p, int stride, int t, int G)
 {
     // Only z > 0 can change the map (max_h starts at 0: manager.cu:57,69).  Common case in one test: 0 < z < 1 and
     // 0 < |x|,|y| <= 1 and both quotients at least eps away from a bin edge -> the fp32 quotient's floor IS the reference's
@@ -80,12 +81,12 @@ __device__ __forceinline__ void rasterise_scan(int* icells, int which, const flo
         const float4* x4 = reinterpret_cast<const float4*>(px);
         const float4* y4 = reinterpret_cast<const float4*>(py);
         const float4* z4 = reinterpret_cast<const float4*>(pz);
-        constexpr int kStage = PF * kRadonWG;       // quads per stage of the whole workgroup
+        const int kStage = PF * G;                  // quads per stage of the scan's lanes
         const int stages = n4 / kStage;             // full stages: every lane owns PF valid quads, no bounds tests
         auto fetch = [&](int s, float4 (&A)[PF], float4 (&Bv)[PF], float4 (&Cv)[PF]) {
 #pragma unroll
             for (int u = 0; u < PF; ++u) {
-                const int k = s * kStage + u * kRadonWG + (int)threadIdx.x;
+                const int k = s * kStage + u * G + t;
                 A[u] = stream_load4(x4 + k); Bv[u] = stream_load4(y4 + k); Cv[u] = stream_load4(z4 + k);
             }
         };
@@ -117,7 +118,7 @@ __device__ __forceinline__ void rasterise_scan(int* icells, int which, const flo
             }
             rasterise(X, Y, Z);
         }
-        for (int k = stages * kStage + (int)threadIdx.x; k < n4; k += kRadonWG) {      // the ragged end: fewer quads than lanes x PF
+        for (int k = stages * kStage + t; k < n4; k += G) {      // the ragged end: fewer quads than lanes x PF
             const float4 A = stream_load4(x4 + k), Bv = stream_load4(y4 + k), Cv = stream_load4(z4 + k);
             put(A.x, Bv.x, Cv.x);
             put(A.y, Bv.y, Cv.y);
@@ -126,7 +127,24 @@ __device__ __forceinline__ void rasterise_scan(int* icells, int which, const flo
         }
         done = n4 << 2;
     }
-    for (int i = done + threadIdx.x; i < n; i += kRadonWG) put(px[i], py[i], pz[i]);
+    for (int i = done + t; i < n; i += G) put(px[i], py[i], pz[i]);
+}
+
+// The scans of one round into the cleared tile.  A round with two scans gives waves 0-7 scan A and waves 8-15 scan B instead of all 16 waves
+// first A, then B: the A and B cells are disjoint ints of the interleaved tile and max is order-free, so the image is the same.  Every SIMD
+// then holds two waves of each stream, whose fetch - wait - rasterise patterns are not in step (the four waves of a SIMD on ONE stream wait
+// together), and a round pays one exposed first fetch and one ragged end instead of two.  Measured (profiles/r08_fused_stream.md): -1 ... -5 %
+// kernel time from box to box; the halves are not balanced when the scans differ in length (the shorter one's waves wait at the barrier).  A round with one scan
+// (the last of an odd batch) keeps all 16 waves on it.  `half`, and with it the scan's pointers and length, is wave-uniform: no divergence.
+template <int PF>
+__device__ __forceinline__ void rasterise_pair(int* icells, int tid, bool two, const float* __restrict__ xyz, const int64_t* __restrict__ offs, int b0,
+                                               const CartP& cp, int stride)
+{
+    const int half = two ? __builtin_amdgcn_readfirstlane(tid >> 9) : 0;
+    const int64_t o = offs[b0 + half];
+    const int n = (int)(offs[b0 + half + 1] - o);
+    const float* px = xyz + 3 * o;
+    rasterise_scan<PF>(icells, half, px, px + n, px + 2 * (size_t)n, n, cp, stride, two ? tid & (kRadonWG / 2 - 1) : tid, two ? kRadonWG / 2 : kRadonWG);
 }
 
 // grid = persistent workgroups (one per compute unit); pair 2k, 2k+1 of the batch per round, rounds handed out by *next_pair
@@ -160,17 +178,19 @@ __global__ __launch_bounds__(kRadonWG) void k_bev_radon2(const float* __restrict
         int2* z2 = reinterpret_cast<int2*>(lds_i);
         for (int i = threadIdx.x; i < rows * p.stride; i += kRadonWG) z2[i] = make_int2(0, 0);
         __syncthreads();
+        // one scan after the other, all 16 waves on each: with the two streams of rasterise_pair this kernel's unrolled ray loop spills 8 more
+        // registers (76 -> 108 bytes of scratch per lane), and it is not the variant that ships
         {
             const int64_t o = offs[b0];
             const int n = (int)(offs[b0 + 1] - o);
             const float* px = xyz + 3 * o;
-            rasterise_scan<PF>(lds_i, 0, px, px + n, px + 2 * (size_t)n, n, cp, p.stride);
+            rasterise_scan<PF>(lds_i, 0, px, px + n, px + 2 * (size_t)n, n, cp, p.stride, (int)threadIdx.x, kRadonWG);
         }
         if (two) {
             const int64_t o = offs[b1];
             const int n = (int)(offs[b1 + 1] - o);
             const float* px = xyz + 3 * o;
-            rasterise_scan<PF>(lds_i, 1, px, px + n, px + 2 * (size_t)n, n, cp, p.stride);
+            rasterise_scan<PF>(lds_i, 1, px, px + n, px + 2 * (size_t)n, n, cp, p.stride, (int)threadIdx.x, kRadonWG);
         }
         __syncthreads();
         if (bev_out) {   // the COMPACT layout of mrs_bev_cart_batch: [b][ix][iy]
@@ -249,18 +269,7 @@ __global__ __launch_bounds__(kRadonWG) void k_bev_radon3(const float* __restrict
         int2* z2 = reinterpret_cast<int2*>(lds_i);
         for (int i = threadIdx.x; i < rows * p.stride; i += kRadonWG) z2[i] = make_int2(0, 0);
         __syncthreads();
-        if (!(dev_skip & 1)) {
-            const int64_t o = offs[b0];
-            const int n = (int)(offs[b0 + 1] - o);
-            const float* px = xyz + 3 * o;
-            rasterise_scan<PF>(lds_i, 0, px, px + n, px + 2 * (size_t)n, n, cp, p.stride);
-        }
-        if (two && !(dev_skip & 1)) {
-            const int64_t o = offs[b1];
-            const int n = (int)(offs[b1 + 1] - o);
-            const float* px = xyz + 3 * o;
-            rasterise_scan<PF>(lds_i, 1, px, px + n, px + 2 * (size_t)n, n, cp, p.stride);
-        }
+        if (!(dev_skip & 1)) rasterise_pair<PF>(lds_i, tid, two, xyz, offs, b0, cp, p.stride);
         __syncthreads();
         if (bev_out) {   // the COMPACT layout of mrs_bev_cart_batch: [b][ix][iy]
             for (int i = threadIdx.x; i < hw; i += kRadonWG) {
