@@ -106,6 +106,26 @@ __device__ __forceinline__ void corr_irfft120(LoadA la, LoadB lb, v2f (&x)[60])
     cfft60_inv(x);
 }
 
+// The same inverse transform for conjugate products that already sit in registers, p(k) = a[k] * conj(b[k]), k = 0..60: the
+// pre-processing of corr_irfft120 on the same values in the same order.  mid() runs between the pre-processing and the
+// 60-point codelet, when every product has been consumed: a caller that loops places requests for its next item there.
+template <class Prod, class Mid>
+__device__ __forceinline__ void irfft120_products(Prod p, v2f (&x)[60], Mid mid)
+{
+#pragma unroll
+    for (int J = 0; J < 30; ++J) {
+        v2f zj, zp;
+        irfft_pre_pair(J, p(J), p(60 - J), zj, zp);
+        x[J] = zj;
+        if (J != 0) x[60 - J] = zp;
+    }
+    const v2f pm = p(30);
+    v2f unused;
+    irfft_pre_pair(30, pm, pm, x[30], unused);
+    mid();
+    cfft60_inv(x);
+}
+
 // real samples (x[m] = (sample 2m, sample 2m + 1)) -> TWICE the spectrum, 2 X[k] = 2 sum_n s[n] exp(-2 pi i k n / 120),
 // k = 0..60, handed to store(k, value) (the caller folds the exact factor 0.5 into its own scale).
 // Z = FFT60(x); S = Z[k] + conj(Z[60-k]), T = (Z[k] - conj(Z[60-k])) exp(-2 pi i k / 120), 2 X[k] = S - i T; the partner
@@ -789,81 +809,121 @@ __global__ __launch_bounds__(NSLOT* kSlotThreads) void k_ring_sweep_mc(const flo
 }
 
 // New-descriptor path of a loop check in ONE launch (row R2 + C1 for pairs): half spectrum of the freshly
-// normalised sinogram (written out: it becomes a database entry / travels to the other ranks) and, straight from
-// the LDS copy of that spectrum, its correlation with the candidate's.  Same arithmetic, op for op, as
-// k_ring_half_spectrum followed by the pairwise k_ring_corr_fft (bitwise identical results), one launch and one
-// round trip of the spectrum through HBM less.  grid = pairs, 128 lanes.
+// normalised sinogram (written out: it becomes a database entry / travels to the other ranks) and its correlation with the
+// candidate's.  Same arithmetic, op for op, as k_ring_half_spectrum followed by the pairwise k_ring_corr_fft (bitwise
+// identical results), one launch and one round trip of the spectrum through HBM less.  128 lanes per workgroup.
 // CT = float2 (exact database entries) or __half2 (fp16 replicas received from other ranks); cand_idx (optional):
 // the candidate of pair i is row cand_idx[i] of `cand` (a pre-selected row of the replicated database) instead of row i.
-template <typename CT>
+// OUT: bit 0 = `out` is written, bit 1 = `out16` is written (compile time: a test per store cuts the forward transform's
+// tail into 122 basic blocks that nothing can be scheduled across).
+// Candidate rows must not be entries that the same launch writes (`out` may be a slice of the database `cand` points
+// into): a workgroup reads its candidate while other workgroups write theirs, in no defined order.
+//
+// grid = min(pairs, 2 x compute units); workgroup b handles the pairs b, b + grid, b + 2 grid, ...  At 350 - 410 registers a SIMD
+// holds one wave, so nothing else hides that wave's memory latency: the loop keeps requests in flight while it computes.
+//   top of a pair        the candidate's column is requested (61 loads; it arrives under the forward transform)
+//   forward transform    writes the new entry; each value X[k] meets the candidate's value on the spot and the conjugate
+//                        product takes the candidate's registers (a lane only ever needs its own column of the new spectrum:
+//                        no LDS copy, no barrier).  The sinogram registers are dead afterwards
+//   pre-pair stage       consumes the products
+//   inverse transform, reduce-scatter, maximum: the NEXT pair's sinogram column (120 loads into the registers of the
+//                        current one) is in flight, requested in two halves around the pre-pair stage
+// and the row index of the next pair is read a whole iteration before its candidate is requested.  Requests beyond the last
+// pair are clamped to the current pair, not branched over: behind a branch the compiler sinks the pre-pair stage below the
+// requests and then waits for them.
+// xbuf (wave 1 -> wave 0) alternates between two buffers with every pair that uses it: a buffer is rewritten two barriers
+// after wave 0 read it.  A pair without a database row skips the second half as a workgroup (the row index is uniform),
+// still writes its spectrum and still requests the next sinogram.
+template <typename CT, int OUT>
 __global__ __launch_bounds__(kSlotThreads) __attribute__((amdgpu_waves_per_eu(1, 1))) void k_ring_spec_corr_pairs(const float* __restrict__ x, const CT* __restrict__ cand,
-                                                                       const int* __restrict__ cand_idx, int n_db,
+                                                                       const int* __restrict__ cand_idx, int n_db, int n_pairs,
                                                                        float2* __restrict__ out, __half2* __restrict__ out16,
                                                                        float denom, float* __restrict__ dist,
                                                                        int* __restrict__ angle)
 {
-    extern __shared__ __attribute__((aligned(16))) v2f qs[];  // [61][128], columns 120..127 zero
-    __shared__ float xbuf[128];
-    const int pair = blockIdx.x;
+    __shared__ float xbuf[2][128];
     const int t = threadIdx.x, wave = t >> 6, lane = t & 63;
     const int d = min(t, kD - 1);
     const bool live_col = t < kD;
-    // the candidate's column is requested first: it arrives while the forward transform of the new sinogram runs (the
-    // workgroup's LDS footprint allows one wave per SIMD anyway, so the 61 - 122 extra registers cost no occupancy)
-    const int row = cand_idx ? cand_idx[pair] : pair;
-    const bool no_row = cand_idx && (row < 0 || row >= n_db);
-    CT raw[kHalf];
-    {
-        const CT* b = cand + (size_t)(no_row ? 0 : row) * kHalf * kD + d;
+    const int stride = gridDim.x;
+    int pair = blockIdx.x;                                    // < n_pairs (launcher)
+    int row = cand_idx ? cand_idx[pair] : pair;
+    int par = 0;
+    v2f s[60];
+    auto request_sino = [&](int p, int m0, int m1) {          // samples 2 m0 .. 2 m1 - 1 of this lane's column of pair p
+        const float* src = x + (size_t)p * kA * kD + d;
 #pragma unroll
-        for (int k = 0; k < kHalf; ++k) raw[k] = b[k * kD];
-    }
-    {
-        const float* src = x + (size_t)pair * kA * kD + d;
-        v2f s[60];
+        for (int m = m0; m < m1; ++m) s[m] = (v2f){src[(2 * m) * kD], src[(2 * m + 1) * kD]};
+        __builtin_amdgcn_sched_barrier(0);
+    };
+    request_sino(pair, 0, 60);
+    for (;;) {
+        const int next = pair + stride;
+        const bool more = next < n_pairs;
+        const int row_next = more && cand_idx ? cand_idx[next] : next;
+        const bool no_row = cand_idx && (row < 0 || row >= n_db);
+        CT raw[kHalf];
+        {
+            const CT* b = cand + (size_t)(no_row ? 0 : row) * kHalf * kD + d;
 #pragma unroll
-        for (int m = 0; m < 60; ++m) s[m] = (v2f){src[(2 * m) * kD], src[(2 * m + 1) * kD]};
-        const size_t o = (size_t)pair * kHalf * kD + d;
-        rfft120(s, [&](int k, v2f twice) {
-            const v2f v = twice * (v2f){0.5f * kOrtho120, 0.5f * kOrtho120};
-            qs[k * kLdsStride + t] = live_col ? v : (v2f){0.0f, 0.0f};
-            if (!live_col) return;
-            if (out) out[o + k * kD] = make_float2(v.x, v.y);
-            if (out16) out16[o + k * kD] = __floats2half2_rn(v.x, v.y);
-        });
-    }
-    __syncthreads();
-    if (no_row) {   // no such database row: the new spectrum is still written, the score says "no match"
-        if (t == 0) { dist[pair] = INFINITY; angle[pair] = 0; }
-        return;
-    }
-    v2f c[60];
-    corr_irfft120([&](int k) { return qs[k * kLdsStride + t]; },
-                  [&](int k) { const float2 g = load_spec(&raw[k]); return (v2f){g.x, g.y}; }, c);
-    float v0, v1;
-    wave_abs_reduce_scatter(c, v0, v1);
-    if (wave == 1) { xbuf[2 * lane] = v0; xbuf[2 * lane + 1] = v1; }
-    __syncthreads();
-    if (wave == 0) {
-        const float sc = kOrtho120;
-        const float s0 = (v0 + xbuf[2 * lane]) * sc, s1 = (v1 + xbuf[2 * lane + 1]) * sc;
-        const int n0 = 2 * lane, n1 = 2 * lane + 1;
-        const int m0 = n0 < 60 ? n0 + 60 : n0 - 60, m1 = n1 < 60 ? n1 + 60 : n1 - 60;
-        float best = -1.0f;
-        int bm = 1 << 30;
-        if (lane < 60) {
-            best = s0; bm = m0;
-            if (s1 > best || (s1 == best && m1 < bm)) { best = s1; bm = m1; }
+            for (int k = 0; k < kHalf; ++k) raw[k] = b[k * kD];
+            __builtin_amdgcn_sched_barrier(0);
         }
-        for (int off = 32; off > 0; off >>= 1) {
-            const float ob = __shfl_xor(best, off, 64);
-            const int om = __shfl_xor(bm, off, 64);
-            if (ob > best || (ob == best && om < bm)) { best = ob; bm = om; }
+        v2f prod[kHalf];                                      // new spectrum * conj(candidate); columns 120..127: zero
+        {
+            const size_t o = (size_t)pair * kHalf * kD + d;
+            rfft120(s, [&](int k, v2f twice) {
+                const v2f v = twice * (v2f){0.5f * kOrtho120, 0.5f * kOrtho120};
+                const float2 g = load_spec(&raw[k]);
+                prod[k] = cmul_conj(live_col ? v : (v2f){0.0f, 0.0f}, (v2f){g.x, g.y});
+                if (!live_col) return;
+                if (OUT & 1) out[o + k * kD] = make_float2(v.x, v.y);
+                if (OUT & 2) out16[o + k * kD] = __floats2half2_rn(v.x, v.y);
+            });
         }
-        if (lane == 0) {
-            dist[pair] = 1.0f - best / denom;
-            angle[pair] = kA / 2 - bm;
+        __builtin_amdgcn_sched_barrier(0);
+        const int ahead = more ? next : pair;
+        request_sino(ahead, 0, 30);
+        auto mid = [&] {
+            __builtin_amdgcn_sched_barrier(0);
+            request_sino(ahead, 30, 60);
+        };
+        if (!no_row) {
+            v2f c[60];
+            irfft120_products([&](int k) { return prod[k]; }, c, mid);
+            float v0, v1;
+            wave_abs_reduce_scatter(c, v0, v1);
+            if (wave == 1) { xbuf[par][2 * lane] = v0; xbuf[par][2 * lane + 1] = v1; }
+            __syncthreads();
+            if (wave == 0) {
+                const float sc = kOrtho120;
+                const float s0 = (v0 + xbuf[par][2 * lane]) * sc, s1 = (v1 + xbuf[par][2 * lane + 1]) * sc;
+                const int n0 = 2 * lane, n1 = 2 * lane + 1;
+                const int m0 = n0 < 60 ? n0 + 60 : n0 - 60, m1 = n1 < 60 ? n1 + 60 : n1 - 60;
+                float best = -1.0f;
+                int bm = 1 << 30;
+                if (lane < 60) {
+                    best = s0; bm = m0;
+                    if (s1 > best || (s1 == best && m1 < bm)) { best = s1; bm = m1; }
+                }
+                for (int off = 32; off > 0; off >>= 1) {
+                    const float ob = __shfl_xor(best, off, 64);
+                    const int om = __shfl_xor(bm, off, 64);
+                    if (ob > best || (ob == best && om < bm)) { best = ob; bm = om; }
+                }
+                if (lane == 0) {
+                    dist[pair] = 1.0f - best / denom;
+                    angle[pair] = kA / 2 - bm;
+                }
+            }
+            par ^= 1;
+        } else {   // no such database row: the new spectrum is still written, the score says "no match"
+            if (t == 0) { dist[pair] = INFINITY; angle[pair] = 0; }
+            mid();
         }
+        if (!more) break;
+        pair = next;
+        row = row_next;
     }
 }
 
@@ -881,12 +941,19 @@ static int spectrum_corr_pairs_launch(mrs_ctx* ctx, const float* d_norm_sino, co
         return MRS_ERR_UNSUPPORTED;
     }
     MRS_HIP_TRY(hipSetDevice(ctx->device));
-    const size_t lds = (size_t)kHalf * kLdsStride * sizeof(v2f);
-    MRS_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_ring_spec_corr_pairs<CT>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    (int)lds));
-    hipLaunchKernelGGL(k_ring_spec_corr_pairs<CT>, dim3(n_pairs), dim3(kSlotThreads), lds, (hipStream_t)stream, d_norm_sino, cand,
-                       d_cand_index, n_db, reinterpret_cast<float2*>(d_half_spec), reinterpret_cast<__half2*>(d_half_spec_f16),
-                       (float)(0.15 * kA * kD), d_dist, d_angle);
+    // two workgroups (one wave per SIMD) are resident per compute unit: each loops over its share of the pairs
+    const int grid = std::min<int>(n_pairs, 2 * (ctx->num_cu > 0 ? ctx->num_cu : 256));
+    auto launch = [&](auto which) {
+        hipLaunchKernelGGL((k_ring_spec_corr_pairs<CT, decltype(which)::value>), dim3(grid), dim3(kSlotThreads), 0, (hipStream_t)stream,
+                           d_norm_sino, cand, d_cand_index, n_db, n_pairs, reinterpret_cast<float2*>(d_half_spec),
+                           reinterpret_cast<__half2*>(d_half_spec_f16), (float)(0.15 * kA * kD), d_dist, d_angle);
+    };
+    switch ((d_half_spec ? 1 : 0) | (d_half_spec_f16 ? 2 : 0)) {
+        case 0: launch(std::integral_constant<int, 0>{}); break;
+        case 1: launch(std::integral_constant<int, 1>{}); break;
+        case 2: launch(std::integral_constant<int, 2>{}); break;
+        default: launch(std::integral_constant<int, 3>{}); break;
+    }
     MRS_HIP_TRY(hipGetLastError());
     return MRS_OK;
 }
