@@ -407,6 +407,56 @@ int mrs_gicp_batch_icp_step(mrs_gicp_batch* h, const mrs_icp_params* p, const do
 int mrs_gicp_batch_icp_profile(mrs_gicp_batch* h, const mrs_icp_params* p, const double* h_poses, int32_t reps, float* out_ms,
                                int64_t* out_counts, mrs_stream stream);
 
+/* Point-to-plane ICP (row G12): pcl::NormalEstimation with setKSearch as GlobalManager::addNormal drives it (global_manager.cpp:2679-2693)
+ * and pcl::IterativeClosestPointWithNormals (TransformationEstimationPointToPlaneLLS + DefaultConvergenceCriteria), the class that helper
+ * feeds; batched over the pairs of a mrs_gicp_batch: same handle, same clouds, same exact searches and k-NN selection.  PCL is not part of
+ * the reference tree: DESIGN.md section 4.16 is the definition, parity with PCL is unpinned.  Names and defaults are PCL's. */
+typedef struct mrs_icp_plane_params {
+    int32_t max_iterations;             /* the six fields of mrs_icp_params, same meaning and defaults               */
+    int32_t force_iterations;
+    double max_correspondence_distance;
+    double transformation_epsilon;
+    double rotation_epsilon;
+    double euclidean_fitness_epsilon;
+    int32_t normal_k;                   /* setKSearch of the target normals computed on demand (15: :2689); 3 .. 32   */
+    double viewpoint[3];               /* setViewPoint of those normals (0, 0, 0)                                    */
+} mrs_icp_plane_params;
+
+void mrs_icp_plane_default_params(mrs_icp_plane_params* p);
+
+/* Normals of every point of side `which` (0 sources, 1 targets) from its min(k, n) nearest neighbours, itself included: unit eigenvector of
+ * the smallest eigenvalue of the neighbours' covariance (fp64), turned towards h_viewpoint (double[3]; NULL = origin), and the curvature
+ * lambda0 / (lambda0 + lambda1 + lambda2); NaN where a cloud has fewer than 3 points.  Kept on the handle, one float4 per point, until the
+ * side's clouds are set again; a call with the k and viewpoint of the normals at hand does nothing.  Asynchronous on `stream`. */
+int mrs_gicp_batch_compute_normals(mrs_gicp_batch* h, int32_t which, int32_t k, const double* h_viewpoint, mrs_stream stream);
+/* (nx, ny, nz, curvature) of every point in INPUT order: float[total points][4].  Refuses when the side holds no normals. */
+int mrs_gicp_batch_get_normals(mrs_gicp_batch* h, int32_t which, float* h_normals4);
+/* Normals the caller already has (pcl::PointXYZINormal's normal_x / normal_y / normal_z), in the order of the points given to set_clouds:
+ * point i's normal at normals[i * stride_floats + 0 .. 2], stride_floats >= 3; with stride_floats >= 4 the fourth float is kept as the
+ * curvature, else 0.  They stay until the side's clouds are set again or mrs_gicp_batch_compute_normals replaces them. */
+int mrs_gicp_batch_set_normals(mrs_gicp_batch* h, int32_t which, const float* d_normals, int32_t stride_floats, mrs_stream stream);
+int mrs_gicp_batch_set_normals_host(mrs_gicp_batch* h, int32_t which, const float* h_normals, int32_t stride_floats);
+
+/* align(output, guess) of every pair; arguments and results as mrs_gicp_batch_align_icp, with one more state: 6 DEGENERATE (the 6 x 6
+ * system of an iteration is rank-deficient, e.g. all target normals parallel: converged = 0, the pose stays).  Target normals: those the
+ * handle holds (given or computed, whatever their k), else computed with p->normal_k and p->viewpoint.  Source normals are not used. */
+int mrs_gicp_batch_align_icp_plane(mrs_gicp_batch* h, const mrs_icp_plane_params* p, const double* h_guess, double* h_final,
+                                   int32_t* h_converged, int32_t* h_iterations, int32_t* h_state, mrs_stream stream);
+
+/* One iteration at given poses (kernel-level parity hook, the twin of mrs_gicp_batch_icp_step): h_sums double[n_pairs][29] = n, the upper
+ * triangle of sum a a^T (21, row-major), sum a r (6), sum |d - s|^2 with s = pose * source point, d its nearest target point, nrm that
+ * point's normal, a = [s x nrm, nrm], r = nrm . (d - s); h_delta double[n_pairs][16] the fitted increment (identity below 3 correspondences
+ * or when degenerate); h_state (optional) int32[n_pairs]: 5, 6, or what one iteration with max_iterations = 1 ends in; d_corr (optional)
+ * int32[total source points] correspondences or -1. */
+int mrs_gicp_batch_icp_plane_step(mrs_gicp_batch* h, const mrs_icp_plane_params* p, const double* h_poses, double* h_sums, double* h_delta,
+                                  int32_t* h_state, int32_t* d_corr, mrs_stream stream);
+
+/* Measurement hook of tools/bench_icp_plane.py (no reference counterpart), as mrs_gicp_batch_icp_profile.  out_ms float[4]: 0 the search
+ * of every source point, 1 the normals of the targets (selection + k_normals_from_knn, p->normal_k), 2 k_icp_plane_sums,
+ * 3 k_icp_plane_update.  out_counts int64[2]: source points, correspondences at the poses.  Leaves computed target normals behind. */
+int mrs_gicp_batch_icp_plane_profile(mrs_gicp_batch* h, const mrs_icp_plane_params* p, const double* h_poses, int32_t reps, float* out_ms,
+                                     int64_t* out_counts, mrs_stream stream);
+
 /* PCL-style GICP (row G11): pcl::GeneralizedIterativeClosestPoint<PointXYZI, PointXYZI> as the PCL_GICP branch of
  * GlobalManager::select_registration_method drives it (global_manager.cpp:2419-2426), batched over the pairs of a mrs_gicp_batch: same handle,
  * same clouds, same exact searches, and the handle's own k-NN covariances (k_correspondences of mrs_gicp_params; computed lazily, cached, shared

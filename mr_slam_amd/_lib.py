@@ -26,7 +26,7 @@ DROPPED = -2**31
 # the int functions whose return value is a value, not a status (plus the void / double / const char* ones)
 VALUE_RETURNING = ("mrs_abi_version", "mrs_ctx_device", "mrs_exchange_available", "mrs_gicp_batch_last_nn_passes",
                    "mrs_gicp_batch_last_searched_fraction", "mrs_status_str", "mrs_last_error", "mrs_gicp_default_params", "mrs_icp_default_params",
-                   "mrs_pclgicp_default_params")
+                   "mrs_pclgicp_default_params", "mrs_icp_plane_default_params")
 
 
 class MrsError(RuntimeError):

@@ -2,6 +2,7 @@
 // The kernels and the design notes are in gicp_device.hpp, included here and nowhere else (one translation unit).
 // Point-to-point ICP (row G9) runs on the same handle: its kernels are in icp_device.hpp, its entry points at the end of the align section.
 // So does PCL-style GICP (row G11): pclgicp_device.hpp, entry points after ICP's.
+// Point-to-plane ICP (row G12) shares ICP's tick loop: its kernels are in icp_plane_device.hpp, the normals' entry points follow the covariances'.
 #include <hipcub/hipcub.hpp>
 
 #include <cstdlib>
@@ -10,6 +11,7 @@
 #include "common.hpp"
 #include "gicp_device.hpp"
 #include "icp_device.hpp"
+#include "icp_plane_device.hpp"
 #include "pclgicp_device.hpp"
 
 // Small batches (<= kLmWindowPairs pairs: ONE registration at a time is how the nodes call it, main_RING.py:81-104, global_manager.cpp:2016-2021)
@@ -20,6 +22,7 @@
 constexpr int kLmWindowPairs = 8;
 constexpr int kLmWindow = 4;
 constexpr int kLmWindowMax = 16;
+constexpr int kNormalsGiven = -1;     // GicpCloud::nrm_key
 using mrs::DeviceBuffer;
 
 // The clouds of one side of a batch (0: sources, 1: targets), in Morton order, with everything built from them.  All device memory is owned
@@ -31,8 +34,11 @@ struct GicpCloud {
     int max_tiles = 0;                // 1024-point tiles of the largest cloud
     bool cov_valid = false;
     bool hier_valid = false;
+    int nrm_key = 0;                  // the normals in `nrm`: 0 none, kNormalsGiven the caller's (set_normals), else the k they were computed with
+    double nrm_vp[3] = {0, 0, 0};     // ... and their viewpoint
     DeviceBuffer<int64_t> d_offs;
     DeviceBuffer<float4> pts;         // total + total / 8 points (+ 16: a mini's 16 candidates are read whole, cand_request)
+    DeviceBuffer<float4> nrm;         // sorted space: (unit normal, curvature) of every point (row G12), allocated by the first call that fills it
     DeviceBuffer<double> cov;         // sorted space: the unit normal of every point (kCovDoubles = 3 doubles; cov6_from_normal); none under no_cov
     DeviceBuffer<int> tile_base;      // [n_pairs] first tile of each cloud
     DeviceBuffer<int> bbox;           // [n_pairs][6] bounding box of each cloud (ordered ints), the Morton grid
@@ -344,6 +350,42 @@ int knn_dev_switches(hipStream_t s)
     return MRS_OK;
 }
 
+// The k nearest neighbours of every point of side `which` (the selection kernel of the handle's search setting), handed to
+// tail(first cloud, clouds, lists) -- the launch of a consumer such as k_cov_from_knn -- through scratch memory.
+template <class Tail>
+int knn_then(mrs_gicp_batch* h, int32_t which, int k, hipStream_t s, Tail&& tail)
+{
+    const GicpCloud& S = h->side[which];
+    if (h->search_core == 1 && h->cold_core == 1) {     // setting 3: the round-4 k-NN kernel (slower than the round-3 one on the bench's scans)
+        MRS_REQUIRE(S.hier_valid, "search setting 3 was selected after set_clouds: set the clouds again");
+        mrs::Scratch knn;
+        int st = knn.alloc(knn_ints(S.offs[h->n_pairs], h->n_pairs, k) * sizeof(int), s);
+        if (st != MRS_OK) return st;
+        if ((st = launch_knn_select(h, which, k, knn.as<int>(), s)) != MRS_OK) return st;
+        tail(0, h->n_pairs, (const int*)knn.as<int>());
+        MRS_HIP_TRY(hipGetLastError());
+        return MRS_OK;
+    }
+    int st = knn_dev_switches(s);
+    if (st != MRS_OK) return st;
+    // the neighbour indices pass from the selection to its consumer through scratch memory: clouds are processed in chunks so that
+    // it stays below ~512 MB (256 clouds x 120 k points x k = 15 would be 1.8 GB held by the scratch cache for the life of the process)
+    const int64_t per_cloud = (int64_t)(knn_ints(S.longest, 1, k) * sizeof(int));
+    const int chunk = (int)std::max<int64_t>(1, std::min<int64_t>(h->n_pairs, (512ll << 20) / per_cloud));
+    mrs::Scratch knn;
+    if ((st = knn.alloc((size_t)chunk * per_cloud, s)) != MRS_OK) return st;
+    for (int c0 = 0; c0 < h->n_pairs; c0 += chunk) {
+        const int nc = std::min(chunk, h->n_pairs - c0);
+        // the kernels index knn by GLOBAL point number (knn_at: (offs[c] + 64 c) k with c counted from the chunk's first cloud): shift the
+        // chunk's buffer so that the chunk's first point lands on its start
+        int* const kn = knn.as<int>() - (size_t)S.offs[c0] * k;
+        launch_knn_cov(h, which, c0, nc, k, kn, s);
+        tail(c0, nc, (const int*)kn);
+    }
+    MRS_HIP_TRY(hipGetLastError());
+    return MRS_OK;
+}
+
 }  // namespace
 
 // Everything of set_clouds that does not look at the points: checks, (re)allocation of the side's buffers, offsets and tile bases, reset of
@@ -409,6 +451,7 @@ static int prepare_side(mrs_gicp_batch* h, int32_t which, const int64_t* h_offse
     S.max_tiles = longest_tiles;
     S.cov_valid = false;
     S.hier_valid = false;
+    S.nrm_key = 0;
     if (which == 1) h->vox.res_built = 0.0;   // new targets: their voxel map is built again (set_clouds_from delivers covariances, so compute_covariances does not run)
     if (which == 0) h->lm.n_seed = (size_t)total;
     if (h->lm.seed) MRS_HIP_TRY(hipMemsetAsync(h->lm.seed.get(), 0xff, h->lm.n_seed * sizeof(int), s));  // -1: no warm start across clouds
@@ -679,39 +722,12 @@ int mrs_gicp_batch_compute_covariances(mrs_gicp_batch* h, int32_t which, int32_t
     MRS_REQUIRE(S.ready, "set_clouds first");
     MRS_HIP_TRY(hipSetDevice(h->ctx->device));
     hipStream_t s = (hipStream_t)stream;
-    const int64_t longest = S.longest;
     const int k = h->prm.k;
-    if (h->search_core == 1 && h->cold_core == 1) {     // setting 3: the round-4 k-NN kernel (slower than the round-3 one on the bench's scans)
-        MRS_REQUIRE(S.hier_valid, "search setting 3 was selected after set_clouds: set the clouds again");
-        mrs::Scratch knn;
-        int st = knn.alloc(knn_ints(S.offs[h->n_pairs], h->n_pairs, k) * sizeof(int), s);
-        if (st != MRS_OK) return st;
-        if ((st = launch_knn_select(h, which, k, knn.as<int>(), s)) != MRS_OK) return st;
-        hipLaunchKernelGGL(k_cov_from_knn, dim3((unsigned)((longest + 255) / 256), h->n_pairs), dim3(256), 0, s, (const float4*)S.pts.get(),
-                           (const int64_t*)S.d_offs.get(), k, (const int*)knn.as<int>(), S.cov.get(), d_knn_out);
-        MRS_HIP_TRY(hipGetLastError());
-        S.cov_valid = true;
-        if (which == 1) h->vox.res_built = 0.0;
-        return MRS_OK;
-    }
-    int st = knn_dev_switches(s);
+    const int st = knn_then(h, which, k, s, [&](int c0, int nc, const int* kn) {
+        hipLaunchKernelGGL(k_cov_from_knn, dim3((unsigned)((S.longest + 255) / 256), nc), dim3(256), 0, s, (const float4*)S.pts.get(),
+                           (const int64_t*)S.d_offs.get() + c0, k, kn, S.cov.get(), d_knn_out);
+    });
     if (st != MRS_OK) return st;
-    // the neighbour indices pass from the selection to the covariance tail through scratch memory: clouds are processed in chunks so that
-    // it stays below ~512 MB (256 clouds x 120 k points x k = 15 would be 1.8 GB held by the scratch cache for the life of the process)
-    const int64_t per_cloud = (int64_t)(knn_ints(longest, 1, k) * sizeof(int));
-    const int chunk = (int)std::max<int64_t>(1, std::min<int64_t>(h->n_pairs, (512ll << 20) / per_cloud));
-    mrs::Scratch knn;
-    if ((st = knn.alloc((size_t)chunk * per_cloud, s)) != MRS_OK) return st;
-    for (int c0 = 0; c0 < h->n_pairs; c0 += chunk) {
-        const int nc = std::min(chunk, h->n_pairs - c0);
-        // the kernels index knn by GLOBAL point number (knn_at: (offs[c] + 64 c) k with c counted from the chunk's first cloud): shift the
-        // chunk's buffer so that the chunk's first point lands on its start
-        int* const kn = knn.as<int>() - (size_t)S.offs[c0] * k;
-        launch_knn_cov(h, which, c0, nc, k, kn, s);
-        hipLaunchKernelGGL(k_cov_from_knn, dim3((unsigned)((longest + 255) / 256), nc), dim3(256), 0, s, (const float4*)S.pts.get(),
-                           (const int64_t*)S.d_offs.get() + c0, k, (const int*)kn, S.cov.get(), d_knn_out);
-    }
-    MRS_HIP_TRY(hipGetLastError());
     S.cov_valid = true;
     if (which == 1) h->vox.res_built = 0.0;
     return MRS_OK;
@@ -740,6 +756,99 @@ int mrs_gicp_batch_get_covariances(mrs_gicp_batch* h, int32_t which, double* h_c
             memcpy(h_cov6 + (size_t)(o + orig) * 6, c6, 6 * sizeof(double));
         }
     }
+    return MRS_OK;
+}
+
+/* ---- surface normals (row G12, contract A of DESIGN.md 4.16; kernels: icp_plane_device.hpp) ---- */
+
+static int normals_room(mrs_gicp_batch* h, int32_t which)
+{
+    GicpCloud& S = h->side[which];
+    return S.nrm.reserve((size_t)S.offs[h->n_pairs], S.pts.capacity());     // grow-only, sized like the points
+}
+
+int mrs_gicp_batch_compute_normals(mrs_gicp_batch* h, int32_t which, int32_t k, const double* h_viewpoint, mrs_stream stream)
+{
+    MRS_REQUIRE(h, "null handle");
+    MRS_REQUIRE(which == 0 || which == 1, "which must be 0 or 1");
+    MRS_REQUIRE(k >= 3 && k <= 32, "normal_k must be in [3, 32]");
+    GicpCloud& S = h->side[which];
+    MRS_REQUIRE(S.ready, "set_clouds first");
+    const double zero[3] = {0.0, 0.0, 0.0};
+    const double* const v = h_viewpoint ? h_viewpoint : zero;
+    if (S.nrm_key == k && memcmp(S.nrm_vp, v, sizeof(zero)) == 0) return MRS_OK;
+    MRS_HIP_TRY(hipSetDevice(h->ctx->device));
+    hipStream_t s = (hipStream_t)stream;
+    int st = normals_room(h, which);
+    if (st != MRS_OK) return st;
+    S.nrm_key = 0;
+    st = knn_then(h, which, k, s, [&](int c0, int nc, const int* kn) {
+        hipLaunchKernelGGL(k_normals_from_knn, dim3((unsigned)((S.longest + 255) / 256), nc), dim3(256), 0, s, (const float4*)S.pts.get(),
+                           (const int64_t*)S.d_offs.get() + c0, k, kn, v[0], v[1], v[2], S.nrm.get());
+    });
+    if (st != MRS_OK) return st;
+    S.nrm_key = k;
+    memcpy(S.nrm_vp, v, sizeof(zero));
+    return MRS_OK;
+}
+
+int mrs_gicp_batch_get_normals(mrs_gicp_batch* h, int32_t which, float* h_normals4)
+{
+    MRS_REQUIRE(h && h_normals4, "null pointer");
+    MRS_REQUIRE(which == 0 || which == 1, "which must be 0 or 1");
+    const GicpCloud& S = h->side[which];
+    MRS_REQUIRE(S.ready && S.nrm_key != 0, "normals neither computed nor given");
+    MRS_HIP_TRY(hipSetDevice(h->ctx->device));
+    MRS_HIP_TRY(hipDeviceSynchronize());
+    const size_t total = (size_t)S.offs[h->n_pairs];
+    std::vector<float4> nrm(total), pts(total);
+    MRS_HIP_TRY(hipMemcpy(nrm.data(), S.nrm.get(), total * sizeof(float4), hipMemcpyDeviceToHost));
+    MRS_HIP_TRY(hipMemcpy(pts.data(), S.pts.get(), total * sizeof(float4), hipMemcpyDeviceToHost));
+    for (int c = 0; c < h->n_pairs; ++c) {  // the library stores clouds in Morton order; .w = original index
+        const int64_t o = S.offs[c];
+        for (int64_t i = o; i < S.offs[c + 1]; ++i) {
+            int orig;
+            memcpy(&orig, &pts[i].w, sizeof(int));
+            memcpy(h_normals4 + (size_t)(o + orig) * 4, &nrm[i], sizeof(float4));
+        }
+    }
+    return MRS_OK;
+}
+
+int mrs_gicp_batch_set_normals(mrs_gicp_batch* h, int32_t which, const float* d_normals, int32_t stride_floats, mrs_stream stream)
+{
+    MRS_REQUIRE(h && d_normals, "null pointer");
+    MRS_REQUIRE(which == 0 || which == 1, "which must be 0 or 1");
+    MRS_REQUIRE(stride_floats >= 3, "stride_floats must be >= 3");
+    GicpCloud& S = h->side[which];
+    MRS_REQUIRE(S.ready, "set_clouds first");
+    MRS_HIP_TRY(hipSetDevice(h->ctx->device));
+    hipStream_t s = (hipStream_t)stream;
+    const int st = normals_room(h, which);
+    if (st != MRS_OK) return st;
+    S.nrm_key = 0;
+    hipLaunchKernelGGL(k_normals_scatter, dim3((unsigned)((S.longest + 255) / 256), h->n_pairs), dim3(256), 0, s, (const float4*)S.pts.get(),
+                       (const int64_t*)S.d_offs.get(), d_normals, stride_floats, S.nrm.get());
+    MRS_HIP_TRY(hipGetLastError());
+    S.nrm_key = kNormalsGiven;
+    S.nrm_vp[0] = S.nrm_vp[1] = S.nrm_vp[2] = 0.0;
+    return MRS_OK;
+}
+
+int mrs_gicp_batch_set_normals_host(mrs_gicp_batch* h, int32_t which, const float* h_normals, int32_t stride_floats)
+{
+    MRS_REQUIRE(h && h_normals, "null pointer");
+    MRS_REQUIRE(which == 0 || which == 1, "which must be 0 or 1");
+    MRS_REQUIRE(stride_floats >= 3, "stride_floats must be >= 3");
+    MRS_REQUIRE(h->side[which].ready, "set_clouds first");
+    MRS_HIP_TRY(hipSetDevice(h->ctx->device));
+    const size_t bytes = (size_t)h->side[which].offs[h->n_pairs] * stride_floats * sizeof(float);
+    mrs::Scratch stage;
+    int st = stage.alloc(bytes, nullptr);
+    if (st != MRS_OK) return st;
+    MRS_HIP_TRY(hipMemcpy(stage.p, h_normals, bytes, hipMemcpyHostToDevice));
+    if ((st = mrs_gicp_batch_set_normals(h, which, stage.as<float>(), stride_floats, nullptr)) != MRS_OK) return st;
+    MRS_HIP_TRY(hipStreamSynchronize(nullptr));     // the staging buffer goes back to the cache only after the kernel has read it
     return MRS_OK;
 }
 
@@ -1042,30 +1151,68 @@ GicpParams icp_search_params(const mrs_gicp_batch* h, const mrs_icp_params* p)
     return sp;
 }
 
-void launch_icp_tick(mrs_gicp_batch* h, const IcpParams& dp, int* n_next, hipStream_t s)
+void launch_icp_plane_sums(mrs_gicp_batch* h, hipStream_t s)
 {
     const GicpCloud &S = h->side[0], &T = h->side[1];
     GicpLmBuffers& L = h->lm;
+    hipLaunchKernelGGL(k_icp_plane_sums, dim3(L.max_blocks, h->n_pairs), dim3(kNNThreads), 0, s, S.pts.get(), S.d_offs.get(), T.pts.get(),
+                       T.nrm.get(), T.d_offs.get(), L.state.get(), L.corr.get(), L.partial.get(), L.max_blocks);
+}
+
+// one iteration's sums and update; plane: point-to-plane (row G12) instead of point-to-point (row G9)
+void launch_icp_tick(mrs_gicp_batch* h, bool plane, const IcpParams& dp, int* n_next, hipStream_t s)
+{
+    const GicpCloud &S = h->side[0], &T = h->side[1];
+    GicpLmBuffers& L = h->lm;
+    if (plane) {
+        launch_icp_plane_sums(h, s);
+        hipLaunchKernelGGL(k_icp_plane_update, dim3(h->n_pairs), dim3(kLmThreads), 0, s, L.state.get(), L.partial.get(), L.nblocks.get(),
+                           L.max_blocks, dp, n_next);
+        return;
+    }
     hipLaunchKernelGGL(k_icp_sums, dim3(L.max_blocks, h->n_pairs), dim3(kNNThreads), 0, s, S.pts.get(), S.d_offs.get(), T.pts.get(), T.d_offs.get(),
                        L.state.get(), L.corr.get(), L.partial.get(), L.max_blocks);
     hipLaunchKernelGGL(k_icp_update, dim3(h->n_pairs), dim3(kLmThreads), 0, s, L.state.get(), L.partial.get(), L.nblocks.get(), L.max_blocks, dp,
                        n_next);
 }
 
-}  // namespace
+// state, block counts and a partial buffer for the terms of the estimator at hand (29 for point-to-plane: one more than GICP's 28)
+int icp_ensure_state(mrs_gicp_batch* h, bool plane)
+{
+    const int st = ensure_state(h);
+    if (st != MRS_OK || !plane) return st;
+    const size_t need = (size_t)h->n_pairs * h->lm.max_blocks * kIcpPlaneTerms;
+    return h->lm.partial.reserve(need, need);
+}
+
+// The target normals of a point-to-plane call: those the handle holds, else computed with the call's k and viewpoint.
+int icp_plane_normals(mrs_gicp_batch* h, const mrs_icp_plane_params* p, mrs_stream stream)
+{
+    MRS_REQUIRE(p->normal_k >= 3 && p->normal_k <= 32, "normal_k must be in [3, 32]");
+    if (h->side[1].nrm_key != 0) return MRS_OK;
+    return mrs_gicp_batch_compute_normals(h, 1, p->normal_k, p->viewpoint, stream);
+}
+
+mrs_icp_params icp_params_of(const mrs_icp_plane_params* p)
+{
+    mrs_icp_params q;
+    q.max_iterations = p->max_iterations;
+    q.force_iterations = p->force_iterations;
+    q.max_correspondence_distance = p->max_correspondence_distance;
+    q.transformation_epsilon = p->transformation_epsilon;
+    q.rotation_epsilon = p->rotation_epsilon;
+    q.euclidean_fitness_epsilon = p->euclidean_fitness_epsilon;
+    return q;
+}
 
 /* The tick loop of mrs_gicp_batch_align with one kind of tick: search, sums, update.  No covariances, no voxel map. */
-int mrs_gicp_batch_align_icp(mrs_gicp_batch* h, const mrs_icp_params* p, const double* h_guess, double* h_final, int32_t* h_converged,
-                             int32_t* h_iterations, int32_t* h_state, mrs_stream stream)
+int icp_align(mrs_gicp_batch* h, const mrs_icp_params* p, bool plane, const double* h_guess, double* h_final, int32_t* h_converged,
+              int32_t* h_iterations, int32_t* h_state, mrs_stream stream)
 {
-    MRS_REQUIRE(h && p && h_final, "null pointer");
-    MRS_REQUIRE(h->clouds_set(), "set source and target clouds first");
-    MRS_REQUIRE(!h->no_cov, "a covariance-free container holds no correspondence buffers");
-    int st = icp_check_params(p);
-    if (st != MRS_OK) return st;
+    int st;
     MRS_HIP_TRY(hipSetDevice(h->ctx->device));
     hipStream_t s = (hipStream_t)stream;
-    if ((st = ensure_state(h)) != MRS_OK) return st;
+    if ((st = icp_ensure_state(h, plane)) != MRS_OK) return st;
     const IcpParams dp = icp_device_params(h, p);
     const GicpParams sp = icp_search_params(h, p);
     GicpLmBuffers& L = h->lm;
@@ -1104,7 +1251,7 @@ int mrs_gicp_batch_align_icp(mrs_gicp_batch* h, const mrs_icp_params* p, const d
             for (int t = 0; t < window; ++t) {
                 h->big_movers = 1;                      // the broad search gates itself on the pair's motion (k_nn_scan: gate)
                 if ((st = nn_pass(h, sp, (ticks == 0 && t == 0) ? 0 : 1, s)) != MRS_OK) return st;
-                launch_icp_tick(h, dp, L.nactive.get() + 4 * t, s);
+                launch_icp_tick(h, plane, dp, L.nactive.get() + 4 * t, s);
             }
             MRS_HIP_TRY(hipGetLastError());
             MRS_HIP_TRY(hipMemcpyAsync(h_win, L.nactive.get(), (size_t)window * 4 * sizeof(int), hipMemcpyDeviceToHost, s));
@@ -1119,7 +1266,7 @@ int mrs_gicp_batch_align_icp(mrs_gicp_batch* h, const mrs_icp_params* p, const d
         MRS_HIP_TRY(hipMemsetAsync(L.nactive.get(), 0, 4 * sizeof(int), s));
         h->big_movers = next[2];
         if ((st = nn_pass(h, sp, nn_ticks == 0 ? 0 : 1, s)) != MRS_OK) return st;
-        launch_icp_tick(h, dp, L.nactive.get(), s);
+        launch_icp_tick(h, plane, dp, L.nactive.get(), s);
         ++nn_ticks;
         MRS_HIP_TRY(hipGetLastError());
         MRS_HIP_TRY(hipMemcpyAsync(next, L.nactive.get(), 3 * sizeof(int), hipMemcpyDeviceToHost, s));
@@ -1138,19 +1285,16 @@ int mrs_gicp_batch_align_icp(mrs_gicp_batch* h, const mrs_icp_params* p, const d
     return MRS_OK;
 }
 
-int mrs_gicp_batch_icp_step(mrs_gicp_batch* h, const mrs_icp_params* p, const double* h_poses, double* h_sums, double* h_delta,
-                            int32_t* d_corr, mrs_stream stream)
+int icp_step(mrs_gicp_batch* h, const mrs_icp_params* p, bool plane, const double* h_poses, double* h_sums, double* h_delta, int32_t* h_state,
+             int32_t* d_corr, mrs_stream stream)
 {
-    MRS_REQUIRE(h && p && h_poses && h_sums && h_delta, "null pointer");
-    MRS_REQUIRE(h->clouds_set(), "set source and target clouds first");
-    MRS_REQUIRE(!h->no_cov, "a covariance-free container holds no correspondence buffers");
-    int st = icp_check_params(p);
-    if (st != MRS_OK) return st;
+    int st;
     MRS_HIP_TRY(hipSetDevice(h->ctx->device));
     hipStream_t s = (hipStream_t)stream;
     const GicpCloud &S = h->side[0], &T = h->side[1];
     GicpLmBuffers& L = h->lm;
-    if ((st = ensure_state(h)) != MRS_OK) return st;
+    const int terms = plane ? kIcpPlaneTerms : kIcpTerms;
+    if ((st = icp_ensure_state(h, plane)) != MRS_OK) return st;
     IcpParams dp = icp_device_params(h, p);
     dp.crit.max_iter = 1;           // one iteration, then the pair stops whatever the criteria say
     dp.crit.force_iters = 0;
@@ -1164,7 +1308,7 @@ int mrs_gicp_batch_icp_step(mrs_gicp_batch* h, const mrs_icp_params* p, const do
     MRS_HIP_TRY(hipMemcpyAsync(L.state.get(), init.data(), init.size() * sizeof(LmState), hipMemcpyHostToDevice, s));
     MRS_HIP_TRY(hipMemsetAsync(L.nactive.get(), 0, 4 * sizeof(int), s));
     if ((st = nn_pass(h, sp, 2, s)) != MRS_OK) return st;
-    launch_icp_tick(h, dp, L.nactive.get(), s);
+    launch_icp_tick(h, plane, dp, L.nactive.get(), s);
     if (d_corr)
         hipLaunchKernelGGL(k_corr_to_original, dim3(64, h->n_pairs), dim3(256), 0, s, S.pts.get(), S.d_offs.get(), T.pts.get(), T.d_offs.get(),
                            L.corr.get(), d_corr);
@@ -1172,10 +1316,78 @@ int mrs_gicp_batch_icp_step(mrs_gicp_batch* h, const mrs_icp_params* p, const do
     MRS_HIP_TRY(hipMemcpyAsync(init.data(), L.state.get(), init.size() * sizeof(LmState), hipMemcpyDeviceToHost, s));
     MRS_HIP_TRY(hipStreamSynchronize(s));
     for (int q = 0; q < h->n_pairs; ++q) {
-        memcpy(h_sums + (size_t)q * kIcpTerms, init[q].H, kIcpTerms * sizeof(double));
+        memcpy(h_sums + (size_t)q * terms, init[q].H, terms * sizeof(double));
         memcpy(h_delta + (size_t)q * 16, init[q].delta, 16 * sizeof(double));
+        if (h_state) h_state[q] = init[q].inner;
     }
     return MRS_OK;
+}
+
+}  // namespace
+
+int mrs_gicp_batch_align_icp(mrs_gicp_batch* h, const mrs_icp_params* p, const double* h_guess, double* h_final, int32_t* h_converged,
+                             int32_t* h_iterations, int32_t* h_state, mrs_stream stream)
+{
+    MRS_REQUIRE(h && p && h_final, "null pointer");
+    MRS_REQUIRE(h->clouds_set(), "set source and target clouds first");
+    MRS_REQUIRE(!h->no_cov, "a covariance-free container holds no correspondence buffers");
+    const int st = icp_check_params(p);
+    if (st != MRS_OK) return st;
+    return icp_align(h, p, false, h_guess, h_final, h_converged, h_iterations, h_state, stream);
+}
+
+int mrs_gicp_batch_icp_step(mrs_gicp_batch* h, const mrs_icp_params* p, const double* h_poses, double* h_sums, double* h_delta,
+                            int32_t* d_corr, mrs_stream stream)
+{
+    MRS_REQUIRE(h && p && h_poses && h_sums && h_delta, "null pointer");
+    MRS_REQUIRE(h->clouds_set(), "set source and target clouds first");
+    MRS_REQUIRE(!h->no_cov, "a covariance-free container holds no correspondence buffers");
+    const int st = icp_check_params(p);
+    if (st != MRS_OK) return st;
+    return icp_step(h, p, false, h_poses, h_sums, h_delta, nullptr, d_corr, stream);
+}
+
+/* ---- point-to-plane ICP (row G12; kernels: icp_plane_device.hpp): ICP's tick loop with the plane estimator behind the target normals ---- */
+
+void mrs_icp_plane_default_params(mrs_icp_plane_params* p)
+{
+    if (!p) return;
+    mrs_icp_params q;
+    mrs_icp_default_params(&q);
+    p->max_iterations = q.max_iterations;
+    p->force_iterations = q.force_iterations;
+    p->max_correspondence_distance = q.max_correspondence_distance;
+    p->transformation_epsilon = q.transformation_epsilon;
+    p->rotation_epsilon = q.rotation_epsilon;
+    p->euclidean_fitness_epsilon = q.euclidean_fitness_epsilon;
+    p->normal_k = 15;                                   // setKSearch(15): global_manager.cpp:2689
+    p->viewpoint[0] = p->viewpoint[1] = p->viewpoint[2] = 0.0;
+}
+
+int mrs_gicp_batch_align_icp_plane(mrs_gicp_batch* h, const mrs_icp_plane_params* p, const double* h_guess, double* h_final,
+                                   int32_t* h_converged, int32_t* h_iterations, int32_t* h_state, mrs_stream stream)
+{
+    MRS_REQUIRE(h && p && h_final, "null pointer");
+    MRS_REQUIRE(h->clouds_set(), "set source and target clouds first");
+    MRS_REQUIRE(!h->no_cov, "a covariance-free container holds no correspondence buffers");
+    const mrs_icp_params q = icp_params_of(p);
+    int st = icp_check_params(&q);
+    if (st != MRS_OK) return st;
+    if ((st = icp_plane_normals(h, p, stream)) != MRS_OK) return st;
+    return icp_align(h, &q, true, h_guess, h_final, h_converged, h_iterations, h_state, stream);
+}
+
+int mrs_gicp_batch_icp_plane_step(mrs_gicp_batch* h, const mrs_icp_plane_params* p, const double* h_poses, double* h_sums, double* h_delta,
+                                  int32_t* h_state, int32_t* d_corr, mrs_stream stream)
+{
+    MRS_REQUIRE(h && p && h_poses && h_sums && h_delta, "null pointer");
+    MRS_REQUIRE(h->clouds_set(), "set source and target clouds first");
+    MRS_REQUIRE(!h->no_cov, "a covariance-free container holds no correspondence buffers");
+    const mrs_icp_params q = icp_params_of(p);
+    int st = icp_check_params(&q);
+    if (st != MRS_OK) return st;
+    if ((st = icp_plane_normals(h, p, stream)) != MRS_OK) return st;
+    return icp_step(h, &q, true, h_poses, h_sums, h_delta, h_state, d_corr, stream);
 }
 
 /* ---- PCL-style GICP (row G11; kernels: pclgicp_device.hpp) ---- */
@@ -1509,11 +1721,11 @@ int mrs_gicp_batch_linearize(mrs_gicp_batch* h, const double* h_poses, double* h
 /* Measurement hook of tools/bench_icp.py: the three stages of one ICP iteration launched ALONE between HIP events on `stream`, at the given
  * poses, `reps` times each (the average goes to out_ms): [0] the search of every source point (the handle's search setting, warm),
  * [1] k_icp_sums, [2] k_icp_update.  out_counts: [0] source points, [1] correspondences at the poses.  Overwrites the batch's correspondences
- * and warm-start seeds. */
-int mrs_gicp_batch_icp_profile(mrs_gicp_batch* h, const mrs_icp_params* p, const double* h_poses, int32_t reps, float* out_ms, int64_t* out_counts,
-                               mrs_stream stream)
+ * and warm-start seeds.  plane (optional): the parameters of a point-to-plane call (tools/bench_icp_plane.py) -- its sums and update kernels
+ * instead, and the targets' normals (selection + k_normals_from_knn) timed into ms_normals. */
+static int icp_profile(mrs_gicp_batch* h, const mrs_icp_params* p, const mrs_icp_plane_params* plane, const double* h_poses, int32_t reps,
+                       float* ms_search, float* ms_normals, float* ms_sums, float* ms_update, int64_t* out_counts, mrs_stream stream)
 {
-    MRS_REQUIRE(h && p && h_poses && out_ms && out_counts, "null pointer");
     MRS_REQUIRE(h->clouds_set(), "set source and target clouds first");
     MRS_REQUIRE(!h->no_cov, "a covariance-free container holds no correspondence buffers");
     MRS_REQUIRE(reps >= 1, "reps must be >= 1");
@@ -1522,7 +1734,7 @@ int mrs_gicp_batch_icp_profile(mrs_gicp_batch* h, const mrs_icp_params* p, const
     MRS_HIP_TRY(hipSetDevice(h->ctx->device));
     hipStream_t s = (hipStream_t)stream;
     GicpLmBuffers& L = h->lm;
-    if ((st = ensure_state(h)) != MRS_OK) return st;
+    if ((st = icp_ensure_state(h, plane != nullptr)) != MRS_OK) return st;
     IcpParams dp = icp_device_params(h, p);
     dp.crit.max_iter = INT32_MAX;       // the update kernel is timed on pairs that stay active: no rule may end them
     dp.crit.force_iters = INT32_MAX;
@@ -1553,9 +1765,19 @@ int mrs_gicp_batch_icp_profile(mrs_gicp_batch* h, const mrs_icp_params* p, const
     };
     const GicpCloud &S = h->side[0], &T = h->side[1];
     int nn_st = MRS_OK;
-    if ((st = timed(out_ms[0], [&]() { const int r = nn_pass(h, sp, 2, s); if (r != MRS_OK) nn_st = r; })) != MRS_OK) return st;
+    if ((st = timed(*ms_search, [&]() { const int r = nn_pass(h, sp, 2, s); if (r != MRS_OK) nn_st = r; })) != MRS_OK) return st;
     if (nn_st != MRS_OK) return nn_st;
-    if ((st = timed(out_ms[1], [&]() {
+    if (plane) {
+        MRS_REQUIRE(plane->normal_k >= 3 && plane->normal_k <= 32, "normal_k must be in [3, 32]");
+        if ((st = timed(*ms_normals, [&]() {
+                 h->side[1].nrm_key = 0;            // computed again, whatever the handle holds
+                 const int r = mrs_gicp_batch_compute_normals(h, 1, plane->normal_k, plane->viewpoint, stream);
+                 if (r != MRS_OK) nn_st = r;
+             })) != MRS_OK) return st;
+        if (nn_st != MRS_OK) return nn_st;
+    }
+    if ((st = timed(*ms_sums, [&]() {
+             if (plane) return launch_icp_plane_sums(h, s);
              hipLaunchKernelGGL(k_icp_sums, dim3(L.max_blocks, h->n_pairs), dim3(kNNThreads), 0, s, S.pts.get(), S.d_offs.get(), T.pts.get(),
                                 T.d_offs.get(), L.state.get(), L.corr.get(), L.partial.get(), L.max_blocks);
          })) != MRS_OK) return st;
@@ -1567,11 +1789,30 @@ int mrs_gicp_batch_icp_profile(mrs_gicp_batch* h, const mrs_icp_params* p, const
         out_counts[0] = (int64_t)L.n_seed; out_counts[1] = c;
     }
     MRS_HIP_TRY(hipMemsetAsync(L.nactive.get(), 0, 4 * sizeof(int), s));
-    if ((st = timed(out_ms[2], [&]() {
-             hipLaunchKernelGGL(k_icp_update, dim3(h->n_pairs), dim3(kLmThreads), 0, s, L.state.get(), L.partial.get(), L.nblocks.get(), L.max_blocks,
-                                dp, L.nactive.get());
+    if ((st = timed(*ms_update, [&]() {
+             if (plane)
+                 hipLaunchKernelGGL(k_icp_plane_update, dim3(h->n_pairs), dim3(kLmThreads), 0, s, L.state.get(), L.partial.get(), L.nblocks.get(),
+                                    L.max_blocks, dp, L.nactive.get());
+             else
+                 hipLaunchKernelGGL(k_icp_update, dim3(h->n_pairs), dim3(kLmThreads), 0, s, L.state.get(), L.partial.get(), L.nblocks.get(),
+                                    L.max_blocks, dp, L.nactive.get());
          })) != MRS_OK) return st;
     return MRS_OK;
+}
+
+int mrs_gicp_batch_icp_profile(mrs_gicp_batch* h, const mrs_icp_params* p, const double* h_poses, int32_t reps, float* out_ms, int64_t* out_counts,
+                               mrs_stream stream)
+{
+    MRS_REQUIRE(h && p && h_poses && out_ms && out_counts, "null pointer");
+    return icp_profile(h, p, nullptr, h_poses, reps, out_ms, nullptr, out_ms + 1, out_ms + 2, out_counts, stream);
+}
+
+int mrs_gicp_batch_icp_plane_profile(mrs_gicp_batch* h, const mrs_icp_plane_params* p, const double* h_poses, int32_t reps, float* out_ms,
+                                     int64_t* out_counts, mrs_stream stream)
+{
+    MRS_REQUIRE(h && p && h_poses && out_ms && out_counts, "null pointer");
+    const mrs_icp_params q = icp_params_of(p);
+    return icp_profile(h, &q, p, h_poses, reps, out_ms, out_ms + 1, out_ms + 2, out_ms + 3, out_counts, stream);
 }
 
 /* Measurement hook (bench.py's GICP rooflines): every kernel of one outer iteration launched ALONE between HIP events on `stream`, at

@@ -42,6 +42,24 @@ def default_icp_params(**kw):
     return p
 
 
+class IcpPlaneParams(C.Structure):
+    _fields_ = IcpParams._fields_ + [("normal_k", C.c_int32), ("viewpoint", C.c_double * 3)]
+
+
+ICP_PLANE_STATES = ICP_STATES + ("DEGENERATE",)     # 6: an iteration's 6 x 6 system was rank-deficient
+
+
+def default_icp_plane_params(**kw):
+    """pcl::IterativeClosestPointWithNormals' defaults (normal_k = 15, viewpoint at the origin), with the given fields replaced"""
+    p = IcpPlaneParams()
+    _lib.load().mrs_icp_plane_default_params(C.byref(p))
+    for k, v in kw.items():
+        if not hasattr(p, k):
+            raise AttributeError(k)
+        setattr(p, k, (C.c_double * 3)(*v) if k == "viewpoint" else v)
+    return p
+
+
 class PclGicpParams(C.Structure):
     _fields_ = [("max_iterations", C.c_int32), ("max_inner_iterations", C.c_int32), ("force_iterations", C.c_int32),
                 ("max_correspondence_distance", C.c_double), ("rotation_epsilon", C.c_double),
@@ -244,6 +262,71 @@ class GicpBatch:
         _lib.load().mrs_gicp_batch_icp_profile(self._h, C.byref(default_icp_params(**params)), poses, int(reps), ms, cnt,
                                                _lib.current_stream(self.device))
         return ({n: float(v) for n, v in zip(("search", "icp_sums", "icp_update"), ms)},
+                {"source_points": int(cnt[0]), "correspondences": int(cnt[1])})
+
+    def compute_normals(self, which, k=15, viewpoint=(0.0, 0.0, 0.0)):
+        """Surface normals of side `which` (row G12: pcl::NormalEstimation with setKSearch(k), setViewPoint), kept on the handle."""
+        v = np.ascontiguousarray(viewpoint, dtype=np.float64).reshape(3)
+        _lib.load().mrs_gicp_batch_compute_normals(self._h, int(which), int(k), v, _lib.current_stream(self.device))
+
+    def normals(self, which):
+        """[N,4] float32 (nx, ny, nz, curvature) of the side's points, in the order they were given (host)."""
+        out = np.empty((int(self._n[which][-1]), 4), np.float32)
+        _lib.load().mrs_gicp_batch_get_normals(self._h, int(which), out)
+        return out
+
+    def set_normals(self, which, normals):
+        """Normals the caller already has: [N, 3 or more] float32 (host array or device tensor), rows in the order of the side's points;
+        a fourth column is kept as the curvature."""
+        lib = _lib.load()
+        if isinstance(normals, torch.Tensor) and normals.is_cuda:
+            nrm = normals.to(torch.float32).contiguous()
+            assert nrm.dim() == 2 and nrm.shape[0] == int(self._n[which][-1])
+            lib.mrs_gicp_batch_set_normals(self._h, int(which), nrm, nrm.shape[1], _lib.current_stream(self.device))
+        else:
+            nrm = np.ascontiguousarray(normals, dtype=np.float32)
+            assert nrm.ndim == 2 and nrm.shape[0] == int(self._n[which][-1])
+            lib.mrs_gicp_batch_set_normals_host(self._h, int(which), nrm, nrm.shape[1])
+
+    def align_icp_plane(self, guesses=None, **params):
+        """Point-to-plane ICP (row G12, pcl::IterativeClosestPointWithNormals) on the batch's clouds and the targets' normals (those the
+        handle holds, else computed with normal_k and viewpoint); params: the fields of IcpPlaneParams (PCL's defaults otherwise).
+        Returns (T [P,4,4] float64, converged [P] bool, iterations [P] int32, state [P] int32: index into ICP_PLANE_STATES)."""
+        P = self.n_pairs
+        g = None
+        if guesses is not None:
+            g = np.ascontiguousarray(np.asarray(guesses, dtype=np.float64).reshape(P, 16))
+        T = np.empty((P, 16), np.float64)
+        conv = np.empty(P, np.int32)
+        its = np.empty(P, np.int32)
+        state = np.empty(P, np.int32)
+        lib = _lib.load()
+        lib.mrs_gicp_batch_align_icp_plane(self._h, C.byref(default_icp_plane_params(**params)), g, T, conv, its, state,
+                                           _lib.current_stream(self.device))
+        self.nn_passes = lib.mrs_gicp_batch_last_nn_passes(self._h)
+        self.searched_fraction = lib.mrs_gicp_batch_last_searched_fraction(self._h)
+        return T.reshape(P, 4, 4), conv.astype(bool), its, state
+
+    def icp_plane_step(self, poses, want_corr=False, **params):
+        """One point-to-plane iteration's correspondences, 29 sums and fitted increment at `poses` (mrs_gicp_batch_icp_plane_step).
+        Returns (sums [P,29], delta [P,4,4], state [P] int32, corr or None)."""
+        P = self.n_pairs
+        poses = np.ascontiguousarray(np.asarray(poses, dtype=np.float64).reshape(P, 16))
+        sums = np.empty((P, 29), np.float64); delta = np.empty((P, 16), np.float64); state = np.empty(P, np.int32)
+        corr = torch.empty(int(self._n[0][-1]), dtype=torch.int32, device=f"cuda:{self.device}") if want_corr else None
+        _lib.load().mrs_gicp_batch_icp_plane_step(self._h, C.byref(default_icp_plane_params(**params)), poses, sums, delta, state, corr,
+                                                  _lib.current_stream(self.device))
+        return sums, delta.reshape(P, 4, 4), state, (corr.cpu().numpy() if want_corr else None)
+
+    def icp_plane_profile(self, poses, reps=3, **params):
+        """HIP-event duration of the stages of one point-to-plane iteration and of the targets' normals, each launched alone at `poses`
+        (mrs_gicp_batch_icp_plane_profile).  Returns (dict of ms, dict of counts)."""
+        P = self.n_pairs
+        poses = np.ascontiguousarray(np.asarray(poses, dtype=np.float64).reshape(P, 16))
+        ms = np.zeros(4, np.float32); cnt = np.zeros(2, np.int64)
+        _lib.load().mrs_gicp_batch_icp_plane_profile(self._h, C.byref(default_icp_plane_params(**params)), poses, int(reps), ms, cnt,
+                                                     _lib.current_stream(self.device))
+        return ({n: float(v) for n, v in zip(("search", "normals", "icp_plane_sums", "icp_plane_update"), ms)},
                 {"source_points": int(cnt[0]), "correspondences": int(cnt[1])})
 
     def align_pcl(self, guesses=None, **params):
