@@ -846,7 +846,7 @@ int mrs_exchange_fetch_plan_destroy(mrs_fetch_plan* plan);
  * reference's callbacks run on concurrent rospy threads); all device work of a handle runs on the handle's own stream, `stream` is the
  * stream that produced a DEVICE argument (the handle waits for it; for appends it is made to wait until the argument has been consumed). */
 typedef struct mrs_loopdb mrs_loopdb;
-enum mrs_loopdb_kind { MRS_LOOPDB_RING = 0, MRS_LOOPDB_RINGPP = 1, MRS_LOOPDB_DISCO = 2, MRS_LOOPDB_SC = 3, MRS_LOOPDB_M2DP = 4 };
+enum mrs_loopdb_kind { MRS_LOOPDB_RING = 0, MRS_LOOPDB_RINGPP = 1, MRS_LOOPDB_DISCO = 2, MRS_LOOPDB_SC = 3, MRS_LOOPDB_M2DP = 4, MRS_LOOPDB_FH = 5 };
 /* where / what a RING or RING++ descriptor argument is:
  *   HOST / DEVICE : the reference's own object -- RING: pc_TIRING, complex64 [1][120][120] (util.py:198; its first 61 rows are what is
  *                   kept); RING++: pc_TIRING, float32 [C][120][120] magnitudes (util.py:247-250; normalised jointly + transformed along the
@@ -854,7 +854,8 @@ enum mrs_loopdb_kind { MRS_LOOPDB_RING = 0, MRS_LOOPDB_RINGPP = 1, MRS_LOOPDB_DI
  *   DEVICE_SPEC   : half spectra in the product's row layout, complex64 [C][61][120] (mrs_ring_half_spectrum / mrs_ring_spectrum_corr_pairs) */
 enum mrs_loopdb_form { MRS_LOOPDB_FORM_HOST = 0, MRS_LOOPDB_FORM_DEVICE = 1, MRS_LOOPDB_FORM_DEVICE_SPEC = 2 };
 
-/* channels: 1 for RING, C (6 in the reference) for RING++, ignored for DiSCO, SC and M2DP; capacity_hint: entries to allocate up front (>= 1) */
+/* channels: 1 for RING, C (6 in the reference) for RING++, ignored for DiSCO, SC and M2DP; for FH it carries the number of buckets
+ * (1 .. MRS_FH_MAX_BINS); capacity_hint: entries to allocate up front (>= 1) */
 int mrs_loopdb_create(mrs_ctx* ctx, int32_t kind, int32_t channels, int32_t capacity_hint, mrs_loopdb** out);
 int mrs_loopdb_destroy(mrs_loopdb* db);
 int mrs_loopdb_size(mrs_loopdb* db, int32_t* out_n);
@@ -908,6 +909,20 @@ int mrs_loopdb_append_m2dp(mrs_loopdb* db, const double* desc, int32_t on_device
  * database returns *h_count = 0 and index -1 without device work. */
 int mrs_loopdb_query_m2dp(mrs_loopdb* db, const double* desc, int32_t on_device, int32_t k, int32_t* h_index, float* h_dist2, int32_t* h_count,
                           mrs_stream stream);
+/* Fast Histogram (MRS_LOOPDB_FH): the list of range histograms a node would keep per robot and compare with getEMD / calculateW
+ * (RING_ros/pr_methods/FastHistogram.py:66-84; the reference ships the descriptor without a node of its own).  hist = double [bins] as
+ * mrs_fh_batch writes it, host (on_device = 0) or device; entries are stored as they come, in fp64, one row of `bins` doubles each. */
+int mrs_loopdb_append_fh(mrs_loopdb* db, const double* hist, int32_t on_device, mrs_stream stream);
+/* getEMD(hist, entry) = calculateW (FastHistogram.py:66-84) against every entry in one launch: the sum over i, in index order, of
+ * |hist_i - entry_i| in fp64, divided by bins -- the reference's bits, not an approximation (one lane per entry walks the buckets in
+ * order).  The k nearest, 1 <= k <= 32, ascending, ties to the lower index: h_index / h_dist [k], *h_count = min(k, n); the slots past it
+ * hold -1 / +inf.  Blocking; an empty database returns *h_count = 0 and index -1 without device work. */
+int mrs_loopdb_query_fh(mrs_loopdb* db, const double* hist, int32_t on_device, int32_t k, int32_t* h_index, double* h_dist, int32_t* h_count,
+                        mrs_stream stream);
+/* The same distances to all n entries, left on the device: d_dist double [n], n = mrs_loopdb_size at the time of the call (the caller
+ * keeps other threads from appending between sizing the array and this call).  The work runs on the handle's stream; `stream` is made to
+ * wait for it, so the caller's later work on `stream` sees the distances.  Not blocking. */
+int mrs_loopdb_distances_fh(mrs_loopdb* db, const double* hist, int32_t on_device, double* d_dist, mrs_stream stream);
 /* the entries as they lie on the device (tests, exchange): valid until the next append that grows the capacity.  SC: d_entries = packed
  * entries (entry_floats apart: sector keys [128], column norms [128], then the [120][120] descriptor), d_signatures = ring keys [n][120] */
 int mrs_loopdb_device_entries(mrs_loopdb* db, const float** d_entries, const float** d_signatures, int32_t* out_n, int64_t* entry_floats);
@@ -963,6 +978,32 @@ int mrs_m2dp_pca_batch(mrs_ctx* ctx, const void* d_points, int32_t is_double, in
 /* One cloud, host arrays in and out (the reference's calling convention): h_points [n][stride], n >= 0; h_desc double [192],
  * h_A double [64][128] (optional).  Blocking. */
 int mrs_m2dp_host(mrs_ctx* ctx, const void* h_points, int32_t is_double, int32_t stride, int32_t n, double* h_desc, double* h_A);
+
+/* ------------------------------------------------------------------------------------
+ * Fast Histogram on device arrays (RING_ros/pr_methods/FastHistogram.py:10-63)
+ * ---------------------------------------------------------------------------------- */
+
+/* points per workgroup of the range and bin kernels (tests probe both sides of it) */
+#define MRS_FH_TILE_POINTS 2048
+/* largest number of buckets */
+#define MRS_FH_MAX_BINS 256
+
+/* statisticsOnRange(cloud, bins) for a batch of clouds in one set of launches, replacing calculateRange's Python loop over the points
+ * (FastHistogram.py:10-21) and statisticsOnRange's per-point distanceJudge call with its loop over all buckets (FastHistogram.py:24-63).
+ * d_points [total][stride] float (is_double = 0; widened to double first) or double (1), xyz first; d_offsets / h_offsets int64
+ * [batch + 1], device and host copies of the same offsets (the convention of mrs_m2dp_batch).  bins in 1 .. MRS_FH_MAX_BINS (the reference's
+ * default is 100).  d_hist double [batch][bins] = counts / n; optional: d_counts int32 [batch][bins], d_range double [batch] = the largest
+ * finite range M of each cloud (0 for an empty one), d_unbound int32 [batch] = the points with 0 < d < M above the last edge fl(bins w),
+ * where the reference raises UnboundLocalError (they are counted in bucket bins - 1).  A point at range d = sqrt((x x + y y) + z z) falls
+ * into the largest i < bins with fl(i w) <= d, w = fl(M / bins), when 0 < d < M, and into bucket bins - 1 otherwise (d == 0, d == M, d not
+ * finite; such points do not take part in M).  An empty cloud gives zeros.  All arithmetic is correctly rounded fp64 and the counts are
+ * integers: the result does not depend on the batch a cloud is in.  Enqueued on `stream`. */
+int mrs_fh_batch(mrs_ctx* ctx, const void* d_points, int32_t is_double, int32_t stride, const int64_t* d_offsets, const int64_t* h_offsets,
+                 int32_t batch, int32_t bins, double* d_hist, int32_t* d_counts, double* d_range, int32_t* d_unbound, mrs_stream stream);
+/* One cloud, host arrays in and out (the reference's calling convention, FastHistogram.py:40): h_points [n][stride], n >= 0; h_hist double
+ * [bins]; optional: h_counts int32 [bins], h_range double [1], h_unbound int32 [1].  Blocking. */
+int mrs_fh_host(mrs_ctx* ctx, const void* h_points, int32_t is_double, int32_t stride, int32_t n, int32_t bins, double* h_hist, int32_t* h_counts,
+                double* h_range, int32_t* h_unbound);
 
 /* ------------------------------------------------------------------------------------
  * Mapping-side DiSCO matcher

@@ -4,8 +4,8 @@
 that `import voxelocc`, `import gputransform`, `import voxelfeat`, `import torch_radon`,
 `import pygicp` in the unmodified LoopDetection nodes resolve to the HIP implementation.  `install(node=True)` adds a `util` module with the
 names the nodes import from RING_ros/util.py.  `install(scancontext=True)` adds `pr_methods.ScanContext` (the Scan Context functions main_SC.py
-imports, mr_slam_amd/compat/ScanContext.py) and `install(m2dp=True)` adds `pr_methods.M2DP` (mr_slam_amd/compat/M2DP.py); nothing registers
-`pr_methods` otherwise.
+imports, mr_slam_amd/compat/ScanContext.py), `install(m2dp=True)` adds `pr_methods.M2DP` (mr_slam_amd/compat/M2DP.py) and
+`install(fasthistogram=True)` adds `pr_methods.FastHistogram` (mr_slam_amd/compat/FastHistogram.py); nothing registers `pr_methods` otherwise.
 """
 import importlib
 import sys
@@ -14,7 +14,7 @@ import types
 _NAMES = ("gputransform", "voxelocc", "voxelfeat", "torch_radon", "pygicp")
 
 
-def install(names=_NAMES, node=False, scancontext=False, m2dp=False):
+def install(names=_NAMES, node=False, scancontext=False, m2dp=False, fasthistogram=False):
     """node=True also registers `util` (the names the nodes pull in with `from util import *`: mr_slam_amd/compat/util.py); the candidate loop
     itself is replaced by `mr_slam_amd.node.bind_detect_loop_icp` (INTEGRATION.md 1a')."""
     for n in tuple(names) + (("util",) if node else ()):
@@ -22,7 +22,7 @@ def install(names=_NAMES, node=False, scancontext=False, m2dp=False):
             sys.modules[n] = importlib.import_module("mr_slam_amd.compat." + n)
         except ModuleNotFoundError:
             pass
-    for wanted, name in ((scancontext, "ScanContext"), (m2dp, "M2DP")):
+    for wanted, name in ((scancontext, "ScanContext"), (m2dp, "M2DP"), (fasthistogram, "FastHistogram")):
         if not wanted:
             continue
         mod = importlib.import_module("mr_slam_amd.compat." + name)

@@ -13,6 +13,8 @@
 // Scan Context (MRS_LOOPDB_SC) replaces the ring-key KDTree + dist_align_sc of main_SC.py:153-172: entries are packed descriptors with their
 // sector keys and column norms (scancontext.hip), the ring keys a dense [n][120] array; a query is a nearest-key sweep + one alignment launch.
 // M2DP (MRS_LOOPDB_M2DP) keeps the 192-d descriptors of m2dp.hip as float32 rows; a query is mrs_signature_knn over them.
+// Fast Histogram (MRS_LOOPDB_FH) keeps the range histograms of fasthist.hip as fp64 rows of `bins` doubles; a query is one sweep that evaluates
+// getEMD (pr_methods/FastHistogram.py:66-72) against every entry with the reference's order of additions, then the k smallest on the host.
 #include "common.hpp"
 #include "fft_codelets.hpp"
 
@@ -32,6 +34,9 @@ constexpr int kScDim = 120, kScMaxK = 64, kSmallSc = 5 * kScMaxK;
 
 // M2DP top-k query results, one copy to the host: index [kM2dpMaxK] | squared distance [kM2dpMaxK]
 constexpr int kM2dpDim = 192, kM2dpMaxK = 32, kSmallM2dp = 2 * kM2dpMaxK;
+
+// Fast Histogram sweep: a workgroup scores kFhEntries entries, kFhChunk buckets at a time
+constexpr int kFhMaxBins = MRS_FH_MAX_BINS, kFhMaxK = 32, kFhEntries = 64, kFhChunk = 64, kFhThreads = 256;
 
 struct Pinned {
     void* p = nullptr;
@@ -162,11 +167,41 @@ __global__ void k_m2dp_to_float(const double* __restrict__ src, float* __restric
     if (threadIdx.x < kM2dpDim) dst[threadIdx.x] = (float)src[threadIdx.x];
 }
 
+// getEMD(q, entry) for every entry: dist[e] = (sum over i, in index order, of |q_i - entry_i|) / bins, all fp64 -- the order of the
+// additions is the reference's, so the bits are.  A workgroup takes kFhEntries consecutive entries (rows of `bins` doubles, contiguous in
+// memory): all its threads bring a [kFhEntries][kFhChunk] block of buckets into LDS with coalesced reads (row stride kFhChunk + 1 doubles:
+// the lanes of the walk below hit different banks), then lane e of the first wave walks row e of the block in order, its running sum kept
+// in a register from one block to the next.
+__global__ __launch_bounds__(kFhThreads) void k_fh_distances(const double* __restrict__ q, const double* __restrict__ entries, int n, int bins,
+                                                             double* __restrict__ dist)
+{
+    __shared__ double blk[kFhEntries * (kFhChunk + 1)];
+    __shared__ double qs[kFhMaxBins];
+    const int t = threadIdx.x;
+    const int e0 = blockIdx.x * kFhEntries;
+    const int ne = min(kFhEntries, n - e0);
+    for (int i = t; i < bins; i += kFhThreads) qs[i] = q[i];
+    double acc = 0.0;
+    for (int c0 = 0; c0 < bins; c0 += kFhChunk) {
+        const int nc = min(kFhChunk, bins - c0);
+        __syncthreads();                                     // the previous block has been walked (and qs is written, the first time)
+        for (int i = t; i < ne * nc; i += kFhThreads) {
+            const int r = i / nc, c = i - r * nc;
+            blk[r * (kFhChunk + 1) + c] = entries[(size_t)(e0 + r) * bins + c0 + c];
+        }
+        __syncthreads();
+        if (t < ne)
+            for (int c = 0; c < nc; ++c) acc += fabs(qs[c0 + c] - blk[t * (kFhChunk + 1) + c]);
+    }
+    if (t < ne) dist[e0 + t] = acc / (double)bins;
+}
+
 }  // namespace
 
 struct mrs_loopdb {
     mrs_ctx* ctx = nullptr;
     int kind = 0, channels = 1;
+    int bins = 0;                             // FH: buckets per histogram
     int sig_dim = 0, R = 0, S = 0;            // DiSCO; SC: sig_dim = R = S = 120 (ring keys [cap][120] in d_sigs)
     int n = 0, cap = 0;
     size_t entry_floats = 0;                  // floats from one entry of d_entries to the next
@@ -310,17 +345,20 @@ int mrs_loopdb_create(mrs_ctx* ctx, int32_t kind, int32_t channels, int32_t capa
     MRS_REQUIRE(ctx && out, "null pointer");
     *out = nullptr;
     MRS_REQUIRE(kind == MRS_LOOPDB_RING || kind == MRS_LOOPDB_RINGPP || kind == MRS_LOOPDB_DISCO || kind == MRS_LOOPDB_SC ||
-                kind == MRS_LOOPDB_M2DP, "unknown kind");
-    if (kind == MRS_LOOPDB_SC || kind == MRS_LOOPDB_M2DP) channels = 1;      // ignored: one descriptor per entry
+                kind == MRS_LOOPDB_M2DP || kind == MRS_LOOPDB_FH, "unknown kind");
+    const int bins = kind == MRS_LOOPDB_FH ? channels : 0;                   // FH: `channels` carries the number of buckets
+    MRS_REQUIRE(kind != MRS_LOOPDB_FH || (bins >= 1 && bins <= kFhMaxBins), "bins in 1..256 (the channels argument of a Fast Histogram database)");
+    if (kind == MRS_LOOPDB_SC || kind == MRS_LOOPDB_M2DP || kind == MRS_LOOPDB_FH) channels = 1;      // ignored: one descriptor per entry
     MRS_REQUIRE(kind != MRS_LOOPDB_RING || channels == 1, "RING descriptors have one channel");
     MRS_REQUIRE(channels >= 1 && channels <= 16, "channels out of range");
     MRS_HIP_TRY(hipSetDevice(ctx->device));
     mrs_loopdb* db = new mrs_loopdb();
-    db->ctx = ctx; db->kind = kind; db->channels = channels;
+    db->ctx = ctx; db->kind = kind; db->channels = channels; db->bins = bins;
     if (kind == MRS_LOOPDB_RING) { db->entry_floats = kTiledFloats; db->in_floats = (size_t)kA * kD * 2; }
     else if (kind == MRS_LOOPDB_RINGPP) { db->entry_floats = (size_t)channels * kTiledFloats; db->in_floats = (size_t)channels * kA * kD; }
     else if (kind == MRS_LOOPDB_DISCO) { db->sig_dim = 1024; db->R = kPR; db->S = kPS; db->entry_floats = (size_t)db->R * db->S * 2; db->in_floats = db->entry_floats; }
     else if (kind == MRS_LOOPDB_M2DP) { db->entry_floats = kM2dpDim; db->in_floats = 2 * (size_t)kM2dpDim; }      // arguments are 192 doubles
+    else if (kind == MRS_LOOPDB_FH) { db->entry_floats = 2 * (size_t)bins; db->in_floats = 2 * (size_t)bins; }    // rows and arguments are `bins` doubles
     else { db->sig_dim = db->R = db->S = kScDim; db->entry_floats = mrs::sc_entry_floats(kScDim, kScDim); db->in_floats = (size_t)kScDim * kScDim; }
     auto fail = [&](int st) { mrs_loopdb_destroy(db); return st; };
 #define LDB_TRY(expr) do { if ((expr) != hipSuccess) { mrs::set_error("%s failed (%s:%d)", #expr, __FILE__, __LINE__); return fail(MRS_ERR_HIP); } } while (0)
@@ -415,7 +453,7 @@ int mrs_loopdb_clear(mrs_loopdb* db)
 int mrs_loopdb_append(mrs_loopdb* db, const void* descriptor, int32_t form, int32_t count, mrs_stream stream)
 {
     MRS_REQUIRE(db && descriptor, "null pointer");
-    MRS_REQUIRE(db->kind == MRS_LOOPDB_RING || db->kind == MRS_LOOPDB_RINGPP, "not a RING / RING++ database (DiSCO: mrs_loopdb_append_disco, SC: mrs_loopdb_append_sc, M2DP: mrs_loopdb_append_m2dp)");
+    MRS_REQUIRE(db->kind == MRS_LOOPDB_RING || db->kind == MRS_LOOPDB_RINGPP, "not a RING / RING++ database (DiSCO: mrs_loopdb_append_disco, SC: mrs_loopdb_append_sc, M2DP: mrs_loopdb_append_m2dp, FH: mrs_loopdb_append_fh)");
     MRS_REQUIRE(form == MRS_LOOPDB_FORM_HOST || form == MRS_LOOPDB_FORM_DEVICE || form == MRS_LOOPDB_FORM_DEVICE_SPEC, "unknown form");
     MRS_REQUIRE(count >= 1 && (count == 1 || form == MRS_LOOPDB_FORM_DEVICE_SPEC), "several entries per call only as device half spectra");
     MRS_HIP_TRY(hipSetDevice(db->ctx->device));
@@ -447,7 +485,7 @@ int mrs_loopdb_query(mrs_loopdb* db, const void* descriptor, int32_t form, float
                      mrs_stream stream)
 {
     MRS_REQUIRE(db && descriptor && h_count, "null pointer");
-    MRS_REQUIRE(db->kind == MRS_LOOPDB_RING || db->kind == MRS_LOOPDB_RINGPP, "not a RING / RING++ database (DiSCO: mrs_loopdb_query_disco, SC: mrs_loopdb_query_sc, M2DP: mrs_loopdb_query_m2dp)");
+    MRS_REQUIRE(db->kind == MRS_LOOPDB_RING || db->kind == MRS_LOOPDB_RINGPP, "not a RING / RING++ database (DiSCO: mrs_loopdb_query_disco, SC: mrs_loopdb_query_sc, M2DP: mrs_loopdb_query_m2dp, FH: mrs_loopdb_query_fh)");
     MRS_REQUIRE(form == MRS_LOOPDB_FORM_HOST || form == MRS_LOOPDB_FORM_DEVICE || form == MRS_LOOPDB_FORM_DEVICE_SPEC, "unknown form");
     MRS_REQUIRE(max_out >= 0 && (max_out == 0 || (h_index && h_dist && h_angle)), "output arrays");
     MRS_REQUIRE(all_capacity >= 0 && (all_capacity == 0 || h_all_dist || h_all_angle), "all_capacity without an array");
@@ -483,7 +521,7 @@ int mrs_loopdb_query_multi(mrs_loopdb* db, const void* descriptors, int32_t form
                            int32_t* h_all_angle, int32_t* h_n, mrs_stream stream)
 {
     MRS_REQUIRE(db && descriptors && h_all_dist && h_all_angle && h_n, "null pointer");
-    MRS_REQUIRE(db->kind == MRS_LOOPDB_RING || db->kind == MRS_LOOPDB_RINGPP, "not a RING / RING++ database (DiSCO: mrs_loopdb_query_disco, SC: mrs_loopdb_query_sc, M2DP: mrs_loopdb_query_m2dp)");
+    MRS_REQUIRE(db->kind == MRS_LOOPDB_RING || db->kind == MRS_LOOPDB_RINGPP, "not a RING / RING++ database (DiSCO: mrs_loopdb_query_disco, SC: mrs_loopdb_query_sc, M2DP: mrs_loopdb_query_m2dp, FH: mrs_loopdb_query_fh)");
     MRS_REQUIRE(form == MRS_LOOPDB_FORM_HOST || form == MRS_LOOPDB_FORM_DEVICE || form == MRS_LOOPDB_FORM_DEVICE_SPEC, "unknown form");
     MRS_REQUIRE(count >= 1 && count <= 1024 && all_capacity >= 0, "count in 1..1024");
     MRS_HIP_TRY(hipSetDevice(db->ctx->device));
@@ -633,7 +671,7 @@ int sc_release_arg(mrs_loopdb* db, int32_t on_device, mrs_stream stream)
 int mrs_loopdb_append_sc(mrs_loopdb* db, const float* sc, int32_t on_device, mrs_stream stream)
 {
     MRS_REQUIRE(db && sc, "null pointer");
-    MRS_REQUIRE(db->kind == MRS_LOOPDB_SC, "not a Scan Context database");
+    MRS_REQUIRE(db->kind == MRS_LOOPDB_SC, "not a Scan Context database (FH: mrs_loopdb_append_fh / mrs_loopdb_query_fh)");
     MRS_HIP_TRY(hipSetDevice(db->ctx->device));
     std::lock_guard<std::mutex> lk(db->mu);
     int st = reserve_locked(db, db->n + 1);
@@ -660,7 +698,7 @@ int mrs_loopdb_query_sc(mrs_loopdb* db, const float* sc, int32_t on_device, int3
                         float* h_key_dist, float* h_dist, int32_t* h_shift, int32_t* h_count, mrs_stream stream)
 {
     MRS_REQUIRE(db && sc && h_index && h_key_dist && h_dist && h_shift && h_count, "null pointer");
-    MRS_REQUIRE(db->kind == MRS_LOOPDB_SC, "not a Scan Context database");
+    MRS_REQUIRE(db->kind == MRS_LOOPDB_SC, "not a Scan Context database (FH: mrs_loopdb_append_fh / mrs_loopdb_query_fh)");
     MRS_REQUIRE(num_candidates >= 1 && num_candidates <= kScMaxK, "num_candidates in 1..64");
     MRS_REQUIRE(std::isfinite(search_ratio) && search_ratio >= 0.0f, "search_ratio >= 0");
     MRS_HIP_TRY(hipSetDevice(db->ctx->device));
@@ -703,7 +741,7 @@ int mrs_loopdb_query_sc_all(mrs_loopdb* db, const float* sc, int32_t on_device, 
                             int32_t* h_all_shift, int32_t* h_best, int32_t* h_n, mrs_stream stream)
 {
     MRS_REQUIRE(db && sc && h_best && h_n, "null pointer");
-    MRS_REQUIRE(db->kind == MRS_LOOPDB_SC, "not a Scan Context database");
+    MRS_REQUIRE(db->kind == MRS_LOOPDB_SC, "not a Scan Context database (FH: mrs_loopdb_append_fh / mrs_loopdb_query_fh)");
     MRS_REQUIRE(std::isfinite(search_ratio) && search_ratio >= 0.0f, "search_ratio >= 0");
     MRS_REQUIRE(all_capacity >= 0 && (all_capacity == 0 || (h_all_dist && h_all_shift)), "all_capacity without arrays");
     MRS_HIP_TRY(hipSetDevice(db->ctx->device));
@@ -759,7 +797,7 @@ int m2dp_to_row(mrs_loopdb* db, const double* desc, int32_t on_device, mrs_strea
 int mrs_loopdb_append_m2dp(mrs_loopdb* db, const double* desc, int32_t on_device, mrs_stream stream)
 {
     MRS_REQUIRE(db && desc, "null pointer");
-    MRS_REQUIRE(db->kind == MRS_LOOPDB_M2DP, "not an M2DP database");
+    MRS_REQUIRE(db->kind == MRS_LOOPDB_M2DP, "not an M2DP database (FH: mrs_loopdb_append_fh / mrs_loopdb_query_fh)");
     MRS_HIP_TRY(hipSetDevice(db->ctx->device));
     std::lock_guard<std::mutex> lk(db->mu);
     int st = reserve_locked(db, db->n + 1);
@@ -774,7 +812,7 @@ int mrs_loopdb_query_m2dp(mrs_loopdb* db, const double* desc, int32_t on_device,
                           mrs_stream stream)
 {
     MRS_REQUIRE(db && desc && h_index && h_dist2 && h_count, "null pointer");
-    MRS_REQUIRE(db->kind == MRS_LOOPDB_M2DP, "not an M2DP database");
+    MRS_REQUIRE(db->kind == MRS_LOOPDB_M2DP, "not an M2DP database (FH: mrs_loopdb_append_fh / mrs_loopdb_query_fh)");
     MRS_REQUIRE(k >= 1 && k <= kM2dpMaxK, "k in 1..32");
     MRS_HIP_TRY(hipSetDevice(db->ctx->device));
     std::lock_guard<std::mutex> lk(db->mu);
@@ -796,6 +834,111 @@ int mrs_loopdb_query_m2dp(mrs_loopdb* db, const double* desc, int32_t on_device,
     }
     *h_count = cnt;
     return MRS_OK;
+}
+
+// ---- Fast Histogram -----------------------------------------------------------------------------------------------------------------
+
+namespace {
+// the histogram argument (`bins` doubles, host or device) as a device pointer the handle's stream may read (lock held); a host argument goes
+// through d_in
+int fh_arg(mrs_loopdb* db, const double* hist, int32_t on_device, mrs_stream stream, const double** src)
+{
+    if (on_device) {
+        *src = hist;
+        return join_in(db, (hipStream_t)stream);
+    }
+    *src = reinterpret_cast<const double*>(db->d_in);
+    return upload(db, hist, (size_t)db->bins * sizeof(double), db->d_in);
+}
+
+// distances of `hist` to the n entries -> d_dist [n] on the handle's stream (lock held, n > 0)
+int fh_sweep(mrs_loopdb* db, const double* hist, int32_t on_device, mrs_stream stream, int n, double* d_dist)
+{
+    const double* src = nullptr;
+    int st = fh_arg(db, hist, on_device, stream, &src);
+    if (st != MRS_OK) return st;
+    hipLaunchKernelGGL(k_fh_distances, dim3((n + kFhEntries - 1) / kFhEntries), dim3(kFhThreads), 0, db->s, src,
+                       reinterpret_cast<const double*>(db->d_entries), n, db->bins, d_dist);
+    MRS_HIP_TRY(hipGetLastError());
+    return MRS_OK;
+}
+}  // namespace
+
+int mrs_loopdb_append_fh(mrs_loopdb* db, const double* hist, int32_t on_device, mrs_stream stream)
+{
+    MRS_REQUIRE(db && hist, "null pointer");
+    MRS_REQUIRE(db->kind == MRS_LOOPDB_FH, "not a Fast Histogram database");
+    MRS_HIP_TRY(hipSetDevice(db->ctx->device));
+    std::lock_guard<std::mutex> lk(db->mu);
+    int st = reserve_locked(db, db->n + 1);
+    if (st != MRS_OK) return st;
+    float* slot = db->d_entries + (size_t)db->n * db->entry_floats;
+    const size_t bytes = (size_t)db->bins * sizeof(double);
+    if (on_device) {
+        st = join_in(db, (hipStream_t)stream);
+        if (st != MRS_OK) return st;
+        MRS_HIP_TRY(hipMemcpyAsync(slot, hist, bytes, hipMemcpyDeviceToDevice, db->s));
+        st = sc_release_arg(db, on_device, stream);
+    } else {
+        st = upload(db, hist, bytes, slot);
+    }
+    if (st != MRS_OK) return st;
+    db->n += 1;
+    return MRS_OK;
+}
+
+int mrs_loopdb_query_fh(mrs_loopdb* db, const double* hist, int32_t on_device, int32_t k, int32_t* h_index, double* h_dist, int32_t* h_count,
+                        mrs_stream stream)
+{
+    MRS_REQUIRE(db && hist && h_index && h_dist && h_count, "null pointer");
+    MRS_REQUIRE(db->kind == MRS_LOOPDB_FH, "not a Fast Histogram database");
+    MRS_REQUIRE(k >= 1 && k <= kFhMaxK, "k in 1..32");
+    MRS_HIP_TRY(hipSetDevice(db->ctx->device));
+    std::lock_guard<std::mutex> lk(db->mu);
+    for (int i = 0; i < k; ++i) { h_index[i] = -1; h_dist[i] = INFINITY; }
+    *h_count = 0;
+    const int n = db->n;
+    if (n == 0) return MRS_OK;
+    // d_dist / h_dist hold 2 x cap floats: room for cap doubles
+    double* d_all = reinterpret_cast<double*>(db->d_dist);
+    const double* h_all = reinterpret_cast<const double*>(db->h_dist);
+    int st = fh_sweep(db, hist, on_device, stream, n, d_all);
+    if (st != MRS_OK) return st;
+    st = sc_release_arg(db, on_device, stream);
+    if (st != MRS_OK) return st;
+    MRS_HIP_TRY(hipMemcpyAsync(db->h_dist, d_all, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, db->s));
+    MRS_HIP_TRY(hipStreamSynchronize(db->s));
+    // the k smallest, ascending, ties to the lower index; a NaN distance (a NaN in either histogram) orders after every number
+    const int cnt = std::min(k, n);
+    std::vector<int32_t> order((size_t)n);
+    for (int i = 0; i < n; ++i) order[i] = i;
+    auto before = [h_all](int32_t a, int32_t b) {
+        const double da = h_all[a], db_ = h_all[b];
+        const bool na = da != da, nb = db_ != db_;
+        if (na != nb) return nb;
+        if (!na && da != db_) return da < db_;
+        return a < b;
+    };
+    std::partial_sort(order.begin(), order.begin() + cnt, order.end(), before);
+    for (int i = 0; i < cnt; ++i) { h_index[i] = order[i]; h_dist[i] = h_all[order[i]]; }
+    *h_count = cnt;
+    return MRS_OK;
+}
+
+int mrs_loopdb_distances_fh(mrs_loopdb* db, const double* hist, int32_t on_device, double* d_dist, mrs_stream stream)
+{
+    MRS_REQUIRE(db && hist, "null pointer");
+    MRS_REQUIRE(db->kind == MRS_LOOPDB_FH, "not a Fast Histogram database");
+    MRS_HIP_TRY(hipSetDevice(db->ctx->device));
+    std::lock_guard<std::mutex> lk(db->mu);
+    const int n = db->n;
+    if (n == 0) return MRS_OK;
+    MRS_REQUIRE(d_dist, "null pointer");
+    int st = join_in(db, (hipStream_t)stream);               // the caller's earlier work on d_dist comes first
+    if (st != MRS_OK) return st;
+    st = fh_sweep(db, hist, on_device, stream, n, d_dist);
+    if (st != MRS_OK) return st;
+    return sc_release_arg(db, 1, stream);                    // `stream` waits for the sweep: its later work sees d_dist
 }
 
 int mrs_loopdb_device_entries(mrs_loopdb* db, const float** d_entries, const float** d_signatures, int32_t* out_n, int64_t* entry_floats)
