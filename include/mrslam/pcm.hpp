@@ -1,0 +1,110 @@
+// mrslam/pcm.hpp -- C++ host-side pairwise consistency maximisation for the Mapping workspace.
+//
+// Stands where GlobalManager reaches distributed_pcm::DistributedPCM::solveCentralized (Mapping/src/global_manager/src/global_manager.cpp:
+// 1301-1310), which for every robot pair builds a global_map::GlobalMap and calls pairwiseConsistencyMaximization(): the consistency matrix
+// of pairwise_consistency.cpp:40-137, a Matrix-Market file under /tmp/log/, and FMC::maxCliqueHeu.  All arithmetic happens in
+// libmrslam_hip.so through the C ABI (mrs_pcm_*); this header only adapts types.  Plain arrays in, std::vector<int> out: no gtsam and no
+// Eigen.  A pose is 16 doubles, the row-major 4x4 (gtsam: pose.matrix(), copied row by row).
+//
+// Vertex numbers follow the order of addLoops.  The reference numbers the loops of a pair in the std::map order of (key1, key2) and keeps
+// the first of equal key pairs: sort and deduplicate that way (referenceOrder) to get its member lists number for number.
+#pragma once
+#include <algorithm>
+#include <cstdint>
+#include <numeric>
+#include <stdexcept>
+#include <string>
+#include <utility>
+#include <vector>
+
+#include "mrslam_hip.h"
+
+namespace mrslam {
+
+class PairwiseConsistency {
+public:
+    // getChiSquaredThreshold (pairwise_consistency.cpp:7-38) for 6 degrees of freedom; the reference aborts on any other p
+    static double chiSquaredThreshold(double p)
+    {
+        static const std::pair<int, double> table[] = {{1, 0.872}, {5, 1.635}, {10, 2.204}, {25, 3.455}, {50, 5.348}, {75, 7.840}};
+        const double scaled = p * 100.0;
+        for (const auto& row : table)
+            if (scaled > row.first - 1e-9 && scaled < row.first + 1e-9) return row.second;
+        throw std::invalid_argument("PairwiseConsistency: confidence probability " + std::to_string(p) + " is not supported");
+    }
+
+    // the order in which the reference numbers loops (ia[u], kb[u]): ascending (ia, kb), the first of equal pairs kept, the others dropped
+    static std::vector<int> referenceOrder(const int32_t* ia, const int32_t* kb, int n)
+    {
+        std::vector<int> order(n);
+        std::iota(order.begin(), order.end(), 0);
+        std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return std::make_pair(ia[a], kb[a]) < std::make_pair(ia[b], kb[b]); });
+        order.erase(std::unique(order.begin(), order.end(), [&](int a, int b) { return ia[a] == ia[b] && kb[a] == kb[b]; }), order.end());
+        return order;
+    }
+
+    explicit PairwiseConsistency(int capacity = MRS_PCM_MAX_LOOPS, double pcm_threshold = 0.01, int device = 0)
+    {
+        const double threshold = chiSquaredThreshold(pcm_threshold);
+        check(mrs_ctx_create(device, &ctx_), "mrs_ctx_create");
+        const int st = mrs_pcm_create(ctx_, capacity, threshold, &h_);
+        if (st != MRS_OK) {
+            const std::string why = std::string(mrs_status_str(st)) + ": " + mrs_last_error();
+            mrs_ctx_destroy(ctx_);
+            throw std::runtime_error("mrs_pcm_create: " + why);
+        }
+    }
+    ~PairwiseConsistency()
+    {
+        mrs_pcm_destroy(h_);
+        mrs_ctx_destroy(ctx_);
+    }
+    PairwiseConsistency(const PairwiseConsistency&) = delete;
+    PairwiseConsistency& operator=(const PairwiseConsistency&) = delete;
+
+    // trajectory poses (buildTrajectory's chain from the identity), [na][16] and [nb][16]; clears the loops
+    void setTrajectories(const double* XA, int na, const double* XB, int nb)
+    {
+        check(mrs_pcm_set_trajectories(h_, XA, na, XB, nb), "mrs_pcm_set_trajectories");
+    }
+    // n loops: Z [n][16], the measured pose of B_kb[u] in the frame of A_ia[u]
+    void addLoops(const int32_t* ia, const int32_t* kb, const double* Z, int n) { check(mrs_pcm_add_loops(h_, ia, kb, Z, n), "mrs_pcm_add_loops"); }
+    void clearLoops() { check(mrs_pcm_clear_loops(h_), "mrs_pcm_clear_loops"); }
+    int size() const
+    {
+        int32_t n = 0;
+        check(mrs_pcm_count(h_, &n), "mrs_pcm_count");
+        return n;
+    }
+
+    // FMC::maxCliqueHeu's max_clique_data: the loops that may enter the pose graph, in the reference's order
+    std::vector<int> solve()
+    {
+        std::vector<int32_t> members(std::max(size(), 1));
+        int32_t n = 0;
+        check(mrs_pcm_solve(h_, members.data(), &n, &rounds_), "mrs_pcm_solve");
+        return std::vector<int>(members.begin(), members.begin() + n);
+    }
+    int rounds() const { return rounds_; }
+
+    // the consistency matrix, [size][size] of 0 / 1
+    std::vector<uint8_t> matrix() const
+    {
+        const size_t n = static_cast<size_t>(size());
+        std::vector<uint8_t> m(n * n);
+        if (n) check(mrs_pcm_get_matrix(h_, m.data()), "mrs_pcm_get_matrix");
+        return m;
+    }
+
+private:
+    static void check(int st, const char* what)
+    {
+        if (st != MRS_OK) throw std::runtime_error(std::string(what) + ": " + mrs_status_str(st) + ": " + mrs_last_error());
+    }
+
+    mrs_ctx* ctx_ = nullptr;
+    mrs_pcm* h_ = nullptr;
+    int32_t rounds_ = 0;
+};
+
+}  // namespace mrslam

@@ -1006,6 +1006,45 @@ int mrs_fh_host(mrs_ctx* ctx, const void* h_points, int32_t is_double, int32_t s
                 double* h_range, int32_t* h_unbound);
 
 /* ------------------------------------------------------------------------------------
+ * Pairwise consistency of the inter-robot loops of one robot pair: what
+ * global_map::GlobalMap::pairwiseConsistencyMaximization computes for DistributedPCM::solveCentralized
+ * (Mapping/src/global_manager/src/global_manager.cpp:1301-1310): the consistency matrix of
+ * pairwise_consistency.cpp:40-137 and the clique of FMC::maxCliqueHeu (findCliqueHeu.cpp:120-243).  DESIGN.md 4.18.
+ * Host arrays in and out; every call is blocking and works on the legacy default stream.  One caller at a time per handle.
+ * ---------------------------------------------------------------------------------- */
+typedef struct mrs_pcm mrs_pcm;
+
+/* most loops one handle holds */
+#define MRS_PCM_MAX_LOOPS 4096
+
+/* capacity in 1 .. MRS_PCM_MAX_LOOPS (more: MRS_ERR_UNSUPPORTED); threshold > 0 and finite: loops u, v are consistent iff
+ * |Logmap(Z_u^-1 (XA_i^-1 XA_j) Z_v (XB_l^-1 XB_k))| < threshold (getChiSquaredThreshold: 0.872 for the launch default p = 0.01) */
+int mrs_pcm_create(mrs_ctx* ctx, int32_t capacity, double threshold, mrs_pcm** out);
+int mrs_pcm_destroy(mrs_pcm* pcm);
+/* The two trajectories as row-major 4x4 poses, double [na][4][4] and [nb][4][4] (buildTrajectory's chain from the identity).  Clears the
+ * loops. */
+int mrs_pcm_set_trajectories(mrs_pcm* pcm, const double* h_XA, int32_t na, const double* h_XB, int32_t nb);
+/* Appends n loops (h_ia[u], h_kb[u], h_Z[u]): h_Z double [n][4][4] is the measured pose of B_k in the frame of A_i.  Vertex numbers follow
+ * the order of addition.  Computes the new rows and columns of the consistency matrix; the bits do not depend on how the loops were split
+ * over calls.  An index outside its trajectory: MRS_ERR_ARG; more loops than the capacity: MRS_ERR_UNSUPPORTED; nothing is added then.  A
+ * loop whose pose is not finite is consistent with no other. */
+int mrs_pcm_add_loops(mrs_pcm* pcm, const int32_t* h_ia, const int32_t* h_kb, const double* h_Z, int32_t n);
+int mrs_pcm_clear_loops(mrs_pcm* pcm);
+int mrs_pcm_count(mrs_pcm* pcm, int32_t* h_count);
+/* FMC::maxCliqueHeu of the current matrix: h_clique int32 [count] receives the member list in the reference's order (the start vertex,
+ * then the vertices in the order the greedy chain took them), h_n_clique its length (0 without loops, where the reference returns -1);
+ * optional h_n_rounds: the speculative rounds it took (at most length + 1). */
+int mrs_pcm_solve(mrs_pcm* pcm, int32_t* h_clique, int32_t* h_n_clique, int32_t* h_n_rounds);
+/* the consistency matrix, uint8 [count][count] of 0 / 1: symmetric, zero diagonal */
+int mrs_pcm_get_matrix(mrs_pcm* pcm, uint8_t* h_dense);
+/* Replaces the loops by `count` vertices with the given adjacency (uint8 [count][count], non-zero = edge), so that the clique stage can be
+ * used without the geometry.  Asymmetric input or a set diagonal: MRS_ERR_ARG.  Such vertices have no distances, and loops cannot be
+ * appended to them: both are MRS_ERR_ARG until the loops are cleared. */
+int mrs_pcm_set_matrix(mrs_pcm* pcm, int32_t count, const uint8_t* h_dense);
+/* the consistency distances, double [count][count], recomputed by this call (they are never stored): symmetric, zero diagonal */
+int mrs_pcm_get_distances(mrs_pcm* pcm, double* h_d);
+
+/* ------------------------------------------------------------------------------------
  * Mapping-side DiSCO matcher
  * ---------------------------------------------------------------------------------- */
 

@@ -1,0 +1,134 @@
+"""Pairwise Consistency Maximisation for the inter-robot loops of one robot pair (Mapping/src/global_manager/src/
+pairwise_consistency_maximization/): which of the verified loops are mutually consistent and may enter the pose graph.
+
+Thin host logic over the C ABI (mrs_pcm_*); there is no CPU fallback.  The consistency matrix and the clique heuristic run on the GPU;
+`chi2_threshold`, `chain_odometry` and `reference_order` restate the three small host steps the reference takes before them.  The contract,
+its two reproduced quirks and its three fixes are in DESIGN.md 4.18.
+"""
+import ctypes as C
+import re
+
+import numpy as np
+
+from . import _lib
+
+MAX_LOOPS = int(re.search(r"#define\s+MRS_PCM_MAX_LOOPS\s+(\d+)", open(_lib.HEADER).read())[1])
+# getChiSquaredThreshold for 6 degrees of freedom (pairwise_consistency.cpp:7-38), keyed by round(100 p)
+_CHI2 = {1: 0.872, 5: 1.635, 10: 2.204, 25: 3.455, 50: 5.348, 75: 7.840}
+
+
+def chi2_threshold(p):
+    """the reference's threshold for confidence probability p (its launch default pcm_thresh is 0.01); it aborts on any other p, this raises"""
+    key = round(float(p) * 100)
+    if key not in _CHI2 or abs(float(p) * 100 - key) > 1e-9:
+        raise ValueError("confidence probability %r is not supported: one of 0.01, 0.05, 0.10, 0.25, 0.50, 0.75" % (p,))
+    return _CHI2[key]
+
+
+def chain_odometry(odom):
+    """buildTrajectory (graph_utils_functions.cpp:37-70): odometry between-poses [n, 4, 4] -> trajectory [n + 1, 4, 4]; the first pose is the
+    identity and pose m + 1 = pose m @ odom[m]"""
+    odom = np.asarray(odom, np.float64).reshape(-1, 4, 4)
+    X = np.empty((odom.shape[0] + 1, 4, 4))
+    X[0] = np.eye(4)
+    for m in range(odom.shape[0]):
+        X[m + 1] = X[m] @ odom[m]
+    return X
+
+
+def reference_order(ia, kb):
+    """indices that put loops (ia, kb) into the reference's vertex order: the std::map order of (key1, key2) (interrobot_measurements.cpp:8-14),
+    where a key pair met again is dropped (std::map::insert keeps the first)"""
+    ia, kb = np.asarray(ia, np.int64).reshape(-1), np.asarray(kb, np.int64).reshape(-1)
+    order = np.lexsort((kb, ia))                                 # stable: the first of equal pairs stays first
+    if order.size:
+        same = np.zeros(order.size, bool)
+        same[1:] = (ia[order][1:] == ia[order][:-1]) & (kb[order][1:] == kb[order][:-1])
+        order = order[~same]
+    return order
+
+
+def _poses(a, what):
+    a = np.ascontiguousarray(a, np.float64)
+    if a.ndim == 2:
+        a = a[None]
+    if a.ndim != 3 or a.shape[1:] != (4, 4):
+        raise ValueError("%s: expected [n, 4, 4] poses, got %s" % (what, a.shape))
+    return a
+
+
+class PcmGraph:
+    """The loops of one robot pair on the device: `set_trajectories(XA, XB)`, `add_loops(ia, kb, Z)` (vertex numbers follow the order of
+    addition; pass them in `reference_order` to number them as the reference does), `solve()` -> (member list in the reference's order,
+    number of rejected loops).  `matrix()` / `distances()` read the consistency matrix and the distances behind it; `set_matrix(A)` puts a
+    given adjacency in place of the loops, for the clique stage alone.  `rounds` is the number of rounds the last solve took."""
+
+    def __init__(self, capacity=MAX_LOOPS, p=0.01, threshold=None, device=0):
+        self.device = int(device)
+        self.capacity = int(capacity)
+        self.threshold = chi2_threshold(p) if threshold is None else float(threshold)
+        self.rounds = 0
+        self._h = C.c_void_p()
+        _lib.load().mrs_pcm_create(_lib.ctx(self.device), self.capacity, self.threshold, C.byref(self._h))
+
+    def __del__(self):
+        try:
+            if getattr(self, "_h", None):
+                _lib.load().mrs_pcm_destroy(self._h)
+        except Exception:
+            pass
+
+    def __len__(self):
+        n = C.c_int32(0)
+        _lib.load().mrs_pcm_count(self._h, C.byref(n))
+        return n.value
+
+    def set_trajectories(self, XA, XB):
+        """trajectory poses [na, 4, 4] and [nb, 4, 4] (see chain_odometry); clears the loops"""
+        XA, XB = _poses(XA, "XA"), _poses(XB, "XB")
+        _lib.load().mrs_pcm_set_trajectories(self._h, XA, XA.shape[0], XB, XB.shape[0])
+
+    def add_loops(self, ia, kb, Z):
+        """appends loops: Z[u] [4, 4] is the measured pose of B_kb[u] in the frame of A_ia[u]"""
+        ia, kb = np.ascontiguousarray(ia, np.int32).reshape(-1), np.ascontiguousarray(kb, np.int32).reshape(-1)
+        Z = _poses(Z, "Z")
+        if not ia.size == kb.size == Z.shape[0]:
+            raise ValueError("ia, kb and Z must have one entry per loop")
+        if ia.size:
+            _lib.load().mrs_pcm_add_loops(self._h, ia, kb, Z, ia.size)
+
+    def clear(self):
+        _lib.load().mrs_pcm_clear_loops(self._h)
+
+    def solve(self):
+        """-> (clique int32 [size], n_rejected): FMC::maxCliqueHeu's member list and the loops it leaves out; empty without loops"""
+        L = len(self)
+        clique = np.zeros(max(L, 1), np.int32)
+        n, rounds = C.c_int32(0), C.c_int32(0)
+        _lib.load().mrs_pcm_solve(self._h, clique, C.byref(n), C.byref(rounds))
+        self.rounds = rounds.value
+        return clique[:n.value].copy(), L - n.value
+
+    def matrix(self):
+        """the consistency matrix, bool [L, L]"""
+        L = len(self)
+        A = np.zeros((L, L), np.uint8)
+        if L:
+            _lib.load().mrs_pcm_get_matrix(self._h, A)
+        return A.astype(bool)
+
+    def set_matrix(self, A):
+        """replaces the loops by the vertices of a symmetric adjacency with a zero diagonal"""
+        A = np.asarray(A)
+        if A.ndim != 2 or A.shape[0] != A.shape[1]:
+            raise ValueError("expected a square matrix, got %s" % (A.shape,))
+        A = np.ascontiguousarray(A != 0, np.uint8)
+        _lib.load().mrs_pcm_set_matrix(self._h, A.shape[0], A if A.size else None)
+
+    def distances(self):
+        """the consistency distances, float64 [L, L], recomputed on demand"""
+        L = len(self)
+        D = np.zeros((L, L), np.float64)
+        if L:
+            _lib.load().mrs_pcm_get_distances(self._h, D)
+        return D
