@@ -1112,6 +1112,65 @@ int mrs_elev_map_closeloop(mrs_elev_map* m, const float* h_update_position2, flo
 int mrs_elev_get_layer(mrs_elev_map* m, int32_t which, float* h_out);
 int mrs_elev_get_frame(mrs_elev_map* m, float* h_central2, int32_t* h_start2);
 
+/* ------------------------------------------------------------------------------------
+ * Globally consistent elevation map: the submap stack of
+ * ElevationMapping::updateLocalMap (elevation_mapping/src/ElevationMapping.cpp:653-815), its correction in updateGlobalMap
+ * (:821-962), the elevation branch of GlobalManager::composeGlobalMap (global_manager.cpp:2133-2152) and
+ * PointMapLayer::updateBounds (pointMap_layer.cpp:100-135).
+ * A cell record is ten 32-bit values: float x, y, z (the elevation), var; int32 r, g, b, frontier; float intensity, travers.
+ * Records go in and come out as [n][10] words, from host memory (h_*) or device memory (d_*): pass exactly one of the two.
+ * Every call is blocking and works on the legacy default stream.  One caller at a time per handle.
+ * ---------------------------------------------------------------------------------- */
+typedef struct mrs_gem mrs_gem;
+
+#define MRS_GEM_WEIGHTED 0     /* z = (vn^2 zo + vo^2 zn) / (vo^2 + vn^2), var = vo^2 vn^2 / (vo^2 + vn^2): the default, a named fix */
+#define MRS_GEM_AS_WRITTEN 1   /* the reference's expressions with C precedence (ElevationMapping.cpp:913-914) */
+#define MRS_GEM_MAX_SUBMAPS 4096
+
+/* resolution > 0: the cell size of the key k = ceil((double)v / resolution); radius (the reference's 15) and min_neighbours (its 3: a
+ * centre submap fuses only when its radius search returns at least that many submaps, itself included) steer mrs_gem_update_global. */
+int mrs_gem_create(mrs_ctx* ctx, double resolution, int32_t rule, float radius, int32_t min_neighbours, mrs_gem** out);
+int mrs_gem_destroy(mrs_gem* gem);
+/* Inserts n records into the open submap, keyed by the bit patterns of (x, y) (so -0.0 and 0.0 are different keys): a key met again
+ * replaces the stored record, within a call and across calls, and keeps its place in the order of first insertion. */
+int mrs_gem_append_cells(mrs_gem* gem, const void* h_cells, const void* d_cells, int64_t n);
+/* The same for the records that pass the window predicate of ElevationMapping.cpp:770-779, evaluated in float: elevation != -10 and
+ * the eight clauses on the signs of h_shift2 and the position against h_current2 -+ length * resolution / 2. */
+int mrs_gem_append_leaving(mrs_gem* gem, const void* h_cells, const void* d_cells, int64_t n, const float* h_current2, const float* h_shift2,
+                           int32_t length, float resolution);
+/* The open submap's records with elevation != -10 become the next submap, in ascending order of first insertion, with pose float
+ * [4][4] row-major and centre (cx, cy); the open submap is empty afterwards.  More than MRS_GEM_MAX_SUBMAPS: MRS_ERR_UNSUPPORTED. */
+int mrs_gem_close_submap(mrs_gem* gem, const float* h_pose16, const float* h_centre2);
+/* any of the three may be NULL: closed submaps, records in them, records appended to the open submap (before de-duplication) */
+int mrs_gem_count(mrs_gem* gem, int32_t* h_submaps, int64_t* h_cells, int64_t* h_open);
+/* Submap `index`: its record count in h_n, optionally its records (capacity in records), its pose [16] and its centre [2]. */
+int mrs_gem_get_submap(mrs_gem* gem, int32_t index, void* h_cells, void* d_cells, int64_t capacity, int64_t* h_n, float* h_pose16,
+                       float* h_centre2);
+/* updateGlobalMap with h_opt_poses float [n_poses][4][4]: K = min(n_poses, submaps); submaps 1 .. K - 1 are moved by
+ * opt[i] * inverse(pose[i]) and take opt[i] as their pose; then, for every centre submap in index order, each neighbour within the
+ * radius is fused into it cell by cell (DESIGN.md 4.19 has the exact order and arithmetic).  All device memory the call needs is
+ * allocated before the first record or pose is changed: a failed allocation leaves the store as it was.  A runtime error after that
+ * point (a failed launch or copy) leaves the store undefined: destroy it. */
+int mrs_gem_update_global(mrs_gem* gem, const float* h_opt_poses, int32_t n_poses);
+/* of the last mrs_gem_update_global: records dropped for a non-finite position or a key outside |k| < 2^23, and cells fused (one count
+ * per matched key and pair) */
+int mrs_gem_stats(mrs_gem* gem, int64_t* h_dropped, int64_t* h_matched);
+/* all submaps concatenated in index order (composingGlobalMap, ElevationMapping.cpp:501-509); h_n alone when both outputs are NULL */
+int mrs_gem_compose(mrs_gem* gem, void* h_cells, void* d_cells, int64_t capacity, int64_t* h_n);
+/* The elevation branch of GlobalManager::composeGlobalMap: submap j of robot r moved by h_poses (float [sum of submaps][4][4], in (robot,
+ * submap) order), then the robots' local maps (h_local_cells or d_local_cells, at most one of the two; records h_local_offsets[r] ..
+ * h_local_offsets[r + 1]; all three may be NULL) moved by h_refs float [n_robots][4][4].  merge_cells != 0 places one grid of `resolution` over the concatenation and folds records of equal
+ * key left to right with `rule`: one record per cell, in key order.  h_n: the record count (with both outputs NULL: an upper bound to
+ * size them by); h_dropped (optional): records without a key, which merge_cells leaves out.  The stores are only read: an error leaves
+ * them as they were (the caller's output may be partly written). */
+int mrs_gem_compose_robots(mrs_ctx* ctx, mrs_gem* const* stores, int32_t n_robots, const float* h_poses, const void* h_local_cells,
+                           const void* d_local_cells, const int64_t* h_local_offsets, const float* h_refs, int32_t merge_cells, int32_t rule,
+                           double resolution, void* h_cells, void* d_cells, int64_t capacity, int64_t* h_n, int64_t* h_dropped);
+/* PointMapLayer::updateBounds: uint8 grid [size_y][size_x], 255 where no point fell; a point sets its cell to 254 if z != -10, z != 10,
+ * travers != -10 and (thresh_type 0: travers < thresh; 1: z > thresh), else to 0; the last point in input order wins. */
+int mrs_gem_costmap(mrs_ctx* ctx, const void* h_cloud, const void* d_cloud, int64_t n, double origin_x, double origin_y, int32_t size_x, int32_t size_y,
+                    double resolution, int32_t thresh_type, double thresh, uint8_t* h_grid, uint8_t* d_grid);
+
 #ifdef __cplusplus
 }
 #endif

@@ -92,6 +92,15 @@ size_t idle_cap()
     return cap;
 }
 
+// has the block's last use completed?  Any other answer than success means "not yet"; it is dropped here, so that it does not stay behind as
+// the thread's last error for the next launch check (hipGetLastError after a kernel launch) to find
+bool event_done(hipEvent_t ev)
+{
+    const hipError_t e = hipEventQuery(ev);
+    if (e != hipSuccess) (void)hipGetLastError();
+    return e == hipSuccess;
+}
+
 // give idle blocks whose last use has completed back to the driver (all of them, or until `keep` bytes remain idle); lock held
 void trim_idle_locked(size_t keep, const void* spare)
 {
@@ -99,7 +108,7 @@ void trim_idle_locked(size_t keep, const void* spare)
     for (const ScratchBlock& b : g_scratch) idle += b.busy ? 0 : b.cap;
     for (size_t i = 0; i < g_scratch.size() && idle > keep;) {
         ScratchBlock& b = g_scratch[i];
-        if (!b.busy && b.p != spare && hipEventQuery(b.ev) == hipSuccess) {
+        if (!b.busy && b.p != spare && event_done(b.ev)) {
             idle -= b.cap;
             (void)hipFree(b.p);
             (void)hipEventDestroy(b.ev);
@@ -123,7 +132,7 @@ void* scratch_acquire(size_t bytes, hipStream_t stream)
             ScratchBlock& b = g_scratch[i];
             if (b.busy || b.device != dev || b.cap < want || b.cap > 4 * want + (1 << 20)) continue;
             // same stream: stream order protects the previous user's work; other stream: only once that work is done
-            if (b.last_stream != stream && hipEventQuery(b.ev) != hipSuccess) continue;
+            if (b.last_stream != stream && !event_done(b.ev)) continue;
             if (best < 0 || b.cap < g_scratch[best].cap) best = i;
         }
         if (best >= 0) {
@@ -159,6 +168,24 @@ void scratch_release(void* p, hipStream_t stream)
         }
     // keep the cache bounded: beyond the idle cap, give finished blocks back (not the one just released: its work is in flight)
     trim_idle_locked(idle_cap(), p);
+}
+
+void scratch_forget_stream(hipStream_t stream)
+{
+    if (!stream) return;
+    (void)hipStreamSynchronize(stream);                     // every block released on it is free from here on
+    std::lock_guard<std::mutex> lock(g_scratch_mu);
+    for (ScratchBlock& b : g_scratch) {
+        if (b.busy || b.last_stream != stream) continue;
+        hipEvent_t fresh = nullptr;
+        if (hipEventCreateWithFlags(&fresh, hipEventDisableTiming) != hipSuccess) {
+            (void)hipGetLastError();
+            continue;
+        }
+        (void)hipEventDestroy(b.ev);                        // a never-recorded event counts as completed
+        b.ev = fresh;
+        b.last_stream = nullptr;
+    }
 }
 
 }  // namespace mrs
@@ -224,7 +251,7 @@ int mrs_ctx_destroy(mrs_ctx* ctx)
     if (ctx->pointfeat_free)
         for (auto& kv : ctx->pointfeat_cache) ctx->pointfeat_free(kv.second);
     for (auto& sl : ctx->side_free) {
-        (void)hipStreamSynchronize(sl.stream);
+        mrs::scratch_forget_stream(sl.stream);               // waits for the stream
         (void)hipHostFree(sl.pinned);
         (void)hipEventDestroy(sl.join);
         (void)hipEventDestroy(sl.fork);

@@ -49,6 +49,11 @@ const char* dev_env(const char* name);
 // adapter test under a GPU-holding parent process; 0 of 40 with plain allocations), silently corrupting results.
 void* scratch_acquire(size_t bytes, hipStream_t stream);
 void scratch_release(void* p, hipStream_t stream);
+// A handle that owns a stream calls this before hipStreamDestroy: it waits for the stream and gives every idle block last used on it a
+// fresh event and no stream, so that the cache never queries an event whose stream no longer exists and never takes a new stream at
+// the old address for the old one.  (Seen in some runs of a long process, DESIGN.md has the counts: a RING query's launch check reported "operation not permitted when
+// stream is capturing" although nothing captures; the only unchecked runtime calls before it were the cache's event queries.)
+void scratch_forget_stream(hipStream_t stream);
 
 struct Scratch {
     void* p = nullptr;

@@ -421,7 +421,10 @@ int mrs_loopdb_destroy(mrs_loopdb* db)
     if (db->h_small) (void)hipHostFree(db->h_small);
     if (db->ev_in) (void)hipEventDestroy(db->ev_in);
     if (db->ev_out) (void)hipEventDestroy(db->ev_out);
-    if (db->s) (void)hipStreamDestroy(db->s);
+    if (db->s) {
+        mrs::scratch_forget_stream(db->s);
+        (void)hipStreamDestroy(db->s);
+    }
     delete db;
     return MRS_OK;
 }

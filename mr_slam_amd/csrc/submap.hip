@@ -388,7 +388,10 @@ int mrs_keyframes_destroy(mrs_keyframes* kf)
     if (kf->h_stage) (void)hipHostFree(kf->h_stage);
     if (kf->ev_in) (void)hipEventDestroy(kf->ev_in);
     if (kf->ev_out) (void)hipEventDestroy(kf->ev_out);
-    if (kf->s) (void)hipStreamDestroy(kf->s);
+    if (kf->s) {
+        mrs::scratch_forget_stream(kf->s);
+        (void)hipStreamDestroy(kf->s);
+    }
     delete kf;
     return MRS_OK;
 }
