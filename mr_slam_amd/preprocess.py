@@ -10,11 +10,14 @@ from . import _lib
 
 def voxel_down_sample(points, voxel_size):
     """open3d voxel_down_sample (main_RING.py:257-259).  points: device tensor [n, s>=3] float32/float64.
-    Returns a float64 device tensor [m,3] of voxel centroids (sorted by voxel index)."""
+    Returns a float64 device tensor [m,3] of voxel centroids (sorted by voxel index).  An empty cloud (n = 0, as a ROS callback can hand
+    over) gives an empty [0,3] result without a launch; the C ABI itself refuses n <= 0."""
     assert points.dtype in (torch.float32, torch.float64)
     d = _lib.device_of(points)
     p = points.contiguous()
     n = p.shape[0]
+    if n == 0:
+        return torch.empty((0, 3), dtype=torch.float64, device=p.device)
     out = torch.empty((n, 3), dtype=torch.float64, device=p.device)
     cnt = C.c_int32(0)
     _lib.load().mrs_voxel_downsample(_lib.ctx(d), p, p.dtype == torch.float64, p.shape[1], n, voxel_size, out, C.byref(cnt),
@@ -25,11 +28,14 @@ def voxel_down_sample(points, voxel_size):
 def voxel_down_sample_batch(points, raw_offsets, voxel_size):
     """voxel_down_sample for a batch of clouds in one set of launches (hash grid; each scan's voxels in order of first occurrence).
     points: device tensor [N, s>=3] float32/float64, raw_offsets: host int64 [B+1] starting at 0.
-    Returns (centroids float64 device [M,3], offsets int64 device [B+1])."""
+    Returns (centroids float64 device [M,3], offsets int64 device [B+1]).  A batch without a single point gives an empty [0,3] result and
+    all-zero offsets without a launch; the C ABI itself refuses a total of 0."""
     assert points.dtype in (torch.float32, torch.float64)
     d = _lib.device_of(points)
     p = points.contiguous()
     h_off = np.ascontiguousarray(raw_offsets, dtype=np.int64)
+    if h_off[-1] == 0:
+        return torch.empty((0, 3), dtype=torch.float64, device=p.device), torch.zeros(h_off.size, dtype=torch.int64, device=p.device)
     d_off = torch.from_numpy(h_off).to(p.device)
     B = h_off.size - 1
     out = torch.empty((int(h_off[-1]), 3), dtype=torch.float64, device=p.device)
@@ -42,11 +48,14 @@ def voxel_down_sample_batch(points, raw_offsets, voxel_size):
 def approx_voxel_grid(points, leaf_size):
     """pcl::ApproximateVoxelGrid as pygicp.downsample(points, leaf) applies it (main_RING.py:84-85; row G1): points device
     tensor [n, s>=3] float32/float64 -> float64 device tensor [m,3] (float-precision centroids in the filter's flush
-    order, bit-identical to the sequential filter)."""
+    order, bit-identical to the sequential filter).  An empty cloud gives an empty [0,3] result without a launch; the C ABI
+    itself refuses n <= 0."""
     assert points.dtype in (torch.float32, torch.float64)
     d = _lib.device_of(points)
     p = points.contiguous()
     n = p.shape[0]
+    if n == 0:
+        return torch.empty((0, 3), dtype=torch.float64, device=p.device)
     out = torch.empty((n, 3), dtype=torch.float64, device=p.device)
     cnt = C.c_int32(0)
     _lib.load().mrs_voxel_downsample_approx(_lib.ctx(d), p, p.dtype == torch.float64, p.shape[1], n, leaf_size, out, C.byref(cnt),
@@ -57,11 +66,15 @@ def approx_voxel_grid(points, leaf_size):
 def load_pc_infer_batch(points, raw_offsets):
     """util.py:91-112 for a batch: points device tensor [N, s>=3] (float32/float64) of raw clouds,
     raw_offsets host int64 [B+1].  Returns (xyz_soa float32 device [3*N] (upper bound, ragged SoA),
-    offsets int64 device [B+1]) ready for bev.cart_bev / polar_bev."""
+    offsets int64 device [B+1]) ready for bev.cart_bev / polar_bev.  A batch without a single point (an empty tensor has no data
+    pointer to hand to the C ABI) gives all-zero offsets without a launch; xyz_soa keeps its minimum length of 3, zeroed, so that
+    what consumes it still gets a buffer."""
     assert points.dtype in (torch.float32, torch.float64)
     d = _lib.device_of(points)
     p = points.contiguous()
     h_off = np.ascontiguousarray(raw_offsets, dtype=np.int64)
+    if h_off[-1] == 0:
+        return torch.zeros(3, dtype=torch.float32, device=p.device), torch.zeros(h_off.size, dtype=torch.int64, device=p.device)
     d_off = torch.from_numpy(h_off).to(p.device)
     B = h_off.size - 1
     out = torch.empty(3 * max(1, int(h_off[-1])), dtype=torch.float32, device=p.device)
