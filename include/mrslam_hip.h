@@ -1171,6 +1171,55 @@ int mrs_gem_compose_robots(mrs_ctx* ctx, mrs_gem* const* stores, int32_t n_robot
 int mrs_gem_costmap(mrs_ctx* ctx, const void* h_cloud, const void* d_cloud, int64_t n, double origin_x, double origin_y, int32_t size_x, int32_t size_y,
                     double resolution, int32_t thresh_type, double thresh, uint8_t* h_grid, uint8_t* d_grid);
 
+/* ------------------------------------------------------------------------------------
+ * FPFH: all neighbours within a radius as CSR rows, SPFH of every point, FPFH of
+ * keypoints (RING_ros/FPFH.py:33-105) and ISS keypoints.  Everywhere: d_points float [N][stride_floats], xyz first, the clouds of a
+ * ragged batch packed one after the other; d_offsets / h_offsets int64 [batch + 1], device and host copies of the same offsets,
+ * offsets[0] = 0 and N = offsets[batch] < 2^31 - 1; batch in 1 .. 65535.  Rows are CSR in the caller's point order: d_row_start int64
+ * [N + 1], d_index int32 [total] of CLOUD-LOCAL indices.  Every kernel that reads rows skips an entry outside its cloud and clamps the
+ * row bounds to [0, total]: rows from anywhere cannot make it read out of bounds.
+ * ---------------------------------------------------------------------------------- */
+#define MRS_FPFH_MAX_BINS 32
+
+/* Step 1 of the radius search: d_row_start [N + 1] and *h_total = row_start[N].  Row i holds every j != i of the same cloud with
+ * ((dx dx + dy dy) + dz dz) <= radius radius, all in fp64 on the float32 coordinates widened (exact differences); coincident points
+ * are members, a point with a NaN coordinate is nobody's neighbour.  radius > 0 and finite.  MRS_ERR_UNSUPPORTED when the total
+ * exceeds 2^31 - 1.  Blocking (one host synchronisation for the total). */
+int mrs_radius_count(mrs_ctx* ctx, const float* d_points, int32_t stride_floats, const int64_t* d_offsets, const int64_t* h_offsets,
+                     int32_t batch, double radius, int64_t* d_row_start, int64_t* h_total, mrs_stream stream);
+/* Step 2: d_index [total], every row ascending, for the d_row_start of step 1 with the same points, offsets and radius.  Enqueued. */
+int mrs_radius_fill(mrs_ctx* ctx, const float* d_points, int32_t stride_floats, const int64_t* d_offsets, const int64_t* h_offsets,
+                    int32_t batch, double radius, const int64_t* d_row_start, int64_t total, int32_t* d_index, mrs_stream stream);
+
+/* SPFH of every point: d_normals float [N][3]; bins in 1 .. MRS_FPFH_MAX_BINS; d_counts int32 [N][3 bins] (optional), d_spfh double
+ * [N][3 bins]: the alpha, phi and theta histograms over [-1, 1], [-1, 1], [-pi, pi] (np.histogram's rule), each divided by its own sum
+ * (zeros when that is 0).  Entry i of row i and a neighbour at distance 0 are skipped.  Enqueued. */
+int mrs_fpfh_spfh(mrs_ctx* ctx, const float* d_points, int32_t stride_floats, const float* d_normals, const int64_t* d_offsets,
+                  int32_t batch, int64_t n, const int64_t* d_row_start, const int32_t* d_index, int64_t total, int32_t bins,
+                  int32_t* d_counts, double* d_spfh, mrs_stream stream);
+/* The same on rows the caller made (sklearn's lists: the point itself may be in its row, order is free).  Blocking: an entry outside
+ * its cloud or row bounds outside [0, total] are MRS_ERR_ARG (the outputs are then computed without those entries). */
+int mrs_fpfh_spfh_from_neighbors(mrs_ctx* ctx, const float* d_points, int32_t stride_floats, const float* d_normals,
+                                 const int64_t* d_offsets, int32_t batch, int64_t n, const int64_t* d_row_start, const int32_t* d_index,
+                                 int64_t total, int32_t bins, int32_t* d_counts, double* d_spfh, mrs_stream stream);
+/* FPFH of K keypoints (d_keypoints int64 [K], packed point indices; NULL: K = n, every point): d_fpfh double [K][3 bins] =
+ * f / |f|, f = spfh_i + (1 / k) sum_j spfh_j / |p_j - p_i| over the k kept entries of row i IN ROW ORDER (ascending for rows of
+ * mrs_radius_fill); zeros when k = 0 or |f| = 0 or the keypoint index is outside [0, n).  Enqueued. */
+int mrs_fpfh_describe(mrs_ctx* ctx, const float* d_points, int32_t stride_floats, const int64_t* d_offsets, int32_t batch, int64_t n,
+                      const int64_t* d_row_start, const int32_t* d_index, int64_t total, int32_t bins, const double* d_spfh,
+                      const int64_t* d_keypoints, int64_t n_keypoints, double* d_fpfh, mrs_stream stream);
+
+/* ISS saliency of every point from its rows at the salient radius plus the point itself: 0 with fewer than min_neighbors members,
+ * else the smallest eigenvalue l3 of the members' fp64 covariance (about their mean, divided by their number) when
+ * l2 < gamma21 l1 and l3 < gamma32 l2, else 0.  d_saliency double [N].  Enqueued. */
+int mrs_iss_saliency(mrs_ctx* ctx, const float* d_points, int32_t stride_floats, const int64_t* d_offsets, int32_t batch, int64_t n,
+                     const int64_t* d_row_start, const int32_t* d_index, int64_t total, int32_t min_neighbors, double gamma21,
+                     double gamma32, double* d_saliency, mrs_stream stream);
+/* d_keep uint8 [N] = 1 iff saliency_i > 0 and, for every j of row i (rows at the non-maximum radius), saliency_i > saliency_j, or
+ * they are equal and i < j.  Enqueued. */
+int mrs_iss_nonmax(mrs_ctx* ctx, const int64_t* d_offsets, int32_t batch, int64_t n, const int64_t* d_row_start, const int32_t* d_index,
+                   int64_t total, const double* d_saliency, uint8_t* d_keep, mrs_stream stream);
+
 #ifdef __cplusplus
 }
 #endif
