@@ -33,7 +33,14 @@ const char* dev_env(const char* name);
         }                                                                                   \
     } while (0)
 
-#define MRS_REQUIRE(cond, msg)                                     \
+// a step that returns a status of its own (and has set the error text): anything but MRS_OK ends the calling function with it
+#define MRS_TRY(expr)                         \
+    do {                                      \
+        const int st__ = (expr);              \
+        if (st__ != MRS_OK) return st__;      \
+    } while (0)
+
+#define MRS_REQUIRE(cond, msg)                                  \
     do {                                                           \
         if (!(cond)) {                                             \
             ::mrs::set_error("bad argument: %s (%s)", msg, #cond); \
@@ -116,6 +123,103 @@ public:
 private:
     T* p_ = nullptr;
     size_t cap_ = 0;
+};
+
+// The hipHostMalloc twin of DeviceBuffer: owner of one pinned host allocation of T (move-only; freed by the destructor).
+template <class T>
+class PinnedBuffer {
+public:
+    PinnedBuffer() = default;
+    PinnedBuffer(const PinnedBuffer&) = delete;
+    PinnedBuffer& operator=(const PinnedBuffer&) = delete;
+    PinnedBuffer(PinnedBuffer&& o) noexcept : p_(o.p_), cap_(o.cap_) { o.p_ = nullptr; o.cap_ = 0; }
+    PinnedBuffer& operator=(PinnedBuffer&& o) noexcept
+    {
+        if (this != &o) { reset(); p_ = o.p_; cap_ = o.cap_; o.p_ = nullptr; o.cap_ = 0; }
+        return *this;
+    }
+    ~PinnedBuffer() { reset(); }
+    void reset()
+    {
+        if (p_) (void)hipHostFree(p_);
+        p_ = nullptr; cap_ = 0;
+    }
+    // Grow-only, as DeviceBuffer::reserve: contents are not carried over, and nothing queued may still use the old block.
+    int reserve(size_t need, size_t cap)
+    {
+        if (need <= cap_) return MRS_OK;
+        reset();
+        const hipError_t e = hipHostMalloc(&p_, cap * sizeof(T), hipHostMallocDefault);
+        if (e != hipSuccess) {
+            p_ = nullptr;
+            set_error("pinned allocation of %zu bytes failed: %s", cap * sizeof(T), hipGetErrorString(e));
+            return MRS_ERR_HIP;
+        }
+        cap_ = cap;
+        return MRS_OK;
+    }
+    T* get() const { return p_; }
+    size_t capacity() const { return cap_; }      // elements
+    explicit operator bool() const { return p_ != nullptr; }
+
+private:
+    T* p_ = nullptr;
+    size_t cap_ = 0;
+};
+
+// Owner of one event without timing (created by create(), destroyed by the destructor; neither copied nor moved).
+struct Event {
+    hipEvent_t e = nullptr;
+    Event() = default;
+    Event(const Event&) = delete;
+    Event& operator=(const Event&) = delete;
+    ~Event() { if (e) (void)hipEventDestroy(e); }
+    int create()
+    {
+        MRS_HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        return MRS_OK;
+    }
+    operator hipEvent_t() const { return e; }
+};
+
+// The non-blocking stream all work of one handle runs on, with the event pair that orders it against a caller's stream.  Stands in for its
+// hipStream_t wherever one is expected.  Declare it FIRST in a handle: it is then destroyed last, after the buffers whose work it carried.
+// The destructor waits for the stream, has the scratch cache forget it (scratch_forget_stream above: the rule of every stream-owning handle,
+// written here once) and only then destroys it; the handle's device must be current.
+struct HandleStream {
+    hipStream_t s = nullptr;
+    Event ev_in, ev_out;
+    HandleStream() = default;
+    HandleStream(const HandleStream&) = delete;
+    HandleStream& operator=(const HandleStream&) = delete;
+    ~HandleStream()
+    {
+        if (!s) return;
+        (void)hipStreamSynchronize(s);
+        scratch_forget_stream(s);
+        (void)hipStreamDestroy(s);
+    }
+    int create()
+    {
+        MRS_HIP_TRY(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+        MRS_TRY(ev_in.create());
+        return ev_out.create();
+    }
+    // what `user` has queued so far (a device argument being produced, an output buffer still in use) comes before the handle's later work
+    int join_in(hipStream_t user)
+    {
+        MRS_HIP_TRY(hipEventRecord(ev_in, user));
+        MRS_HIP_TRY(hipStreamWaitEvent(s, ev_in, 0));
+        return MRS_OK;
+    }
+    // the reverse: `user`'s later work comes after what the handle's stream has queued so far
+    int release_to(hipStream_t user)
+    {
+        MRS_HIP_TRY(hipEventRecord(ev_out, s));
+        MRS_HIP_TRY(hipStreamWaitEvent(user, ev_out, 0));
+        return MRS_OK;
+    }
+    operator hipStream_t() const { return s; }
 };
 
 // Device lookup table that reproduces the reference's sector() step function exactly

@@ -285,7 +285,7 @@ int ingest_locked(mrs_keyframes* kf, int n_clouds, const void* data, bool on_dev
         mrs::Scratch tables, blob;
         if ((st = tables.alloc(b_tables, s)) != MRS_OK) return st;
         if ((st = stage_reserve(kf, b_tables + (on_device ? 0 : bytes))) != MRS_OK) return st;
-        char* h = static_cast<char*>(kf->h_stage);
+        char* h = kf->h_stage.get();
         memset(h, 0, b_tables);
         CloudInfo* h_info = reinterpret_cast<CloudInfo*>(h);
         for (int c = 0; c < n_clouds; ++c) h_info[c].bounds[0] = h_info[c].bounds[1] = h_info[c].bounds[2] = 0xffffffffu;
@@ -313,8 +313,7 @@ int ingest_locked(mrs_keyframes* kf, int n_clouds, const void* data, bool on_dev
         const float* raw = static_cast<const float*>(data);
         mark(0);
         if (on_device) {
-            MRS_HIP_TRY(hipEventRecord(kf->ev_in, user));
-            MRS_HIP_TRY(hipStreamWaitEvent(s, kf->ev_in, 0));
+            MRS_TRY(kf->s.join_in(user));
         } else {
             if ((st = blob.alloc(bytes, s)) != MRS_OK) return st;
             memcpy(h + b_tables, data, bytes);
@@ -481,11 +480,9 @@ int mrs_keyframes_get_points(mrs_keyframes* kf, int32_t id, float* out, int32_t 
     if (n > 0) {
         const size_t bytes = (size_t)n * sizeof(float4);
         if (on_device) {          // `out` may still be in use on the caller's stream, which then waits for the copy
-            MRS_HIP_TRY(hipEventRecord(kf->ev_in, (hipStream_t)stream));
-            MRS_HIP_TRY(hipStreamWaitEvent(kf->s, kf->ev_in, 0));
+            MRS_TRY(kf->s.join_in((hipStream_t)stream));
             MRS_HIP_TRY(hipMemcpyAsync(out, kf->arena.get() + first, bytes, hipMemcpyDeviceToDevice, kf->s));
-            MRS_HIP_TRY(hipEventRecord(kf->ev_out, kf->s));
-            MRS_HIP_TRY(hipStreamWaitEvent((hipStream_t)stream, kf->ev_out, 0));
+            MRS_TRY(kf->s.release_to((hipStream_t)stream));
         } else {
             MRS_HIP_TRY(hipMemcpyAsync(out, kf->arena.get() + first, bytes, hipMemcpyDeviceToHost, kf->s));
             MRS_HIP_TRY(hipStreamSynchronize(kf->s));

@@ -15,12 +15,50 @@
 // M2DP (MRS_LOOPDB_M2DP) keeps the 192-d descriptors of m2dp.hip as float32 rows; a query is mrs_signature_knn over them.
 // Fast Histogram (MRS_LOOPDB_FH) keeps the range histograms of fasthist.hip as fp64 rows of `bins` doubles; a query is one sweep that evaluates
 // getEMD (pr_methods/FastHistogram.py:66-72) against every entry with the reference's order of additions, then the k smallest on the host.
+//
+// The handle (struct mrs_loopdb) owns everything through members that free themselves: its stream and the ev_in / ev_out pair
+// (mrs::HandleStream, declared first and so destroyed last), every device array (mrs::DeviceBuffer<T>), every pinned array
+// (mrs::PinnedBuffer<T>), the stage slots (pinned block + event).  Destroying a handle is `delete`; a create that fails half way deletes what
+// it has.  Growing (reserve_locked) allocates the new arrays as locals, copies, synchronises and only then moves them into the handle.
+// What a kind keeps per entry and takes as an argument is one table: layout_of() below.  The small result of a top-k query is one struct
+// per kind (ScTopK, M2dpTopK, DiscoBest); the distance rows of an all-entries query are bytes read through dist_angle() / dist_f64().
+//
+// Arguments.  A call's descriptor is on the host or on the device (`form` / `on_device`); `stream` is the caller's stream for a device one.
+//   in   arg_in():  device -> HandleStream::join_in(stream), the handle's stream then reads the caller's pointer;
+//                   host   -> upload(): the next of four pinned slots (waiting for the slot's previous copy), ONE copy to d_in or to the
+//                             place the call names, the slot's event recorded.
+//   out  arg_out(): device -> HandleStream::release_to(stream): the caller's stream passes once the handle's has read the argument; host -> nothing.
+// Per call, in stream order (H = host argument, D = device argument; "sync" = hipStreamSynchronize of the handle's stream):
+//   call                 H                                               D
+//   append  RING         upload -> d_query; tile                         join; copy -> d_query; tile; release
+//   append  RING++       upload -> d_in; normalise; spectrum; tile       join; normalise; spectrum; tile; release
+//   append  half spectra -                                               join; tile from the caller's pointer; release
+//   query   RING family  as append up to d_query; sweep; copy rows; sync the same, no release (the sync covers it)
+//   query_multi          per descriptor as append into scratch; sweep;   join; ONE copy of all spectra (or per descriptor as append);
+//                        2 x copy 2D; sync                               sweep; 2 x copy 2D; release; sync
+//   append_disco         upload -> signature slot; upload -> spectrum    join (once, for both); copy; copy; release
+//                        slot (two pinned slots, two copies)
+//   query_disco          upload of signature | spectrum -> d_in (ONE     join (once); nearest; phase (writes the pinned result); sync
+//                        slot, ONE copy); nearest; phase; sync
+//   append_sc            upload -> d_in; pack                            join; pack; release
+//   query_sc             upload -> d_in; pack; nearest; align;           join; pack; nearest; align; release; copy result; sync
+//                        copy result; sync
+//   query_sc_all         upload -> d_in; pack; align; copy rows; sync    join; pack; align; release; copy rows; sync
+//   append_m2dp          upload -> d_in; to float32 in the slot          join; to float32; release
+//   query_m2dp           upload -> d_in; to float32; knn; copy result;   join; to float32; release; knn; copy result; sync
+//                        sync
+//   append_fh            upload -> the entry's slot                      join; copy -> the slot; release
+//   query_fh             upload -> d_in; distances; copy rows; sync      join; distances; release; copy rows; sync
+//   distances_fh         join (for d_dist); upload -> d_in; distances;   join (for d_dist); join; distances; release
+//                        release
 #include "common.hpp"
 #include "fft_codelets.hpp"
 
 #include <algorithm>
 #include <cmath>
+#include <cstddef>
 #include <cstdlib>
+#include <memory>
 
 namespace {
 
@@ -29,19 +67,70 @@ constexpr size_t kSpecFloats = (size_t)kHalf * kD * 2;       // one [61][120] co
 constexpr size_t kTiledFloats = MRS_RING_TILED_ENTRY_BYTES / 4;
 constexpr int kStageSlots = 4;
 
-// SC top-k query results, one copy to the host: index [kScMaxK] | dist [kScMaxK] | shift [kScMaxK] | squared key distance [kScMaxK] (fp64)
-constexpr int kScDim = 120, kScMaxK = 64, kSmallSc = 5 * kScMaxK;
-
-// M2DP top-k query results, one copy to the host: index [kM2dpMaxK] | squared distance [kM2dpMaxK]
-constexpr int kM2dpDim = 192, kM2dpMaxK = 32, kSmallM2dp = 2 * kM2dpMaxK;
+constexpr int kScDim = 120, kScMaxK = 64;
+constexpr int kM2dpDim = 192, kM2dpMaxK = 32;
 
 // Fast Histogram sweep: a workgroup scores kFhEntries entries, kFhChunk buckets at a time
 constexpr int kFhMaxBins = MRS_FH_MAX_BINS, kFhMaxK = 32, kFhEntries = 64, kFhChunk = 64, kFhThreads = 256;
 
-struct Pinned {
-    void* p = nullptr;
-    hipEvent_t ev = nullptr;
+// The small result of a query, one block per kind: the kernels write its fields on the device and ONE copy brings the block to the host
+// (DiSCO's kernel writes the pinned block itself).
+struct ScTopK { int32_t idx[kScMaxK]; float dist[kScMaxK]; int32_t shift[kScMaxK]; double key_d2[kScMaxK]; };   // key_d2: squared key distance
+struct M2dpTopK { int32_t idx[kM2dpMaxK]; float d2[kM2dpMaxK]; };
+struct DiscoBest { int32_t index; float dist2; int32_t argmax; int32_t pad; };
+static_assert(sizeof(ScTopK) == 5 * kScMaxK * 4 && offsetof(ScTopK, key_d2) == 3 * kScMaxK * 4, "SC result block layout");
+static_assert(sizeof(M2dpTopK) == 2 * kM2dpMaxK * 4, "M2DP result block layout");
+static_assert(sizeof(DiscoBest) == 16, "DiSCO result block layout");
+
+// What a kind keeps and takes, from (kind, channels of RING++ or bins of FH):
+//   kind    entry (floats to the next)              argument in the reference's form (floats)  sig_dim          stage slot         slack
+//   RING    one DMA-tiled plane                     [120][120] complex64                       -                the argument       1 entry
+//   RING++  C DMA-tiled planes                      [C][120][120] float32                      -                the argument       1 entry
+//   DiSCO   spectrum [40][120] complex64            the spectrum                               1024 signature   signature|spectrum -
+//   SC      packed entry (scancontext.hip)          [120][120] float32                         120 ring key     the argument       -
+//   M2DP    192 float32                             192 doubles                                -                the argument       -
+//   FH      `bins` doubles                          `bins` doubles                             -                the argument       -
+// slack: the tiled sweep reads up to 1 KiB past the last entry, so the tiled kinds keep one zeroed entry behind the capacity.
+struct Layout {
+    size_t entry_floats = 0;      // floats from one entry of d_entries to the next
+    size_t in_floats = 0;         // floats of one argument
+    int sig_dim = 0;              // floats per row of d_sigs (0: the kind keeps none)
+    size_t stage_bytes = 0;       // bytes of one pinned stage slot
+    bool slack = false;
+};
+constexpr int kPR = 40, kPS = 120;      // DiSCO spectrum rows x columns
+Layout layout_of(int kind, int channels_or_bins)
+{
+    const size_t c = (size_t)channels_or_bins;
+    Layout L;
+    switch (kind) {
+    case MRS_LOOPDB_RING: L.entry_floats = kTiledFloats; L.in_floats = (size_t)kA * kD * 2; L.slack = true; break;
+    case MRS_LOOPDB_RINGPP: L.entry_floats = c * kTiledFloats; L.in_floats = c * kA * kD; L.slack = true; break;
+    case MRS_LOOPDB_DISCO: L.entry_floats = L.in_floats = (size_t)kPR * kPS * 2; L.sig_dim = 1024; break;
+    case MRS_LOOPDB_SC: L.entry_floats = mrs::sc_entry_floats(kScDim, kScDim); L.in_floats = (size_t)kScDim * kScDim; L.sig_dim = kScDim; break;
+    case MRS_LOOPDB_M2DP: L.entry_floats = kM2dpDim; L.in_floats = 2 * (size_t)kM2dpDim; break;
+    default: L.entry_floats = L.in_floats = 2 * c; break;      // MRS_LOOPDB_FH
+    }
+    L.stage_bytes = (L.in_floats + (kind == MRS_LOOPDB_DISCO ? (size_t)L.sig_dim : 0)) * sizeof(float);
+    return L;
+}
+
+// A pinned block a host argument passes through, and the event after which it may be overwritten
+struct StageSlot {
+    mrs::PinnedBuffer<char> p;
+    mrs::Event ev;
     bool used = false;
+};
+
+template <class T>
+struct ResultBlock {
+    mrs::DeviceBuffer<T> d;
+    mrs::PinnedBuffer<T> h;
+    int alloc()
+    {
+        MRS_TRY(d.reserve(1, 1));
+        return h.reserve(1, 1);
+    }
 };
 
 // ---- DiSCO query kernels ---------------------------------------------------------------------------------------------
@@ -75,7 +164,7 @@ __global__ __launch_bounds__(256) void k_sig_nearest(const float* __restrict__ q
 // corr = ifft2(a conj(b), ortho), |corr| (+ 1e-15 under the root), fftshift2d, first maximum.  One workgroup, everything in LDS, 40 x 120:
 // rows: 120-point inverse transforms as two in-register 60-point codelets (even / odd samples; 80 lanes) + one radix-2 step;
 // columns: 40-point direct transforms (192 k complex multiply-adds spread over 960 work items, the lane's 40 inputs in registers).
-constexpr int kPR = 40, kPS = 120, kPhaseThreads = 512;
+constexpr int kPhaseThreads = 512;
 __global__ __launch_bounds__(kPhaseThreads) void k_disco_phase_one(const float2* __restrict__ spectra, unsigned long long* __restrict__ best,
                                                                    const float2* __restrict__ cur, const float2* __restrict__ tw,
                                                                    int* __restrict__ out_index, float* __restrict__ out_d2, int* __restrict__ out_arg)
@@ -199,141 +288,152 @@ __global__ __launch_bounds__(kFhThreads) void k_fh_distances(const double* __res
 }  // namespace
 
 struct mrs_loopdb {
+    mrs::HandleStream s;                      // first: destroyed last, after the buffers whose work it carried
     mrs_ctx* ctx = nullptr;
-    int kind = 0, channels = 1;
+    int kind = 0;
+    int channels = 1;                         // RING: 1; RING++: planes per entry
     int bins = 0;                             // FH: buckets per histogram
-    int sig_dim = 0, R = 0, S = 0;            // DiSCO; SC: sig_dim = R = S = 120 (ring keys [cap][120] in d_sigs)
+    Layout L;
     int n = 0, cap = 0;
-    size_t entry_floats = 0;                  // floats from one entry of d_entries to the next
-    size_t in_floats = 0;                     // floats of a descriptor in the reference's form (what append / query take)
-    float* d_entries = nullptr;               // RING / RING++: [cap + 1][C] DMA-tiled planes (one entry of slack); DiSCO: spectra [cap][R][S] complex64
-    float* d_sigs = nullptr;                  // DiSCO: [cap][dim]; SC: ring keys [cap][120]
-    float* d_dist = nullptr;                  // [2 cap]: [n] distances, [n] angles
-    int32_t* d_angle = nullptr;               // = d_dist + n of the query at hand (one allocation, one copy)
-    float* h_dist = nullptr;                  // pinned [2 cap]
-    int32_t* h_angle = nullptr;
-    float* d_in = nullptr;                    // one descriptor in the reference's form (device copy of a host argument)
-    float* d_tmp = nullptr;                   // RING++: the normalised channels
-    float* d_query = nullptr;                 // the query in database form (row layout: [C][61][120] complex64)
-    float* d_tw = nullptr;                    // DiSCO: exp(+2 pi i k / S), k < S, then exp(+2 pi i k / R), k < R
-    unsigned long long* d_best = nullptr;     // DiSCO: packed (distance bits, index)
-    int32_t* d_small = nullptr;               // DiSCO: index, distance bits, argmax; SC: the kSmallSc words of a top-k query
-    int32_t* h_small = nullptr;               // pinned
-    bool phase_attr_set = false;              // DiSCO: the phase kernel's LDS attribute has been set on this handle's device
-    Pinned stage[kStageSlots];
+    mrs::DeviceBuffer<float> d_entries;       // [cap (+ 1 of slack)] entries, L.entry_floats apart (FH: rows of doubles)
+    mrs::DeviceBuffer<float> d_sigs;          // [cap][L.sig_dim]: DiSCO signatures, SC ring keys
+    // Distance rows of an all-entries query, kRowBytes per entry of capacity: [n] float distances | [n] int32 angles or shifts back to back
+    // (wherever n stands: ONE copy brings both to the host), or [n] doubles (FH).  Read through dist_angle() / dist_f64() only.
+    mrs::DeviceBuffer<char> d_rows;
+    mrs::PinnedBuffer<char> h_rows;
+    mrs::DeviceBuffer<float> d_in;            // a host argument on the device (L.stage_bytes)
+    mrs::DeviceBuffer<float> d_tmp;           // RING++: the normalised channels; SC: the query's ring key
+    mrs::DeviceBuffer<float> d_query;         // the query in database form (RING family: row layout [C][61][120] complex64)
+    ResultBlock<ScTopK> sc;
+    ResultBlock<M2dpTopK> m2dp;
+    struct {
+        int R = kPR, S = kPS;
+        mrs::DeviceBuffer<float> d_tw;                  // exp(+2 pi i k / S), k < S, then exp(+2 pi i k / R), k < R
+        mrs::DeviceBuffer<unsigned long long> d_best;   // packed (distance bits, index)
+        mrs::PinnedBuffer<DiscoBest> h_result;          // written by k_disco_phase_one
+        bool phase_attr_set = false;                    // the phase kernel's LDS attribute has been set on this handle's device
+    } disco;
+    StageSlot stage[kStageSlots];
     int stage_next = 0;
-    size_t stage_bytes = 0;
-    hipStream_t s = nullptr;
-    hipEvent_t ev_in = nullptr, ev_out = nullptr;
     std::mutex mu;
+
+    ~mrs_loopdb() { if (s) (void)hipStreamSynchronize(s); }      // nothing queued outlives the buffers
 };
 
 namespace {
 
-void free_arrays(mrs_loopdb* db)
+constexpr size_t kRowBytes = sizeof(float) + sizeof(int32_t);
+static_assert(kRowBytes == sizeof(double), "a distance row holds (float, int32) pairs or doubles");
+struct DistAngle { float* dist; int32_t* angle; };
+DistAngle dist_angle(char* rows, int n)
 {
-    if (db->d_entries) (void)hipFree(db->d_entries);
-    if (db->d_sigs) (void)hipFree(db->d_sigs);
-    if (db->d_dist) (void)hipFree(db->d_dist);
-    if (db->h_dist) (void)hipHostFree(db->h_dist);
-    db->d_entries = db->d_sigs = db->d_dist = nullptr;
-    db->d_angle = nullptr; db->h_dist = nullptr; db->h_angle = nullptr;
+    float* d = reinterpret_cast<float*>(rows);
+    return {d, reinterpret_cast<int32_t*>(d + n)};
+}
+double* dist_f64(char* rows) { return reinterpret_cast<double*>(rows); }
+
+// The one place that tells a call it has the wrong kind of database
+enum Want { kWantRingAppend, kWantRingQuery, kWantDisco, kWantSc, kWantM2dp, kWantFh };
+int require_kind(const mrs_loopdb* db, Want w)
+{
+    static const struct { int kind; const char *msg, *cond; } rule[] = {
+        {MRS_LOOPDB_RING, "not a RING / RING++ database (DiSCO: mrs_loopdb_append_disco, SC: mrs_loopdb_append_sc, M2DP: mrs_loopdb_append_m2dp, FH: mrs_loopdb_append_fh)",
+         "db->kind == MRS_LOOPDB_RING || db->kind == MRS_LOOPDB_RINGPP"},
+        {MRS_LOOPDB_RING, "not a RING / RING++ database (DiSCO: mrs_loopdb_query_disco, SC: mrs_loopdb_query_sc, M2DP: mrs_loopdb_query_m2dp, FH: mrs_loopdb_query_fh)",
+         "db->kind == MRS_LOOPDB_RING || db->kind == MRS_LOOPDB_RINGPP"},
+        {MRS_LOOPDB_DISCO, "not a DiSCO database", "db->kind == MRS_LOOPDB_DISCO"},
+        {MRS_LOOPDB_SC, "not a Scan Context database (FH: mrs_loopdb_append_fh / mrs_loopdb_query_fh)", "db->kind == MRS_LOOPDB_SC"},
+        {MRS_LOOPDB_M2DP, "not an M2DP database (FH: mrs_loopdb_append_fh / mrs_loopdb_query_fh)", "db->kind == MRS_LOOPDB_M2DP"},
+        {MRS_LOOPDB_FH, "not a Fast Histogram database", "db->kind == MRS_LOOPDB_FH"},
+    };
+    if (db->kind == rule[w].kind || (rule[w].kind == MRS_LOOPDB_RING && db->kind == MRS_LOOPDB_RINGPP)) return MRS_OK;
+    mrs::set_error("bad argument: %s (%s)", rule[w].msg, rule[w].cond);
+    return MRS_ERR_ARG;
 }
 
-// capacity >= want (doubling): new arrays, device-to-device copy of what is there, old ones freed after the copy; lock held
+// Capacity >= want (doubling), lock held: new buffers as locals, what is there copied on the handle's stream, one synchronisation, then the
+// handle takes them.  Nothing of the handle is touched before every allocation and copy has succeeded, and a failure frees the locals on the
+// way out: a retry after an out-of-memory error starts from where the first attempt did.
 int reserve_locked(mrs_loopdb* db, int want)
 {
     if (want <= db->cap) return MRS_OK;
     int cap = std::max(db->cap, 256);
     while (cap < want) cap *= 2;
-    float *ne = nullptr, *ns = nullptr, *nd = nullptr, *hd = nullptr;
-    int32_t *na = nullptr, *ha = nullptr;
-    const size_t slack = (db->kind == MRS_LOOPDB_RING || db->kind == MRS_LOOPDB_RINGPP) ? 1 : 0;   // the tiled sweep reads up to 1 KiB past the last entry
-    // every failure path releases what this call has allocated so far (the out-of-memory case must not get worse on retry)
-    auto grow = [&]() -> hipError_t {
-        hipError_t e = hipMalloc(&ne, ((size_t)cap + slack) * db->entry_floats * sizeof(float));
-        if (e != hipSuccess) return e;
-        if (slack && (e = hipMemsetAsync(ne + (size_t)cap * db->entry_floats, 0, db->entry_floats * sizeof(float), db->s)) != hipSuccess) return e;
-        if (db->sig_dim > 0 && (e = hipMalloc(&ns, (size_t)cap * db->sig_dim * sizeof(float))) != hipSuccess) return e;
-        // distances and angles of a query lie back to back ([n] floats, [n] ints: the angles start at element n, wherever n stands) so that ONE
-        // copy brings both to the host; d_dist / h_dist own the 2 x cap elements, d_angle / h_angle are not separate allocations
-        if ((e = hipMalloc(&nd, (size_t)2 * cap * sizeof(float))) != hipSuccess) return e;
-        if ((e = hipHostMalloc(&hd, (size_t)2 * cap * sizeof(float), hipHostMallocDefault)) != hipSuccess) return e;
-        if (db->n > 0) {
-            if ((e = hipMemcpyAsync(ne, db->d_entries, (size_t)db->n * db->entry_floats * sizeof(float), hipMemcpyDeviceToDevice, db->s)) != hipSuccess) return e;
-            if (ns && (e = hipMemcpyAsync(ns, db->d_sigs, (size_t)db->n * db->sig_dim * sizeof(float), hipMemcpyDeviceToDevice, db->s)) != hipSuccess) return e;
-        }
-        return hipStreamSynchronize(db->s);
-    };
-    const hipError_t e = grow();
-    if (e != hipSuccess) {
-        (void)hipStreamSynchronize(db->s);
-        if (ne) (void)hipFree(ne);
-        if (ns) (void)hipFree(ns);
-        if (nd) (void)hipFree(nd);
-        if (hd) (void)hipHostFree(hd);
-        mrs::set_error("growing a loop database to %d entries failed: %s", cap, hipGetErrorString(e));
-        return MRS_ERR_HIP;
+    const Layout& L = db->L;
+    mrs::DeviceBuffer<float> entries, sigs;
+    mrs::DeviceBuffer<char> d_rows;
+    mrs::PinnedBuffer<char> h_rows;
+    const size_t ne = ((size_t)cap + (L.slack ? 1 : 0)) * L.entry_floats, ns = (size_t)cap * L.sig_dim, nr = (size_t)cap * kRowBytes;
+    MRS_TRY(entries.reserve(ne, ne));
+    if (L.slack) MRS_HIP_TRY(hipMemsetAsync(entries.get() + (size_t)cap * L.entry_floats, 0, L.entry_floats * sizeof(float), db->s));
+    if (ns > 0) MRS_TRY(sigs.reserve(ns, ns));
+    MRS_TRY(d_rows.reserve(nr, nr));
+    MRS_TRY(h_rows.reserve(nr, nr));
+    if (db->n > 0) {
+        MRS_HIP_TRY(hipMemcpyAsync(entries.get(), db->d_entries.get(), (size_t)db->n * L.entry_floats * sizeof(float), hipMemcpyDeviceToDevice, db->s));
+        if (ns > 0) MRS_HIP_TRY(hipMemcpyAsync(sigs.get(), db->d_sigs.get(), (size_t)db->n * L.sig_dim * sizeof(float), hipMemcpyDeviceToDevice, db->s));
     }
-    free_arrays(db);
-    db->d_entries = ne; db->d_sigs = ns; db->d_dist = nd; db->d_angle = na; db->h_dist = hd; db->h_angle = ha;
+    MRS_HIP_TRY(hipStreamSynchronize(db->s));
+    db->d_entries = std::move(entries); db->d_sigs = std::move(sigs); db->d_rows = std::move(d_rows); db->h_rows = std::move(h_rows);
     db->cap = cap;
     return MRS_OK;
 }
 
-// the caller's stream has produced a device argument: the handle's stream waits for it
-int join_in(mrs_loopdb* db, hipStream_t user)
+// ---- Arguments in and out ------------------------------------------------------------------------------------------------------------
+// Host parts -> device buffer `dst` through ONE pinned slot and ONE copy (the caller's memory is free again when this returns).  Two parts
+// land back to back: DiSCO's signature | spectrum.
+struct Part { const void* p; size_t bytes; };
+int upload(mrs_loopdb* db, void* dst, Part a, Part b = {nullptr, 0})
 {
-    MRS_HIP_TRY(hipEventRecord(db->ev_in, user));
-    MRS_HIP_TRY(hipStreamWaitEvent(db->s, db->ev_in, 0));
+    StageSlot& slot = db->stage[db->stage_next];
+    db->stage_next = (db->stage_next + 1) % kStageSlots;
+    if (slot.used) MRS_HIP_TRY(hipEventSynchronize(slot.ev));
+    memcpy(slot.p.get(), a.p, a.bytes);
+    if (b.bytes) memcpy(slot.p.get() + a.bytes, b.p, b.bytes);
+    MRS_HIP_TRY(hipMemcpyAsync(dst, slot.p.get(), a.bytes + b.bytes, hipMemcpyHostToDevice, db->s));
+    MRS_HIP_TRY(hipEventRecord(slot.ev, db->s));
+    slot.used = true;
     return MRS_OK;
 }
 
-// host argument -> device buffer `dst` through a pinned slot (the caller's memory is free again when this returns)
-int upload(mrs_loopdb* db, const void* h_src, size_t bytes, void* dst)
+// Argument in: *src is where the handle's stream may read the `bytes` of `arg`.  A device argument is the caller's own pointer once the
+// handle's stream has joined `user`; a host argument is staged into `host_dst` (d_in unless a call has a better place) and read from there.
+int arg_in(mrs_loopdb* db, const void* arg, size_t bytes, bool on_device, mrs_stream user, const void** src, void* host_dst = nullptr)
 {
-    Pinned& p = db->stage[db->stage_next];
-    db->stage_next = (db->stage_next + 1) % kStageSlots;
-    if (p.used) MRS_HIP_TRY(hipEventSynchronize(p.ev));
-    memcpy(p.p, h_src, bytes);
-    MRS_HIP_TRY(hipMemcpyAsync(dst, p.p, bytes, hipMemcpyHostToDevice, db->s));
-    MRS_HIP_TRY(hipEventRecord(p.ev, db->s));
-    p.used = true;
-    return MRS_OK;
+    if (on_device) {
+        *src = arg;
+        return db->s.join_in((hipStream_t)user);
+    }
+    if (!host_dst) host_dst = db->d_in.get();
+    *src = host_dst;
+    return upload(db, host_dst, {arg, bytes});
+}
+
+// Argument out: the caller may overwrite its device argument (or read a device result) once ITS stream has passed this point
+int arg_out(mrs_loopdb* db, bool on_device, mrs_stream user)
+{
+    return on_device ? db->s.release_to((hipStream_t)user) : MRS_OK;
 }
 
 // a RING / RING++ descriptor in the given form -> row-layout half spectra [C][61][120] at `d_spec` (device), on the handle's stream
-int to_half_spectrum(mrs_loopdb* db, const void* desc, int form, float* d_spec, hipStream_t user)
+int to_half_spectrum(mrs_loopdb* db, const void* desc, int form, float* d_spec, mrs_stream user)
 {
     const int C = db->channels;
-    if (form == MRS_LOOPDB_FORM_DEVICE_SPEC) {
-        int st = join_in(db, user);
-        if (st != MRS_OK) return st;
-        MRS_HIP_TRY(hipMemcpyAsync(d_spec, desc, (size_t)C * kSpecFloats * sizeof(float), hipMemcpyDeviceToDevice, db->s));
-        return MRS_OK;
-    }
-    if (db->kind == MRS_LOOPDB_RING) {
-        // the reference's TIRING [1][120][120] complex64 (util.py:198): its first 61 angle-frequency rows ARE the half spectrum
-        if (form == MRS_LOOPDB_FORM_HOST) return upload(db, desc, kSpecFloats * sizeof(float), d_spec);
-        int st = join_in(db, user);
-        if (st != MRS_OK) return st;
-        MRS_HIP_TRY(hipMemcpyAsync(d_spec, desc, kSpecFloats * sizeof(float), hipMemcpyDeviceToDevice, db->s));
+    const bool on_device = form != MRS_LOOPDB_FORM_HOST;
+    const void* src = nullptr;
+    if (form == MRS_LOOPDB_FORM_DEVICE_SPEC || db->kind == MRS_LOOPDB_RING) {
+        // half spectra already, or the reference's TIRING [1][120][120] complex64 (util.py:198) whose first 61 angle-frequency rows ARE the half
+        // spectrum (C = 1): a host argument is staged straight into place, a device one copied there
+        const size_t bytes = (size_t)C * kSpecFloats * sizeof(float);
+        MRS_TRY(arg_in(db, desc, bytes, on_device, user, &src, d_spec));
+        if (on_device) MRS_HIP_TRY(hipMemcpyAsync(d_spec, src, bytes, hipMemcpyDeviceToDevice, db->s));
         return MRS_OK;
     }
     // RING++: the reference's TIRING [C][120][120] float32 magnitudes; fast_corr_RINGplusplus normalises jointly and transforms along the
     // angle axis at every comparison (util.py:339-343) -- done once here
-    const float* src = static_cast<const float*>(desc);
-    if (form == MRS_LOOPDB_FORM_HOST) {
-        int st = upload(db, desc, db->in_floats * sizeof(float), db->d_in);
-        if (st != MRS_OK) return st;
-        src = db->d_in;
-    } else {
-        int st = join_in(db, user);
-        if (st != MRS_OK) return st;
-    }
-    int st = mrs_normalize_groups(db->ctx, src, db->d_tmp, 1, C * kA * kD, db->s);
-    if (st != MRS_OK) return st;
-    return mrs_ring_half_spectrum(db->ctx, db->d_tmp, C, kA, kD, d_spec, db->s);
+    MRS_TRY(arg_in(db, desc, db->L.in_floats * sizeof(float), on_device, user, &src));
+    MRS_TRY(mrs_normalize_groups(db->ctx, static_cast<const float*>(src), db->d_tmp.get(), 1, C * kA * kD, db->s));
+    return mrs_ring_half_spectrum(db->ctx, db->d_tmp.get(), C, kA, kD, d_spec, db->s);
 }
 
 }  // namespace
@@ -352,53 +452,33 @@ int mrs_loopdb_create(mrs_ctx* ctx, int32_t kind, int32_t channels, int32_t capa
     MRS_REQUIRE(kind != MRS_LOOPDB_RING || channels == 1, "RING descriptors have one channel");
     MRS_REQUIRE(channels >= 1 && channels <= 16, "channels out of range");
     MRS_HIP_TRY(hipSetDevice(ctx->device));
-    mrs_loopdb* db = new mrs_loopdb();
+    std::unique_ptr<mrs_loopdb> db(new mrs_loopdb());      // an early return deletes it: every member frees itself
     db->ctx = ctx; db->kind = kind; db->channels = channels; db->bins = bins;
-    if (kind == MRS_LOOPDB_RING) { db->entry_floats = kTiledFloats; db->in_floats = (size_t)kA * kD * 2; }
-    else if (kind == MRS_LOOPDB_RINGPP) { db->entry_floats = (size_t)channels * kTiledFloats; db->in_floats = (size_t)channels * kA * kD; }
-    else if (kind == MRS_LOOPDB_DISCO) { db->sig_dim = 1024; db->R = kPR; db->S = kPS; db->entry_floats = (size_t)db->R * db->S * 2; db->in_floats = db->entry_floats; }
-    else if (kind == MRS_LOOPDB_M2DP) { db->entry_floats = kM2dpDim; db->in_floats = 2 * (size_t)kM2dpDim; }      // arguments are 192 doubles
-    else if (kind == MRS_LOOPDB_FH) { db->entry_floats = 2 * (size_t)bins; db->in_floats = 2 * (size_t)bins; }    // rows and arguments are `bins` doubles
-    else { db->sig_dim = db->R = db->S = kScDim; db->entry_floats = mrs::sc_entry_floats(kScDim, kScDim); db->in_floats = (size_t)kScDim * kScDim; }
-    auto fail = [&](int st) { mrs_loopdb_destroy(db); return st; };
-#define LDB_TRY(expr) do { if ((expr) != hipSuccess) { mrs::set_error("%s failed (%s:%d)", #expr, __FILE__, __LINE__); return fail(MRS_ERR_HIP); } } while (0)
-    LDB_TRY(hipStreamCreateWithFlags(&db->s, hipStreamNonBlocking));
-    LDB_TRY(hipEventCreateWithFlags(&db->ev_in, hipEventDisableTiming));
-    LDB_TRY(hipEventCreateWithFlags(&db->ev_out, hipEventDisableTiming));
-    db->stage_bytes = (kind == MRS_LOOPDB_DISCO ? db->in_floats + (size_t)db->sig_dim : db->in_floats) * sizeof(float);      // DiSCO: signature | spectrum in one slot
-    for (Pinned& p : db->stage) {
-        LDB_TRY(hipHostMalloc(&p.p, db->stage_bytes, hipHostMallocDefault));
-        LDB_TRY(hipEventCreateWithFlags(&p.ev, hipEventDisableTiming));
+    const Layout& L = db->L = layout_of(kind, kind == MRS_LOOPDB_FH ? bins : channels);
+    MRS_TRY(db->s.create());
+    for (StageSlot& p : db->stage) {
+        MRS_TRY(p.p.reserve(L.stage_bytes, L.stage_bytes));
+        MRS_TRY(p.ev.create());
     }
-    LDB_TRY(hipMalloc(&db->d_in, (db->in_floats + (size_t)db->sig_dim) * sizeof(float)));
-    LDB_TRY(hipMalloc(&db->d_tmp, db->in_floats * sizeof(float)));
-    LDB_TRY(hipMalloc(&db->d_query, std::max((size_t)channels * kSpecFloats, db->entry_floats) * sizeof(float)));
+    const size_t n_in = L.stage_bytes / sizeof(float), n_query = std::max((size_t)channels * kSpecFloats, L.entry_floats);
+    MRS_TRY(db->d_in.reserve(n_in, n_in));
+    MRS_TRY(db->d_tmp.reserve(L.in_floats, L.in_floats));
+    MRS_TRY(db->d_query.reserve(n_query, n_query));
     if (kind == MRS_LOOPDB_DISCO) {
-        std::vector<float> tw(2 * (size_t)(db->S + db->R));
-        for (int k = 0; k < db->S; ++k) { tw[2 * k] = (float)cos(2.0 * M_PI * k / db->S); tw[2 * k + 1] = (float)sin(2.0 * M_PI * k / db->S); }
-        for (int k = 0; k < db->R; ++k) { tw[2 * (db->S + k)] = (float)cos(2.0 * M_PI * k / db->R); tw[2 * (db->S + k) + 1] = (float)sin(2.0 * M_PI * k / db->R); }
-        LDB_TRY(hipMalloc(&db->d_tw, tw.size() * sizeof(float)));
-        LDB_TRY(hipMemcpy(db->d_tw, tw.data(), tw.size() * sizeof(float), hipMemcpyHostToDevice));
-        LDB_TRY(hipMalloc(&db->d_best, sizeof(unsigned long long)));
-        LDB_TRY(hipMemset(db->d_best, 0xff, sizeof(unsigned long long)));       // armed; k_disco_phase_one re-arms it after every query
-        LDB_TRY(hipMalloc(&db->d_small, 4 * sizeof(int32_t)));
-        LDB_TRY(hipHostMalloc(&db->h_small, 4 * sizeof(int32_t), hipHostMallocDefault));
+        auto& D = db->disco;
+        std::vector<float> tw(2 * (size_t)(D.S + D.R));
+        for (int k = 0; k < D.S; ++k) { tw[2 * k] = (float)cos(2.0 * M_PI * k / D.S); tw[2 * k + 1] = (float)sin(2.0 * M_PI * k / D.S); }
+        for (int k = 0; k < D.R; ++k) { tw[2 * (D.S + k)] = (float)cos(2.0 * M_PI * k / D.R); tw[2 * (D.S + k) + 1] = (float)sin(2.0 * M_PI * k / D.R); }
+        MRS_TRY(D.d_tw.reserve(tw.size(), tw.size()));
+        MRS_HIP_TRY(hipMemcpy(D.d_tw.get(), tw.data(), tw.size() * sizeof(float), hipMemcpyHostToDevice));
+        MRS_TRY(D.d_best.reserve(1, 1));
+        MRS_HIP_TRY(hipMemset(D.d_best.get(), 0xff, sizeof(unsigned long long)));       // armed; k_disco_phase_one re-arms it after every query
+        MRS_TRY(D.h_result.reserve(1, 1));
     }
-    if (kind == MRS_LOOPDB_SC) {
-        LDB_TRY(hipMalloc(&db->d_small, kSmallSc * sizeof(int32_t)));
-        LDB_TRY(hipHostMalloc(&db->h_small, kSmallSc * sizeof(int32_t), hipHostMallocDefault));
-    }
-    if (kind == MRS_LOOPDB_M2DP) {
-        LDB_TRY(hipMalloc(&db->d_small, kSmallM2dp * sizeof(int32_t)));
-        LDB_TRY(hipHostMalloc(&db->h_small, kSmallM2dp * sizeof(int32_t), hipHostMallocDefault));
-    }
-#undef LDB_TRY
-    {
-        std::lock_guard<std::mutex> lk(db->mu);
-        const int st = reserve_locked(db, std::max(capacity_hint, 1));
-        if (st != MRS_OK) return fail(st);
-    }
-    *out = db;
+    if (kind == MRS_LOOPDB_SC) MRS_TRY(db->sc.alloc());
+    if (kind == MRS_LOOPDB_M2DP) MRS_TRY(db->m2dp.alloc());
+    MRS_TRY(reserve_locked(db.get(), std::max(capacity_hint, 1)));      // nobody else holds the handle yet
+    *out = db.release();
     return MRS_OK;
 }
 
@@ -406,25 +486,6 @@ int mrs_loopdb_destroy(mrs_loopdb* db)
 {
     if (!db) return MRS_OK;
     (void)hipSetDevice(db->ctx->device);
-    if (db->s) (void)hipStreamSynchronize(db->s);
-    free_arrays(db);
-    for (Pinned& p : db->stage) {
-        if (p.p) (void)hipHostFree(p.p);
-        if (p.ev) (void)hipEventDestroy(p.ev);
-    }
-    if (db->d_in) (void)hipFree(db->d_in);
-    if (db->d_tmp) (void)hipFree(db->d_tmp);
-    if (db->d_query) (void)hipFree(db->d_query);
-    if (db->d_tw) (void)hipFree(db->d_tw);
-    if (db->d_best) (void)hipFree(db->d_best);
-    if (db->d_small) (void)hipFree(db->d_small);
-    if (db->h_small) (void)hipHostFree(db->h_small);
-    if (db->ev_in) (void)hipEventDestroy(db->ev_in);
-    if (db->ev_out) (void)hipEventDestroy(db->ev_out);
-    if (db->s) {
-        mrs::scratch_forget_stream(db->s);
-        (void)hipStreamDestroy(db->s);
-    }
     delete db;
     return MRS_OK;
 }
@@ -456,29 +517,20 @@ int mrs_loopdb_clear(mrs_loopdb* db)
 int mrs_loopdb_append(mrs_loopdb* db, const void* descriptor, int32_t form, int32_t count, mrs_stream stream)
 {
     MRS_REQUIRE(db && descriptor, "null pointer");
-    MRS_REQUIRE(db->kind == MRS_LOOPDB_RING || db->kind == MRS_LOOPDB_RINGPP, "not a RING / RING++ database (DiSCO: mrs_loopdb_append_disco, SC: mrs_loopdb_append_sc, M2DP: mrs_loopdb_append_m2dp, FH: mrs_loopdb_append_fh)");
+    MRS_TRY(require_kind(db, kWantRingAppend));
     MRS_REQUIRE(form == MRS_LOOPDB_FORM_HOST || form == MRS_LOOPDB_FORM_DEVICE || form == MRS_LOOPDB_FORM_DEVICE_SPEC, "unknown form");
     MRS_REQUIRE(count >= 1 && (count == 1 || form == MRS_LOOPDB_FORM_DEVICE_SPEC), "several entries per call only as device half spectra");
     MRS_HIP_TRY(hipSetDevice(db->ctx->device));
     std::lock_guard<std::mutex> lk(db->mu);
-    int st = reserve_locked(db, db->n + count);
-    if (st != MRS_OK) return st;
+    MRS_TRY(reserve_locked(db, db->n + count));
     const int C = db->channels;
-    const float* spec = db->d_query;
-    if (form == MRS_LOOPDB_FORM_DEVICE_SPEC) {             // already row-layout half spectra on the device: permuted straight into the slots
-        st = join_in(db, (hipStream_t)stream);
-        if (st != MRS_OK) return st;
-        spec = static_cast<const float*>(descriptor);
-    } else {
-        st = to_half_spectrum(db, descriptor, form, db->d_query, (hipStream_t)stream);
-        if (st != MRS_OK) return st;
-    }
-    st = mrs_ring_spec_to_tiled(db->ctx, spec, count * C, db->d_entries + (size_t)db->n * db->entry_floats, db->s);
-    if (st != MRS_OK) return st;
-    if (form != MRS_LOOPDB_FORM_HOST) {   // the caller may overwrite its device buffer once ITS stream has passed this point
-        MRS_HIP_TRY(hipEventRecord(db->ev_out, db->s));
-        MRS_HIP_TRY(hipStreamWaitEvent((hipStream_t)stream, db->ev_out, 0));
-    }
+    const void* spec = db->d_query.get();
+    if (form == MRS_LOOPDB_FORM_DEVICE_SPEC)               // already row-layout half spectra on the device: permuted straight into the slots
+        MRS_TRY(arg_in(db, descriptor, 0, true, stream, &spec));
+    else
+        MRS_TRY(to_half_spectrum(db, descriptor, form, db->d_query.get(), stream));
+    MRS_TRY(mrs_ring_spec_to_tiled(db->ctx, static_cast<const float*>(spec), count * C, db->d_entries.get() + (size_t)db->n * db->L.entry_floats, db->s));
+    MRS_TRY(arg_out(db, form != MRS_LOOPDB_FORM_HOST, stream));
     db->n += count;
     return MRS_OK;
 }
@@ -488,7 +540,7 @@ int mrs_loopdb_query(mrs_loopdb* db, const void* descriptor, int32_t form, float
                      mrs_stream stream)
 {
     MRS_REQUIRE(db && descriptor && h_count, "null pointer");
-    MRS_REQUIRE(db->kind == MRS_LOOPDB_RING || db->kind == MRS_LOOPDB_RINGPP, "not a RING / RING++ database (DiSCO: mrs_loopdb_query_disco, SC: mrs_loopdb_query_sc, M2DP: mrs_loopdb_query_m2dp, FH: mrs_loopdb_query_fh)");
+    MRS_TRY(require_kind(db, kWantRingQuery));
     MRS_REQUIRE(form == MRS_LOOPDB_FORM_HOST || form == MRS_LOOPDB_FORM_DEVICE || form == MRS_LOOPDB_FORM_DEVICE_SPEC, "unknown form");
     MRS_REQUIRE(max_out >= 0 && (max_out == 0 || (h_index && h_dist && h_angle)), "output arrays");
     MRS_REQUIRE(all_capacity >= 0 && (all_capacity == 0 || h_all_dist || h_all_angle), "all_capacity without an array");
@@ -498,25 +550,22 @@ int mrs_loopdb_query(mrs_loopdb* db, const void* descriptor, int32_t form, float
     const int n = db->n;
     if (h_n) *h_n = n;                                     // the entries this call scored (another thread may append right after)
     if (n == 0) return MRS_OK;                             // `for idx in range(0)`: no candidates, no work
-    int st = to_half_spectrum(db, descriptor, form, db->d_query, (hipStream_t)stream);
-    if (st != MRS_OK) return st;
-    db->d_angle = reinterpret_cast<int32_t*>(db->d_dist + n);
-    db->h_angle = reinterpret_cast<int32_t*>(db->h_dist + n);
-    st = mrs_ring_corr_fft_sweep_tiled(db->ctx, db->d_query, db->d_entries, n, db->channels, db->d_dist, db->d_angle, db->s);
-    if (st != MRS_OK) return st;
-    MRS_HIP_TRY(hipMemcpyAsync(db->h_dist, db->d_dist, (size_t)2 * n * sizeof(float), hipMemcpyDeviceToHost, db->s));
+    MRS_TRY(to_half_spectrum(db, descriptor, form, db->d_query.get(), stream));
+    const DistAngle d = dist_angle(db->d_rows.get(), n), h = dist_angle(db->h_rows.get(), n);
+    MRS_TRY(mrs_ring_corr_fft_sweep_tiled(db->ctx, db->d_query.get(), db->d_entries.get(), n, db->channels, d.dist, d.angle, db->s));
+    MRS_HIP_TRY(hipMemcpyAsync(h.dist, d.dist, (size_t)n * kRowBytes, hipMemcpyDeviceToHost, db->s));
     MRS_HIP_TRY(hipStreamSynchronize(db->s));
     // `if dist < cfg.dist_threshold: idxs.append(idx) ...` in index order (main_RING.py:133-140)
     int cnt = 0;
     for (int i = 0; i < n; ++i)
-        if (db->h_dist[i] < dist_threshold) {
-            if (cnt < max_out) { h_index[cnt] = i; h_dist[cnt] = db->h_dist[i]; h_angle[cnt] = db->h_angle[i]; }
+        if (h.dist[i] < dist_threshold) {
+            if (cnt < max_out) { h_index[cnt] = i; h_dist[cnt] = h.dist[i]; h_angle[cnt] = h.angle[i]; }
             ++cnt;
         }
     *h_count = cnt;                                         // may exceed max_out: the caller then asks again with larger arrays
     const size_t m = (size_t)std::min(n, all_capacity);     // never past the caller's arrays, whatever was appended since it sized them
-    if (h_all_dist) memcpy(h_all_dist, db->h_dist, m * sizeof(float));
-    if (h_all_angle) memcpy(h_all_angle, db->h_angle, m * sizeof(int32_t));
+    if (h_all_dist) memcpy(h_all_dist, h.dist, m * sizeof(float));
+    if (h_all_angle) memcpy(h_all_angle, h.angle, m * sizeof(int32_t));
     return MRS_OK;
 }
 
@@ -524,7 +573,7 @@ int mrs_loopdb_query_multi(mrs_loopdb* db, const void* descriptors, int32_t form
                            int32_t* h_all_angle, int32_t* h_n, mrs_stream stream)
 {
     MRS_REQUIRE(db && descriptors && h_all_dist && h_all_angle && h_n, "null pointer");
-    MRS_REQUIRE(db->kind == MRS_LOOPDB_RING || db->kind == MRS_LOOPDB_RINGPP, "not a RING / RING++ database (DiSCO: mrs_loopdb_query_disco, SC: mrs_loopdb_query_sc, M2DP: mrs_loopdb_query_m2dp, FH: mrs_loopdb_query_fh)");
+    MRS_TRY(require_kind(db, kWantRingQuery));
     MRS_REQUIRE(form == MRS_LOOPDB_FORM_HOST || form == MRS_LOOPDB_FORM_DEVICE || form == MRS_LOOPDB_FORM_DEVICE_SPEC, "unknown form");
     MRS_REQUIRE(count >= 1 && count <= 1024 && all_capacity >= 0, "count in 1..1024");
     MRS_HIP_TRY(hipSetDevice(db->ctx->device));
@@ -535,26 +584,21 @@ int mrs_loopdb_query_multi(mrs_loopdb* db, const void* descriptors, int32_t form
     const int C = db->channels;
     const size_t spec_floats = (size_t)C * kSpecFloats;
     mrs::Scratch qbuf, out;
-    int st = qbuf.alloc((size_t)count * spec_floats * sizeof(float), db->s);
-    if (st != MRS_OK) return st;
-    st = out.alloc((size_t)count * 2 * n * sizeof(float), db->s);
-    if (st != MRS_OK) return st;
+    MRS_TRY(qbuf.alloc((size_t)count * spec_floats * sizeof(float), db->s));
+    MRS_TRY(out.alloc((size_t)count * 2 * n * sizeof(float), db->s));
     float* d_q = qbuf.as<float>();
     if (form == MRS_LOOPDB_FORM_DEVICE_SPEC) {
-        st = join_in(db, (hipStream_t)stream);
-        if (st != MRS_OK) return st;
-        MRS_HIP_TRY(hipMemcpyAsync(d_q, descriptors, (size_t)count * spec_floats * sizeof(float), hipMemcpyDeviceToDevice, db->s));
+        const void* src = nullptr;
+        MRS_TRY(arg_in(db, descriptors, 0, true, stream, &src));
+        MRS_HIP_TRY(hipMemcpyAsync(d_q, src, (size_t)count * spec_floats * sizeof(float), hipMemcpyDeviceToDevice, db->s));
     } else {
-        const size_t step = db->kind == MRS_LOOPDB_RING ? (size_t)kA * kD * 2 : db->in_floats;     // floats from one descriptor to the next in the caller's array
-        for (int i = 0; i < count; ++i) {
-            st = to_half_spectrum(db, static_cast<const float*>(descriptors) + (size_t)i * step, form, d_q + (size_t)i * spec_floats, (hipStream_t)stream);
-            if (st != MRS_OK) return st;
+        for (int i = 0; i < count; ++i) {      // the caller's descriptors lie L.in_floats apart
+            MRS_TRY(to_half_spectrum(db, static_cast<const float*>(descriptors) + (size_t)i * db->L.in_floats, form, d_q + (size_t)i * spec_floats, stream));
         }
     }
     float* d_dist = out.as<float>();                                     // [count][n] distances, then [count][n] angles
     int32_t* d_angle = reinterpret_cast<int32_t*>(d_dist + (size_t)count * n);
-    st = mrs_ring_corr_fft_sweep_tiled_q(db->ctx, d_q, count, db->d_entries, n, C, d_dist, d_angle, db->s);
-    if (st != MRS_OK) return st;
+    MRS_TRY(mrs_ring_corr_fft_sweep_tiled_q(db->ctx, d_q, count, db->d_entries.get(), n, C, d_dist, d_angle, db->s));
     const size_t m = (size_t)std::min(n, all_capacity);
     if (m > 0) {
         MRS_HIP_TRY(hipMemcpy2DAsync(h_all_dist, (size_t)all_capacity * sizeof(float), d_dist, (size_t)n * sizeof(float), m * sizeof(float), count,
@@ -562,10 +606,7 @@ int mrs_loopdb_query_multi(mrs_loopdb* db, const void* descriptors, int32_t form
         MRS_HIP_TRY(hipMemcpy2DAsync(h_all_angle, (size_t)all_capacity * sizeof(int32_t), d_angle, (size_t)n * sizeof(int32_t), m * sizeof(int32_t), count,
                                      hipMemcpyDeviceToHost, db->s));
     }
-    if (form != MRS_LOOPDB_FORM_HOST) {
-        MRS_HIP_TRY(hipEventRecord(db->ev_out, db->s));
-        MRS_HIP_TRY(hipStreamWaitEvent((hipStream_t)stream, db->ev_out, 0));
-    }
+    MRS_TRY(arg_out(db, form != MRS_LOOPDB_FORM_HOST, stream));
     MRS_HIP_TRY(hipStreamSynchronize(db->s));
     return MRS_OK;
 }
@@ -573,26 +614,23 @@ int mrs_loopdb_query_multi(mrs_loopdb* db, const void* descriptors, int32_t form
 int mrs_loopdb_append_disco(mrs_loopdb* db, const float* signature, const float* spectrum, int32_t on_device, mrs_stream stream)
 {
     MRS_REQUIRE(db && signature && spectrum, "null pointer");
-    MRS_REQUIRE(db->kind == MRS_LOOPDB_DISCO, "not a DiSCO database");
+    MRS_TRY(require_kind(db, kWantDisco));
     MRS_HIP_TRY(hipSetDevice(db->ctx->device));
     std::lock_guard<std::mutex> lk(db->mu);
-    int st = reserve_locked(db, db->n + 1);
-    if (st != MRS_OK) return st;
-    float* sig = db->d_sigs + (size_t)db->n * db->sig_dim;
-    float* spec = db->d_entries + (size_t)db->n * db->entry_floats;
+    MRS_TRY(reserve_locked(db, db->n + 1));
+    float* sig = db->d_sigs.get() + (size_t)db->n * db->L.sig_dim;
+    float* spec = db->d_entries.get() + (size_t)db->n * db->L.entry_floats;
+    const size_t sb = (size_t)db->L.sig_dim * sizeof(float), eb = db->L.entry_floats * sizeof(float);
+    // two arguments with a destination each, so not arg_in: one join covers a device pair, a host pair takes a slot and a copy each
     if (on_device) {
-        st = join_in(db, (hipStream_t)stream);
-        if (st != MRS_OK) return st;
-        MRS_HIP_TRY(hipMemcpyAsync(sig, signature, (size_t)db->sig_dim * sizeof(float), hipMemcpyDeviceToDevice, db->s));
-        MRS_HIP_TRY(hipMemcpyAsync(spec, spectrum, db->entry_floats * sizeof(float), hipMemcpyDeviceToDevice, db->s));
-        MRS_HIP_TRY(hipEventRecord(db->ev_out, db->s));
-        MRS_HIP_TRY(hipStreamWaitEvent((hipStream_t)stream, db->ev_out, 0));
+        MRS_TRY(db->s.join_in((hipStream_t)stream));
+        MRS_HIP_TRY(hipMemcpyAsync(sig, signature, sb, hipMemcpyDeviceToDevice, db->s));
+        MRS_HIP_TRY(hipMemcpyAsync(spec, spectrum, eb, hipMemcpyDeviceToDevice, db->s));
     } else {
-        st = upload(db, signature, (size_t)db->sig_dim * sizeof(float), sig);
-        if (st != MRS_OK) return st;
-        st = upload(db, spectrum, db->entry_floats * sizeof(float), spec);
-        if (st != MRS_OK) return st;
+        MRS_TRY(upload(db, sig, {signature, sb}));
+        MRS_TRY(upload(db, spec, {spectrum, eb}));
     }
+    MRS_TRY(arg_out(db, on_device, stream));
     db->n += 1;
     return MRS_OK;
 }
@@ -601,45 +639,37 @@ int mrs_loopdb_query_disco(mrs_loopdb* db, const float* signature, const float* 
                            int32_t* h_flat_argmax, mrs_stream stream)
 {
     MRS_REQUIRE(db && signature && spectrum && h_index && h_dist2 && h_flat_argmax, "null pointer");
-    MRS_REQUIRE(db->kind == MRS_LOOPDB_DISCO, "not a DiSCO database");
+    MRS_TRY(require_kind(db, kWantDisco));
     MRS_HIP_TRY(hipSetDevice(db->ctx->device));
     std::lock_guard<std::mutex> lk(db->mu);
     *h_index = -1; *h_dist2 = INFINITY; *h_flat_argmax = 0;
     const int n = db->n;
     if (n == 0) return MRS_OK;
+    auto& D = db->disco;
     const float *sig = signature, *spec = spectrum;
-    int st;
     if (on_device) {
-        st = join_in(db, (hipStream_t)stream);
-        if (st != MRS_OK) return st;
+        MRS_TRY(db->s.join_in((hipStream_t)stream));
     } else {
         // signature | spectrum through ONE pinned slot and ONE copy
-        Pinned& p = db->stage[db->stage_next];
-        db->stage_next = (db->stage_next + 1) % kStageSlots;
-        if (p.used) MRS_HIP_TRY(hipEventSynchronize(p.ev));
-        const size_t sb = (size_t)db->sig_dim * sizeof(float), eb = db->entry_floats * sizeof(float);
-        memcpy(p.p, signature, sb);
-        memcpy(static_cast<char*>(p.p) + sb, spectrum, eb);
-        MRS_HIP_TRY(hipMemcpyAsync(db->d_in, p.p, sb + eb, hipMemcpyHostToDevice, db->s));
-        MRS_HIP_TRY(hipEventRecord(p.ev, db->s));
-        p.used = true;
-        sig = db->d_in; spec = db->d_in + db->sig_dim;
+        MRS_TRY(upload(db, db->d_in.get(), {signature, (size_t)db->L.sig_dim * sizeof(float)}, {spectrum, db->L.entry_floats * sizeof(float)}));
+        sig = db->d_in.get(); spec = db->d_in.get() + db->L.sig_dim;
     }
     const int blocks = std::max(1, std::min((n + 3) / 4, 4 * (db->ctx->num_cu > 0 ? db->ctx->num_cu : 256)));
-    hipLaunchKernelGGL(k_sig_nearest, dim3(blocks), dim3(256), 0, db->s, sig, db->d_sigs, n, db->sig_dim, db->d_best);
-    const size_t lds = (size_t)(2 * db->R * db->S + db->S + db->R) * sizeof(float2);
-    if (!db->phase_attr_set) {
+    hipLaunchKernelGGL(k_sig_nearest, dim3(blocks), dim3(256), 0, db->s, sig, db->d_sigs.get(), n, db->L.sig_dim, D.d_best.get());
+    const size_t lds = (size_t)(2 * D.R * D.S + D.S + D.R) * sizeof(float2);
+    if (!D.phase_attr_set) {
         MRS_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_disco_phase_one), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        db->phase_attr_set = true;
+        D.phase_attr_set = true;
     }
-    hipLaunchKernelGGL(k_disco_phase_one, dim3(1), dim3(kPhaseThreads), lds, db->s, reinterpret_cast<const float2*>(db->d_entries), db->d_best,
-                       reinterpret_cast<const float2*>(spec), reinterpret_cast<const float2*>(db->d_tw), db->h_small,
-                       reinterpret_cast<float*>(db->h_small + 1), db->h_small + 2);
+    DiscoBest* res = D.h_result.get();
+    hipLaunchKernelGGL(k_disco_phase_one, dim3(1), dim3(kPhaseThreads), lds, db->s, reinterpret_cast<const float2*>(db->d_entries.get()),
+                       D.d_best.get(), reinterpret_cast<const float2*>(spec), reinterpret_cast<const float2*>(D.d_tw.get()), &res->index,
+                       &res->dist2, &res->argmax);
     MRS_HIP_TRY(hipGetLastError());
     MRS_HIP_TRY(hipStreamSynchronize(db->s));
-    *h_index = db->h_small[0];
-    memcpy(h_dist2, &db->h_small[1], sizeof(float));
-    *h_flat_argmax = db->h_small[2];
+    *h_index = res->index;
+    *h_dist2 = res->dist2;
+    *h_flat_argmax = res->argmax;
     return MRS_OK;
 }
 
@@ -649,50 +679,24 @@ namespace {
 // the query descriptor -> packed entry at d_query + its ring key at d_tmp, on the handle's stream (lock held)
 int sc_query_prep(mrs_loopdb* db, const float* sc, int32_t on_device, mrs_stream stream)
 {
-    const float* src = sc;
-    if (on_device) {
-        int st = join_in(db, (hipStream_t)stream);
-        if (st != MRS_OK) return st;
-    } else {
-        int st = upload(db, sc, db->in_floats * sizeof(float), db->d_in);
-        if (st != MRS_OK) return st;
-        src = db->d_in;
-    }
-    return mrs::sc_pack(src, 1, kScDim, kScDim, db->d_query, db->entry_floats, db->d_tmp, nullptr, db->s);
-}
-
-// the caller may reuse its device argument once ITS stream has passed this point
-int sc_release_arg(mrs_loopdb* db, int32_t on_device, mrs_stream stream)
-{
-    if (!on_device) return MRS_OK;
-    MRS_HIP_TRY(hipEventRecord(db->ev_out, db->s));
-    MRS_HIP_TRY(hipStreamWaitEvent((hipStream_t)stream, db->ev_out, 0));
-    return MRS_OK;
+    const void* src = nullptr;
+    MRS_TRY(arg_in(db, sc, db->L.in_floats * sizeof(float), on_device, stream, &src));
+    return mrs::sc_pack(static_cast<const float*>(src), 1, kScDim, kScDim, db->d_query.get(), db->L.entry_floats, db->d_tmp.get(), nullptr, db->s);
 }
 }  // namespace
 
 int mrs_loopdb_append_sc(mrs_loopdb* db, const float* sc, int32_t on_device, mrs_stream stream)
 {
     MRS_REQUIRE(db && sc, "null pointer");
-    MRS_REQUIRE(db->kind == MRS_LOOPDB_SC, "not a Scan Context database (FH: mrs_loopdb_append_fh / mrs_loopdb_query_fh)");
+    MRS_TRY(require_kind(db, kWantSc));
     MRS_HIP_TRY(hipSetDevice(db->ctx->device));
     std::lock_guard<std::mutex> lk(db->mu);
-    int st = reserve_locked(db, db->n + 1);
-    if (st != MRS_OK) return st;
-    const float* src = sc;
-    if (on_device) {
-        st = join_in(db, (hipStream_t)stream);
-        if (st != MRS_OK) return st;
-    } else {
-        st = upload(db, sc, db->in_floats * sizeof(float), db->d_in);
-        if (st != MRS_OK) return st;
-        src = db->d_in;
-    }
-    st = mrs::sc_pack(src, 1, kScDim, kScDim, db->d_entries + (size_t)db->n * db->entry_floats, db->entry_floats,
-                      db->d_sigs + (size_t)db->n * db->sig_dim, nullptr, db->s);
-    if (st != MRS_OK) return st;
-    st = sc_release_arg(db, on_device, stream);
-    if (st != MRS_OK) return st;
+    MRS_TRY(reserve_locked(db, db->n + 1));
+    const void* src = nullptr;
+    MRS_TRY(arg_in(db, sc, db->L.in_floats * sizeof(float), on_device, stream, &src));
+    MRS_TRY(mrs::sc_pack(static_cast<const float*>(src), 1, kScDim, kScDim, db->d_entries.get() + (size_t)db->n * db->L.entry_floats, db->L.entry_floats,
+                      db->d_sigs.get() + (size_t)db->n * db->L.sig_dim, nullptr, db->s));
+    MRS_TRY(arg_out(db, on_device, stream));
     db->n += 1;
     return MRS_OK;
 }
@@ -701,7 +705,7 @@ int mrs_loopdb_query_sc(mrs_loopdb* db, const float* sc, int32_t on_device, int3
                         float* h_key_dist, float* h_dist, int32_t* h_shift, int32_t* h_count, mrs_stream stream)
 {
     MRS_REQUIRE(db && sc && h_index && h_key_dist && h_dist && h_shift && h_count, "null pointer");
-    MRS_REQUIRE(db->kind == MRS_LOOPDB_SC, "not a Scan Context database (FH: mrs_loopdb_append_fh / mrs_loopdb_query_fh)");
+    MRS_TRY(require_kind(db, kWantSc));
     MRS_REQUIRE(num_candidates >= 1 && num_candidates <= kScMaxK, "num_candidates in 1..64");
     MRS_REQUIRE(std::isfinite(search_ratio) && search_ratio >= 0.0f, "search_ratio >= 0");
     MRS_HIP_TRY(hipSetDevice(db->ctx->device));
@@ -711,30 +715,22 @@ int mrs_loopdb_query_sc(mrs_loopdb* db, const float* sc, int32_t on_device, int3
     *h_count = 0;
     const int n = db->n;
     if (n == 0) return MRS_OK;                             // `if len(Ringkey_candidates) < 1: return`
-    int st = sc_query_prep(db, sc, on_device, stream);
-    if (st != MRS_OK) return st;
-    int32_t* d_idx = db->d_small;
-    float* d_dist = reinterpret_cast<float*>(db->d_small + kScMaxK);
-    int32_t* d_shift = db->d_small + 2 * kScMaxK;
-    double* d_d2 = reinterpret_cast<double*>(db->d_small + 3 * kScMaxK);
+    MRS_TRY(sc_query_prep(db, sc, on_device, stream));
+    ScTopK* d = db->sc.d.get();
+    const ScTopK* h = db->sc.h.get();
     const int cnt = std::min(k, n);
     // KDTree(ring keys).query(k) then dist_align_sc(SC_candidate, SC_current, search_ratio) for each candidate (main_SC.py:159-167)
-    st = mrs::sc_nearest(db->d_tmp, db->d_sigs, n, kScDim, k, d_idx, d_d2, db->s);
-    if (st != MRS_OK) return st;
-    st = mrs::sc_align(db->ctx, db->d_entries, db->entry_floats, d_idx, cnt, db->d_query, 0, kScDim, kScDim, 0,
-                       mrs::sc_search_radius(search_ratio, kScDim), d_dist, d_shift, db->s);
-    if (st != MRS_OK) return st;
-    st = sc_release_arg(db, on_device, stream);
-    if (st != MRS_OK) return st;
-    MRS_HIP_TRY(hipMemcpyAsync(db->h_small, db->d_small, kSmallSc * sizeof(int32_t), hipMemcpyDeviceToHost, db->s));
+    MRS_TRY(mrs::sc_nearest(db->d_tmp.get(), db->d_sigs.get(), n, kScDim, k, d->idx, d->key_d2, db->s));
+    MRS_TRY(mrs::sc_align(db->ctx, db->d_entries.get(), db->L.entry_floats, d->idx, cnt, db->d_query.get(), 0, kScDim, kScDim, 0,
+                       mrs::sc_search_radius(search_ratio, kScDim), d->dist, d->shift, db->s));
+    MRS_TRY(arg_out(db, on_device, stream));
+    MRS_HIP_TRY(hipMemcpyAsync(db->sc.h.get(), d, sizeof(ScTopK), hipMemcpyDeviceToHost, db->s));
     MRS_HIP_TRY(hipStreamSynchronize(db->s));
-    const float* hd = reinterpret_cast<const float*>(db->h_small + kScMaxK);
-    const double* hd2 = reinterpret_cast<const double*>(db->h_small + 3 * kScMaxK);
     for (int i = 0; i < cnt; ++i) {
-        h_index[i] = db->h_small[i];
-        h_key_dist[i] = (float)std::sqrt(hd2[i]);
-        h_dist[i] = hd[i];
-        h_shift[i] = db->h_small[2 * kScMaxK + i];
+        h_index[i] = h->idx[i];
+        h_key_dist[i] = (float)std::sqrt(h->key_d2[i]);
+        h_dist[i] = h->dist[i];
+        h_shift[i] = h->shift[i];
     }
     *h_count = cnt;
     return MRS_OK;
@@ -744,7 +740,7 @@ int mrs_loopdb_query_sc_all(mrs_loopdb* db, const float* sc, int32_t on_device, 
                             int32_t* h_all_shift, int32_t* h_best, int32_t* h_n, mrs_stream stream)
 {
     MRS_REQUIRE(db && sc && h_best && h_n, "null pointer");
-    MRS_REQUIRE(db->kind == MRS_LOOPDB_SC, "not a Scan Context database (FH: mrs_loopdb_append_fh / mrs_loopdb_query_fh)");
+    MRS_TRY(require_kind(db, kWantSc));
     MRS_REQUIRE(std::isfinite(search_ratio) && search_ratio >= 0.0f, "search_ratio >= 0");
     MRS_REQUIRE(all_capacity >= 0 && (all_capacity == 0 || (h_all_dist && h_all_shift)), "all_capacity without arrays");
     MRS_HIP_TRY(hipSetDevice(db->ctx->device));
@@ -753,25 +749,21 @@ int mrs_loopdb_query_sc_all(mrs_loopdb* db, const float* sc, int32_t on_device, 
     *h_n = n;
     *h_best = -1;
     if (n == 0) return MRS_OK;
-    int st = sc_query_prep(db, sc, on_device, stream);
-    if (st != MRS_OK) return st;
-    db->d_angle = reinterpret_cast<int32_t*>(db->d_dist + n);
-    db->h_angle = reinterpret_cast<int32_t*>(db->h_dist + n);
-    st = mrs::sc_align(db->ctx, db->d_entries, db->entry_floats, nullptr, n, db->d_query, 0, kScDim, kScDim, 0,
-                       mrs::sc_search_radius(search_ratio, kScDim), db->d_dist, db->d_angle, db->s);
-    if (st != MRS_OK) return st;
-    st = sc_release_arg(db, on_device, stream);
-    if (st != MRS_OK) return st;
-    MRS_HIP_TRY(hipMemcpyAsync(db->h_dist, db->d_dist, (size_t)2 * n * sizeof(float), hipMemcpyDeviceToHost, db->s));
+    MRS_TRY(sc_query_prep(db, sc, on_device, stream));
+    const DistAngle d = dist_angle(db->d_rows.get(), n), h = dist_angle(db->h_rows.get(), n);
+    MRS_TRY(mrs::sc_align(db->ctx, db->d_entries.get(), db->L.entry_floats, nullptr, n, db->d_query.get(), 0, kScDim, kScDim, 0,
+                       mrs::sc_search_radius(search_ratio, kScDim), d.dist, d.angle, db->s));
+    MRS_TRY(arg_out(db, on_device, stream));
+    MRS_HIP_TRY(hipMemcpyAsync(h.dist, d.dist, (size_t)n * kRowBytes, hipMemcpyDeviceToHost, db->s));
     MRS_HIP_TRY(hipStreamSynchronize(db->s));
     int best = 0;                                          // first minimum over the entries, as a loop over them would keep it
     for (int i = 1; i < n; ++i)
-        if (db->h_dist[i] < db->h_dist[best]) best = i;
+        if (h.dist[i] < h.dist[best]) best = i;
     *h_best = best;
     const size_t m = (size_t)std::min(n, all_capacity);    // never past the caller's arrays
     if (m > 0) {
-        memcpy(h_all_dist, db->h_dist, m * sizeof(float));
-        memcpy(h_all_shift, db->h_angle, m * sizeof(int32_t));
+        memcpy(h_all_dist, h.dist, m * sizeof(float));
+        memcpy(h_all_shift, h.angle, m * sizeof(int32_t));
     }
     return MRS_OK;
 }
@@ -782,31 +774,22 @@ namespace {
 // the descriptor argument (192 doubles, host or device) -> float32 [192] at `dst`, on the handle's stream (lock held)
 int m2dp_to_row(mrs_loopdb* db, const double* desc, int32_t on_device, mrs_stream stream, float* dst)
 {
-    const double* src = desc;
-    if (on_device) {
-        int st = join_in(db, (hipStream_t)stream);
-        if (st != MRS_OK) return st;
-    } else {
-        int st = upload(db, desc, kM2dpDim * sizeof(double), db->d_in);
-        if (st != MRS_OK) return st;
-        src = reinterpret_cast<const double*>(db->d_in);
-    }
-    hipLaunchKernelGGL(k_m2dp_to_float, dim3(1), dim3(256), 0, db->s, src, dst);
+    const void* src = nullptr;
+    MRS_TRY(arg_in(db, desc, kM2dpDim * sizeof(double), on_device, stream, &src));
+    hipLaunchKernelGGL(k_m2dp_to_float, dim3(1), dim3(256), 0, db->s, static_cast<const double*>(src), dst);
     MRS_HIP_TRY(hipGetLastError());
-    return sc_release_arg(db, on_device, stream);
+    return arg_out(db, on_device, stream);
 }
 }  // namespace
 
 int mrs_loopdb_append_m2dp(mrs_loopdb* db, const double* desc, int32_t on_device, mrs_stream stream)
 {
     MRS_REQUIRE(db && desc, "null pointer");
-    MRS_REQUIRE(db->kind == MRS_LOOPDB_M2DP, "not an M2DP database (FH: mrs_loopdb_append_fh / mrs_loopdb_query_fh)");
+    MRS_TRY(require_kind(db, kWantM2dp));
     MRS_HIP_TRY(hipSetDevice(db->ctx->device));
     std::lock_guard<std::mutex> lk(db->mu);
-    int st = reserve_locked(db, db->n + 1);
-    if (st != MRS_OK) return st;
-    st = m2dp_to_row(db, desc, on_device, stream, db->d_entries + (size_t)db->n * db->entry_floats);
-    if (st != MRS_OK) return st;
+    MRS_TRY(reserve_locked(db, db->n + 1));
+    MRS_TRY(m2dp_to_row(db, desc, on_device, stream, db->d_entries.get() + (size_t)db->n * db->L.entry_floats));
     db->n += 1;
     return MRS_OK;
 }
@@ -815,7 +798,7 @@ int mrs_loopdb_query_m2dp(mrs_loopdb* db, const double* desc, int32_t on_device,
                           mrs_stream stream)
 {
     MRS_REQUIRE(db && desc && h_index && h_dist2 && h_count, "null pointer");
-    MRS_REQUIRE(db->kind == MRS_LOOPDB_M2DP, "not an M2DP database (FH: mrs_loopdb_append_fh / mrs_loopdb_query_fh)");
+    MRS_TRY(require_kind(db, kWantM2dp));
     MRS_REQUIRE(k >= 1 && k <= kM2dpMaxK, "k in 1..32");
     MRS_HIP_TRY(hipSetDevice(db->ctx->device));
     std::lock_guard<std::mutex> lk(db->mu);
@@ -823,18 +806,14 @@ int mrs_loopdb_query_m2dp(mrs_loopdb* db, const double* desc, int32_t on_device,
     *h_count = 0;
     const int n = db->n;
     if (n == 0) return MRS_OK;
-    int st = m2dp_to_row(db, desc, on_device, stream, db->d_query);
-    if (st != MRS_OK) return st;
-    st = mrs_signature_knn(db->ctx, db->d_query, 1, db->d_entries, n, kM2dpDim, k, db->d_small, reinterpret_cast<float*>(db->d_small + kM2dpMaxK),
-                           db->s);
-    if (st != MRS_OK) return st;
-    MRS_HIP_TRY(hipMemcpyAsync(db->h_small, db->d_small, kSmallM2dp * sizeof(int32_t), hipMemcpyDeviceToHost, db->s));
+    MRS_TRY(m2dp_to_row(db, desc, on_device, stream, db->d_query.get()));
+    M2dpTopK* d = db->m2dp.d.get();
+    const M2dpTopK* h = db->m2dp.h.get();
+    MRS_TRY(mrs_signature_knn(db->ctx, db->d_query.get(), 1, db->d_entries.get(), n, kM2dpDim, k, d->idx, d->d2, db->s));
+    MRS_HIP_TRY(hipMemcpyAsync(db->m2dp.h.get(), d, sizeof(M2dpTopK), hipMemcpyDeviceToHost, db->s));
     MRS_HIP_TRY(hipStreamSynchronize(db->s));
     const int cnt = std::min(k, n);
-    for (int i = 0; i < cnt; ++i) {
-        h_index[i] = db->h_small[i];
-        memcpy(&h_dist2[i], &db->h_small[kM2dpMaxK + i], sizeof(float));
-    }
+    for (int i = 0; i < cnt; ++i) { h_index[i] = h->idx[i]; h_dist2[i] = h->d2[i]; }
     *h_count = cnt;
     return MRS_OK;
 }
@@ -842,26 +821,13 @@ int mrs_loopdb_query_m2dp(mrs_loopdb* db, const double* desc, int32_t on_device,
 // ---- Fast Histogram -----------------------------------------------------------------------------------------------------------------
 
 namespace {
-// the histogram argument (`bins` doubles, host or device) as a device pointer the handle's stream may read (lock held); a host argument goes
-// through d_in
-int fh_arg(mrs_loopdb* db, const double* hist, int32_t on_device, mrs_stream stream, const double** src)
-{
-    if (on_device) {
-        *src = hist;
-        return join_in(db, (hipStream_t)stream);
-    }
-    *src = reinterpret_cast<const double*>(db->d_in);
-    return upload(db, hist, (size_t)db->bins * sizeof(double), db->d_in);
-}
-
-// distances of `hist` to the n entries -> d_dist [n] on the handle's stream (lock held, n > 0)
+// distances of `hist` (`bins` doubles, host or device) to the n entries -> d_dist [n] on the handle's stream (lock held, n > 0)
 int fh_sweep(mrs_loopdb* db, const double* hist, int32_t on_device, mrs_stream stream, int n, double* d_dist)
 {
-    const double* src = nullptr;
-    int st = fh_arg(db, hist, on_device, stream, &src);
-    if (st != MRS_OK) return st;
-    hipLaunchKernelGGL(k_fh_distances, dim3((n + kFhEntries - 1) / kFhEntries), dim3(kFhThreads), 0, db->s, src,
-                       reinterpret_cast<const double*>(db->d_entries), n, db->bins, d_dist);
+    const void* src = nullptr;
+    MRS_TRY(arg_in(db, hist, (size_t)db->bins * sizeof(double), on_device, stream, &src));
+    hipLaunchKernelGGL(k_fh_distances, dim3((n + kFhEntries - 1) / kFhEntries), dim3(kFhThreads), 0, db->s, static_cast<const double*>(src),
+                       reinterpret_cast<const double*>(db->d_entries.get()), n, db->bins, d_dist);
     MRS_HIP_TRY(hipGetLastError());
     return MRS_OK;
 }
@@ -870,22 +836,16 @@ int fh_sweep(mrs_loopdb* db, const double* hist, int32_t on_device, mrs_stream s
 int mrs_loopdb_append_fh(mrs_loopdb* db, const double* hist, int32_t on_device, mrs_stream stream)
 {
     MRS_REQUIRE(db && hist, "null pointer");
-    MRS_REQUIRE(db->kind == MRS_LOOPDB_FH, "not a Fast Histogram database");
+    MRS_TRY(require_kind(db, kWantFh));
     MRS_HIP_TRY(hipSetDevice(db->ctx->device));
     std::lock_guard<std::mutex> lk(db->mu);
-    int st = reserve_locked(db, db->n + 1);
-    if (st != MRS_OK) return st;
-    float* slot = db->d_entries + (size_t)db->n * db->entry_floats;
+    MRS_TRY(reserve_locked(db, db->n + 1));
+    float* slot = db->d_entries.get() + (size_t)db->n * db->L.entry_floats;
     const size_t bytes = (size_t)db->bins * sizeof(double);
-    if (on_device) {
-        st = join_in(db, (hipStream_t)stream);
-        if (st != MRS_OK) return st;
-        MRS_HIP_TRY(hipMemcpyAsync(slot, hist, bytes, hipMemcpyDeviceToDevice, db->s));
-        st = sc_release_arg(db, on_device, stream);
-    } else {
-        st = upload(db, hist, bytes, slot);
-    }
-    if (st != MRS_OK) return st;
+    const void* src = nullptr;
+    MRS_TRY(arg_in(db, hist, bytes, on_device, stream, &src, slot));      // a host histogram is staged straight into its slot
+    if (on_device) MRS_HIP_TRY(hipMemcpyAsync(slot, src, bytes, hipMemcpyDeviceToDevice, db->s));
+    MRS_TRY(arg_out(db, on_device, stream));
     db->n += 1;
     return MRS_OK;
 }
@@ -894,7 +854,7 @@ int mrs_loopdb_query_fh(mrs_loopdb* db, const double* hist, int32_t on_device, i
                         mrs_stream stream)
 {
     MRS_REQUIRE(db && hist && h_index && h_dist && h_count, "null pointer");
-    MRS_REQUIRE(db->kind == MRS_LOOPDB_FH, "not a Fast Histogram database");
+    MRS_TRY(require_kind(db, kWantFh));
     MRS_REQUIRE(k >= 1 && k <= kFhMaxK, "k in 1..32");
     MRS_HIP_TRY(hipSetDevice(db->ctx->device));
     std::lock_guard<std::mutex> lk(db->mu);
@@ -902,14 +862,11 @@ int mrs_loopdb_query_fh(mrs_loopdb* db, const double* hist, int32_t on_device, i
     *h_count = 0;
     const int n = db->n;
     if (n == 0) return MRS_OK;
-    // d_dist / h_dist hold 2 x cap floats: room for cap doubles
-    double* d_all = reinterpret_cast<double*>(db->d_dist);
-    const double* h_all = reinterpret_cast<const double*>(db->h_dist);
-    int st = fh_sweep(db, hist, on_device, stream, n, d_all);
-    if (st != MRS_OK) return st;
-    st = sc_release_arg(db, on_device, stream);
-    if (st != MRS_OK) return st;
-    MRS_HIP_TRY(hipMemcpyAsync(db->h_dist, d_all, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, db->s));
+    double* d_all = dist_f64(db->d_rows.get());
+    double* h_all = dist_f64(db->h_rows.get());
+    MRS_TRY(fh_sweep(db, hist, on_device, stream, n, d_all));
+    MRS_TRY(arg_out(db, on_device, stream));
+    MRS_HIP_TRY(hipMemcpyAsync(h_all, d_all, (size_t)n * kRowBytes, hipMemcpyDeviceToHost, db->s));
     MRS_HIP_TRY(hipStreamSynchronize(db->s));
     // the k smallest, ascending, ties to the lower index; a NaN distance (a NaN in either histogram) orders after every number
     const int cnt = std::min(k, n);
@@ -931,17 +888,15 @@ int mrs_loopdb_query_fh(mrs_loopdb* db, const double* hist, int32_t on_device, i
 int mrs_loopdb_distances_fh(mrs_loopdb* db, const double* hist, int32_t on_device, double* d_dist, mrs_stream stream)
 {
     MRS_REQUIRE(db && hist, "null pointer");
-    MRS_REQUIRE(db->kind == MRS_LOOPDB_FH, "not a Fast Histogram database");
+    MRS_TRY(require_kind(db, kWantFh));
     MRS_HIP_TRY(hipSetDevice(db->ctx->device));
     std::lock_guard<std::mutex> lk(db->mu);
     const int n = db->n;
     if (n == 0) return MRS_OK;
     MRS_REQUIRE(d_dist, "null pointer");
-    int st = join_in(db, (hipStream_t)stream);               // the caller's earlier work on d_dist comes first
-    if (st != MRS_OK) return st;
-    st = fh_sweep(db, hist, on_device, stream, n, d_dist);
-    if (st != MRS_OK) return st;
-    return sc_release_arg(db, 1, stream);                    // `stream` waits for the sweep: its later work sees d_dist
+    MRS_TRY(db->s.join_in((hipStream_t)stream));             // the caller's earlier work on d_dist comes first
+    MRS_TRY(fh_sweep(db, hist, on_device, stream, n, d_dist));
+    return arg_out(db, true, stream);                        // `stream` waits for the sweep: its later work sees d_dist
 }
 
 int mrs_loopdb_device_entries(mrs_loopdb* db, const float** d_entries, const float** d_signatures, int32_t* out_n, int64_t* entry_floats)
@@ -950,10 +905,10 @@ int mrs_loopdb_device_entries(mrs_loopdb* db, const float** d_entries, const flo
     std::lock_guard<std::mutex> lk(db->mu);
     MRS_HIP_TRY(hipSetDevice(db->ctx->device));
     MRS_HIP_TRY(hipStreamSynchronize(db->s));
-    *d_entries = db->d_entries;
-    if (d_signatures) *d_signatures = db->d_sigs;
+    *d_entries = db->d_entries.get();
+    if (d_signatures) *d_signatures = db->d_sigs.get();
     *out_n = db->n;
-    if (entry_floats) *entry_floats = (int64_t)db->entry_floats;
+    if (entry_floats) *entry_floats = (int64_t)db->L.entry_floats;
     return MRS_OK;
 }
 

@@ -390,7 +390,7 @@ int mrs_map_compose(int32_t n_stores, mrs_keyframes* const* stores, int32_t n_se
     int st = tables.alloc(b_tables, s);
     if (st != MRS_OK) return st;
     if ((st = stage_reserve(kf, b_tables)) != MRS_OK) return st;
-    char* h = static_cast<char*>(kf->h_stage);
+    char* h = kf->h_stage.get();
     memset(h, 0, b_tables);
     Info* hi = reinterpret_cast<Info*>(h);
     hi->bounds[0] = hi->bounds[1] = hi->bounds[2] = 0xffffffffu;
@@ -415,12 +415,8 @@ int mrs_map_compose(int32_t n_stores, mrs_keyframes* const* stores, int32_t n_se
 
     // appends may still be in flight on the other stores' streams; d_prev and d_out belong to the caller's stream
     for (mrs_keyframes* u : uniq)
-        if (u != kf) {
-            MRS_HIP_TRY(hipEventRecord(u->ev_out, u->s));
-            MRS_HIP_TRY(hipStreamWaitEvent(s, u->ev_out, 0));
-        }
-    MRS_HIP_TRY(hipEventRecord(kf->ev_in, (hipStream_t)stream));
-    MRS_HIP_TRY(hipStreamWaitEvent(s, kf->ev_in, 0));
+        if (u != kf) MRS_TRY(u->s.release_to(s));      // the other store's own ev_out
+    MRS_TRY(kf->s.join_in((hipStream_t)stream));
     MRS_HIP_TRY(hipMemcpyAsync(w, h, b_tables, hipMemcpyHostToDevice, s));
     // development aid (MRS_DEV=1 MRS_MAP_TIMING=1, tools/bench_globalmap.py): events between the steps, one line on stderr per call
     const bool timing = mrs::dev_env("MRS_MAP_TIMING") != nullptr;

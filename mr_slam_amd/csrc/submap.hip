@@ -20,6 +20,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
+#include <memory>
 
 namespace {
 
@@ -299,15 +300,14 @@ int assemble_locked(mrs_keyframes* kf, int n_submaps, int n_seg, const int32_t* 
     void* d_tmp = w;
 
     if ((st = stage_reserve(kf, std::max(b_tables, b_offs))) != MRS_OK) return st;
-    char* h = static_cast<char*>(kf->h_stage);
+    char* h = kf->h_stage.get();
     memset(h, 0, b_tables);
     memcpy(h, segs.data(), ns * sizeof(Segment));
     memcpy(h + b_segs, tiles.data(), n_tiles * sizeof(Tile));
     memcpy(h + b_segs + b_tiles, sub_base.data(), (n_submaps + 1) * sizeof(int));
     unsigned* hb = reinterpret_cast<unsigned*>(h + b_segs + b_tiles + b_sub);
     for (int b = 0; b < n_submaps; ++b) hb[6 * b] = hb[6 * b + 1] = hb[6 * b + 2] = 0xffffffffu;      // minima; the maxima and the flag start at 0
-    MRS_HIP_TRY(hipEventRecord(kf->ev_in, user));               // d_out may still be in use on the caller's stream
-    MRS_HIP_TRY(hipStreamWaitEvent(kf->s, kf->ev_in, 0));
+    MRS_TRY(kf->s.join_in(user));        // d_out may still be in use on the caller's stream
     MRS_HIP_TRY(hipMemcpyAsync(d_segs, h, b_tables, hipMemcpyHostToDevice, kf->s));
     // development aid (MRS_DEV=1 MRS_SUBMAP_TIMING=1, tools/bench_submap.py): events between the steps, one line on stderr per call
     const bool timing = mrs::dev_env("MRS_SUBMAP_TIMING") != nullptr;
@@ -364,18 +364,11 @@ int mrs_keyframes_create(mrs_ctx* ctx, int64_t capacity_hint_points, mrs_keyfram
     *out = nullptr;
     MRS_REQUIRE(capacity_hint_points >= 0 && capacity_hint_points <= kMaxArenaPoints, "capacity hint negative or above 2^34 points");
     MRS_HIP_TRY(hipSetDevice(ctx->device));
-    mrs_keyframes* kf = new mrs_keyframes();
+    std::unique_ptr<mrs_keyframes> kf(new mrs_keyframes());      // an early return deletes it: every member frees itself
     kf->ctx = ctx;
-    auto fail = [&](int st) { mrs_keyframes_destroy(kf); return st; };
-#define KF_TRY(expr) do { if ((expr) != hipSuccess) { mrs::set_error("%s failed (%s:%d)", #expr, __FILE__, __LINE__); return fail(MRS_ERR_HIP); } } while (0)
-    KF_TRY(hipStreamCreateWithFlags(&kf->s, hipStreamNonBlocking));
-    KF_TRY(hipEventCreateWithFlags(&kf->ev_in, hipEventDisableTiming));
-    KF_TRY(hipEventCreateWithFlags(&kf->ev_out, hipEventDisableTiming));
-#undef KF_TRY
-    // nobody else can hold the handle yet: no lock (fail() deletes it)
-    const int st = arena_reserve(kf, std::max<long long>(capacity_hint_points, 1));
-    if (st != MRS_OK) return fail(st);
-    *out = kf;
+    MRS_TRY(kf->s.create());
+    MRS_TRY(arena_reserve(kf.get(), std::max<long long>(capacity_hint_points, 1)));      // nobody else can hold the handle yet: no lock
+    *out = kf.release();
     return MRS_OK;
 }
 
@@ -383,15 +376,6 @@ int mrs_keyframes_destroy(mrs_keyframes* kf)
 {
     if (!kf) return MRS_OK;
     (void)hipSetDevice(kf->ctx->device);
-    if (kf->s) (void)hipStreamSynchronize(kf->s);
-    kf->arena.reset();
-    if (kf->h_stage) (void)hipHostFree(kf->h_stage);
-    if (kf->ev_in) (void)hipEventDestroy(kf->ev_in);
-    if (kf->ev_out) (void)hipEventDestroy(kf->ev_out);
-    if (kf->s) {
-        mrs::scratch_forget_stream(kf->s);
-        (void)hipStreamDestroy(kf->s);
-    }
     delete kf;
     return MRS_OK;
 }
@@ -426,18 +410,17 @@ int mrs_keyframes_append(mrs_keyframes* kf, const void* points, int32_t on_devic
         const void* src = points;
         mrs::Scratch raw;
         if (on_device) {
-            MRS_HIP_TRY(hipEventRecord(kf->ev_in, (hipStream_t)stream));
-            MRS_HIP_TRY(hipStreamWaitEvent(kf->s, kf->ev_in, 0));
+            MRS_TRY(kf->s.join_in((hipStream_t)stream));
             if (as_is) MRS_HIP_TRY(hipMemcpyAsync(dst, points, bytes, hipMemcpyDeviceToDevice, kf->s));
         } else {
             if ((st = stage_reserve(kf, bytes)) != MRS_OK) return st;
-            memcpy(kf->h_stage, points, bytes);
+            memcpy(kf->h_stage.get(), points, bytes);
             void* to = dst;
             if (!as_is) {
                 if ((st = raw.alloc(bytes, kf->s)) != MRS_OK) return st;
                 to = raw.p;
             }
-            MRS_HIP_TRY(hipMemcpyAsync(to, kf->h_stage, bytes, hipMemcpyHostToDevice, kf->s));
+            MRS_HIP_TRY(hipMemcpyAsync(to, kf->h_stage.get(), bytes, hipMemcpyHostToDevice, kf->s));
             src = to;
         }
         if (!as_is) {
@@ -447,8 +430,7 @@ int mrs_keyframes_append(mrs_keyframes* kf, const void* points, int32_t on_devic
             MRS_HIP_TRY(hipGetLastError());
         }
         if (on_device) {          // the caller may overwrite its buffer once ITS stream has passed this point
-            MRS_HIP_TRY(hipEventRecord(kf->ev_out, kf->s));
-            MRS_HIP_TRY(hipStreamWaitEvent((hipStream_t)stream, kf->ev_out, 0));
+            MRS_TRY(kf->s.release_to((hipStream_t)stream));
         } else {
             MRS_HIP_TRY(hipStreamSynchronize(kf->s));       // the staging buffer and the caller's memory are free again
         }

@@ -8,15 +8,15 @@
 #include <cmath>
 
 struct mrs_keyframes {
+    mrs::HandleStream s;                      // first: destroyed last, after the buffers whose work it carried
     mrs_ctx* ctx = nullptr;
     mrs::DeviceBuffer<float4> arena;
     std::vector<long long> offsets{0};        // [n + 1] first point of every keyframe
     std::vector<float> poses;                 // [n][16] row-major
-    void* h_stage = nullptr;                  // pinned: host points on their way in, the tables of a call, the offsets on their way out
-    size_t stage_bytes = 0;
-    hipStream_t s = nullptr;
-    hipEvent_t ev_in = nullptr, ev_out = nullptr;
+    mrs::PinnedBuffer<char> h_stage;          // host points on their way in, the tables of a call, the offsets on their way out
     std::mutex mu;
+
+    ~mrs_keyframes() { if (s) (void)hipStreamSynchronize(s); }      // nothing queued outlives the buffers
 };
 
 namespace mrs {
@@ -105,15 +105,11 @@ inline size_t round256(size_t b) { return (b + 255) & ~(size_t)255; }
 // the handle's pinned staging buffer grown to `bytes` (doubling); lock held
 inline int stage_reserve(mrs_keyframes* kf, size_t bytes)
 {
-    if (bytes <= kf->stage_bytes) return MRS_OK;
-    size_t cap = std::max(kf->stage_bytes, (size_t)1 << 20);
+    if (bytes <= kf->h_stage.capacity()) return MRS_OK;
+    size_t cap = std::max(kf->h_stage.capacity(), (size_t)1 << 20);
     while (cap < bytes) cap *= 2;
     MRS_HIP_TRY(hipStreamSynchronize(kf->s));
-    if (kf->h_stage) (void)hipHostFree(kf->h_stage);
-    kf->h_stage = nullptr; kf->stage_bytes = 0;
-    MRS_HIP_TRY(hipHostMalloc(&kf->h_stage, cap, hipHostMallocDefault));
-    kf->stage_bytes = cap;
-    return MRS_OK;
+    return kf->h_stage.reserve(bytes, cap);
 }
 
 // Room for `want` points: a new arena (doubling), what is there copied on the device; lock held.  Without `old` the call waits for the copy and
