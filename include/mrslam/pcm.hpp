@@ -87,6 +87,19 @@ public:
     }
     int rounds() const { return rounds_; }
 
+    // FMC::maxClique's max_clique_data, the `use_heuristics = false` side of GlobalMap's constructor: a MAXIMUM clique in ascending order,
+    // searched with a budget of max_nodes nodes.  proof(): 2 = size proven and list canonical, 1 = size proven, 0 = the budget ran out and
+    // the list is the best clique found (never smaller than solve()'s).  Unlike the reference it never returns a size with an empty list.
+    std::vector<int> solveExact(int64_t max_nodes = MRS_PCM_EXACT_DEFAULT_NODES)
+    {
+        std::vector<int32_t> members(std::max(size(), 1));
+        int32_t n = 0;
+        check(mrs_pcm_solve_exact(h_, max_nodes, members.data(), &n, &proof_, &nodes_), "mrs_pcm_solve_exact");
+        return std::vector<int>(members.begin(), members.begin() + n);
+    }
+    int proof() const { return proof_; }
+    int64_t nodes() const { return nodes_; }
+
     // the consistency matrix, [size][size] of 0 / 1
     std::vector<uint8_t> matrix() const
     {
@@ -105,6 +118,8 @@ private:
     mrs_ctx* ctx_ = nullptr;
     mrs_pcm* h_ = nullptr;
     int32_t rounds_ = 0;
+    int32_t proof_ = 0;
+    int64_t nodes_ = 0;
 };
 
 }  // namespace mrslam

@@ -1035,6 +1035,24 @@ int mrs_pcm_count(mrs_pcm* pcm, int32_t* h_count);
  * then the vertices in the order the greedy chain took them), h_n_clique its length (0 without loops, where the reference returns -1);
  * optional h_n_rounds: the speculative rounds it took (at most length + 1). */
 int mrs_pcm_solve(mrs_pcm* pcm, int32_t* h_clique, int32_t* h_n_clique, int32_t* h_n_rounds);
+/* The exact search expands at most MRS_PCM_EXACT_LAUNCH_NODES nodes per wave and launch in at most MRS_PCM_EXACT_MAX_WAVES waves, so a call
+ * may count up to MRS_PCM_EXACT_OVERSHOOT nodes more than its budget.  The default budget is about one second of search on an MI355X at
+ * the node rate measured on long searches, 27 000 to 74 000 nodes per second (profiles/pcm_exact_notes.md). */
+#define MRS_PCM_EXACT_LAUNCH_NODES 4096
+#define MRS_PCM_EXACT_MAX_WAVES 1024
+#define MRS_PCM_EXACT_OVERSHOOT 4194304
+#define MRS_PCM_EXACT_DEFAULT_NODES 50000
+/* A MAXIMUM clique of the current matrix, what FMC::maxClique(gio, 0, data) returns (findClique.cpp:29-154): h_clique
+ * int32 [count] receives, in ASCENDING order, the maximum clique whose members sorted descending form the lexicographically largest
+ * sequence; h_n_clique its size (0 without loops; [count - 1] without edges).  The search is a branch and bound with a budget of
+ * max_nodes nodes (a node: one vertex taken into the current clique).  h_proof: 2 = size proven and list canonical (bit-stable from run to
+ * run and over any split of the loops); 1 = size proven, the list is a clique of that size; 0 = the budget ran out first: the list is the
+ * best clique found, never smaller than mrs_pcm_solve's.  h_nodes: the nodes counted, at most max_nodes + MRS_PCM_EXACT_OVERSHOOT.
+ * max_nodes = 0: the heuristic's clique, ascending, proof 0, nodes 0.  max_nodes < 0 or a null pointer: MRS_ERR_ARG.  Unlike the
+ * reference, a call never returns a size with an empty list.  mrs_pcm_solve is not affected. */
+int mrs_pcm_solve_exact(mrs_pcm* pcm, int64_t max_nodes, int32_t* h_clique, int32_t* h_n_clique, int32_t* h_proof, int64_t* h_nodes);
+/* the search launches the last mrs_pcm_solve_exact of this handle made (for measurements) */
+int mrs_pcm_exact_launches(mrs_pcm* pcm, int64_t* h_launches);
 /* the consistency matrix, uint8 [count][count] of 0 / 1: symmetric, zero diagonal */
 int mrs_pcm_get_matrix(mrs_pcm* pcm, uint8_t* h_dense);
 /* Replaces the loops by `count` vertices with the given adjacency (uint8 [count][count], non-zero = edge), so that the clique stage can be

@@ -21,7 +21,9 @@
 #include "common.hpp"
 #include "pcm_pose.hpp"
 
+#include <algorithm>
 #include <cmath>
+#include <vector>
 
 namespace {
 
@@ -130,6 +132,229 @@ __global__ __launch_bounds__(kThreads) void k_pcm_greedy(const u64* __restrict__
     if (!list && lane == 0 && icc > max_clq) atomicMin(winner, ((u64)(unsigned)c << 32) | (unsigned)icc);
 }
 
+// ------------------------------------------------------------------ the exact maximum clique (mrs_pcm_solve_exact)
+//   seed    : the heuristic's size is the first incumbent;
+//   shrink  : k_pcm_peel, the k-core of the bit rows: a vertex with fewer than `need_deg` living neighbours dies, until nothing changes
+//             (the k-core is unique, so neither the order of the removals nor a stale read of `alive` changes the result);
+//   search  : k_pcm_exact, a wave per slot and a subproblem per top vertex c (c and its living smaller neighbours), handed out from L - 1
+//             down by a ticket counter.  Within a subproblem the depth-first search is strictly descending: a level holds its candidate
+//             set P (a 64-bit word per lane), the branch vertex is the highest of P (a ballot and two counts of leading zeros), and taking
+//             it is one coalesced row load and an AND.  A level is left when it is empty, when its size bound fails (d + |P| < need), or
+//             when its highest vertex lies below the level's colouring cut.  Phase 1 looks for a clique larger than the shared incumbent
+//             (need = best + 1, best rises by atomicMax: a hint that only tightens pruning), phase 2 for the first clique of the proven size
+//             omega in every subproblem (need = omega); the winner of phase 2 is the highest top vertex that finds one (atomicMax), which
+//             does not depend on the order of arrival.
+//   colour  : greedy sequential colouring of P in ASCENDING vertex order, class by class on the bit words.  A vertex of colour k has a
+//             neighbour of every lower colour below it, and P below any vertex m is properly coloured by the colours handed out so far.
+//             With k0 = need - d, only the classes 1 .. k0 - 1 are built: the lowest vertex they leave uncoloured is the cut, and a branch
+//             on any m below it cannot reach `need` (its candidates have k0 - 1 colours at most, itself included).  One colouring per level,
+//             not per child, and it keeps the descending order phase 2 needs.
+//   launches: a wave takes at most kExactSteps steps (vertices taken, levels left, vertices coloured, tickets) per launch and then stores
+//             its level; everything below is already in its stack, so that the host re-launches until no slot has work or the node budget
+//             is spent.  No wave waits for another.
+constexpr int kExactWaves = MRS_PCM_EXACT_MAX_WAVES, kExactSteps = MRS_PCM_EXACT_LAUNCH_NODES;
+constexpr int kIdle = -1, kRetired = -2, kFound = -3, kCutUnset = -1;
+constexpr size_t kExactStackBytes = (size_t)64 << 20;          // cap of all slots' stacks together; the number of slots follows from it
+static_assert((long long)kExactWaves * kExactSteps == MRS_PCM_EXACT_OVERSHOOT, "the overshoot is concurrent waves x the per-launch cap");
+static_assert(kExactWaves < (1 << 16),"the winner word of phase 2 is (top + 1) << 16 | slot");
+
+struct ExactStatus {
+    u64 nodes;          // vertices taken into a clique so far, both phases
+    int active;         // slots that still have work after this launch
+    int best;           // the incumbent's size
+    unsigned winner;    // phase 2: (top vertex + 1) << 16 | slot of the highest top vertex that found a clique of size omega; 0 = none
+    int ticket;         // the next subproblem is the top vertex L - 1 - ticket
+    int pad[2];
+};
+
+__device__ __forceinline__ u64 shfl64(u64 x, int src)
+{
+    const unsigned lo = (unsigned)__shfl((int)(unsigned)x, src, 64), hi = (unsigned)__shfl((int)(unsigned)(x >> 32), src, 64);
+    return ((u64)hi << 32) | lo;
+}
+
+__device__ __forceinline__ int wave_sum(int c)
+{
+    for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);
+    return c;
+}
+
+// a wave per vertex: dies if fewer than need_deg of its neighbours are alive
+__global__ __launch_bounds__(kThreads) void k_pcm_peel(const u64* __restrict__ rows, int L, int words, int need_deg, u64* alive, int* changed)
+{
+    const int lane = threadIdx.x & 63, u = blockIdx.x * kWaves + (threadIdx.x >> 6);
+    if (u >= L) return;
+    if (!((alive[u >> 6] >> (u & 63)) & 1ull)) return;
+    const int c = wave_sum(lane < words ? __popcll(rows[(size_t)u * words + lane] & alive[lane]) : 0);
+    if (lane == 0 && c < need_deg) {
+        atomicAnd(&alive[u >> 6], ~(1ull << (u & 63)));
+        *changed = 1;
+    }
+}
+
+// deg [L]: the living neighbours of a living vertex, 0 for a dead one; a wave per vertex
+__global__ __launch_bounds__(kThreads) void k_pcm_alive_degrees(const u64* __restrict__ rows, const u64* __restrict__ alive, int L, int words,
+                                                                int* __restrict__ deg)
+{
+    const int lane = threadIdx.x & 63, u = blockIdx.x * kWaves + (threadIdx.x >> 6);
+    if (u >= L) return;
+    const bool lives = (alive[u >> 6] >> (u & 63)) & 1ull;
+    const int c = wave_sum(lane < words && lives ? __popcll(rows[(size_t)u * words + lane] & alive[lane]) : 0);
+    if (lane == 0) deg[u] = c;
+}
+
+// One launch of the search: see above.  Per slot: top [1] (the top vertex, or kIdle / kRetired / kFound), depth [1], and maxd + 1 levels of
+// path / cut / stack (level d holds the candidates of the clique path [0, d)); phase 1 also keeps the largest clique the slot has found
+// (best_size, best_list).  A slot's state is written and read by lane-matched accesses of its own wave only.
+__global__ __launch_bounds__(kThreads) void k_pcm_exact(const u64* __restrict__ rows, const u64* __restrict__ alive, int L, int words, int maxd,
+                                                        int nslots, int phase, int omega, ExactStatus* st, int* s_top, int* s_depth, int* path,
+                                                        int* cut, u64* stack, int* s_best, int* best_list)
+{
+    const int lane = threadIdx.x & 63, slot = blockIdx.x * kWaves + (threadIdx.x >> 6);
+    if (slot >= nslots) return;
+    int v = s_top[slot];
+    if (v == kRetired || v == kFound) return;
+    int* mypath = path + (size_t)slot * (maxd + 1);
+    int* mycut = cut + (size_t)slot * (maxd + 1);
+    int* mybest = best_list + (size_t)slot * (maxd + 1);
+    u64* mystack = stack + (size_t)slot * (maxd + 1) * words;
+    const u64 A = lane < words ? alive[lane] : 0ull;
+    int d = 0, cutv = kCutUnset;
+    u64 P = 0ull;
+    if (v >= 0) {
+        d = s_depth[slot];                                       // 1 .. maxd, as stored below
+        P = lane < words ? mystack[(size_t)d * words + lane] : 0ull;
+        cutv = __shfl(lane == 0 ? mycut[d] : 0, 0, 64);
+    }
+    int need = phase == 1 ? __hip_atomic_load(&st->best, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + 1 : omega;
+    int win_top = -1;                                            // phase 2: the highest top vertex known to have found its clique
+    unsigned nodes = 0;
+    int tick = 0;
+    for (int step = 0; step < kExactSteps; ++step) {
+        if ((++tick & 15) == 0) {
+            if (phase == 1) {
+                need = __hip_atomic_load(&st->best, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + 1;
+            } else {
+                win_top = (int)(__hip_atomic_load(&st->winner, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >> 16) - 1;
+                if (v >= 0 && win_top > v) v = kIdle;            // a higher top vertex has won: this subproblem no longer matters
+            }
+        }
+        if (v < 0) {                                             // take the next subproblem
+            int t = 0;
+            if (lane == 0) t = atomicAdd(&st->ticket, 1);
+            t = __shfl(t, 0, 64);
+            const int c = L - 1 - t;
+            if (c < 0 || c < win_top) {                          // tickets only go down from here
+                v = kRetired;
+                break;
+            }
+            if (!((alive[c >> 6] >> (c & 63)) & 1ull)) continue;
+            const int w = c >> 6;
+            const u64 below = lane < w ? ~0ull : lane == w ? (1ull << (c & 63)) - 1ull : 0ull;
+            v = c;
+            d = 1;
+            P = (lane < words ? rows[(size_t)c * words + lane] : 0ull) & A & below;
+            cutv = kCutUnset;
+            if (lane == 0) mypath[0] = c;
+            ++nodes;
+            continue;
+        }
+        // level d: the clique path [0, d) and its candidates P, all of them below path [d - 1]
+        const u64 lanes = __ballot(P != 0ull);
+        bool leave = false;
+        int hi = 0, m = 0;
+        if (!lanes) {                                            // nothing extends the clique: it has d members
+            if (d >= need) {
+                if (phase == 1) {
+                    if (lane == 0) {
+                        atomicMax(&st->best, d);
+                        if (d > s_best[slot]) {
+                            s_best[slot] = d;
+                            for (int i = 0; i < kMaxLoops; ++i) {    // d <= maxd: lane 0 wrote the path, lane 0 copies it
+                                if (i >= d) break;
+                                mybest[i] = mypath[i];
+                            }
+                        }
+                    }
+                    need = d + 1;
+                } else {
+                    if (lane == 0) {
+                        s_depth[slot] = d;
+                        atomicMax(&st->winner, ((unsigned)(v + 1) << 16) | (unsigned)slot);
+                    }
+                    v = kFound;                                  // the path stays in the slot for the host
+                    break;
+                }
+            }
+            leave = true;
+        } else if (d + wave_sum(__popcll(P)) < need || d >= maxd) {     // the size bound; d >= maxd cannot happen with candidates left: a fence
+            leave = true;
+        } else {
+            if (cutv == kCutUnset) {                             // colour the level once
+                const int k0 = need - d;
+                cutv = 0;
+                if (k0 > 1) {
+                    u64 U = P;
+                    for (int k = 1; k < kMaxLoops + 1; ++k) {
+                        if (k >= k0 || !__ballot(U != 0ull)) break;
+                        u64 Q = U;
+                        for (int i = 0; i < kMaxLoops; ++i) {    // every pass colours one vertex
+                            const u64 ql = __ballot(Q != 0ull);
+                            if (!ql) break;
+                            const int lo = __ffsll((long long)ql) - 1;
+                            const int b = __ffsll((long long)shfl64(Q, lo)) - 1;
+                            const int x = 64 * lo + b;           // a bit of P: a living vertex, so x < L <= the rows allocated
+                            if (lane == lo) {
+                                U &= ~(1ull << b);
+                                Q &= ~(1ull << b);
+                            }
+                            Q &= ~(lane < words ? rows[(size_t)x * words + lane] : 0ull);
+                            ++step;
+                        }
+                    }
+                    const u64 ul = __ballot(U != 0ull);
+                    const int lo = ul ? __ffsll((long long)ul) - 1 : 0;
+                    const u64 word = shfl64(U, lo);
+                    cutv = ul ? 64 * lo + __ffsll((long long)word) - 1 : kMaxLoops;      // nothing left: no branch of this level can reach `need`
+                }
+            }
+            hi = 63 - __clzll((long long)lanes);
+            m = 64 * hi + 63 - __clzll((long long)shfl64(P, hi));    // a bit of P: a living vertex, so m < L <= the rows allocated
+            leave = m < cutv;
+        }
+        if (leave) {
+            if (--d == 0) {
+                v = kIdle;
+                continue;
+            }
+            P = lane < words ? mystack[(size_t)d * words + lane] : 0ull;
+            cutv = __shfl(lane == 0 ? mycut[d] : 0, 0, 64);
+            continue;
+        }
+        // take m: what stays of this level goes to the stack, the next level is P & N(m); here 1 <= d < maxd
+        if (lane == hi) P &= ~(1ull << (m & 63));
+        if (lane < words) mystack[(size_t)d * words + lane] = P;
+        if (lane == 0) {
+            mycut[d] = cutv;
+            mypath[d] = m;
+        }
+        P &= lane < words ? rows[(size_t)m * words + lane] : 0ull;
+        ++d;
+        cutv = kCutUnset;
+        ++nodes;
+    }
+    if (v >= 0 && lane < words) mystack[(size_t)d * words + lane] = P;      // 1 <= d <= maxd: the stack has maxd + 1 levels
+    if (lane == 0) {
+        s_top[slot] = v;
+        if (v >= 0) {
+            s_depth[slot] = d;
+            mycut[d] = cutv;
+        }
+        if (v >= 0 || v == kIdle) atomicAdd(&st->active, 1);
+        if (nodes) atomicAdd(&st->nodes, (u64)nodes);
+    }
+}
+
 inline unsigned blocks_for(long long items, int per_block) { return (unsigned)((items + per_block - 1) / per_block); }
 
 }  // namespace
@@ -144,6 +369,11 @@ struct mrs_pcm {
     mrs::DeviceBuffer<double> XA, XB, rec;
     mrs::DeviceBuffer<u64> rows, elig, winner;
     mrs::DeviceBuffer<int> deg, list;
+    // mrs_pcm_solve_exact only, allocated by its first call and sized by the matrix it met (ExactLayout)
+    mrs::DeviceBuffer<u64> x_alive, x_stack;
+    mrs::DeviceBuffer<int> x_ints;
+    mrs::DeviceBuffer<ExactStatus> x_status;
+    int64_t x_launches = 0;                  // launches of k_pcm_exact in the last mrs_pcm_solve_exact
 };
 
 namespace {
@@ -169,6 +399,96 @@ int pcm_fill_rows(mrs_pcm* p, int L0, int L1)
                            p->threshold, 0, L0, w0, nw - w0, p->words, p->rows.get());
     MRS_HIP_TRY(hipGetLastError());
     return MRS_OK;
+}
+
+// ---- host side of the exact search
+// the slots of k_pcm_exact: `ints` holds top | depth | best size [nslots] and path | cut | best list [nslots][maxd + 1]
+struct ExactLayout {
+    int nslots = 0, maxd = 0;
+    int *top = nullptr, *depth = nullptr, *best = nullptr, *path = nullptr, *cut = nullptr, *best_list = nullptr;
+};
+
+// maxd: an upper bound on the size of any clique the phase can hold.  The stacks take (maxd + 1) * words words per slot, kExactStackBytes
+// in all at most, and the number of slots follows from that.
+int pcm_exact_layout(mrs_pcm* p, int maxd, ExactLayout* lay)
+{
+    const size_t level = (size_t)(maxd + 1), per_slot = level * p->words;
+    size_t n = kExactStackBytes / (per_slot * sizeof(u64));
+    n = std::min<size_t>(std::min<size_t>(std::max<size_t>(n, 1), kExactWaves), (size_t)p->L);
+    MRS_TRY(p->x_stack.reserve(n * per_slot, n * per_slot));
+    const size_t ints = 3 * n + 3 * n * level;
+    MRS_TRY(p->x_ints.reserve(ints, ints));
+    MRS_TRY(p->x_status.reserve(1, 1));
+    lay->nslots = (int)n;
+    lay->maxd = maxd;
+    lay->top = p->x_ints.get();
+    lay->depth = lay->top + n;
+    lay->best = lay->depth + n;
+    lay->path = lay->best + n;
+    lay->cut = lay->path + n * level;
+    lay->best_list = lay->cut + n * level;
+    return MRS_OK;
+}
+
+// the need_deg-core of the matrix into x_alive -> the number of living vertices and the largest degree among them
+int pcm_exact_peel(mrs_pcm* p, int need_deg, int* n_alive, int* max_deg)
+{
+    const int L = p->L;
+    MRS_TRY(p->x_alive.reserve(64, 64));
+    u64 alive[64] = {};
+    for (int v = 0; v < L; ++v) alive[v >> 6] |= 1ull << (v & 63);
+    MRS_HIP_TRY(hipMemcpy(p->x_alive.get(), alive, sizeof(alive), hipMemcpyHostToDevice));
+    mrs::Scratch tmp;                                             // deg [L] | changed [1]
+    MRS_TRY(tmp.alloc((size_t)(L + 1) * sizeof(int), nullptr));
+    int* d_deg = tmp.as<int>();
+    int* d_changed = d_deg + L;
+    for (int round = 0; need_deg > 0 && round <= L; ++round) {    // every round but the last removes a vertex: at most L + 1 of them
+        MRS_HIP_TRY(hipMemsetAsync(d_changed, 0, sizeof(int), nullptr));
+        hipLaunchKernelGGL(k_pcm_peel, dim3(blocks_for(L, kWaves)), dim3(kThreads), 0, nullptr, p->rows.get(), L, p->words, need_deg, p->x_alive.get(),
+                           d_changed);
+        MRS_HIP_TRY(hipGetLastError());
+        int changed = 0;
+        MRS_HIP_TRY(hipMemcpy(&changed, d_changed, sizeof(int), hipMemcpyDeviceToHost));
+        if (!changed) break;
+    }
+    hipLaunchKernelGGL(k_pcm_alive_degrees, dim3(blocks_for(L, kWaves)), dim3(kThreads), 0, nullptr, p->rows.get(), p->x_alive.get(), L, p->words,
+                       d_deg);
+    MRS_HIP_TRY(hipGetLastError());
+    std::vector<int> deg(L);
+    MRS_HIP_TRY(hipMemcpy(deg.data(), d_deg, (size_t)L * sizeof(int), hipMemcpyDeviceToHost));
+    MRS_HIP_TRY(hipMemcpy(alive, p->x_alive.get(), sizeof(alive), hipMemcpyDeviceToHost));
+    *n_alive = 0;
+    for (int w = 0; w < 64; ++w) *n_alive += __builtin_popcountll(alive[w]);
+    *max_deg = *std::max_element(deg.begin(), deg.end());
+    return MRS_OK;
+}
+
+// launches of one phase until no slot has work left (*done) or the node budget is spent
+int pcm_exact_phase(mrs_pcm* p, const ExactLayout& lay, int phase, int omega, int64_t max_nodes, ExactStatus* hs, bool* done)
+{
+    constexpr long long kMaxLaunches = 1ll << 32;                // every launch takes a step in every slot that has work: a fence
+    *done = false;
+    MRS_HIP_TRY(hipMemsetAsync(lay.top, 0xff, (size_t)lay.nslots * sizeof(int), nullptr));      // kIdle
+    if (phase == 1) MRS_HIP_TRY(hipMemsetAsync(lay.best, 0, (size_t)lay.nslots * sizeof(int), nullptr));
+    hs->ticket = 0;
+    hs->winner = 0;
+    for (long long launch = 0; launch < kMaxLaunches; ++launch) {
+        if ((int64_t)hs->nodes >= max_nodes) return MRS_OK;
+        hs->active = 0;
+        MRS_HIP_TRY(hipMemcpy(p->x_status.get(), hs, sizeof(*hs), hipMemcpyHostToDevice));
+        hipLaunchKernelGGL(k_pcm_exact, dim3(blocks_for(lay.nslots, kWaves)), dim3(kThreads), 0, nullptr, p->rows.get(), p->x_alive.get(), p->L,
+                           p->words, lay.maxd, lay.nslots, phase, omega, p->x_status.get(), lay.top, lay.depth, lay.path, lay.cut,
+                           p->x_stack.get(), lay.best, lay.best_list);
+        MRS_HIP_TRY(hipGetLastError());
+        ++p->x_launches;
+        MRS_HIP_TRY(hipMemcpy(hs, p->x_status.get(), sizeof(*hs), hipMemcpyDeviceToHost));
+        if (hs->active == 0) {
+            *done = true;
+            return MRS_OK;
+        }
+    }
+    mrs::set_error("the exact clique search did not end within %lld launches", kMaxLaunches);
+    return MRS_ERR_HIP;
 }
 
 }  // namespace
@@ -321,6 +641,89 @@ int mrs_pcm_solve(mrs_pcm* pcm, int32_t* h_clique, int32_t* h_n_clique, int32_t*
     MRS_HIP_TRY(hipMemcpy(h_clique, pcm->list.get(), (size_t)max_clq * sizeof(int32_t), hipMemcpyDeviceToHost));
     *h_n_clique = max_clq;
     if (h_n_rounds) *h_n_rounds = rounds;
+    return MRS_OK;
+}
+
+int mrs_pcm_solve_exact(mrs_pcm* pcm, int64_t max_nodes, int32_t* h_clique, int32_t* h_n_clique, int32_t* h_proof, int64_t* h_nodes)
+{
+    MRS_REQUIRE(max_nodes >= 0, "max_nodes must not be negative");
+    MRS_REQUIRE(pcm && h_n_clique && h_proof && h_nodes, "null pointer");
+    const int L = pcm->L;
+    MRS_REQUIRE(h_clique || L == 0, "null pointer");
+    *h_n_clique = 0;
+    *h_proof = 2;
+    *h_nodes = 0;
+    pcm->x_launches = 0;
+    if (L == 0) return MRS_OK;
+    // the seed: the heuristic's clique, ascending
+    std::vector<int32_t> incumbent(L);
+    int32_t seed = 0;
+    MRS_TRY(mrs_pcm_solve(pcm, incumbent.data(), &seed, nullptr));
+    incumbent.resize(seed);
+    std::sort(incumbent.begin(), incumbent.end());
+    ExactStatus hs = {};
+    hs.best = seed;
+    const auto finish = [&](const std::vector<int32_t>& members, int proof) {
+        std::copy(members.begin(), members.end(), h_clique);
+        *h_n_clique = (int32_t)members.size();
+        *h_proof = proof;
+        *h_nodes = (int64_t)hs.nodes;
+        return MRS_OK;
+    };
+    if (max_nodes == 0) return finish(incumbent, 0);
+    MRS_HIP_TRY(hipSetDevice(pcm->ctx->device));
+
+    // phase 1: the size.  A member of a clique larger than the seed has at least `seed` neighbours among the members.
+    ExactLayout lay;
+    int n_alive = 0, max_deg = 0;
+    MRS_TRY(pcm_exact_peel(pcm, seed, &n_alive, &max_deg));
+    if (n_alive > 0) {
+        bool done = false;
+        MRS_TRY(pcm_exact_layout(pcm, std::min(n_alive, max_deg + 1), &lay));
+        MRS_TRY(pcm_exact_phase(pcm, lay, 1, 0, max_nodes, &hs, &done));
+        if (hs.best < seed || hs.best > lay.maxd) {
+            mrs::set_error("the exact clique search returned the size %d (seed %d, bound %d)", hs.best, seed, lay.maxd);
+            return MRS_ERR_HIP;
+        }
+        if (hs.best > seed) {                                     // the slot that found the incumbent holds its members
+            std::vector<int> sizes(lay.nslots);
+            MRS_HIP_TRY(hipMemcpy(sizes.data(), lay.best, sizes.size() * sizeof(int), hipMemcpyDeviceToHost));
+            const int slot = (int)(std::find(sizes.begin(), sizes.end(), hs.best) - sizes.begin());
+            if (slot == lay.nslots) {
+                mrs::set_error("no slot of the exact clique search holds the clique of size %d", hs.best);
+                return MRS_ERR_HIP;
+            }
+            incumbent.resize(hs.best);
+            MRS_HIP_TRY(hipMemcpy(incumbent.data(), lay.best_list + (size_t)slot * (lay.maxd + 1), (size_t)hs.best * sizeof(int32_t),
+                                  hipMemcpyDeviceToHost));
+            std::sort(incumbent.begin(), incumbent.end());
+        }
+        if (!done) return finish(incumbent, 0);
+    }
+    const int omega = hs.best;
+    if ((int64_t)hs.nodes >= max_nodes) return finish(incumbent, 1);
+
+    // phase 2: the canonical list.  A member of a clique of size omega has omega - 1 neighbours among the members.
+    bool done = false;
+    MRS_TRY(pcm_exact_peel(pcm, omega - 1, &n_alive, &max_deg));
+    MRS_TRY(pcm_exact_layout(pcm, omega, &lay));
+    MRS_TRY(pcm_exact_phase(pcm, lay, 2, omega, max_nodes, &hs, &done));
+    if (!done) return finish(incumbent, 1);
+    const int slot = (int)(hs.winner & 0xffffu);
+    if (hs.winner == 0 || slot >= lay.nslots) {
+        mrs::set_error("the exact clique search proved the size %d and found no clique of it", omega);
+        return MRS_ERR_HIP;
+    }
+    std::vector<int32_t> members(omega);
+    MRS_HIP_TRY(hipMemcpy(members.data(), lay.path + (size_t)slot * (lay.maxd + 1), (size_t)omega * sizeof(int32_t), hipMemcpyDeviceToHost));
+    std::reverse(members.begin(), members.end());                // the path is descending
+    return finish(members, 2);
+}
+
+int mrs_pcm_exact_launches(mrs_pcm* pcm, int64_t* h_launches)
+{
+    MRS_REQUIRE(pcm && h_launches, "null pointer");
+    *h_launches = pcm->x_launches;
     return MRS_OK;
 }
 

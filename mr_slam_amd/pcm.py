@@ -13,6 +13,8 @@ import numpy as np
 from . import _lib
 
 MAX_LOOPS = int(re.search(r"#define\s+MRS_PCM_MAX_LOOPS\s+(\d+)", open(_lib.HEADER).read())[1])
+EXACT_DEFAULT_NODES, EXACT_OVERSHOOT = (int(re.search(r"#define\s+MRS_PCM_EXACT_%s\s+(\d+)" % k, open(_lib.HEADER).read())[1])
+                                        for k in ("DEFAULT_NODES", "OVERSHOOT"))
 # getChiSquaredThreshold for 6 degrees of freedom (pairwise_consistency.cpp:7-38), keyed by round(100 p)
 _CHI2 = {1: 0.872, 5: 1.635, 10: 2.204, 25: 3.455, 50: 5.348, 75: 7.840}
 
@@ -61,13 +63,15 @@ class PcmGraph:
     """The loops of one robot pair on the device: `set_trajectories(XA, XB)`, `add_loops(ia, kb, Z)` (vertex numbers follow the order of
     addition; pass them in `reference_order` to number them as the reference does), `solve()` -> (member list in the reference's order,
     number of rejected loops).  `matrix()` / `distances()` read the consistency matrix and the distances behind it; `set_matrix(A)` puts a
-    given adjacency in place of the loops, for the clique stage alone.  `rounds` is the number of rounds the last solve took."""
+    given adjacency in place of the loops, for the clique stage alone.  `rounds` is the number of rounds the last solve took.
+    `solve_exact()` -> (a MAXIMUM clique in ascending order, number of rejected loops) with `proof` and `nodes`."""
 
     def __init__(self, capacity=MAX_LOOPS, p=0.01, threshold=None, device=0):
         self.device = int(device)
         self.capacity = int(capacity)
         self.threshold = chi2_threshold(p) if threshold is None else float(threshold)
         self.rounds = 0
+        self.proof, self.nodes, self.launches = 0, 0, 0
         self._h = C.c_void_p()
         _lib.load().mrs_pcm_create(_lib.ctx(self.device), self.capacity, self.threshold, C.byref(self._h))
 
@@ -107,6 +111,21 @@ class PcmGraph:
         n, rounds = C.c_int32(0), C.c_int32(0)
         _lib.load().mrs_pcm_solve(self._h, clique, C.byref(n), C.byref(rounds))
         self.rounds = rounds.value
+        return clique[:n.value].copy(), L - n.value
+
+    def solve_exact(self, max_nodes=None):
+        """-> (clique int32 [size] ASCENDING, n_rejected): a maximum clique, FMC::maxClique's member list (DESIGN.md 4.21), searched with a budget
+        of `max_nodes` nodes (None: EXACT_DEFAULT_NODES).  Sets `proof` (2: size proven and list canonical; 1: size proven; 0: the budget ran
+        out, the list is the best clique found) and `nodes`.  `solve()` and `rounds` are not affected."""
+        L = len(self)
+        clique = np.zeros(max(L, 1), np.int32)
+        n, proof, nodes = C.c_int32(0), C.c_int32(0), C.c_int64(0)
+        _lib.load().mrs_pcm_solve_exact(self._h, EXACT_DEFAULT_NODES if max_nodes is None else int(max_nodes), clique, C.byref(n),
+                                        C.byref(proof), C.byref(nodes))
+        self.proof, self.nodes = proof.value, nodes.value
+        launches = C.c_int64(0)
+        _lib.load().mrs_pcm_exact_launches(self._h, C.byref(launches))
+        self.launches = launches.value
         return clique[:n.value].copy(), L - n.value
 
     def matrix(self):
