@@ -1238,6 +1238,39 @@ int mrs_iss_saliency(mrs_ctx* ctx, const float* d_points, int32_t stride_floats,
 int mrs_iss_nonmax(mrs_ctx* ctx, const int64_t* d_offsets, int32_t batch, int64_t n, const int64_t* d_row_start, const int32_t* d_index,
                    int64_t total, const double* d_saliency, uint8_t* d_keep, mrs_stream stream);
 
+/* ------------------------------------------------------------------------------------
+ * RANSAC pose from point correspondences: per pair of a ragged batch, `hypotheses`
+ * seeded triples, pre-rejected by edge length and collinearity, fitted (Kabsch), scored by their integer inlier count over all
+ * correspondences of the pair, the best one (ties to the lowest hypothesis) refitted on its inliers.  All arithmetic in fp64 on the
+ * widened float32 coordinates; results do not depend on the batch a pair is in or on the call.
+ * ---------------------------------------------------------------------------------- */
+#define MRS_RANSAC_MAX_HYPOTHESES 65536
+#define MRS_RANSAC_MAX_REFINE 16
+
+typedef struct mrs_ransac_params {
+    int32_t hypotheses;       /* 1 .. MRS_RANSAC_MAX_HYPOTHESES triples per pair */
+    int32_t refine_iters;     /* 0 .. MRS_RANSAC_MAX_REFINE refits on the inlier set */
+    double max_distance;      /* inlier iff |R p + t - q|^2 <= max_distance^2; finite, > 0 */
+    double edge_similarity;   /* in [0, 1]: a triple needs dp >= s^2 dq and dq >= s^2 dp on every edge; 0 leaves only dp, dq > 0 */
+    double min_sin2;          /* in [0, 1): a triple needs |e1 x e2|^2 > min_sin2 |e1|^2 |e2|^2 on both sides */
+} mrs_ransac_params;
+
+/* d_src / d_dst float [total][stride_floats], xyz first: row m of d_src corresponds to row m of d_dst; d_offsets / h_offsets int64
+ * [n_pairs + 1], device and host copies of the same offsets, offsets[0] = 0, ascending, a pair's size below 2^31 - 1; n_pairs in
+ * 0 .. 65535; h_seeds one seed per pair.  d_T double [n_pairs][16] row-major; d_info int32 [n_pairs][4] = {inliers, best hypothesis,
+ * valid hypotheses, refits done}; d_mask uint8 [total] (may be NULL): 1 for the inliers of the returned pose.  A pair with fewer than 3
+ * correspondences or without a valid hypothesis gets the identity, {0, -1, valid, 0} and a zero mask.  A correspondence with a
+ * non-finite coordinate is never an inlier and rejects every triple that holds it.  MRS_ERR_ARG before any launch, nothing written,
+ * for a null pointer or a parameter outside its range.  Enqueued: one chain on `stream`, no host synchronisation. */
+int mrs_ransac_pose_batch(mrs_ctx* ctx, const float* d_src, const float* d_dst, int32_t stride_floats, const int64_t* d_offsets,
+                          const int64_t* h_offsets, int32_t n_pairs, const uint64_t* h_seeds, const mrs_ransac_params* params,
+                          double* d_T, int32_t* d_info, uint8_t* d_mask, mrs_stream stream);
+/* The same call with the times of its three stages between events (for measurements): h_stage_ms float [3] = milliseconds of the models
+ * (draw, pre-rejection, fit, compaction), the scoring and the refit.  Blocking. */
+int mrs_ransac_pose_batch_profile(mrs_ctx* ctx, const float* d_src, const float* d_dst, int32_t stride_floats, const int64_t* d_offsets,
+                                  const int64_t* h_offsets, int32_t n_pairs, const uint64_t* h_seeds, const mrs_ransac_params* params,
+                                  double* d_T, int32_t* d_info, uint8_t* d_mask, float* h_stage_ms, mrs_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

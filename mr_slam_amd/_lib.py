@@ -43,7 +43,7 @@ class BevCfg(C.Structure):
 _SCALARS = {"int": C.c_int32, "int32_t": C.c_int32, "int64_t": C.c_int64, "float": C.c_float, "double": C.c_double}
 _RESTYPES = {"int": C.c_int32, "double": C.c_double, "char*": C.c_char_p, "void": None}
 _ELEMENTS = {"float": ("float32", "complex64"), "double": ("float64", "complex128"), "int32_t": ("int32",),
-             "int64_t": ("int64",), "uint8_t": ("uint8",)}      # void and the opaque types take any element type
+             "int64_t": ("int64",), "uint8_t": ("uint8",), "uint64_t": ("uint64",)}      # void and the opaque types take any element type
 
 
 def parse_header(path):

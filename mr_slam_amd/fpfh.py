@@ -1,12 +1,14 @@
 """FPFH on device tensors (RING_ros/FPFH.py): all neighbours within a radius as CSR rows, the SPFH of every point, the FPFH of keypoints,
-ISS keypoints and a nearest-descriptor match.
+ISS keypoints, a nearest-descriptor match, the correspondences it gives and the RANSAC pose from correspondences.
 
 Thin host logic over the C ABI (mrs_radius_*, mrs_fpfh_*, mrs_iss_*, mrs_signature_knn); there is no CPU fallback.  Points are a packed
 [N, stride >= 3] float32 device tensor, the clouds of a ragged batch one after the other, with int64 offsets [batch + 1] starting at 0;
 normals are [N, 3] float32.  Float32 inputs are widened to float64 before anything is computed.  Rows are (row_start int64 [N + 1], index
 int32 [total]) in the caller's point order, every row ascending, CLOUD-LOCAL indices.  The contract, the summation orders and the named
-deviations from the reference (a neighbour at distance 0, an empty histogram, a keypoint without neighbours) are in DESIGN.md 4.20.
+deviations from the reference (a neighbour at distance 0, an empty histogram, a keypoint without neighbours) are in DESIGN.md 4.20; the
+RANSAC contract (draw, pre-rejection, scoring, refit) is in DESIGN.md 4.22.
 """
+import ctypes as C
 import re
 
 import numpy as np
@@ -17,6 +19,13 @@ from . import _lib
 DEFAULT_BINS = 5
 MAX_BINS = int(re.search(r"#define\s+MRS_FPFH_MAX_BINS\s+(\d+)", open(_lib.HEADER).read())[1])
 MATCH_MAX_K = 32
+RANSAC_MAX_HYPOTHESES = int(re.search(r"#define\s+MRS_RANSAC_MAX_HYPOTHESES\s+(\d+)", open(_lib.HEADER).read())[1])
+
+
+class RansacParams(C.Structure):
+    """mrs_ransac_params"""
+    _fields_ = [("hypotheses", C.c_int32), ("refine_iters", C.c_int32), ("max_distance", C.c_double), ("edge_similarity", C.c_double),
+                ("min_sin2", C.c_double)]
 
 
 def _check_bins(bins):
@@ -166,3 +175,47 @@ def match(a, b, k=1):
     if qa.shape[0] and qb.shape[0]:
         _lib.load().mrs_signature_knn(_lib.ctx(d), qa, qa.shape[0], qb, qb.shape[0], qa.shape[1], k, index, dist2, _lib.current_stream(d))
     return index, dist2
+
+
+def correspondences(fa, fb, k=1, mutual=False):
+    """index pairs (ia, ib int64 device tensors) from the descriptors of two keypoint sets: every row i of fa with each of its k nearest
+    rows j of fb (match: ascending distance, ties to the lower index), i ascending.  mutual=True keeps i -> j only if the nearest row
+    of fa for j is i.  Plain torch over match(); gather the points with them for ransac_pose."""
+    index, _ = match(fa, fb, k)
+    ia = torch.arange(index.shape[0], device=index.device, dtype=torch.int64).repeat_interleave(index.shape[1])
+    ib = index.reshape(-1).to(torch.int64)
+    keep = ib >= 0
+    if mutual and fa.shape[0] and fb.shape[0]:
+        back, _ = match(fb, fa, 1)
+        keep &= back[:, 0].to(torch.int64)[ib.clamp(min=0)] == ia
+    return ia[keep], ib[keep]
+
+
+def ransac_pose(src, dst, offsets, max_distance, seeds=None, hypotheses=4096, edge_similarity=0.9, min_sin2=1e-6, refine_iters=3,
+                return_mask=False, profile=False):
+    """RANSAC pose of every pair of a ragged batch from point correspondences: src / dst packed [total, stride >= 3]
+    float32, row m of src corresponds to row m of dst; offsets int64 [P + 1]; seeds one uint64 per pair (0 .. P - 1 when None).
+    -> (T float64 [P, 4, 4] with dst ~ T src, info int32 [P, 4] = inliers, best hypothesis, valid hypotheses, refits done[, mask uint8
+    [total]]) on the device.  A pair without a pose (fewer than 3 correspondences, every triple rejected) gets the identity and
+    info = (0, -1, valid, 0).  Enqueued on the current stream; a pair's result does not depend on the batch it is in.
+    profile=True (measurements; blocking) appends the milliseconds of the three stages (models, score, refit) to the result."""
+    d, p = _points(src)
+    q = dst.detach().to(p.device, torch.float32).contiguous()
+    assert q.shape == p.shape, (tuple(p.shape), tuple(q.shape))
+    h_off, d_off = _offsets(offsets, p)
+    P = h_off.numel() - 1
+    h_seeds = np.arange(P, dtype=np.uint64) if seeds is None else np.ascontiguousarray(np.asarray(seeds).astype(np.uint64)).reshape(-1)
+    assert h_seeds.size == P, (h_seeds.size, P)
+    par = RansacParams(int(hypotheses), int(refine_iters), float(max_distance), float(edge_similarity), float(min_sin2))
+    T = torch.empty((P, 4, 4), dtype=torch.float64, device=p.device)
+    info = torch.empty((P, 4), dtype=torch.int32, device=p.device)
+    mask = torch.empty(p.shape[0], dtype=torch.uint8, device=p.device) if return_mask else None
+    out = (T, info, mask) if return_mask else (T, info)
+    if profile:
+        ms = np.zeros(3, np.float32)
+        _lib.load().mrs_ransac_pose_batch_profile(_lib.ctx(d), p, q, p.shape[1], d_off, h_off, P, h_seeds, C.byref(par), T, info, mask, ms,
+                                                  _lib.current_stream(d))
+        return out + (ms,)
+    _lib.load().mrs_ransac_pose_batch(_lib.ctx(d), p, q, p.shape[1], d_off, h_off, P, h_seeds, C.byref(par), T, info, mask,
+                                      _lib.current_stream(d))
+    return out
