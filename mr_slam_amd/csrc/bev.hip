@@ -634,7 +634,7 @@ int host_sector(int quad, float q, float gap_sector)
 
 inline float bits_to_float(uint32_t u) { float f; memcpy(&f, &u, 4); return f; }
 
-int build_sector_lut(mrs_ctx* ctx, int S, mrs::SectorLut& lut)
+int build_sector_lut(int S, mrs::SectorLut& lut)
 {
     const float gap = (float)(360.0 / (float)S);
     std::vector<float> thr[4];
@@ -674,11 +674,10 @@ int build_sector_lut(mrs_ctx* ctx, int S, mrs::SectorLut& lut)
             hv[quad * longest + j] = val[quad][j];
         }
     }
-    MRS_HIP_TRY(hipMalloc(&lut.d_thr, ht.size() * sizeof(float)));
-    MRS_HIP_TRY(hipMalloc(&lut.d_val, hv.size() * sizeof(int)));
-    MRS_HIP_TRY(hipMemcpy(lut.d_thr, ht.data(), ht.size() * sizeof(float), hipMemcpyHostToDevice));
-    MRS_HIP_TRY(hipMemcpy(lut.d_val, hv.data(), hv.size() * sizeof(int), hipMemcpyHostToDevice));
-    (void)ctx;
+    MRS_TRY(lut.d_thr.reserve(ht.size(), ht.size()));
+    MRS_TRY(lut.d_val.reserve(hv.size(), hv.size()));
+    MRS_HIP_TRY(hipMemcpy(lut.d_thr.get(), ht.data(), ht.size() * sizeof(float), hipMemcpyHostToDevice));
+    MRS_HIP_TRY(hipMemcpy(lut.d_val.get(), hv.data(), hv.size() * sizeof(int), hipMemcpyHostToDevice));
     return MRS_OK;
 }
 
@@ -703,13 +702,12 @@ int make_polar(mrs_ctx* ctx, const mrs_bev_cfg* c, PolarP& p)
         std::lock_guard<std::mutex> g(ctx->mu);
         auto it = ctx->sector_luts.find(p.S);
         if (it == ctx->sector_luts.end()) {
-            mrs::SectorLut lut;
-            const int st = build_sector_lut(ctx, p.S, lut);
-            if (st != MRS_OK) return st;
-            it = ctx->sector_luts.emplace(p.S, lut).first;
+            mrs::SectorLut lut;      // a failed build frees what it had allocated
+            MRS_TRY(build_sector_lut(p.S, lut));
+            it = ctx->sector_luts.emplace(p.S, std::move(lut)).first;
         }
-        p.thr = it->second.d_thr;
-        p.val = it->second.d_val;
+        p.thr = it->second.d_thr.get();
+        p.val = it->second.d_val.get();
         p.stride = it->second.stride;
         for (int q = 0; q < 4; ++q) p.cnt[q] = it->second.cnt[q];
     }

@@ -33,38 +33,27 @@ const char* dev_env(const char* name)
     return on ? v : nullptr;
 }
 
-int side_acquire(mrs_ctx* ctx, SideSlot* out)
+int side_acquire(mrs_ctx* ctx, std::unique_ptr<SideSlot>* out)
 {
     {
         std::lock_guard<std::mutex> lk(ctx->side_mu);
         if (!ctx->side_free.empty()) {
-            *out = ctx->side_free.back();
+            *out = std::move(ctx->side_free.back());
             ctx->side_free.pop_back();
             return MRS_OK;
         }
     }
-    SideSlot sl;
-    hipError_t e = hipStreamCreateWithFlags(&sl.stream, hipStreamNonBlocking);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&sl.fork, hipEventDisableTiming);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&sl.join, hipEventDisableTiming);
-    if (e == hipSuccess) e = hipHostMalloc(&sl.pinned, kSidePinnedInts * sizeof(int), hipHostMallocDefault);
-    if (e != hipSuccess) {
-        if (sl.pinned) (void)hipHostFree(sl.pinned);
-        if (sl.join) (void)hipEventDestroy(sl.join);
-        if (sl.fork) (void)hipEventDestroy(sl.fork);
-        if (sl.stream) (void)hipStreamDestroy(sl.stream);
-        set_error("side stream slot: %s", hipGetErrorString(e));
-        return MRS_ERR_HIP;
-    }
-    *out = sl;
+    std::unique_ptr<SideSlot> sl(new SideSlot());      // an early return deletes it: every part frees itself
+    MRS_TRY(sl->create());
+    *out = std::move(sl);
     return MRS_OK;
 }
 
-void side_release(mrs_ctx* ctx, const SideSlot& slot)
+void side_release(mrs_ctx* ctx, std::unique_ptr<SideSlot> slot)
 {
-    if (!slot.stream) return;
+    if (!slot) return;
     std::lock_guard<std::mutex> lk(ctx->side_mu);
-    ctx->side_free.push_back(slot);
+    ctx->side_free.push_back(std::move(slot));
 }
 
 // ---- scratch allocator (see common.hpp) -------------------------------------------------------------------------
@@ -242,21 +231,6 @@ int mrs_ctx_destroy(mrs_ctx* ctx)
 {
     if (!ctx) return MRS_OK;
     (void)hipSetDevice(ctx->device);
-    for (auto& kv : ctx->sector_luts) {
-        if (kv.second.d_thr) (void)hipFree(kv.second.d_thr);
-        if (kv.second.d_val) (void)hipFree(kv.second.d_val);
-    }
-    for (auto& kv : ctx->twiddles)
-        if (kv.second) (void)hipFree(kv.second);
-    if (ctx->pointfeat_free)
-        for (auto& kv : ctx->pointfeat_cache) ctx->pointfeat_free(kv.second);
-    for (auto& sl : ctx->side_free) {
-        mrs::scratch_forget_stream(sl.stream);               // waits for the stream
-        (void)hipHostFree(sl.pinned);
-        (void)hipEventDestroy(sl.join);
-        (void)hipEventDestroy(sl.fork);
-        (void)hipStreamDestroy(sl.stream);
-    }
     delete ctx;
     return MRS_OK;
 }

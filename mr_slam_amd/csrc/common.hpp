@@ -7,6 +7,7 @@
 #include <cstdio>
 #include <cstring>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <vector>
 
@@ -167,19 +168,68 @@ private:
     size_t cap_ = 0;
 };
 
-// Owner of one event without timing (created by create(), destroyed by the destructor; neither copied nor moved).
+// Owner of one event (created by create(), destroyed by the destructor; neither copied nor moved): without timing unless create() is given
+// hipEventDefault.
 struct Event {
     hipEvent_t e = nullptr;
     Event() = default;
     Event(const Event&) = delete;
     Event& operator=(const Event&) = delete;
     ~Event() { if (e) (void)hipEventDestroy(e); }
-    int create()
+    int create(unsigned flags = hipEventDisableTiming)
     {
-        MRS_HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        MRS_HIP_TRY(hipEventCreateWithFlags(&e, flags));
         return MRS_OK;
     }
     operator hipEvent_t() const { return e; }
+};
+
+// The development aid "events between the steps of a call" (MRS_DEV=1 with the entry point's MRS_*_TIMING switch): mark(i) records timed
+// event i on the stream, ms(from) is the time from event `from` to event from + 1, or 0 when either is missing.  Switched off it makes no
+// runtime call at all; switched on, a call that fails only costs a figure.  The events are destroyed on every way out.
+class StageMarks {
+public:
+    static constexpr int kMax = 8;
+    StageMarks(bool on, hipStream_t s) : on_(on), s_(s) {}
+    explicit operator bool() const { return on_; }
+    void mark(int i)
+    {
+        if (on_ && hipEventCreate(&ev_[i].e) == hipSuccess) (void)hipEventRecord(ev_[i], s_);
+    }
+    float ms(int from) const
+    {
+        float t = 0.0f;
+        if (ev_[from].e && ev_[from + 1].e) (void)hipEventElapsedTime(&t, ev_[from], ev_[from + 1]);
+        return t;
+    }
+
+private:
+    bool on_;
+    hipStream_t s_;
+    Event ev_[kMax];
+};
+
+// The two timed events of a profiling entry point, and the time of one launch averaged over `reps` of them.
+struct RepTimer {
+    Event e0, e1;
+    int create()
+    {
+        MRS_TRY(e0.create(hipEventDefault));
+        return e1.create(hipEventDefault);
+    }
+    template <class F>
+    int timed(float& ms, int reps, hipStream_t s, F&& launch)
+    {
+        launch();                                     // warm
+        MRS_HIP_TRY(hipEventRecord(e0, s));
+        for (int r = 0; r < reps; ++r) launch();
+        MRS_HIP_TRY(hipEventRecord(e1, s));
+        MRS_HIP_TRY(hipEventSynchronize(e1));
+        MRS_HIP_TRY(hipGetLastError());
+        MRS_HIP_TRY(hipEventElapsedTime(&ms, e0, e1));
+        ms /= (float)reps;
+        return MRS_OK;
+    }
 };
 
 // The non-blocking stream all work of one handle runs on, with the event pair that orders it against a caller's stream.  Stands in for its
@@ -225,8 +275,8 @@ struct HandleStream {
 // Device lookup table that reproduces the reference's sector() step function exactly
 // (built on the host with the host libm, see bev.hip).
 struct SectorLut {
-    float* d_thr = nullptr;  // [4][stride] ascending change points of q=|y|/|x| per quadrant
-    int* d_val = nullptr;    // [4][stride] sector value from thr[j] on
+    DeviceBuffer<float> d_thr;  // [4][stride] ascending change points of q=|y|/|x| per quadrant
+    DeviceBuffer<int> d_val;    // [4][stride] sector value from thr[j] on
     int stride = 0;
     int cnt[4] = {0, 0, 0, 0};
 };
@@ -249,30 +299,35 @@ namespace mrs {
 // A second stream + fork / join events + a small pinned buffer, kept in a per-context pool: a registration of one pair (the nodes' shape)
 // borrows one for the duration of mrs_gicp_batch_align.  Creating them per handle cost 0.4 ms per FastGICP object (the nodes construct one
 // per registration, main_RING.py:84); concurrent callers (three rospy callback threads) each get their own slot.
-struct SideSlot {
-    hipStream_t stream = nullptr;
-    hipEvent_t fork = nullptr, join = nullptr;
-    int* pinned = nullptr;      // kSidePinnedInts ints
-};
 constexpr int kSidePinnedInts = 64;
-int side_acquire(mrs_ctx* ctx, SideSlot* out);   // MRS_OK / MRS_ERR_HIP
-void side_release(mrs_ctx* ctx, const SideSlot& slot);
+struct SideSlot {
+    HandleStream stream;        // its ev_in is the fork event, its ev_out the join event
+    PinnedBuffer<int> pinned;   // kSidePinnedInts ints
+    int create()
+    {
+        MRS_TRY(stream.create());
+        return pinned.reserve(kSidePinnedInts, kSidePinnedInts);
+    }
+};
+int side_acquire(mrs_ctx* ctx, std::unique_ptr<SideSlot>* out);   // MRS_OK / MRS_ERR_HIP
+void side_release(mrs_ctx* ctx, std::unique_ptr<SideSlot> slot);  // an empty pointer is ignored
 }  // namespace mrs
 
+// mrs_ctx_destroy deletes the context with its device current.  Members are destroyed in reverse order of declaration, and the order below is
+// chosen for that: first the tables (sector_luts, then twiddles), then the point-feature cache, then the side slots.
 struct mrs_ctx {
-    std::mutex side_mu;
-    std::vector<mrs::SideSlot> side_free;
     int device = 0;
     int num_cu = 0;
     size_t lds_bytes = 0;
-    std::mutex mu;
-    std::map<int, mrs::SectorLut> sector_luts;  // keyed by num_sector
-    // device-resident constant tables for the correlation / Radon kernels (lazily built)
-    std::map<int, float*> twiddles;             // keyed by FFT length
+    std::mutex side_mu;
+    std::vector<std::unique_ptr<mrs::SideSlot>> side_free;
     // mrs_pointfeat_batch keeps its Morton-ordered cloud container between calls (keyed by the number of scans per call, at most 4 sizes):
     // creating and freeing ~1.5 GB of device buffers per call cost as much as the kernels on some boxes.  One caller at a time uses a cached
-    // container (try_lock); a concurrent caller works on a temporary one.
+    // container (try_lock); a concurrent caller works on a temporary one.  gicp.hip binds each container's deleter when it caches it.
     std::mutex pointfeat_mu;
-    std::map<int, void*> pointfeat_cache;
-    void (*pointfeat_free)(void*) = nullptr;    // set by gicp.hip when it caches a container
+    std::map<int, std::shared_ptr<void>> pointfeat_cache;
+    std::mutex mu;
+    // device-resident constant tables for the correlation / Radon kernels (lazily built)
+    std::map<int, mrs::DeviceBuffer<float>> twiddles;   // keyed by FFT length
+    std::map<int, mrs::SectorLut> sector_luts;          // keyed by num_sector
 };

@@ -22,8 +22,8 @@ struct mrs_elev_map {
     mrs_ctx* ctx = nullptr;
     int L = 0;
     float res = 0, mahal_thr = 0, obstacle_thr = 0;
-    float* lowest = nullptr; float* elevation = nullptr; float* variance = nullptr; float* intensity = nullptr; float* traver = nullptr;
-    int* cr = nullptr; int* cg = nullptr; int* cb = nullptr;
+    mrs::DeviceBuffer<float> lowest, elevation, variance, intensity, traver;      // L * L cells each
+    mrs::DeviceBuffer<int> cr, cg, cb;
     float central[2] = {0, 0};
     int start[2] = {0, 0};
     float sensor_z = 0;
@@ -392,17 +392,15 @@ int mrs_elev_create(mrs_ctx* ctx, int32_t length, float resolution, float mahala
     MRS_REQUIRE(length > 0 && length <= 8192 && resolution > 0.0f, "bad map geometry");
     *out = nullptr;
     MRS_HIP_TRY(hipSetDevice(ctx->device));
-    mrs_elev_map* m = new mrs_elev_map();
+    std::unique_ptr<mrs_elev_map> m(new mrs_elev_map());      // an early return deletes it: every layer frees itself
     m->ctx = ctx; m->L = length; m->res = resolution; m->mahal_thr = mahalanobis_threshold; m->obstacle_thr = obstacle_threshold;
     const size_t cells = (size_t)length * length;
-    float** fp[5] = {&m->lowest, &m->elevation, &m->variance, &m->intensity, &m->traver};
-    int** ip[3] = {&m->cr, &m->cg, &m->cb};
-    for (auto p : fp) MRS_HIP_TRY(hipMalloc(p, cells * 4));
-    for (auto p : ip) MRS_HIP_TRY(hipMalloc(p, cells * 4));
-    hipLaunchKernelGGL(k_elev_fill, dim3(nb((int)cells)), dim3(256), 0, nullptr, m->lowest, m->elevation, m->variance, m->intensity,
-                       m->traver, m->cr, m->cg, m->cb, (int)cells, 0);
+    for (auto* l : {&m->lowest, &m->elevation, &m->variance, &m->intensity, &m->traver}) MRS_TRY(l->reserve(cells, cells));
+    for (auto* l : {&m->cr, &m->cg, &m->cb}) MRS_TRY(l->reserve(cells, cells));
+    hipLaunchKernelGGL(k_elev_fill, dim3(nb((int)cells)), dim3(256), 0, nullptr, m->lowest.get(), m->elevation.get(), m->variance.get(), m->intensity.get(),
+                       m->traver.get(), m->cr.get(), m->cg.get(), m->cb.get(), (int)cells, 0);
     MRS_HIP_TRY(hipDeviceSynchronize());
-    *out = m;
+    *out = m.release();
     return MRS_OK;
 }
 
@@ -410,10 +408,6 @@ int mrs_elev_destroy(mrs_elev_map* m)
 {
     if (!m) return MRS_OK;
     (void)hipSetDevice(m->ctx->device);
-    float* fp[5] = {m->lowest, m->elevation, m->variance, m->intensity, m->traver};
-    int* ip[3] = {m->cr, m->cg, m->cb};
-    for (auto p : fp) if (p) (void)hipFree(p);
-    for (auto p : ip) if (p) (void)hipFree(p);
     delete m;
     return MRS_OK;
 }
@@ -433,8 +427,8 @@ int mrs_elev_move(mrs_elev_map* m, const float* h_position3, float* h_central2, 
     }
     const int L = m->L, cells = L * L;
     auto clear = [&](int start, int shift, bool row) {
-        hipLaunchKernelGGL(k_elev_clear_region, dim3(nb(L * shift)), dim3(256), 0, nullptr, m->elevation, m->variance, m->intensity,
-                           m->cr, m->cg, m->cb, L, start, shift, row ? 1 : 0);
+        hipLaunchKernelGGL(k_elev_clear_region, dim3(nb(L * shift)), dim3(256), 0, nullptr, m->elevation.get(), m->variance.get(), m->intensity.get(),
+                           m->cr.get(), m->cg.get(), m->cb.get(), L, start, shift, row ? 1 : 0);
     };
     for (int i = 0; i < 2; ++i) {
         if (ishift[i] != 0) {
@@ -442,8 +436,8 @@ int mrs_elev_move(mrs_elev_map* m, const float* h_position3, float* h_central2, 
             // whose `indexShift >= length` (:1031) sends a shift <= -L into the partial clear with a region longer than the
             // map: undefined there (it writes past every layer).
             if (std::abs(ishift[i]) >= L) {
-                hipLaunchKernelGGL(k_elev_fill, dim3(nb(cells)), dim3(256), 0, nullptr, m->lowest, m->elevation, m->variance,
-                                   m->intensity, m->traver, m->cr, m->cg, m->cb, cells, 1);
+                hipLaunchKernelGGL(k_elev_fill, dim3(nb(cells)), dim3(256), 0, nullptr, m->lowest.get(), m->elevation.get(), m->variance.get(),
+                                   m->intensity.get(), m->traver.get(), m->cr.get(), m->cg.get(), m->cb.get(), cells, 1);
             } else {
                 const int sign = ishift[i] > 0 ? 1 : -1;
                 const int s0 = m->start[i] - (sign > 0 ? 1 : 0);
@@ -496,7 +490,7 @@ int mrs_elev_process_points(mrs_elev_map* m, int32_t n, const float* h_x, const 
     mrs::Scratch keys, perm;
     st = bucket(dgi, n, m->L * m->L, s, keys, perm);
     if (st != MRS_OK) return st;
-    hipLaunchKernelGGL(k_elev_lowest, dim3(nb(n)), dim3(256), 0, s, keys.as<unsigned>(), perm.as<int>(), n, dzt, dv, m->lowest);
+    hipLaunchKernelGGL(k_elev_lowest, dim3(nb(n)), dim3(256), 0, s, keys.as<unsigned>(), perm.as<int>(), n, dzt, dv, m->lowest.get());
     MRS_HIP_TRY(hipGetLastError());
     MRS_HIP_TRY(hipMemcpyAsync(h_var, dv, (size_t)n * 4, hipMemcpyDeviceToHost, s));
     MRS_HIP_TRY(hipMemcpyAsync(h_x_ts, dxt, (size_t)n * 4, hipMemcpyDeviceToHost, s));
@@ -527,8 +521,8 @@ int mrs_elev_fuse(mrs_elev_map* m, int32_t n, const int32_t* h_index, const int3
     st = bucket(di, n, m->L * m->L, s, keys, perm);
     if (st != MRS_OK) return st;
     hipLaunchKernelGGL(k_elev_fuse, dim3(nb(n)), dim3(256), 0, s, keys.as<unsigned>(), perm.as<int>(), n, dr, dg, db, dit, dh, dv,
-                       m->elevation, m->variance, m->intensity, m->cr, m->cg, m->cb);
-    hipLaunchKernelGGL(k_elev_var_floor, dim3(nb(m->L * m->L)), dim3(256), 0, s, m->variance, m->L * m->L);
+                       m->elevation.get(), m->variance.get(), m->intensity.get(), m->cr.get(), m->cg.get(), m->cb.get());
+    hipLaunchKernelGGL(k_elev_var_floor, dim3(nb(m->L * m->L)), dim3(256), 0, s, m->variance.get(), m->L * m->L);
     MRS_HIP_TRY(hipGetLastError());
     MRS_HIP_TRY(hipStreamSynchronize(s));
     return MRS_OK;
@@ -538,7 +532,7 @@ int mrs_elev_mapvar_update(mrs_elev_map* m, float var_update)  // Mapvar_update 
 {
     MRS_REQUIRE(m, "null handle");
     MRS_HIP_TRY(hipSetDevice(m->ctx->device));
-    hipLaunchKernelGGL(k_elev_var_add, dim3(nb(m->L * m->L)), dim3(256), 0, nullptr, m->variance, m->L * m->L, var_update);
+    hipLaunchKernelGGL(k_elev_var_add, dim3(nb(m->L * m->L)), dim3(256), 0, nullptr, m->variance.get(), m->L * m->L, var_update);
     MRS_HIP_TRY(hipGetLastError());
     return MRS_OK;
 }
@@ -556,8 +550,8 @@ int mrs_elev_map_feature(mrs_elev_map* m, float* h_elevation, float* h_var, int3
     if (st != MRS_OK) return st;
     float* oe = buf.as<float>(); float* ov = oe + cells; float* oro = ov + cells; float* osl = oro + cells; float* otr = osl + cells; float* oin = otr + cells;
     int* orr = reinterpret_cast<int*>(oin + cells); int* og = orr + cells; int* ob = og + cells;
-    hipLaunchKernelGGL(k_elev_feature, dim3(nb(cells)), dim3(256), 0, s, frame_of(m), m->elevation, m->variance, m->intensity, m->cr, m->cg,
-                       m->cb, m->traver, oe, ov, orr, og, ob, oro, osl, otr, oin);
+    hipLaunchKernelGGL(k_elev_feature, dim3(nb(cells)), dim3(256), 0, s, frame_of(m), m->elevation.get(), m->variance.get(), m->intensity.get(), m->cr.get(), m->cg.get(),
+                       m->cb.get(), m->traver.get(), oe, ov, orr, og, ob, oro, osl, otr, oin);
     MRS_HIP_TRY(hipGetLastError());
     void* dst[9] = {h_elevation, h_var, h_rough, h_slope, h_traver, h_intensity, h_colorR, h_colorG, h_colorB};
     const void* src[9] = {oe, ov, oro, osl, otr, oin, orr, og, ob};
@@ -572,9 +566,9 @@ int mrs_elev_raytracing(mrs_elev_map* m)
     MRS_REQUIRE(m, "null handle");
     MRS_HIP_TRY(hipSetDevice(m->ctx->device));
     const int cells = m->L * m->L;
-    hipLaunchKernelGGL(k_elev_raytrace, dim3(nb(cells)), dim3(256), 0, nullptr, frame_of(m), m->obstacle_thr, m->sensor_z, m->traver,
-                       m->lowest, m->variance, m->elevation);
-    hipLaunchKernelGGL(k_fill_f, dim3(nb(cells)), dim3(256), 0, nullptr, m->lowest, cells, 10.0f);
+    hipLaunchKernelGGL(k_elev_raytrace, dim3(nb(cells)), dim3(256), 0, nullptr, frame_of(m), m->obstacle_thr, m->sensor_z, m->traver.get(),
+                       m->lowest.get(), m->variance.get(), m->elevation.get());
+    hipLaunchKernelGGL(k_fill_f, dim3(nb(cells)), dim3(256), 0, nullptr, m->lowest.get(), cells, 10.0f);
     MRS_HIP_TRY(hipGetLastError());
     MRS_HIP_TRY(hipDeviceSynchronize());
     return MRS_OK;
@@ -592,7 +586,7 @@ int mrs_elev_map_optmove(mrs_elev_map* m, const float* h_opt_p2, float height_up
         h_aligned2[i] = m->central[i] + m->res * is;
     }
     m->central[0] = h_aligned2[0]; m->central[1] = h_aligned2[1];
-    hipLaunchKernelGGL(k_elev_height_add, dim3(nb(m->L * m->L)), dim3(256), 0, nullptr, m->elevation, m->L * m->L, height_update);
+    hipLaunchKernelGGL(k_elev_height_add, dim3(nb(m->L * m->L)), dim3(256), 0, nullptr, m->elevation.get(), m->L * m->L, height_update);
     MRS_HIP_TRY(hipGetLastError());
     return MRS_OK;
 }
@@ -608,7 +602,7 @@ int mrs_elev_map_closeloop(mrs_elev_map* m, const float* h_update_position2, flo
         const int is = static_cast<int>(ps / m->res + 0.5 * (ps > 0 ? 1 : -1));
         m->central[i] = position_to_range(m->central[i], (float)is * m->res, m->res);
     }
-    hipLaunchKernelGGL(k_elev_height_add, dim3(nb(m->L * m->L)), dim3(256), 0, nullptr, m->elevation, m->L * m->L, height_update);
+    hipLaunchKernelGGL(k_elev_height_add, dim3(nb(m->L * m->L)), dim3(256), 0, nullptr, m->elevation.get(), m->L * m->L, height_update);
     MRS_HIP_TRY(hipGetLastError());
     return MRS_OK;
 }
@@ -619,7 +613,7 @@ int mrs_elev_get_layer(mrs_elev_map* m, int32_t which, float* h_out)
     MRS_REQUIRE(m && h_out, "null pointer");
     MRS_REQUIRE(which >= 0 && which < 5, "which must be in [0, 4]");
     MRS_HIP_TRY(hipSetDevice(m->ctx->device));
-    const float* src[5] = {m->lowest, m->elevation, m->variance, m->intensity, m->traver};
+    const float* src[5] = {m->lowest.get(), m->elevation.get(), m->variance.get(), m->intensity.get(), m->traver.get()};
     MRS_HIP_TRY(hipDeviceSynchronize());
     MRS_HIP_TRY(hipMemcpy(h_out, src[which], (size_t)m->L * m->L * 4, hipMemcpyDeviceToHost));
     return MRS_OK;

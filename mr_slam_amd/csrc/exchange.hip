@@ -171,26 +171,11 @@ struct mrs_fetch_plan {
     int n_rows = 0;
     int64_t rows_per_rank = 0;
     std::vector<int64_t> send_off, recv_off;      // [W + 1] prefix counts per peer
-    int64_t* d_sidx = nullptr;                     // local rows I send, grouped by peer, in the peer's request order
-    int64_t* d_rpos = nullptr;                     // position in the caller's output of every row I receive, grouped by owner
-    void* sendbuf = nullptr;
-    void* recvbuf = nullptr;
+    mrs::DeviceBuffer<int64_t> d_sidx;             // local rows I send, grouped by peer, in the peer's request order
+    mrs::DeviceBuffer<int64_t> d_rpos;             // position in the caller's output of every row I receive, grouped by owner
+    mrs::DeviceBuffer<uint4> sendbuf, recvbuf;     // staging, in 16-byte units
     int64_t buf_entry_bytes = 0;                   // sendbuf / recvbuf are sized for entries of this many bytes
 };
-
-extern "C++" {
-namespace {
-void free_plan(mrs_fetch_plan* p)
-{
-    if (!p) return;
-    if (p->d_sidx) (void)hipFree(p->d_sidx);
-    if (p->d_rpos) (void)hipFree(p->d_rpos);
-    if (p->sendbuf) (void)hipFree(p->sendbuf);
-    if (p->recvbuf) (void)hipFree(p->recvbuf);
-    delete p;
-}
-}  // namespace
-}
 
 int mrs_exchange_fetch_plan_create(mrs_exchange* x, int64_t rows_per_rank, const int64_t* d_global_rows, int32_t n_rows, mrs_stream stream,
                                    mrs_fetch_plan** out)
@@ -212,7 +197,7 @@ int mrs_exchange_fetch_plan_create(mrs_exchange* x, int64_t rows_per_rank, const
         MRS_HIP_TRY(hipStreamSynchronize(s));
     }
     for (int64_t r : req) MRS_REQUIRE(r >= 0 && r < rows_per_rank * W, "requested row outside the database");
-    mrs_fetch_plan* p = new mrs_fetch_plan();
+    std::unique_ptr<mrs_fetch_plan> p(new mrs_fetch_plan());      // an early return deletes it: every table frees itself
     p->x = x; p->n_rows = n_rows; p->rows_per_rank = rows_per_rank;
     // what I send to every peer (local row indices, in the peer's request order) and where what I receive goes (positions in the output)
     std::vector<int64_t> send_idx, recv_pos;
@@ -227,16 +212,12 @@ int mrs_exchange_fetch_plan_create(mrs_exchange* x, int64_t rows_per_rank, const
             if (req[(size_t)me * n_rows + k] / rows_per_rank == o) recv_pos.push_back(k);
         p->recv_off[o + 1] = (int64_t)recv_pos.size();
     }
-    hipError_t e = hipMalloc(&p->d_sidx, std::max<size_t>(send_idx.size(), 1) * sizeof(int64_t));
-    if (e == hipSuccess) e = hipMalloc(&p->d_rpos, (size_t)n_rows * sizeof(int64_t));
-    if (e == hipSuccess && !send_idx.empty()) e = hipMemcpy(p->d_sidx, send_idx.data(), send_idx.size() * sizeof(int64_t), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(p->d_rpos, recv_pos.data(), recv_pos.size() * sizeof(int64_t), hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        free_plan(p);
-        mrs::set_error("fetch plan tables: %s", hipGetErrorString(e));
-        return MRS_ERR_HIP;
-    }
-    *out = p;
+    const size_t n_sidx = std::max<size_t>(send_idx.size(), 1);
+    MRS_TRY(p->d_sidx.reserve(n_sidx, n_sidx));
+    MRS_TRY(p->d_rpos.reserve((size_t)n_rows, (size_t)n_rows));
+    if (!send_idx.empty()) MRS_HIP_TRY(hipMemcpy(p->d_sidx.get(), send_idx.data(), send_idx.size() * sizeof(int64_t), hipMemcpyHostToDevice));
+    MRS_HIP_TRY(hipMemcpy(p->d_rpos.get(), recv_pos.data(), recv_pos.size() * sizeof(int64_t), hipMemcpyHostToDevice));
+    *out = p.release();
     return MRS_OK;
 }
 
@@ -246,7 +227,7 @@ int mrs_exchange_fetch_plan_destroy(mrs_fetch_plan* p)
         (void)hipSetDevice(p->x->ctx->device);
         (void)hipDeviceSynchronize();              // a fetch of this plan may still be in flight on some stream
     }
-    free_plan(p);
+    delete p;
     return MRS_OK;
 }
 
@@ -271,19 +252,17 @@ int mrs_exchange_fetch_planned(mrs_fetch_plan* p, const void* d_local_db, int64_
     const int64_t n_send = p->send_off[W];
     if (p->buf_entry_bytes < entry_bytes) {        // first use (or larger entries): the plan owns its staging buffers; fetches of ONE plan must
         MRS_HIP_TRY(hipStreamSynchronize(s));      // follow each other in stream order (they share them)
-        if (p->sendbuf) (void)hipFree(p->sendbuf);
-        if (p->recvbuf) (void)hipFree(p->recvbuf);
-        p->sendbuf = p->recvbuf = nullptr;
-        p->buf_entry_bytes = 0;
-        MRS_HIP_TRY(hipMalloc(&p->sendbuf, (size_t)std::max<int64_t>(n_send, 1) * entry_bytes));
-        MRS_HIP_TRY(hipMalloc(&p->recvbuf, (size_t)p->n_rows * entry_bytes));
+        p->buf_entry_bytes = 0;                    // set again only once both buffers exist
+        const size_t su = (size_t)(std::max<int64_t>(n_send, 1) * units), ru = (size_t)(p->n_rows * units);
+        MRS_TRY(p->sendbuf.reserve(su, su));
+        MRS_TRY(p->recvbuf.reserve(ru, ru));
         p->buf_entry_bytes = entry_bytes;
     }
     if (n_send > 0)
-        hipLaunchKernelGGL(k_gather_rows16, dim3((unsigned)n_send), dim3(256), 0, s, static_cast<const uint4*>(d_local_db), p->d_sidx, units,
-                           static_cast<uint4*>(p->sendbuf));
-    char* sb = static_cast<char*>(p->sendbuf);
-    char* rb = static_cast<char*>(p->recvbuf);
+        hipLaunchKernelGGL(k_gather_rows16, dim3((unsigned)n_send), dim3(256), 0, s, static_cast<const uint4*>(d_local_db), p->d_sidx.get(), units,
+                           p->sendbuf.get());
+    char* sb = reinterpret_cast<char*>(p->sendbuf.get());
+    char* rb = reinterpret_cast<char*>(p->recvbuf.get());
     if (W > 1) {
         MRS_NCCL_TRY(rccl().GroupStart());
         ncclResult_t bad = ncclSuccess;
@@ -302,7 +281,7 @@ int mrs_exchange_fetch_planned(mrs_fetch_plan* p, const void* d_local_db, int64_
     const int64_t mine = p->send_off[me + 1] - p->send_off[me];
     if (mine > 0)
         MRS_HIP_TRY(hipMemcpyAsync(rb + p->recv_off[me] * entry_bytes, sb + p->send_off[me] * entry_bytes, (size_t)(mine * entry_bytes), hipMemcpyDeviceToDevice, s));
-    hipLaunchKernelGGL(k_scatter_rows16, dim3((unsigned)p->n_rows), dim3(256), 0, s, static_cast<const uint4*>(p->recvbuf), p->d_rpos, units, static_cast<uint4*>(d_out));
+    hipLaunchKernelGGL(k_scatter_rows16, dim3((unsigned)p->n_rows), dim3(256), 0, s, p->recvbuf.get(), p->d_rpos.get(), units, static_cast<uint4*>(d_out));
     MRS_HIP_TRY(hipGetLastError());
     return MRS_OK;
 }
@@ -317,7 +296,7 @@ int mrs_exchange_fetch_rows(mrs_exchange* x, const void* d_local_db, int64_t row
     if (st != MRS_OK) return st;
     st = mrs_exchange_fetch_planned(p, d_local_db, entry_bytes, d_out, stream);
     if (st == MRS_OK && hipStreamSynchronize((hipStream_t)stream) != hipSuccess) { mrs::set_error("row fetch: stream synchronisation failed"); st = MRS_ERR_HIP; }
-    free_plan(p);
+    delete p;
     return st;
 }
 

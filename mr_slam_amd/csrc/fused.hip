@@ -434,9 +434,9 @@ int mrs_ring_descriptors_batch(mrs_radon_plan* plan, const float* d_xyz, const i
     p.A = plan->n_angles; p.D = plan->det; p.H = plan->H; p.W = plan->W;
     p.stride = (plan->W + 2 * kPad) | 1;
     const size_t nr = (size_t)p.A * p.D;
-    p.meta = plan->d_meta;
-    p.base = plan->d_meta + nr;
-    p.q = reinterpret_cast<const float*>(plan->d_meta + 2 * nr);
+    p.meta = plan->d_meta.get();
+    p.base = p.meta + nr;
+    p.q = reinterpret_cast<const float*>(p.meta + 2 * nr);
     p.vm = p.q + nr;
     p.nrm = p.vm + nr;
     const size_t lds = 2 * (size_t)(p.H + 2 * kPad) * p.stride * sizeof(float);
@@ -450,7 +450,7 @@ int mrs_ring_descriptors_batch(mrs_radon_plan* plan, const float* d_xyz, const i
     unsigned stagger_ticks = (unsigned)plan->fused_stagger_us * 100u;   // wall_clock64 ticks at 100 MHz
     if (pairs <= grid) stagger_ticks = 0;   // a single round: nothing to phase-shift, the delay would only add latency
     unsigned* d_ctr = ctr.as<unsigned>();
-    int* d_deg = plan->d_degenerate;
+    int* d_deg = plan->d_degenerate.get();
     if (plan->fused_variant >= 1 && plan->d_slot && plan->slot_per_lane == per_lane) {
         // variant 2 parks 2 x rays raw sums in the tile after the march: they must fit it
         const bool once = plan->fused_variant == 2 && 2 * (size_t)rays * sizeof(float) <= lds;
@@ -460,7 +460,7 @@ int mrs_ring_descriptors_batch(mrs_radon_plan* plan, const float* d_xyz, const i
                                             : fused_kernel_slots<16, 0>(pf));
         if (lds > 48 * 1024) MRS_HIP_TRY(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         SlotP sp;
-        sp.slot = plan->d_slot; sp.nrm = plan->d_slot_nrm; sp.ray = plan->d_slot_ray;
+        sp.slot = plan->d_slot.get(); sp.nrm = plan->d_slot_nrm.get(); sp.ray = plan->d_slot_ray.get();
         mrs::Scratch parkbuf;          // only a BEV-only call has no output to park the raw sums in (they are then never read)
         float* d_park = nullptr;
         if (!d_sino && !d_sino_norm) {

@@ -744,13 +744,7 @@ int mrs_gem_update_global(mrs_gem* gem, const float* h_opt_poses, int32_t n_pose
     const long long N = gem->off.back();
     const float r2 = gem->radius * gem->radius;
     // development aid (MRS_DEV=1 MRS_GEM_TIMING=1, tools/bench_gem.py): events between the steps, one line on stderr per call
-    const bool timing = mrs::dev_env("MRS_GEM_TIMING") != nullptr;
-    struct Events {           // destroyed on every way out
-        hipEvent_t e[7] = {};
-        ~Events() { for (hipEvent_t x : e) if (x) (void)hipEventDestroy(x); }
-    } events;
-    hipEvent_t* tev = events.e;
-    auto mark = [&](int i) { if (timing && hipEventCreate(&tev[i]) == hipSuccess) (void)hipEventRecord(tev[i], nullptr); };
+    mrs::StageMarks marks(mrs::dev_env("MRS_GEM_TIMING") != nullptr, nullptr);
 
     // neighbour lists from the centres, in float32: (distance^2, index) ascending, the centre submap itself first
     std::vector<int> list, list_off(1, 0);
@@ -803,7 +797,7 @@ int mrs_gem_update_global(mrs_gem* gem, const float* h_opt_poses, int32_t n_pose
     MRS_HIP_TRY(hipMemsetAsync(gem->counters.get(), 0, 2 * sizeof(u64), nullptr));
 
     // (a) move submaps 1 .. K - 1
-    mark(0);
+    marks.mark(0);
     const long long first = gem->off[std::min(1, K)], moved = gem->off[K] - first;
     if (moved > 0) hipLaunchKernelGGL(k_gem_move, dim3(blocks_for(moved)), dim3(kThreads), 0, nullptr, gem->arena.cols(), first, moved, d_off, nsub, d_T);
     MRS_HIP_TRY(hipGetLastError());
@@ -814,7 +808,7 @@ int mrs_gem_update_global(mrs_gem* gem, const float* h_opt_poses, int32_t n_pose
     }
 
     // (c) canonical form of every submap that takes part, in one chain
-    mark(1);
+    marks.mark(1);
     const int h_init[4] = {INT_MAX, INT_MIN, INT_MAX, INT_MIN};
     int h_range[4];
     MRS_HIP_TRY(hipMemcpy(d_range, h_init, sizeof(h_init), hipMemcpyHostToDevice));
@@ -828,14 +822,14 @@ int mrs_gem_update_global(mrs_gem* gem, const float* h_opt_poses, int32_t n_pose
         if (!part[s]) longest_raw = std::max(longest_raw, gem->off[s + 1] - gem->off[s]);
     const int y_bits = bit_width((u64)((long long)h_range[3] - h_range[2])), x_bits = bit_width((u64)((long long)h_range[1] - h_range[0] + 1));
     const int low_bits = std::max(std::max(x_bits + y_bits, bit_width((u64)(longest_raw - 1))), 1), end_bit = low_bits + bit_width((u64)(nsub - 1));
-    mark(2);
+    marks.mark(2);
     const u64* keys = nullptr;
     const int* vals = nullptr;
     hipLaunchKernelGGL(k_gem_keys, dim3(blocks_for(N)), dim3(kThreads), 0, nullptr, gem->arena.cols(), N, d_off, nsub, d_part, gem->resolution, h_range[0],
                        h_range[2], y_bits, low_bits, w.k0, w.v0);
-    mark(3);
+    marks.mark(3);
     if ((st = w.sort(N, end_bit, &keys, &vals)) != MRS_OK) return st;
-    mark(4);
+    marks.mark(4);
     hipLaunchKernelGGL(k_gem_keep, dim3(blocks_for(N)), dim3(kThreads), 0, nullptr, keys, vals, N, gem->arena.cols(), d_part, y_bits, low_bits, w.a,
                        gem->counters.get());
     if ((st = w.exclusive_sum(w.a, w.b, N)) != MRS_OK) return st;
@@ -847,7 +841,7 @@ int mrs_gem_update_global(mrs_gem* gem, const float* h_opt_poses, int32_t n_pose
     MRS_HIP_TRY(hipMemcpy(new_off.data(), d_new_off, new_off.size() * 8, hipMemcpyDeviceToHost));
     std::swap(gem->arena, gem->spare);
     gem->off = new_off;
-    mark(5);
+    marks.mark(5);
 
     // (b) one launch per centre submap with enough neighbours, in index order
     for (size_t c = 0; c + 1 < list_off.size(); ++c) {
@@ -858,18 +852,14 @@ int mrs_gem_update_global(mrs_gem* gem, const float* h_opt_poses, int32_t n_pose
                            list_off[c + 1] - list_off[c], gem->rule, gem->counters.get() + 1);
     }
     MRS_HIP_TRY(hipGetLastError());
-    mark(6);
+    marks.mark(6);
     u64 h_counters[2] = {0, 0};
     MRS_HIP_TRY(hipMemcpy(h_counters, gem->counters.get(), sizeof(h_counters), hipMemcpyDeviceToHost));
     gem->dropped = (long long)h_counters[0];
     gem->matched = (long long)h_counters[1];
-    if (timing) {
-        float ms[6] = {};
-        for (int i = 0; i < 6; ++i)
-            if (tev[i] && tev[i + 1]) (void)hipEventElapsedTime(&ms[i], tev[i], tev[i + 1]);
+    if (marks)
         fprintf(stderr, "[mrslam] gem update steps ms: move %.4f range %.4f keys %.4f sort %.4f heads+gather %.4f fuse %.4f records %lld bits %d launches %zu\n",
-                ms[0], ms[1], ms[2], ms[3], ms[4], ms[5], N, end_bit, list_off.size() - 1);
-    }
+                marks.ms(0), marks.ms(1), marks.ms(2), marks.ms(3), marks.ms(4), marks.ms(5), N, end_bit, list_off.size() - 1);
     return MRS_OK;
 }
 

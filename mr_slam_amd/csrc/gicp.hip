@@ -976,32 +976,32 @@ int mrs_gicp_batch_get_voxel_map(mrs_gicp_batch* h, int32_t* h_n_voxels, int32_t
 // idle: on the normal way out it is (the last window was synchronised); on any other way out work may still run on its stream, or a window's
 // counters may still be on their way into its pinned buffer from `s`, so both streams are drained first.
 struct AlignSide {
-    mrs_ctx* ctx; hipStream_t s; mrs::SideSlot sl; bool completed;
+    mrs_ctx* ctx; hipStream_t s; std::unique_ptr<mrs::SideSlot> sl; bool completed;
     ~AlignSide()
     {
-        if (!completed && sl.stream) {
-            (void)hipStreamSynchronize(sl.stream);
+        if (!completed && sl) {
+            (void)hipStreamSynchronize(sl->stream);
             (void)hipStreamSynchronize(s);
         }
-        mrs::side_release(ctx, sl);
+        mrs::side_release(ctx, std::move(sl));
     }
 };
 
 // The covariances an alignment needs and the handle does not hold yet (mrs_gicp_batch_align, mrs_gicp_batch_align_pcl), enqueued on `s`.
-static int covariances_first(mrs_gicp_batch* h, bool small, const mrs::SideSlot& sl, hipStream_t s)
+static int covariances_first(mrs_gicp_batch* h, bool small, mrs::SideSlot* sl, hipStream_t s)      // sl: the call's slot when `small`
 {
     int st;
     if (small && !h->side[0].cov_valid && !h->side[1].cov_valid && !mrs::dev_env("MRS_GICP_SERIAL_COV")) {
         // both clouds are new (every registration of the nodes): a cloud of 30-40 k points fills 150 of the 256 compute units with one wave per
         // SIMD, so the two k-NN + covariance passes run side by side on two streams instead of back to back
-        MRS_HIP_TRY(hipEventRecord(sl.fork, s));
-        MRS_HIP_TRY(hipStreamWaitEvent(sl.stream, sl.fork, 0));
-        st = mrs_gicp_batch_compute_covariances(h, 1, nullptr, (mrs_stream)sl.stream);
+        mrs::HandleStream& side = sl->stream;
+        MRS_TRY(side.join_in(s));                                    // fork
+        st = mrs_gicp_batch_compute_covariances(h, 1, nullptr, (mrs_stream)side.s);
         if (st != MRS_OK) return st;
-        MRS_HIP_TRY(hipEventRecord(sl.join, sl.stream));
+        MRS_HIP_TRY(hipEventRecord(side.ev_out, side));              // join: recorded here, waited for behind the other cloud's pass
         st = mrs_gicp_batch_compute_covariances(h, 0, nullptr, (mrs_stream)s);
         if (st != MRS_OK) return st;
-        MRS_HIP_TRY(hipStreamWaitEvent(s, sl.join, 0));
+        MRS_HIP_TRY(hipStreamWaitEvent(s, side.ev_out, 0));
     }
     for (int w = 0; w < 2; ++w)
         if (!h->side[w].cov_valid) { st = mrs_gicp_batch_compute_covariances(h, w, nullptr, (mrs_stream)s); if (st != MRS_OK) return st; }
@@ -1024,7 +1024,7 @@ int mrs_gicp_batch_align(mrs_gicp_batch* h, const double* h_guess, double* h_fin
     // a second stream, two events and a pinned buffer from the context's pool for the duration of this call (small batches only)
     AlignSide side{h->ctx, s, {}, false};
     if (small && (st = mrs::side_acquire(h->ctx, &side.sl)) != MRS_OK) return st;
-    if ((st = covariances_first(h, small, side.sl, s)) != MRS_OK) return st;
+    if ((st = covariances_first(h, small, side.sl.get(), s)) != MRS_OK) return st;
     if (h->prm.voxel_res > 0.0) {
         st = build_voxel_map(h, s);
         if (st != MRS_OK) return st;
@@ -1050,7 +1050,7 @@ int mrs_gicp_batch_align(mrs_gicp_batch* h, const double* h_guess, double* h_fin
     if (const char* v = mrs::dev_env("MRS_GICP_WINDOW")) window = std::max(0, std::min(kLmWindowMax, atoi(v)));
     if (small && window > 1 && h->prm.voxel_res <= 0.0) {
         static_assert(kLmWindowMax * 4 <= mrs::kSidePinnedInts, "the slot's pinned buffer holds a window's counters");
-        int* const h_win = side.sl.pinned;
+        int* const h_win = side.sl->pinned.get();
         const bool alternate = h->n_pairs == 1;
         const long max_ticks_w = alternate ? 2 * max_ticks : max_ticks;      // a sat-out tick does no work: the bound counts work ticks
         while (next[0] + next[1] > 0 && ticks < max_ticks_w) {
@@ -1237,15 +1237,15 @@ int icp_align(mrs_gicp_batch* h, const mrs_icp_params* p, bool plane, const doub
     if (P <= kLmWindowPairs && window > 1) {
         // the pinned buffer of a context slot receives a window's counters (its stream and events are not used here)
         struct Side {
-            mrs_ctx* ctx; hipStream_t s; mrs::SideSlot sl; bool completed;
+            mrs_ctx* ctx; hipStream_t s; std::unique_ptr<mrs::SideSlot> sl; bool completed;
             ~Side()
             {
-                if (!completed && sl.pinned) (void)hipStreamSynchronize(s);
-                mrs::side_release(ctx, sl);
+                if (!completed && sl) (void)hipStreamSynchronize(s);
+                mrs::side_release(ctx, std::move(sl));
             }
         } side{h->ctx, s, {}, false};
         if ((st = mrs::side_acquire(h->ctx, &side.sl)) != MRS_OK) return st;
-        int* const h_win = side.sl.pinned;
+        int* const h_win = side.sl->pinned.get();
         while (next[0] > 0 && ticks < max_ticks) {
             MRS_HIP_TRY(hipMemsetAsync(L.nactive.get(), 0, (size_t)window * 4 * sizeof(int), s));
             for (int t = 0; t < window; ++t) {
@@ -1501,7 +1501,7 @@ int mrs_gicp_batch_align_pcl(mrs_gicp_batch* h, const mrs_pclgicp_params* p, con
     const bool small = P <= kLmWindowPairs;
     AlignSide side{h->ctx, s, {}, false};
     if (small && (st = mrs::side_acquire(h->ctx, &side.sl)) != MRS_OK) return st;
-    if ((st = covariances_first(h, small, side.sl, s)) != MRS_OK) return st;
+    if ((st = covariances_first(h, small, side.sl.get(), s)) != MRS_OK) return st;
     std::vector<LmState> init(P);
     pcl_init_states(init, h_guess, true);
     MRS_HIP_TRY(hipMemcpyAsync(L.state.get(), init.data(), init.size() * sizeof(LmState), hipMemcpyHostToDevice, s));
@@ -1512,7 +1512,7 @@ int mrs_gicp_batch_align_pcl(mrs_gicp_batch* h, const mrs_pclgicp_params* p, con
     int window = kLmWindow;
     if (const char* v = mrs::dev_env("MRS_GICP_WINDOW")) window = std::max(0, std::min(kLmWindowMax, atoi(v)));
     if (small && window > 1) {
-        int* const h_win = side.sl.pinned;
+        int* const h_win = side.sl->pinned.get();
         while (next[0] > 0 && ticks < max_ticks) {
             MRS_HIP_TRY(hipMemsetAsync(L.nactive.get(), 0, (size_t)window * 4 * sizeof(int), s));
             for (int t = 0; t < window; ++t) {
@@ -1626,26 +1626,12 @@ int mrs_gicp_batch_pcl_profile(mrs_gicp_batch* h, const mrs_pclgicp_params* p, c
     pcl_init_states(init, h_poses, false);
     MRS_HIP_TRY(hipMemcpyAsync(L.state.get(), init.data(), init.size() * sizeof(LmState), hipMemcpyHostToDevice, s));
     MRS_HIP_TRY(hipStreamSynchronize(s));
-    struct Events {
-        hipEvent_t e0 = nullptr, e1 = nullptr;
-        ~Events() { if (e0) (void)hipEventDestroy(e0); if (e1) (void)hipEventDestroy(e1); }
-    } ev;
-    MRS_HIP_TRY(hipEventCreate(&ev.e0)); MRS_HIP_TRY(hipEventCreate(&ev.e1));
-    auto timed = [&](float& ms, auto&& launch) -> int {
-        launch();                                     // warm
-        MRS_HIP_TRY(hipEventRecord(ev.e0, s));
-        for (int r = 0; r < reps; ++r) launch();
-        MRS_HIP_TRY(hipEventRecord(ev.e1, s));
-        MRS_HIP_TRY(hipEventSynchronize(ev.e1));
-        MRS_HIP_TRY(hipGetLastError());
-        MRS_HIP_TRY(hipEventElapsedTime(&ms, ev.e0, ev.e1));
-        ms /= (float)reps;
-        return MRS_OK;
-    };
+    mrs::RepTimer timer;
+    MRS_TRY(timer.create());
     int nn_st = MRS_OK;
-    if ((st = timed(out_ms[0], [&]() { const int r = nn_pass(h, sp, 2, s); if (r != MRS_OK) nn_st = r; })) != MRS_OK) return st;
+    if ((st = timer.timed(out_ms[0], reps, s, [&]() { const int r = nn_pass(h, sp, 2, s); if (r != MRS_OK) nn_st = r; })) != MRS_OK) return st;
     if (nn_st != MRS_OK) return nn_st;
-    if ((st = timed(out_ms[1], [&]() { launch_pcl_sums(h, s); })) != MRS_OK) return st;
+    if ((st = timer.timed(out_ms[1], reps, s, [&]() { launch_pcl_sums(h, s); })) != MRS_OK) return st;
     {
         std::vector<int> corr(L.n_seed);
         MRS_HIP_TRY(hipMemcpy(corr.data(), L.corr.get(), corr.size() * sizeof(int), hipMemcpyDeviceToHost));
@@ -1660,7 +1646,7 @@ int mrs_gicp_batch_pcl_profile(mrs_gicp_batch* h, const mrs_pclgicp_params* p, c
     if ((st = start.alloc(init.size() * sizeof(LmState), s)) != MRS_OK) return st;
     MRS_HIP_TRY(hipMemcpyAsync(start.p, init.data(), init.size() * sizeof(LmState), hipMemcpyHostToDevice, s));
     MRS_HIP_TRY(hipStreamSynchronize(s));
-    if ((st = timed(out_ms[2], [&]() {
+    if ((st = timer.timed(out_ms[2], reps, s, [&]() {
              (void)hipMemcpyAsync(L.state.get(), start.p, init.size() * sizeof(LmState), hipMemcpyDeviceToDevice, s);
              launch_pcl_update(h, dp, L.nactive.get(), s);
          })) != MRS_OK) return st;
@@ -1747,36 +1733,22 @@ static int icp_profile(mrs_gicp_batch* h, const mrs_icp_params* p, const mrs_icp
     }
     MRS_HIP_TRY(hipMemcpyAsync(L.state.get(), init.data(), init.size() * sizeof(LmState), hipMemcpyHostToDevice, s));
     MRS_HIP_TRY(hipStreamSynchronize(s));
-    struct Events {
-        hipEvent_t e0 = nullptr, e1 = nullptr;
-        ~Events() { if (e0) (void)hipEventDestroy(e0); if (e1) (void)hipEventDestroy(e1); }
-    } ev;
-    MRS_HIP_TRY(hipEventCreate(&ev.e0)); MRS_HIP_TRY(hipEventCreate(&ev.e1));
-    auto timed = [&](float& ms, auto&& launch) -> int {
-        launch();                                     // warm
-        MRS_HIP_TRY(hipEventRecord(ev.e0, s));
-        for (int r = 0; r < reps; ++r) launch();
-        MRS_HIP_TRY(hipEventRecord(ev.e1, s));
-        MRS_HIP_TRY(hipEventSynchronize(ev.e1));
-        MRS_HIP_TRY(hipGetLastError());
-        MRS_HIP_TRY(hipEventElapsedTime(&ms, ev.e0, ev.e1));
-        ms /= (float)reps;
-        return MRS_OK;
-    };
+    mrs::RepTimer timer;
+    MRS_TRY(timer.create());
     const GicpCloud &S = h->side[0], &T = h->side[1];
     int nn_st = MRS_OK;
-    if ((st = timed(*ms_search, [&]() { const int r = nn_pass(h, sp, 2, s); if (r != MRS_OK) nn_st = r; })) != MRS_OK) return st;
+    if ((st = timer.timed(*ms_search, reps, s, [&]() { const int r = nn_pass(h, sp, 2, s); if (r != MRS_OK) nn_st = r; })) != MRS_OK) return st;
     if (nn_st != MRS_OK) return nn_st;
     if (plane) {
         MRS_REQUIRE(plane->normal_k >= 3 && plane->normal_k <= 32, "normal_k must be in [3, 32]");
-        if ((st = timed(*ms_normals, [&]() {
+        if ((st = timer.timed(*ms_normals, reps, s, [&]() {
                  h->side[1].nrm_key = 0;            // computed again, whatever the handle holds
                  const int r = mrs_gicp_batch_compute_normals(h, 1, plane->normal_k, plane->viewpoint, stream);
                  if (r != MRS_OK) nn_st = r;
              })) != MRS_OK) return st;
         if (nn_st != MRS_OK) return nn_st;
     }
-    if ((st = timed(*ms_sums, [&]() {
+    if ((st = timer.timed(*ms_sums, reps, s, [&]() {
              if (plane) return launch_icp_plane_sums(h, s);
              hipLaunchKernelGGL(k_icp_sums, dim3(L.max_blocks, h->n_pairs), dim3(kNNThreads), 0, s, S.pts.get(), S.d_offs.get(), T.pts.get(),
                                 T.d_offs.get(), L.state.get(), L.corr.get(), L.partial.get(), L.max_blocks);
@@ -1789,7 +1761,7 @@ static int icp_profile(mrs_gicp_batch* h, const mrs_icp_params* p, const mrs_icp
         out_counts[0] = (int64_t)L.n_seed; out_counts[1] = c;
     }
     MRS_HIP_TRY(hipMemsetAsync(L.nactive.get(), 0, 4 * sizeof(int), s));
-    if ((st = timed(*ms_update, [&]() {
+    if ((st = timer.timed(*ms_update, reps, s, [&]() {
              if (plane)
                  hipLaunchKernelGGL(k_icp_plane_update, dim3(h->n_pairs), dim3(kLmThreads), 0, s, L.state.get(), L.partial.get(), L.nblocks.get(),
                                     L.max_blocks, dp, L.nactive.get());
@@ -1850,36 +1822,22 @@ int mrs_gicp_batch_profile(mrs_gicp_batch* h, const double* h_poses, int32_t rep
         MRS_HIP_TRY(hipStreamSynchronize(s));
         return MRS_OK;
     };
-    // everything this function borrows goes back on EVERY way out (the MRS_HIP_TRY returns included): the two events and the search settings
+    // the search settings this function changes go back on EVERY way out (the MRS_HIP_TRY returns included)
     struct Guard {
-        mrs_gicp_batch* h; int core, cold; bool cert; hipEvent_t e0 = nullptr, e1 = nullptr;
-        ~Guard() {
-            h->search_core = core; h->cold_core = cold; h->use_certificates = cert;
-            if (e0) (void)hipEventDestroy(e0);
-            if (e1) (void)hipEventDestroy(e1);
-        }
+        mrs_gicp_batch* h; int core, cold; bool cert;
+        ~Guard() { h->search_core = core; h->cold_core = cold; h->use_certificates = cert; }
     } guard{h, h->search_core, h->cold_core, h->use_certificates};
-    MRS_HIP_TRY(hipEventCreate(&guard.e0)); MRS_HIP_TRY(hipEventCreate(&guard.e1));
-    const hipEvent_t e0 = guard.e0, e1 = guard.e1;
-    auto timed = [&](float& ms, auto&& launch) -> int {
-        launch();                                     // warm
-        MRS_HIP_TRY(hipEventRecord(e0, s));
-        for (int r = 0; r < reps; ++r) launch();
-        MRS_HIP_TRY(hipEventRecord(e1, s));
-        MRS_HIP_TRY(hipEventSynchronize(e1));
-        MRS_HIP_TRY(hipGetLastError());
-        MRS_HIP_TRY(hipEventElapsedTime(&ms, e0, e1));
-        ms /= (float)reps;
-        return MRS_OK;
-    };
+    mrs::RepTimer timer;
+    MRS_TRY(timer.create());
+    const hipEvent_t e0 = timer.e0, e1 = timer.e1;
     h->search_core = 1; h->cold_core = 0; h->use_certificates = true;      // restored by `guard`
     auto round3 = [&]() { launch_nn_scan(h, h->prm, nullptr, 0, s); };
     auto linearize = [&]() { launch_linearize(h, 0, s); };
     if ((st = upload(0, 0.0)) != MRS_OK) return st;
     round3();                                         // seeds + correspondences at the poses
     if ((st = knn_dev_switches(s)) != MRS_OK) return st;
-    if ((st = timed(out_ms[2], round3)) != MRS_OK) return st;
-    if ((st = timed(out_ms[0], linearize)) != MRS_OK) return st;
+    if ((st = timer.timed(out_ms[2], reps, s, round3)) != MRS_OK) return st;
+    if ((st = timer.timed(out_ms[0], reps, s, linearize)) != MRS_OK) return st;
     {   // correspondences at the poses
         std::vector<int> corr(L.n_seed);
         MRS_HIP_TRY(hipMemcpy(corr.data(), L.corr.get(), corr.size() * sizeof(int), hipMemcpyDeviceToHost));
@@ -1887,11 +1845,11 @@ int mrs_gicp_batch_profile(mrs_gicp_batch* h, const double* h_poses, int32_t rep
         for (int v : corr) c += v >= 0;
         out_counts[0] = (int64_t)L.n_seed; out_counts[1] = c;
     }
-    if ((st = timed(out_ms[4], [&]() { launch_nn_scan_g(h, h->prm, false, s); })) != MRS_OK) return st;      // leaves certificates at the poses
+    if ((st = timer.timed(out_ms[4], reps, s, [&]() { launch_nn_scan_g(h, h->prm, false, s); })) != MRS_OK) return st;      // leaves certificates at the poses
     launch_nn_store_pose(h, 0, s);
-    if ((st = timed(out_ms[3], [&]() { launch_nn_certify(h, h->prm, s); })) != MRS_OK) return st;
+    if ((st = timer.timed(out_ms[3], reps, s, [&]() { launch_nn_certify(h, h->prm, s); })) != MRS_OK) return st;
     if ((st = upload(1, 0.0)) != MRS_OK) return st;
-    if ((st = timed(out_ms[1], linearize)) != MRS_OK) return st;
+    if ((st = timer.timed(out_ms[1], reps, s, linearize)) != MRS_OK) return st;
     // a pass after a 1 mm step: certify + search the work lists (the certificates are those of the unmoved poses: t_prev stays)
     if ((st = upload(0, 1e-3)) != MRS_OK) return st;
     {
@@ -1927,8 +1885,8 @@ int mrs_gicp_batch_profile(mrs_gicp_batch* h, const double* h_poses, int32_t rep
         const int k = h->prm.k;
         mrs::Scratch knn;
         if ((st = knn.alloc(knn_ints(L.n_seed, P, k) * sizeof(int), s)) != MRS_OK) return st;
-        if ((st = timed(out_ms[5], [&]() { launch_knn_cov(h, 0, 0, P, k, knn.as<int>(), s); })) != MRS_OK) return st;
-        if ((st = timed(out_ms[6], [&]() {
+        if ((st = timer.timed(out_ms[5], reps, s, [&]() { launch_knn_cov(h, 0, 0, P, k, knn.as<int>(), s); })) != MRS_OK) return st;
+        if ((st = timer.timed(out_ms[6], reps, s, [&]() {
                  hipLaunchKernelGGL(k_cov_from_knn, dim3((unsigned)((S.longest + 255) / 256), P), dim3(256), 0, s, (const float4*)S.pts.get(),
                                     (const int64_t*)S.d_offs.get(), k, (const int*)knn.as<int>(), S.cov.get(), (int*)nullptr);
              })) != MRS_OK) return st;
@@ -2026,15 +1984,14 @@ int mrs_pointfeat_batch(mrs_ctx* ctx, const float* d_points, int32_t stride_floa
     std::unique_lock<std::mutex> lk(ctx->pointfeat_mu, std::try_to_lock);
     if (lk.owns_lock()) {
         auto it = ctx->pointfeat_cache.find(batch);
-        if (it != ctx->pointfeat_cache.end()) { h = static_cast<mrs_gicp_batch*>(it->second); cached = true; }
+        if (it != ctx->pointfeat_cache.end()) { h = static_cast<mrs_gicp_batch*>(it->second.get()); cached = true; }
     }
     if (!h) {
         st = mrs_gicp_batch_create(ctx, batch, &h);
         if (st != MRS_OK) return st;
         h->no_cov = true;          // no covariance buffer (48 B per point) for the feature front end
         if (lk.owns_lock() && ctx->pointfeat_cache.size() < 4) {
-            ctx->pointfeat_cache[batch] = h;
-            ctx->pointfeat_free = [](void* p) { (void)mrs_gicp_batch_destroy(static_cast<mrs_gicp_batch*>(p)); };
+            ctx->pointfeat_cache[batch] = std::shared_ptr<void>(h, [](void* p) { (void)mrs_gicp_batch_destroy(static_cast<mrs_gicp_batch*>(p)); });
             cached = true;
         }
     }

@@ -302,16 +302,10 @@ int ingest_locked(mrs_keyframes* kf, int n_clouds, const void* data, bool on_dev
         long long* d_counts = reinterpret_cast<long long*>(w + b_info + b_tiles + 2 * b_first);
 
         // development aid (MRS_DEV=1 MRS_INTAKE_TIMING=1, tools/bench_intake.py): events between the steps, one line on stderr per call
-        const bool timing = mrs::dev_env("MRS_INTAKE_TIMING") != nullptr;
-        struct Events {           // destroyed on every way out
-            hipEvent_t e[8] = {};
-            ~Events() { for (hipEvent_t x : e) if (x) (void)hipEventDestroy(x); }
-        } events;
-        hipEvent_t* tev = events.e;
-        auto mark = [&](int i) { if (timing && hipEventCreate(&tev[i]) == hipSuccess) (void)hipEventRecord(tev[i], s); };
+        mrs::StageMarks marks(mrs::dev_env("MRS_INTAKE_TIMING") != nullptr, s);
 
         const float* raw = static_cast<const float*>(data);
-        mark(0);
+        marks.mark(0);
         if (on_device) {
             MRS_TRY(kf->s.join_in(user));
         } else {
@@ -322,13 +316,13 @@ int ingest_locked(mrs_keyframes* kf, int n_clouds, const void* data, bool on_dev
         }
         MRS_HIP_TRY(hipMemcpyAsync(w, h, b_tables, hipMemcpyHostToDevice, s));
         const bool vec16 = point_step == 16 && ((uintptr_t)raw & 15) == 0;      // chosen from the arguments
-        mark(1);
+        marks.mark(1);
         if (vec16) hipLaunchKernelGGL(k_in_bounds<true>, dim3(n_tiles), dim3(kThreads), 0, s, raw, L, d_tiles, d_first, inv, d_info);
         else hipLaunchKernelGGL(k_in_bounds<false>, dim3(n_tiles), dim3(kThreads), 0, s, raw, L, d_tiles, d_first, inv, d_info);
         hipLaunchKernelGGL(k_in_grid, dim3((n_clouds + 63) / 64), dim3(64), 0, s, d_info, n_clouds);
         MRS_HIP_TRY(hipGetLastError());
         MRS_HIP_TRY(hipMemcpyAsync(h, d_info, (size_t)n_clouds * sizeof(CloudInfo), hipMemcpyDeviceToHost, s));
-        mark(2);
+        marks.mark(2);
         MRS_HIP_TRY(hipStreamSynchronize(s));                    // synchronisation 1 of 2: the key widths decide how much is sorted
         long long n_valid = 0;
         int shift = 0;
@@ -377,14 +371,14 @@ int ingest_locked(mrs_keyframes* kf, int n_clouds, const void* data, bool on_dev
             void* d_tmp = q;
 
             MRS_HIP_TRY(hipMemcpyAsync(d_sorted, h_sorted, (size_t)(n_clouds + 1) * sizeof(int), hipMemcpyHostToDevice, s));
-            mark(3);
+            marks.mark(3);
             if (vec16) hipLaunchKernelGGL(k_in_keys<true>, dim3(n_tiles), dim3(kThreads), 0, s, raw, L, d_tiles, d_first, d_info, n_clouds, shift, inv, d_keys0, d_vals0);
             else hipLaunchKernelGGL(k_in_keys<false>, dim3(n_tiles), dim3(kThreads), 0, s, raw, L, d_tiles, d_first, d_info, n_clouds, shift, inv, d_keys0, d_vals0);
-            mark(4);
+            marks.mark(4);
             hipcub::DoubleBuffer<unsigned long long> keys(d_keys0, d_keys1);
             hipcub::DoubleBuffer<int> vals(d_vals0, d_vals1);
             MRS_HIP_TRY(hipcub::DeviceRadixSort::SortPairs(d_tmp, b_sort, keys, vals, (int)n_in, 0, end_bit, s));
-            mark(5);
+            marks.mark(5);
             const unsigned long long* d_sorted_keys = keys.Current();
             const int* d_pos = vals.Current();
             int* d_keep = vals.Alternate();                       // first the run heads, then the verdicts
@@ -402,23 +396,18 @@ int ingest_locked(mrs_keyframes* kf, int n_clouds, const void* data, bool on_dev
                 hipLaunchKernelGGL(k_in_means<false>, dim3(blocks), dim3(kThreads), 0, s, raw, L, d_sorted_keys, d_pos, d_part, (int)n_valid, f.z_lo, f.z_hi,
                                    f.set_intensity, f.intensity, d_vox, d_keep);
             }
-            mark(6);
+            marks.mark(6);
             MRS_HIP_TRY(hipcub::DeviceScan::InclusiveSum(d_tmp, b_scan, d_keep, d_rank, (int)n_valid, s));
             hipLaunchKernelGGL(k_in_scatter, dim3(blocks), dim3(kThreads), 0, s, d_vox, d_keep, d_rank, (int)n_valid, tail);
             hipLaunchKernelGGL(k_in_counts, dim3((n_clouds + 1 + 63) / 64), dim3(64), 0, s, d_rank, d_sorted, n_clouds, d_counts);
-            mark(7);
+            marks.mark(7);
             MRS_HIP_TRY(hipGetLastError());
             MRS_HIP_TRY(hipMemcpyAsync(h_counts, d_counts, (size_t)(n_clouds + 1) * 8, hipMemcpyDeviceToHost, s));
             MRS_HIP_TRY(hipStreamSynchronize(s));                // synchronisation 2 of 2: the survivors of every cloud
             for (int c = 0; c <= n_clouds; ++c) survivors[c] = h_counts[c];
-            if (timing) {
-                float ms[6] = {};                                // events 2 and 3 bracket the first synchronisation: not a step
-                const int from[6] = {0, 1, 3, 4, 5, 6};
-                for (int i = 0; i < 6; ++i)
-                    if (tev[from[i]] && tev[from[i] + 1]) (void)hipEventElapsedTime(&ms[i], tev[from[i]], tev[from[i] + 1]);
+            if (marks)                                           // events 2 and 3 bracket the first synchronisation: not a step
                 fprintf(stderr, "[mrslam] intake steps ms: upload %.4f bounds+grid %.4f keys %.4f sort %.4f means %.4f scan+scatter %.4f points %lld bits %d\n",
-                        ms[0], ms[1], ms[2], ms[3], ms[4], ms[5], n_in, end_bit);
-            }
+                        marks.ms(0), marks.ms(1), marks.ms(3), marks.ms(4), marks.ms(5), marks.ms(6), n_in, end_bit);
         }
     }
     // the store changes only here, after everything that can fail

@@ -419,19 +419,13 @@ int mrs_map_compose(int32_t n_stores, mrs_keyframes* const* stores, int32_t n_se
     MRS_TRY(kf->s.join_in((hipStream_t)stream));
     MRS_HIP_TRY(hipMemcpyAsync(w, h, b_tables, hipMemcpyHostToDevice, s));
     // development aid (MRS_DEV=1 MRS_MAP_TIMING=1, tools/bench_globalmap.py): events between the steps, one line on stderr per call
-    const bool timing = mrs::dev_env("MRS_MAP_TIMING") != nullptr;
-    struct Events {           // destroyed on every way out
-        hipEvent_t e[7] = {};
-        ~Events() { for (hipEvent_t x : e) if (x) (void)hipEventDestroy(x); }
-    } events;
-    hipEvent_t* tev = events.e;
-    auto mark = [&](int i) { if (timing && hipEventCreate(&tev[i]) == hipSuccess) (void)hipEventRecord(tev[i], s); };
-    mark(0);
+    mrs::StageMarks marks(mrs::dev_env("MRS_MAP_TIMING") != nullptr, s);
+    marks.mark(0);
     hipLaunchKernelGGL(k_mc_bounds, dim3(std::min(n_tiles, kBoundsBlocks)), dim3(kThreads), 0, s, d_src, d_segs, d_tiles, n_tiles, inv, d_info);
     hipLaunchKernelGGL(k_mc_grid, dim3(1), dim3(64), 0, s, d_info);
     MRS_HIP_TRY(hipGetLastError());
     MRS_HIP_TRY(hipMemcpyAsync(h, d_info, sizeof(Info), hipMemcpyDeviceToHost, s));
-    mark(1);
+    marks.mark(1);
     MRS_HIP_TRY(hipStreamSynchronize(s));                        // synchronisation 1 of 2: the key width decides how much is sorted
     const Info info = *hi;
     if (info.overflow) {
@@ -465,13 +459,13 @@ int mrs_map_compose(int32_t n_stores, mrs_keyframes* const* stores, int32_t n_se
     Carry* d_carry = reinterpret_cast<Carry*>(w); w += b_carry;
     void* d_tmp = w;
 
-    mark(2);
+    marks.mark(2);
     hipLaunchKernelGGL(k_mc_keys, dim3(n_tiles), dim3(kThreads), 0, s, d_src, d_segs, d_tiles, d_info, inv, d_keys0, d_vals0);
-    mark(3);
+    marks.mark(3);
     hipcub::DoubleBuffer<unsigned long long> keys(d_keys0, d_keys1);
     hipcub::DoubleBuffer<int> vals(d_vals0, d_vals1);
     MRS_HIP_TRY(hipcub::DeviceRadixSort::SortPairs(d_tmp, b_sort, keys, vals, (int)n_in, 0, end_bit, s));
-    mark(4);
+    marks.mark(4);
     const unsigned long long* d_sorted = keys.Current();
     const int* d_pos = vals.Current();
     int* d_head = vals.Alternate();
@@ -479,24 +473,18 @@ int mrs_map_compose(int32_t n_stores, mrs_keyframes* const* stores, int32_t n_se
     const int blocks = (int)std::min<long long>(((long long)n_valid + kThreads - 1) / kThreads, 8192);
     hipLaunchKernelGGL(k_mc_heads, dim3(blocks), dim3(kThreads), 0, s, d_sorted, n_valid, d_head);
     MRS_HIP_TRY(hipcub::DeviceScan::InclusiveSum(d_tmp, b_scan, d_head, d_rank, n_valid, s));
-    mark(5);
+    marks.mark(5);
     hipLaunchKernelGGL(k_mc_means, dim3(n_mean_tiles), dim3(kThreads), 0, s, d_bases, d_origin, d_segs, ns, d_sorted, d_pos, d_rank, n_valid,
                        reinterpret_cast<float4*>(d_out), d_carry);
     hipLaunchKernelGGL(k_mc_stitch, dim3((n_mean_tiles + kThreads - 1) / kThreads), dim3(kThreads), 0, s, d_carry, n_mean_tiles,
                        reinterpret_cast<float4*>(d_out));
-    mark(6);
+    marks.mark(6);
     MRS_HIP_TRY(hipGetLastError());
     MRS_HIP_TRY(hipMemcpyAsync(h, d_rank + (n_valid - 1), sizeof(int), hipMemcpyDeviceToHost, s));
     MRS_HIP_TRY(hipStreamSynchronize(s));                        // synchronisation 2 of 2: the number of voxels
-    if (timing) {
-        float ms[5] = {};                                        // events 1 and 2 bracket the first synchronisation: not a step
-        for (int i = 0; i < 5; ++i) {
-            const int a = i == 0 ? 0 : i + 1;
-            if (tev[a] && tev[a + 1]) (void)hipEventElapsedTime(&ms[i], tev[a], tev[a + 1]);
-        }
-        fprintf(stderr, "[mrslam] map steps ms: bounds+grid %.4f keys %.4f sort %.4f heads+scan %.4f means+stitch %.4f points %lld bits %d\n", ms[0],
-                ms[1], ms[2], ms[3], ms[4], n_in, end_bit);
-    }
+    if (marks)                                                   // events 1 and 2 bracket the first synchronisation: not a step
+        fprintf(stderr, "[mrslam] map steps ms: bounds+grid %.4f keys %.4f sort %.4f heads+scan %.4f means+stitch %.4f points %lld bits %d\n",
+                marks.ms(0), marks.ms(2), marks.ms(3), marks.ms(4), marks.ms(5), n_in, end_bit);
     *out_points = *reinterpret_cast<const int*>(h);
     return MRS_OK;
 }

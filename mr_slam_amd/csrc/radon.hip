@@ -402,19 +402,16 @@ int mrs_radon_plan_create(mrs_ctx* ctx, const float* h_angles, int32_t n_angles,
             }
         }
     }
-    mrs_radon_plan* pl = new mrs_radon_plan();
+    std::unique_ptr<mrs_radon_plan> pl(new mrs_radon_plan());      // an early return deletes it: every table frees itself
     pl->ctx = ctx;
     pl->n_angles = n_angles; pl->det = det_count; pl->H = height; pl->W = width;
     pl->spacing = det_spacing;
     pl->in_lds = lds <= ctx->lds_bytes;
     pl->two_in_lds = 2 * lds + 1024 <= ctx->lds_bytes;
-    if (hipMalloc(&pl->d_degenerate, sizeof(int)) != hipSuccess || hipMemset(pl->d_degenerate, 0, sizeof(int)) != hipSuccess ||
-        hipMalloc(&pl->d_meta, tab.size() * sizeof(int)) != hipSuccess ||
-        hipMemcpy(pl->d_meta, tab.data(), tab.size() * sizeof(int), hipMemcpyHostToDevice) != hipSuccess) {
+    if (pl->d_degenerate.reserve(1, 1) != MRS_OK || hipMemset(pl->d_degenerate.get(), 0, sizeof(int)) != hipSuccess ||
+        pl->d_meta.reserve(tab.size(), tab.size()) != MRS_OK ||
+        hipMemcpy(pl->d_meta.get(), tab.data(), tab.size() * sizeof(int), hipMemcpyHostToDevice) != hipSuccess) {
         mrs::set_error("could not upload the ray table");
-        if (pl->d_meta) (void)hipFree(pl->d_meta);
-        if (pl->d_degenerate) (void)hipFree(pl->d_degenerate);
-        delete pl;
         return MRS_ERR_HIP;
     }
     // slot tables (two-image kernels): rays dealt to lane slots by orientation, length and LDS bank (radon_deal.hpp)
@@ -427,21 +424,19 @@ int mrs_radon_plan_create(mrs_ctx* ctx, const float* h_angles, int32_t n_angles,
         const size_t slots = im.ray.size();
         if (slots != (size_t)radon_deal::walked_per_lane(per_lane) * kRadonWG) {
             mrs::set_error("slot table of %zu entries for %d rays per lane", pl->h_slot_ray.size(), per_lane);
-            mrs_radon_plan_destroy(pl);
             return MRS_ERR_ARG;
         }
-        if (hipMalloc(&pl->d_slot, slots * sizeof(int4)) != hipSuccess || hipMalloc(&pl->d_slot_nrm, slots * sizeof(float)) != hipSuccess ||
-            hipMalloc(&pl->d_slot_ray, slots * sizeof(int)) != hipSuccess ||
-            hipMemcpy(pl->d_slot, im.slot.data(), slots * sizeof(int4), hipMemcpyHostToDevice) != hipSuccess ||
-            hipMemcpy(pl->d_slot_nrm, im.nrm.data(), slots * sizeof(float), hipMemcpyHostToDevice) != hipSuccess ||
-            hipMemcpy(pl->d_slot_ray, im.ray.data(), slots * sizeof(int), hipMemcpyHostToDevice) != hipSuccess) {
+        if (pl->d_slot.reserve(slots, slots) != MRS_OK || pl->d_slot_nrm.reserve(slots, slots) != MRS_OK ||
+            pl->d_slot_ray.reserve(slots, slots) != MRS_OK ||
+            hipMemcpy(pl->d_slot.get(), im.slot.data(), slots * sizeof(int4), hipMemcpyHostToDevice) != hipSuccess ||
+            hipMemcpy(pl->d_slot_nrm.get(), im.nrm.data(), slots * sizeof(float), hipMemcpyHostToDevice) != hipSuccess ||
+            hipMemcpy(pl->d_slot_ray.get(), im.ray.data(), slots * sizeof(int), hipMemcpyHostToDevice) != hipSuccess) {
             mrs::set_error("could not upload the slot tables");
-            mrs_radon_plan_destroy(pl);
             return MRS_ERR_HIP;
         }
         pl->slot_per_lane = per_lane;
     }
-    *out_plan = pl;
+    *out_plan = pl.release();
     return MRS_OK;
 }
 
@@ -449,11 +444,6 @@ int mrs_radon_plan_destroy(mrs_radon_plan* plan)
 {
     if (!plan) return MRS_OK;
     (void)hipSetDevice(plan->ctx->device);
-    if (plan->d_slot) (void)hipFree(plan->d_slot);
-    if (plan->d_slot_nrm) (void)hipFree(plan->d_slot_nrm);
-    if (plan->d_slot_ray) (void)hipFree(plan->d_slot_ray);
-    if (plan->d_meta) (void)hipFree(plan->d_meta);
-    if (plan->d_degenerate) (void)hipFree(plan->d_degenerate);
     delete plan;
     return MRS_OK;
 }
@@ -474,8 +464,8 @@ int mrs_radon_plan_degenerate_count(mrs_radon_plan* plan, int32_t reset, int32_t
     MRS_HIP_TRY(hipSetDevice(plan->ctx->device));
     MRS_HIP_TRY(hipDeviceSynchronize());
     int v = 0;
-    MRS_HIP_TRY(hipMemcpy(&v, plan->d_degenerate, sizeof(int), hipMemcpyDeviceToHost));
-    if (reset) MRS_HIP_TRY(hipMemset(plan->d_degenerate, 0, sizeof(int)));
+    MRS_HIP_TRY(hipMemcpy(&v, plan->d_degenerate.get(), sizeof(int), hipMemcpyDeviceToHost));
+    if (reset) MRS_HIP_TRY(hipMemset(plan->d_degenerate.get(), 0, sizeof(int)));
     *out_count = v;
     return MRS_OK;
 }
@@ -502,15 +492,16 @@ int mrs_radon_forward(mrs_radon_plan* plan, const float* d_img, int32_t batch, f
     p.A = plan->n_angles; p.D = plan->det; p.H = plan->H; p.W = plan->W;
     p.stride = (plan->W + 2 * kPad) | 1;
     const size_t nr = (size_t)p.A * p.D;
-    p.meta = plan->d_meta;
-    p.base = plan->d_meta + nr;
-    p.q = reinterpret_cast<const float*>(plan->d_meta + 2 * nr);
+    p.meta = plan->d_meta.get();
+    p.base = p.meta + nr;
+    p.q = reinterpret_cast<const float*>(p.meta + 2 * nr);
     p.vm = p.q + nr;
     p.nrm = p.vm + nr;
     const size_t lds = (size_t)(p.H + 2 * kPad) * p.stride * sizeof(float);
     hipStream_t s = (hipStream_t)stream;
     const int rays = p.A * p.D;
     const int per_lane = (rays + kRadonWG - 1) / kRadonWG;
+    int* const d_deg = plan->d_degenerate.get();
     if (!plan->in_lds) {
         mrs::Scratch padded, tmp;
         const size_t plane = (size_t)(p.H + 2 * kPad) * p.stride;
@@ -524,7 +515,7 @@ int mrs_radon_forward(mrs_radon_plan* plan, const float* d_img, int32_t batch, f
         }
         hipLaunchKernelGGL(k_radon_pad, dim3(std::min((p.H * p.W + 255) / 256, 1024), batch), dim3(256), 0, s, d_img, p, padded.as<float>());
         hipLaunchKernelGGL(k_radon_global, dim3(std::min((rays + 255) / 256, 4096), batch), dim3(256), 0, s, padded.as<float>(), p, raw);
-        if (d_sino_norm) hipLaunchKernelGGL(k_normalize, dim3(batch), dim3(1024), 0, s, raw, d_sino_norm, rays, plan->d_degenerate);
+        if (d_sino_norm) hipLaunchKernelGGL(k_normalize, dim3(batch), dim3(1024), 0, s, raw, d_sino_norm, rays, d_deg);
         MRS_HIP_TRY(hipGetLastError());
         return MRS_OK;
     }
@@ -541,7 +532,7 @@ int mrs_radon_forward(mrs_radon_plan* plan, const float* d_img, int32_t batch, f
         if (lds > 48 * 1024)
             MRS_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         hipLaunchKernelGGL(kern, dim3(per_lane, batch), dim3(kRadonWG), lds, s, d_img, p, raw);
-        if (d_sino_norm) hipLaunchKernelGGL(k_normalize, dim3(batch), dim3(1024), 0, s, raw, d_sino_norm, rays, plan->d_degenerate);
+        if (d_sino_norm) hipLaunchKernelGGL(k_normalize, dim3(batch), dim3(1024), 0, s, raw, d_sino_norm, rays, d_deg);
     } else if (per_lane <= 16 && plan->two_in_lds && batch > 1) {
         // two images per workgroup share the per-sample index arithmetic (march2).  The slot tables of the fused descriptor kernel (rays dealt
         // to lanes by length, rolled ray loop, sums parked in the output) were tried here too: same bits, +13 % time (0.298 vs 0.262 ms per 1024
@@ -550,14 +541,13 @@ int mrs_radon_forward(mrs_radon_plan* plan, const float* d_img, int32_t batch, f
         if (2 * lds > 48 * 1024)
             MRS_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)(2 * lds)));
-        hipLaunchKernelGGL(kern, dim3((batch + 1) / 2), dim3(kRadonWG), 2 * lds, s, d_img, p, batch, d_sino, d_sino_norm,
-                           plan->d_degenerate);
+        hipLaunchKernelGGL(kern, dim3((batch + 1) / 2), dim3(kRadonWG), 2 * lds, s, d_img, p, batch, d_sino, d_sino_norm, d_deg);
     } else if (per_lane <= 16) {
         auto kern = per_lane <= 15 ? (p.stride == 125 ? k_radon<15, 125> : k_radon<15, 0>) : k_radon<16, 0>;
         if (lds > 48 * 1024)
             MRS_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL(kern, dim3(batch), dim3(kRadonWG), lds, s, d_img, p, d_sino, d_sino_norm, plan->d_degenerate);
+        hipLaunchKernelGGL(kern, dim3(batch), dim3(kRadonWG), lds, s, d_img, p, d_sino, d_sino_norm, d_deg);
     } else {
         mrs::Scratch tmp;
         float* raw = d_sino;
@@ -571,7 +561,7 @@ int mrs_radon_forward(mrs_radon_plan* plan, const float* d_img, int32_t batch, f
                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         hipLaunchKernelGGL(k_radon_big, dim3(batch), dim3(kRadonWG), lds, s, d_img, p, raw);
         if (d_sino_norm)
-            hipLaunchKernelGGL(k_normalize, dim3(batch), dim3(1024), 0, s, raw, d_sino_norm, rays, plan->d_degenerate);
+            hipLaunchKernelGGL(k_normalize, dim3(batch), dim3(1024), 0, s, raw, d_sino_norm, rays, d_deg);
     }
     MRS_HIP_TRY(hipGetLastError());
     return MRS_OK;

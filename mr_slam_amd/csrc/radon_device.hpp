@@ -10,8 +10,8 @@ struct mrs_radon_plan {
     int n_angles = 0, det = 0, H = 0, W = 0;
     float spacing = 1.0f;
     bool in_lds = true;      // the zero-bordered image fits the LDS (else: global-memory path)
-    int* d_meta = nullptr;   // ray table, one allocation: meta | base | q | vm | n, each [n_angles*det]
-    int* d_degenerate = nullptr;  // sinograms with zero / non-finite std seen by the fused normalisation
+    mrs::DeviceBuffer<int> d_meta;   // ray table, one allocation: meta | base | q | vm | n, each [n_angles*det]
+    mrs::DeviceBuffer<int> d_degenerate;  // sinograms with zero / non-finite std seen by the fused normalisation
     bool two_in_lds = false; // two interleaved images fit the LDS (k_radon2)
     // tuning of the fused rasterise + Radon kernel (fused.hip; mrs_radon_plan_set_option)
     int fused_stagger_us = 70;  // odd workgroups start this many microseconds late (phase-shifts the HBM-bound and the VALU-bound halves)
@@ -23,9 +23,9 @@ struct mrs_radon_plan {
     // slot tables of the two-image kernels: lane slot s = k * 1024 + lane carries ray slot_ray[s] (-1: idle).  The 64 lanes of a wave march
     // rays of one orientation and (almost) the same length: a wave executes the longest of its rays, and in (angle, detector) order 16 %
     // of the lane-steps were idle.  Which 32 of them share a lane group is chosen against the LDS bank model of radon_deal.hpp
-    int4* d_slot = nullptr;     // {n_steps | ydom << 16, LDS byte offset of the first texel line (single-image units), q bits, vm bits}
-    float* d_slot_nrm = nullptr;
-    int* d_slot_ray = nullptr;
+    mrs::DeviceBuffer<int4> d_slot;     // {n_steps | ydom << 16, LDS byte offset of the first texel line (single-image units), q bits, vm bits}
+    mrs::DeviceBuffer<float> d_slot_nrm;
+    mrs::DeviceBuffer<int> d_slot_ray;
     int slot_per_lane = 0;
     std::vector<int> h_slot_ray;   // host copy of d_slot_ray (mrs_radon_plan_slot_rays)
 };

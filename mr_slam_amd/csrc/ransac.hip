@@ -275,17 +275,6 @@ __global__ __launch_bounds__(kThreads) void k_refit(const float* __restrict__ sr
 
 bool finite_in(double v, double lo, double hi) { return v >= lo && v <= hi; }       // false for NaN
 
-// four timed events of a profiled call
-struct TimedEvents {
-    hipEvent_t e[4] = {nullptr, nullptr, nullptr, nullptr};
-    ~TimedEvents() { for (hipEvent_t x : e) if (x) (void)hipEventDestroy(x); }
-    int create()
-    {
-        for (hipEvent_t& x : e) MRS_HIP_TRY(hipEventCreate(&x));
-        return MRS_OK;
-    }
-};
-
 
 // stage_ms (optional, [3]): the times of the three stages (models = verdict + fit, score, refit) between events, summed over the
 // rounds; the call then waits for the stream
@@ -310,8 +299,9 @@ int ransac_run(mrs_ctx* ctx, const float* d_src, const float* d_dst, int32_t str
     if (stage_ms) stage_ms[0] = stage_ms[1] = stage_ms[2] = 0.f;
     if (n_pairs == 0) return MRS_OK;
     MRS_HIP_TRY(hipSetDevice(ctx->device));
-    TimedEvents ev;
-    if (stage_ms) MRS_TRY(ev.create());
+    mrs::Event ev[4];                                            // the four timed events of a profiled call
+    if (stage_ms)
+        for (mrs::Event& e : ev) MRS_TRY(e.create(hipEventDefault));
 
     Params P;
     P.H = params->hypotheses;
@@ -353,28 +343,28 @@ int ransac_run(mrs_ctx* ctx, const float* d_src, const float* d_dst, int32_t str
         const int np = std::min(group, n_pairs - pair0);
         const size_t n_tiles = tile_first[round + 1] - tile_first[round];
         const dim3 grid_h((unsigned)n_chunks, (unsigned)np);
-        if (stage_ms) MRS_HIP_TRY(hipEventRecord(ev.e[0], s));
+        if (stage_ms) MRS_HIP_TRY(hipEventRecord(ev[0], s));
         hipLaunchKernelGGL(k_verdict, grid_h, dim3(kThreads), 0, s, d_src, d_dst, stride_floats, d_offsets, seeds.as<uint64_t>(), pair0, P,
                            flags.as<uint8_t>(), chunk_count.as<int>());
         hipLaunchKernelGGL(k_models, grid_h, dim3(kThreads), 0, s, d_src, d_dst, stride_floats, d_offsets, seeds.as<uint64_t>(), pair0, P,
                            flags.as<uint8_t>(), chunk_count.as<int>(), models.as<double>(), model_h.as<int>(), n_valid.as<int>());
-        if (stage_ms) MRS_HIP_TRY(hipEventRecord(ev.e[1], s));
+        if (stage_ms) MRS_HIP_TRY(hipEventRecord(ev[1], s));
         if (n_tiles) {
             MRS_HIP_TRY(hipMemsetAsync(counts.p, 0, (size_t)np * H * sizeof(int), s));
             // the grid's x holds the tiles (up to 2^31 - 1), y the model blocks (at most 256)
             hipLaunchKernelGGL(k_score, dim3((unsigned)n_tiles, (unsigned)n_chunks), dim3(kThreads), 0, s, d_src, d_dst, stride_floats, d_offsets,
                                tiles.as<int2>() + tile_first[round], pair0, P, models.as<double>(), n_valid.as<int>(), counts.as<int>());
         }
-        if (stage_ms) MRS_HIP_TRY(hipEventRecord(ev.e[2], s));
+        if (stage_ms) MRS_HIP_TRY(hipEventRecord(ev[2], s));
         hipLaunchKernelGGL(k_refit, dim3((unsigned)np), dim3(kThreads), 0, s, d_src, d_dst, stride_floats, d_offsets, pair0, P, models.as<double>(),
                            model_h.as<int>(), n_valid.as<int>(), counts.as<int>(), cur_mask.as<uint8_t>(), d_T, d_info, d_mask);
         MRS_HIP_TRY(hipGetLastError());
         if (stage_ms) {
-            MRS_HIP_TRY(hipEventRecord(ev.e[3], s));
-            MRS_HIP_TRY(hipEventSynchronize(ev.e[3]));
+            MRS_HIP_TRY(hipEventRecord(ev[3], s));
+            MRS_HIP_TRY(hipEventSynchronize(ev[3]));
             for (int k = 0; k < 3; ++k) {
                 float ms = 0.f;
-                MRS_HIP_TRY(hipEventElapsedTime(&ms, ev.e[k], ev.e[k + 1]));
+                MRS_HIP_TRY(hipEventElapsedTime(&ms, ev[k], ev[k + 1]));
                 stage_ms[k] += ms;
             }
         }

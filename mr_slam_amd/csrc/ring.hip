@@ -354,12 +354,12 @@ int get_twiddles(mrs_ctx* ctx, int N, const float2** out)
             h[2 * k] = (float)cos(a);
             h[2 * k + 1] = (float)sin(a);
         }
-        float* d = nullptr;
-        MRS_HIP_TRY(hipMalloc(&d, h.size() * sizeof(float)));
-        MRS_HIP_TRY(hipMemcpy(d, h.data(), h.size() * sizeof(float), hipMemcpyHostToDevice));
-        it = ctx->twiddles.emplace(N, d).first;
+        mrs::DeviceBuffer<float> d;
+        MRS_TRY(d.reserve(h.size(), h.size()));
+        MRS_HIP_TRY(hipMemcpy(d.get(), h.data(), h.size() * sizeof(float), hipMemcpyHostToDevice));
+        it = ctx->twiddles.emplace(N, std::move(d)).first;
     }
-    *out = reinterpret_cast<const float2*>(it->second);
+    *out = reinterpret_cast<const float2*>(it->second.get());
     return MRS_OK;
 }
 

@@ -310,41 +310,31 @@ int assemble_locked(mrs_keyframes* kf, int n_submaps, int n_seg, const int32_t* 
     MRS_TRY(kf->s.join_in(user));        // d_out may still be in use on the caller's stream
     MRS_HIP_TRY(hipMemcpyAsync(d_segs, h, b_tables, hipMemcpyHostToDevice, kf->s));
     // development aid (MRS_DEV=1 MRS_SUBMAP_TIMING=1, tools/bench_submap.py): events between the steps, one line on stderr per call
-    const bool timing = mrs::dev_env("MRS_SUBMAP_TIMING") != nullptr;
-    struct Events {           // destroyed on every way out
-        hipEvent_t e[6] = {};
-        ~Events() { for (hipEvent_t x : e) if (x) (void)hipEventDestroy(x); }
-    } events;
-    hipEvent_t* tev = events.e;
-    auto mark = [&](int i) { if (timing && hipEventCreate(&tev[i]) == hipSuccess) (void)hipEventRecord(tev[i], kf->s); };
+    mrs::StageMarks marks(mrs::dev_env("MRS_SUBMAP_TIMING") != nullptr, kf->s);
     const float4* arena = kf->arena.get();
-    mark(0);
+    marks.mark(0);
     hipLaunchKernelGGL(k_cells, dim3(n_tiles), dim3(kThreads), 0, kf->s, arena, d_segs, d_tiles, crop, inv, d_bounds);
     hipLaunchKernelGGL(k_grid, dim3((n_submaps + 63) / 64), dim3(64), 0, kf->s, d_bounds, n_submaps, d_grids, d_overflow);
-    mark(1);
+    marks.mark(1);
     hipLaunchKernelGGL(k_keys, dim3(n_tiles), dim3(kThreads), 0, kf->s, arena, d_segs, d_tiles, d_grids, crop, inv, d_keys, d_vals);
-    mark(2);
+    marks.mark(2);
     MRS_HIP_TRY(hipcub::DeviceSegmentedRadixSort::SortPairs(d_tmp, b_sort, d_keys, d_keys_s, d_vals, d_vals_s, (int)n_in, n_submaps, d_sub, d_sub + 1,
                                                             0, 64, kf->s));
-    mark(3);
+    marks.mark(3);
     hipLaunchKernelGGL(k_heads, dim3(n_tiles), dim3(kThreads), 0, kf->s, d_keys_s, d_segs, d_tiles, d_sub, d_head);
     MRS_HIP_TRY(hipcub::DeviceScan::ExclusiveSum(d_tmp, b_scan, d_head, d_slot, (int)n_in, kf->s));
-    mark(4);
+    marks.mark(4);
     const int mean_blocks = (int)std::min<long long>((n_in + kThreads - 1) / kThreads, 8192);
     hipLaunchKernelGGL(k_means, dim3(mean_blocks), dim3(kThreads), 0, kf->s, arena, d_segs, ns, d_keys_s, d_vals_s, d_head, d_slot, n_in, crop,
                        reinterpret_cast<float4*>(d_out));
     hipLaunchKernelGGL(k_offsets, dim3((n_submaps + 2 + 63) / 64), dim3(64), 0, kf->s, d_head, d_slot, d_sub, n_submaps, d_overflow, d_offs);
-    mark(5);
+    marks.mark(5);
     MRS_HIP_TRY(hipGetLastError());
     MRS_HIP_TRY(hipMemcpyAsync(h, d_offs, (size_t)(n_submaps + 2) * 8, hipMemcpyDeviceToHost, kf->s));
     MRS_HIP_TRY(hipStreamSynchronize(kf->s));                   // the one synchronisation of the call
-    if (timing) {
-        float ms[5] = {};
-        for (int i = 0; i < 5; ++i)
-            if (tev[i] && tev[i + 1]) (void)hipEventElapsedTime(&ms[i], tev[i], tev[i + 1]);
-        fprintf(stderr, "[mrslam] submap steps ms: cells+grid %.4f keys %.4f sort %.4f heads+scan %.4f means+offsets %.4f points %lld\n", ms[0], ms[1],
-                ms[2], ms[3], ms[4], n_in);
-    }
+    if (marks)
+        fprintf(stderr, "[mrslam] submap steps ms: cells+grid %.4f keys %.4f sort %.4f heads+scan %.4f means+offsets %.4f points %lld\n", marks.ms(0),
+                marks.ms(1), marks.ms(2), marks.ms(3), marks.ms(4), n_in);
     const long long* ho = reinterpret_cast<const long long*>(h);
     if (ho[n_submaps + 1]) {
         mrs::set_error("a submap's voxel grid needs keys of more than 63 bits (leaf %g): choose a larger leaf", (double)leaf);

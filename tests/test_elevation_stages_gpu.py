@@ -291,3 +291,38 @@ def test_two_maps_do_not_share_state(elevation):
         for x, y in zip(a, b):
             np.testing.assert_array_equal(x, y)
         assert (got[L][-1][3][1] != -10).sum() > (100 if L == 20 else 300)
+
+
+# ------------------------------------------------------------------------------------------------ create / destroy
+def test_create_refuses_bad_lengths_and_leaves_no_handle(elevation):
+    import ctypes as C
+    from mr_slam_amd import _lib
+    for length in (0, 8193):
+        h = C.c_void_p()
+        with pytest.raises(_lib.MrsError) as e:
+            _lib.load().mrs_elev_create(_lib.ctx(0), length, 0.5, 2.0, 0.6, C.byref(h))
+        assert e.value.status == 1 and not h.value          # MRS_ERR_ARG, no handle
+
+
+def _small_session(elevation):
+    """an 8 x 8 map through move, process_points and fuse with 16 points behind the robot, all of them on the map"""
+    L, rng = 8, np.random.default_rng(88)
+    m = elevation.ElevationMap(L, 0.5)
+    out = [m.move([0.5, -0.5, 0.9])]
+    xs, ys, zs = rng.uniform(-1.9, 1.9, 16).astype(F), rng.uniform(-1.95, -1.55, 16).astype(F), rng.uniform(-0.7, -0.5, 16).astype(F)
+    assert EC.passes_filter(xs, ys).all()
+    res = EC.process(m, xs, ys, zs, EC.transform(0, 0.9, (0.5, -0.5)))
+    assert (res["map_index"] >= 0).all()
+    m.fuse(res["map_index"], *EC.colours_for(rng, 16), res["z_ts"], res["var"])
+    out += [res, EC.layers(m), m.map_feature()]
+    assert (out[2][1] != -10).sum() >= 4
+    return out
+
+
+def test_destroy_then_a_fresh_map_reproduces(elevation):
+    """the five layers and map_feature of a small session, on a map created after the first one was destroyed: the same bits"""
+    first = EC.flatten(_small_session(elevation))           # its map is destroyed when the session returns
+    again = EC.flatten(_small_session(elevation))
+    assert len(first) == len(again) >= 25
+    for a, b in zip(first, again):
+        assert a.dtype == b.dtype and a.tobytes() == b.tobytes()

@@ -366,6 +366,19 @@ def test_exchange_through_the_c_abi_on_one_rank():
     assert torch.equal(buf[0], torch.view_as_real(spec))
 
 
+def test_fetch_plan_regrows_its_staging_buffers():
+    """one plan over one rank and four rows, fetched with 16-byte entries, then 32-byte ones (the plan's staging buffers grow), then 16-byte
+    ones again (they stay): every fetch equals indexing the local table"""
+    import torch
+    from mr_slam_amd import shard
+    x = shard.Exchange(device=0)
+    rows = torch.tensor([3, 0, 2, 3], device="cuda:0")
+    plan = x.fetch_plan(rows, 4)
+    for width in (4, 8, 4):
+        db = torch.arange(4 * width, dtype=torch.float32, device="cuda:0").reshape(4, width) + 0.5 * width
+        assert torch.equal(plan.fetch(db), db[rows]), width
+
+
 def test_one_twin_queried_from_two_threads_while_a_third_appends():
     """callback1 and callback3 both score against TIRING2 on separate rospy threads (main_RING.py:284-288, 378-382), and ctypes
     drops the GIL during mrs_loopdb_query.  Every call owns its output arrays and takes n from the C side: two threads hammering ONE twin with

@@ -167,3 +167,24 @@ def test_normalised_sinogram_and_degenerate_count(run, batch):
         np.testing.assert_allclose(r["norm"][b], want, rtol=2e-5, atol=2e-6)
     assert not r["raw"][r["idx"] == ZERO].any() and not r["norm"][r["idx"] == ZERO].any()
     assert r["degenerate"] == sum(blank[i] for i in r["idx"]), "degenerate count is not the number of blank images in the batch"
+
+
+def test_plans_of_one_geometry_own_their_tables():
+    """two plans of one small geometry (8 angles x 8 detectors on 8 x 8: slot tables) alive together, one destroyed before the other is
+    read again: equal slot tables, every ray dealt once; a geometry with more than 16 rays per lane creates without slot tables"""
+    import torch
+    assert torch.cuda.is_available()
+    from mr_slam_amd import ring
+    ang = _angles(TWO_PI, 8)
+    a, b = ring.RadonPlan(8, ang, 1.0, 8, 8), ring.RadonPlan(8, ang, 1.0, 8, 8)
+    rays_a, rays_b = a.slot_rays(), b.slot_rays()
+    assert rays_a.size == 1024 and np.array_equal(rays_a, rays_b)
+    assert np.array_equal(np.sort(rays_a[rays_a >= 0]), np.arange(64)) and (rays_a[rays_a < 0] == -1).all()
+    del a
+    assert np.array_equal(b.slot_rays(), rays_b)
+    x = torch.from_numpy(_images(8, 8)).to("cuda:0").contiguous()
+    first = b.forward(x)[0].cpu().numpy()
+    c = ring.RadonPlan(8, ang, 1.0, 8, 8)
+    assert np.array_equal(_bits(c.forward(x)[0].cpu().numpy()), _bits(first))
+    big = ring.RadonPlan(130, _angles(TWO_PI, 130), 1.0, 16, 16)            # 16 900 rays: 17 per lane
+    assert big.slot_rays().size == 0

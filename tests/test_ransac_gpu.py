@@ -196,3 +196,23 @@ def test_end_to_end_keypoints_descriptors_matches_pose_gicp():
     print("gicp converged", conv, "iterations", its, "translation error %.3e" % np.abs(Tg[0][:3, 3] - K.E2E_T).max())
     assert bool(np.asarray(conv).reshape(-1)[0])
     assert np.abs(np.asarray(Tg[0])[:3, 3] - K.E2E_T).max() < K.E2E_D and np.abs(np.asarray(Tg[0])[:3, :3] - Rm).max() < 0.02
+
+
+def test_profiled_call_returns_the_same_result_and_three_stage_times():
+    """mrs_ransac_pose_batch_profile on two pairs of eight correspondences, 64 hypotheses: T, info and the mask of the plain call with the
+    same seeds, bit for bit, and the three stage times"""
+    from mr_slam_amd import fpfh
+    rng = np.random.default_rng(16)
+    src = rng.uniform(-1, 1, (16, 3)).astype(np.float32)
+    dst = (src + np.float32([0.5, -0.25, 0.125])).astype(np.float32)
+    s, d = torch.tensor(src).to(DEV), torch.tensor(dst).to(DEV)
+    kw = dict(seeds=[3, 4], hypotheses=64, return_mask=True)
+    plain = fpfh.ransac_pose(s, d, [0, 8, 16], K.D, **kw)
+    *profiled, ms = fpfh.ransac_pose(s, d, [0, 8, 16], K.D, profile=True, **kw)
+    torch.cuda.synchronize()
+    print("stage ms", ms.tolist())
+    assert ms.shape == (3,) and np.isfinite(ms).all() and (ms >= 0).all()
+    assert len(profiled) == 3
+    for a, b in zip(plain, profiled):
+        assert a.cpu().numpy().tobytes() == b.cpu().numpy().tobytes()
+    assert plain[1].cpu().numpy()[:, 0].min() >= 3          # a pose was found for both pairs

@@ -377,10 +377,10 @@ int main(int argc, char** argv)
     RadonP p;
     p.A = A; p.D = D; p.H = H; p.W = W; p.stride = (W + 2 * kPad) | 1;
     const size_t nr = (size_t)A * D;
-    p.meta = plan->d_meta; p.base = plan->d_meta + nr;
-    p.q = reinterpret_cast<const float*>(plan->d_meta + 2 * nr); p.vm = p.q + nr; p.nrm = p.vm + nr;
+    p.meta = plan->d_meta.get(); p.base = p.meta + nr;
+    p.q = reinterpret_cast<const float*>(p.meta + 2 * nr); p.vm = p.q + nr; p.nrm = p.vm + nr;
     const size_t lds = 2 * (size_t)(H + 2 * kPad) * p.stride * sizeof(float);
-    int* d_deg = plan->d_degenerate;
+    int* d_deg = plan->d_degenerate.get();
     int batch = B;
     const Variant vars[] = {
         {"base (15 rays unrolled, U=6)", (void*)k_base<125>},
