@@ -1,11 +1,12 @@
 // gicp.hip -- host side of the batched GICP refinement: the handle (owning device buffers), the launch helpers and the C entry points.
 // The kernels and the design notes are in gicp_device.hpp, included here and nowhere else (one translation unit).
-// Point-to-point ICP (row G9) runs on the same handle: its kernels are in icp_device.hpp, its entry points at the end of the align section.
-// So does PCL-style GICP (row G11): pclgicp_device.hpp, entry points after ICP's.
-// Point-to-plane ICP (row G12) shares ICP's tick loop: its kernels are in icp_plane_device.hpp, the normals' entry points follow the covariances'.
+// Four registration methods run on the one handle, each an Estimator behind the one tick driver (run_ticks): fast_gicp's LM-GICP and its voxelised
+// variant, point-to-point ICP (row G9, icp_device.hpp), PCL-style GICP (row G11, pclgicp_device.hpp) and point-to-plane ICP (row G12,
+// icp_plane_device.hpp; the normals' entry points follow the covariances').
 #include <hipcub/hipcub.hpp>
 
 #include <cstdlib>
+#include <functional>
 #include <type_traits>
 
 #include "common.hpp"
@@ -203,7 +204,8 @@ int build_leaf_hier(mrs_gicp_batch* h, int w, const unsigned long long* d_keys, 
 }
 
 // ---- the one launch site of every kernel that more than one entry point starts ----
-// (kept after build_leaf_hier and before the entry points: the compiler emits template kernels in the order of their first use)
+// (kept after build_leaf_hier and before the entry points: the compiler emits template kernels in the order of their first use.  For the same
+// reason one of them, launch_pcl_sums, stands further down, in front of the tick driver.)
 
 // The round-3 scan of every source point.  Source points per lane: fewer points per wave = a more compact query set = sharper sub-tile
 // culling; more = every LDS candidate read serves more distance evaluations.  Measured (120k x 120k, MI355X):
@@ -269,6 +271,55 @@ void launch_linearize_voxel(mrs_gicp_batch* h, hipStream_t s)
     hipLaunchKernelGGL(k_linearize_voxel, dim3(h->lm.max_blocks, h->n_pairs), dim3(kNNThreads), 0, s, S.pts.get(), S.d_offs.get(), S.cov.get(),
                        h->vox.keys.get(), h->vox.mean.get(), h->vox.cov.get(), h->vox.n, h->lm.state.get(), h->prm, h->lm.partial.get(),
                        h->lm.max_blocks);
+}
+
+// The update kernels share one contract for the tick's counters n_next: [0] pairs that iterate again, [2] those of [0] that moved far, [3] the tick
+// carried a search.  Only k_lm_update writes [1] (pairs in an LM trial).
+void launch_lm_update(mrs_gicp_batch* h, int* n_next, int trial_only, hipStream_t s)
+{
+    GicpLmBuffers& L = h->lm;
+    hipLaunchKernelGGL(k_lm_update, dim3(h->n_pairs), dim3(kLmThreads), 0, s, L.state.get(), L.partial.get(), L.nblocks.get(), L.max_blocks, h->prm,
+                       n_next, trial_only);
+}
+
+// one ICP iteration's sums; plane: point-to-plane (row G12) instead of point-to-point (row G9)
+void launch_icp_sums(mrs_gicp_batch* h, bool plane, hipStream_t s)
+{
+    const GicpCloud &S = h->side[0], &T = h->side[1];
+    GicpLmBuffers& L = h->lm;
+    const dim3 grid(L.max_blocks, h->n_pairs);
+    if (plane)
+        hipLaunchKernelGGL(k_icp_plane_sums, grid, dim3(kNNThreads), 0, s, S.pts.get(), S.d_offs.get(), T.pts.get(), T.nrm.get(), T.d_offs.get(),
+                           L.state.get(), L.corr.get(), L.partial.get(), L.max_blocks);
+    else
+        hipLaunchKernelGGL(k_icp_sums, grid, dim3(kNNThreads), 0, s, S.pts.get(), S.d_offs.get(), T.pts.get(), T.d_offs.get(), L.state.get(),
+                           L.corr.get(), L.partial.get(), L.max_blocks);
+}
+
+void launch_icp_update(mrs_gicp_batch* h, bool plane, const IcpParams& dp, int* n_next, hipStream_t s)
+{
+    GicpLmBuffers& L = h->lm;
+    if (plane)
+        hipLaunchKernelGGL(k_icp_plane_update, dim3(h->n_pairs), dim3(kLmThreads), 0, s, L.state.get(), L.partial.get(), L.nblocks.get(),
+                           L.max_blocks, dp, n_next);
+    else
+        hipLaunchKernelGGL(k_icp_update, dim3(h->n_pairs), dim3(kLmThreads), 0, s, L.state.get(), L.partial.get(), L.nblocks.get(), L.max_blocks,
+                           dp, n_next);
+}
+
+void launch_pcl_update(mrs_gicp_batch* h, const PclGicpParams& dp, int* n_next, hipStream_t s)
+{
+    GicpLmBuffers& L = h->lm;
+    hipLaunchKernelGGL(k_pclgicp_update, dim3(h->n_pairs), dim3(kLmThreads), 0, s, L.state.get(), L.partial.get(), L.nblocks.get(), L.max_blocks,
+                       h->side[1].bbox.get(), dp, n_next);
+}
+
+// the correspondences of the last search as indices into the clouds as they were given (d_corr: one int per source point)
+void launch_corr_to_original(mrs_gicp_batch* h, int32_t* d_corr, hipStream_t s)
+{
+    const GicpCloud &S = h->side[0], &T = h->side[1];
+    hipLaunchKernelGGL(k_corr_to_original, dim3(64, h->n_pairs), dim3(256), 0, s, S.pts.get(), S.d_offs.get(), T.pts.get(), T.d_offs.get(),
+                       h->lm.corr.get(), d_corr);
 }
 
 // f(integral_constant<KMAX>) for the smallest list size that holds k neighbours.  WITH_30: the rung of RING++'s k (k_knn_cov: 30 list slots =
@@ -972,7 +1023,10 @@ int mrs_gicp_batch_get_voxel_map(mrs_gicp_batch* h, int32_t* h_n_voxels, int32_t
     return MRS_OK;
 }
 
-// The context slot (second stream, two events, pinned buffer) an alignment of a small batch holds for the duration of the call.  It goes back
+/* ---- alignments: one tick driver (run_ticks) and the frame around it (run_alignment), four estimators ---- */
+
+// The context slot (second stream, two events, pinned buffer) an alignment of a small batch borrows for the duration of the call when it needs
+// one: for covariances side by side (the stream and the events) or for a window's counters (the pinned buffer).  It goes back
 // idle: on the normal way out it is (the last window was synchronised); on any other way out work may still run on its stream, or a window's
 // counters may still be on their way into its pinned buffer from `s`, so both streams are drained first.
 struct AlignSide {
@@ -987,13 +1041,18 @@ struct AlignSide {
     }
 };
 
-// The covariances an alignment needs and the handle does not hold yet (mrs_gicp_batch_align, mrs_gicp_batch_align_pcl), enqueued on `s`.
-static int covariances_first(mrs_gicp_batch* h, bool small, mrs::SideSlot* sl, hipStream_t s)      // sl: the call's slot when `small`
+// both clouds of a small batch are new (every registration of the nodes): a cloud of 30-40 k points fills 150 of the 256 compute units with one
+// wave per SIMD, so the two k-NN + covariance passes run side by side on two streams instead of back to back
+static bool covariances_side_by_side(const mrs_gicp_batch* h)
+{
+    return h->n_pairs <= kLmWindowPairs && !h->side[0].cov_valid && !h->side[1].cov_valid && !mrs::dev_env("MRS_GICP_SERIAL_COV");
+}
+
+// The covariances the handle does not hold yet, enqueued on `s`.  sl: the call's slot when they run side by side, else null.
+static int covariances_first(mrs_gicp_batch* h, mrs::SideSlot* sl, hipStream_t s)
 {
     int st;
-    if (small && !h->side[0].cov_valid && !h->side[1].cov_valid && !mrs::dev_env("MRS_GICP_SERIAL_COV")) {
-        // both clouds are new (every registration of the nodes): a cloud of 30-40 k points fills 150 of the 256 compute units with one wave per
-        // SIMD, so the two k-NN + covariance passes run side by side on two streams instead of back to back
+    if (sl) {
         mrs::HandleStream& side = sl->stream;
         MRS_TRY(side.join_in(s));                                    // fork
         st = mrs_gicp_batch_compute_covariances(h, 1, nullptr, (mrs_stream)side.s);
@@ -1008,103 +1067,228 @@ static int covariances_first(mrs_gicp_batch* h, bool small, mrs::SideSlot* sl, h
     return MRS_OK;
 }
 
+namespace {
+
+// A launch site of the section further up that has to stand down here: k_pclgicp_sums<0, kPclTerms> is first used behind set_clouds_from's
+// k_copy_segments<...>, and the compiler emits template kernels in the order of their first use.
+void launch_pcl_sums(mrs_gicp_batch* h, hipStream_t s)
+{
+    const GicpCloud &S = h->side[0], &T = h->side[1];
+    GicpLmBuffers& L = h->lm;
+    // one launch over all 74 terms: it has no scratch at 2 waves per SIMD (DESIGN.md 4.15), so the two-range form is not needed
+    hipLaunchKernelGGL((k_pclgicp_sums<0, kPclTerms>), dim3(L.max_blocks, h->n_pairs), dim3(kNNThreads), 0, s, S.pts.get(), S.d_offs.get(),
+                       S.cov.get(), T.pts.get(), T.d_offs.get(), T.cov.get(), T.bbox.get(), L.state.get(), L.corr.get(), L.partial.get(), L.max_blocks);
+}
+
+// One registration method as the tick driver sees it.  A tick is one search of the pairs that iterate (nn_pass) and the estimator's two kernels:
+// the sums over the correspondences and the per-pair update, which writes the tick's counters (see launch_lm_update).
+struct Estimator {
+    GicpParams sp;              // the searches' parameters: the handle's, with the call's own correspondence distance for ICP and PCL-GICP
+    long max_ticks = 0;
+    bool covariances = false;   // reads the clouds' covariances
+    bool searches = true;       // false: the voxelised LM estimator, which looks its correspondences up in the targets' voxel map
+    bool may_window = true;     // every kernel of a tick gates itself on the pair's device-side state (k_linearize_voxel does not)
+    bool alternate = false;     // LM on ONE pair: windows enqueue every second tick without its search (trial_only)
+    std::function<void(int* n_next, int trial_only, hipStream_t s)> tick;       // launches the sums and the update
+};
+
+// ticks per window; MRS_DEV=1 MRS_GICP_WINDOW=n (0 or 1: the per-tick schedule)
+int lm_window()
+{
+    const char* const v = mrs::dev_env("MRS_GICP_WINDOW");
+    return v ? std::max(0, std::min(kLmWindowMax, atoi(v))) : kLmWindow;
+}
+
+// ticks per window of this call, 0: the per-tick schedule
+int window_of(const mrs_gicp_batch* h, const Estimator& est)
+{
+    const int window = h->n_pairs <= kLmWindowPairs && est.may_window ? lm_window() : 0;
+    return window > 1 ? window : 0;
+}
+
+// The estimator's ticks until no pair iterates or max_ticks is reached; *nn_ticks: the ticks that carried a search.  With a slot, a small
+// batch runs them in windows (see kLmWindowPairs) and the host reads a window's counters once; whatever is left, and every other batch, runs tick
+// by tick.  The per-tick loop is written for LM, whose ticks are linearisations (next[0]) or trials (next[1]); for the three estimators without
+// trials next[1] stays 0 and `next[0] > 0` is the loop's own condition.
+int run_ticks(mrs_gicp_batch* h, const Estimator& est, mrs::SideSlot* slot, hipStream_t s, long* nn_ticks)
+{
+    int* const counters = h->lm.nactive.get();      // [kLmWindowMax][4]
+    int st;
+    long ticks = 0;
+    *nn_ticks = 0;
+    int next[3] = {h->n_pairs, 0, h->n_pairs};      // pairs to iterate (LM: to linearise), pairs in an LM trial, pairs of [0] that moved far
+    const int window = slot ? window_of(h, est) : 0;
+    if (window > 0) {
+        static_assert(kLmWindowMax * 4 <= mrs::kSidePinnedInts, "the slot's pinned buffer holds a window's counters");
+        int* const h_win = slot->pinned.get();
+        const long bound = est.alternate ? 2 * est.max_ticks : est.max_ticks;      // a sat-out tick does no work: the bound counts work ticks
+        while (next[0] + next[1] > 0 && ticks < bound) {
+            MRS_HIP_TRY(hipMemsetAsync(counters, 0, (size_t)window * 4 * sizeof(int), s));
+            for (int t = 0; t < window; ++t) {
+                // ONE pair alternates between a linearisation and (at least) one LM trial: every second tick is enqueued without its four
+                // search kernels (an empty launch still costs ~5 us on the stream: 20 us per trial tick, ~160 us per registration).  If the
+                // pair needs a linearisation on such a tick after all (it only does after a rejected trial shifted the rhythm) it sits the
+                // tick out -- k_linearize / k_lm_update leave it alone -- and takes the next one: same transitions, same bits.
+                const int trial_only = (est.alternate && ((ticks + t) & 1)) ? 1 : 0;
+                h->big_movers = 1;                      // the broad search gates itself on the pair's motion (k_nn_scan: gate)
+                if (!trial_only && (st = nn_pass(h, est.sp, (ticks == 0 && t == 0) ? 0 : 1, s)) != MRS_OK) return st;
+                est.tick(counters + 4 * t, trial_only, s);
+            }
+            MRS_HIP_TRY(hipGetLastError());
+            MRS_HIP_TRY(hipMemcpyAsync(h_win, counters, (size_t)window * 4 * sizeof(int), hipMemcpyDeviceToHost, s));
+            MRS_HIP_TRY(hipStreamSynchronize(s));
+            for (int t = 0; t < window; ++t) *nn_ticks += h_win[4 * t + 3];
+            for (int i = 0; i < 3; ++i) next[i] = h_win[4 * (window - 1) + i];
+            ticks += window;
+        }
+    }
+    while (next[0] + next[1] > 0 && ticks < est.max_ticks) {
+        MRS_HIP_TRY(hipMemsetAsync(counters, 0, 4 * sizeof(int), s));
+        if (est.searches && next[0] > 0) {   // only linearisations search; LM trials score the cached correspondences
+            h->big_movers = next[2];
+            if ((st = nn_pass(h, est.sp, *nn_ticks == 0 ? 0 : 1, s)) != MRS_OK) return st;
+        }
+        if (next[0] > 0) ++*nn_ticks;
+        est.tick(counters, 0, s);
+        MRS_HIP_TRY(hipGetLastError());
+        MRS_HIP_TRY(hipMemcpyAsync(next, counters, 3 * sizeof(int), hipMemcpyDeviceToHost, s));
+        MRS_HIP_TRY(hipStreamSynchronize(s));
+        ++ticks;
+    }
+    return MRS_OK;
+}
+
+// Every pair active at its pose (h_poses; null: the identity).  narrow: through float, as the references' align() takes a Matrix4f guess.
+// y0_max: the previous iteration's error starts at DBL_MAX (ICP).
+void init_states(std::vector<LmState>& init, const double* h_poses, bool narrow, bool y0_max)
+{
+    for (size_t p = 0; p < init.size(); ++p) {
+        LmState& S = init[p];
+        memset(&S, 0, sizeof(LmState));
+        for (int i = 0; i < 16; ++i) {
+            const double g = h_poses ? h_poses[p * 16 + i] : (i % 5 == 0 ? 1.0 : 0.0);
+            S.x[i] = S.xi[i] = narrow ? (double)(float)g : g;
+        }
+        if (y0_max) S.y0 = DBL_MAX;
+        S.active = 1;
+    }
+}
+
+// what an alignment hands back, per pair (all but `final` optional)
+struct AlignOut {
+    double* final; int32_t *converged, *iterations, *state; double* hessian;
+};
+
+int read_results(mrs_gicp_batch* h, std::vector<LmState>& states, const AlignOut& out)
+{
+    MRS_HIP_TRY(hipMemcpy(states.data(), h->lm.state.get(), states.size() * sizeof(LmState), hipMemcpyDeviceToHost));
+    for (size_t p = 0; p < states.size(); ++p) {
+        const LmState& S = states[p];
+        for (int i = 0; i < 16; ++i) out.final[p * 16 + i] = (double)(float)S.x[i];  // final_transformation_ is float
+        if (out.converged) out.converged[p] = S.converged;
+        if (out.iterations) out.iterations[p] = S.outer;
+        if (out.state) out.state[p] = S.inner;
+        if (out.hessian) memcpy(out.hessian + p * 36, S.final_H, sizeof(S.final_H));
+    }
+    return MRS_OK;
+}
+
+// An alignment from `states` (init_states) to `out`, behind the caller's checks and its ensure_state -- device-side state first: its
+// (blocking) upload of the per-pair block counts would otherwise wait for the covariance kernels enqueued here and keep the host from enqueuing
+// the first ticks behind them.
+int run_alignment(mrs_gicp_batch* h, const Estimator& est, std::vector<LmState>& states, const AlignOut& out, hipStream_t s)
+{
+    int st;
+    const bool fork = est.covariances && covariances_side_by_side(h);
+    AlignSide side{h->ctx, s, {}, false};
+    if ((fork || window_of(h, est) > 0) && (st = mrs::side_acquire(h->ctx, &side.sl)) != MRS_OK) return st;
+    if (est.covariances && (st = covariances_first(h, fork ? side.sl.get() : nullptr, s)) != MRS_OK) return st;
+    if (!est.searches && (st = build_voxel_map(h, s)) != MRS_OK) return st;
+    MRS_HIP_TRY(hipMemcpyAsync(h->lm.state.get(), states.data(), states.size() * sizeof(LmState), hipMemcpyHostToDevice, s));
+    if (h->cert.searched) MRS_HIP_TRY(hipMemsetAsync(h->cert.searched.get(), 0, (size_t)h->n_pairs * kStatStride * sizeof(unsigned long long), s));
+    long nn_ticks = 0;
+    if ((st = run_ticks(h, est, side.sl.get(), s, &nn_ticks)) != MRS_OK) return st;
+    // every tick loop ends in a synchronisation of `s` and runs at least once (n_pairs >= 1, max_ticks >= 1): nothing is in flight here
+    if ((st = record_search_stats(h, nn_ticks)) != MRS_OK) return st;
+    if ((st = read_results(h, states, out)) != MRS_OK) return st;
+    side.completed = true;
+    return MRS_OK;
+}
+
+// The one-iteration hooks' prelude: the states at the given poses uploaded, a tick's counters cleared, one plain search with the handle's
+// search setting (sp null: none)
+int step_prelude(mrs_gicp_batch* h, const std::vector<LmState>& init, const GicpParams* sp, hipStream_t s)
+{
+    MRS_HIP_TRY(hipMemcpyAsync(h->lm.state.get(), init.data(), init.size() * sizeof(LmState), hipMemcpyHostToDevice, s));
+    MRS_HIP_TRY(hipMemsetAsync(h->lm.nactive.get(), 0, 4 * sizeof(int), s));
+    return sp ? nn_pass(h, *sp, 2, s) : MRS_OK;
+}
+
+// ... and what their epilogues share: the correspondences in the caller's numbering if wanted, and the states on their way back if wanted
+// (the hook adds its own copies and synchronises)
+int step_epilogue(mrs_gicp_batch* h, int32_t* d_corr, std::vector<LmState>* states, hipStream_t s)
+{
+    if (d_corr) launch_corr_to_original(h, d_corr, s);
+    MRS_HIP_TRY(hipGetLastError());
+    if (states) MRS_HIP_TRY(hipMemcpyAsync(states->data(), h->lm.state.get(), states->size() * sizeof(LmState), hipMemcpyDeviceToHost, s));
+    return MRS_OK;
+}
+
+// The ICP and PCL-GICP profile hooks' prelude: the states at the given poses on the device, the timer's events, and one plain search of every
+// source point (the handle's search setting, warm) timed alone into ms
+int profile_prelude(mrs_gicp_batch* h, const std::vector<LmState>& init, const GicpParams& sp, mrs::RepTimer& timer, int reps, float& ms,
+                    hipStream_t s)
+{
+    MRS_HIP_TRY(hipMemcpyAsync(h->lm.state.get(), init.data(), init.size() * sizeof(LmState), hipMemcpyHostToDevice, s));
+    MRS_HIP_TRY(hipStreamSynchronize(s));
+    MRS_TRY(timer.create());
+    int nn_st = MRS_OK;
+    const int st = timer.timed(ms, reps, s, [&]() { const int r = nn_pass(h, sp, 2, s); if (r != MRS_OK) nn_st = r; });
+    return st != MRS_OK ? st : nn_st;
+}
+
+// out_counts[0]: source points, [1]: those with a correspondence after the last search.  Blocking.
+int count_correspondences(mrs_gicp_batch* h, int64_t* out_counts)
+{
+    std::vector<int> corr(h->lm.n_seed);
+    MRS_HIP_TRY(hipMemcpy(corr.data(), h->lm.corr.get(), corr.size() * sizeof(int), hipMemcpyDeviceToHost));
+    int64_t c = 0;
+    for (int v : corr) c += v >= 0;
+    out_counts[0] = (int64_t)corr.size(); out_counts[1] = c;
+    return MRS_OK;
+}
+
+}  // namespace
+
+/* fast_gicp's LM-GICP, voxelised when the handle's voxel_resolution is positive.  An outer iteration is a linearisation and up to lm_max_iter
+ * trials, a tick each. */
 int mrs_gicp_batch_align(mrs_gicp_batch* h, const double* h_guess, double* h_final, int32_t* h_converged,
                          int32_t* h_iterations, double* h_hessian, mrs_stream stream)
 {
     MRS_REQUIRE(h && h_final, "null pointer");
     MRS_REQUIRE(h->clouds_set(), "set source and target clouds first");
     MRS_HIP_TRY(hipSetDevice(h->ctx->device));
-    hipStream_t s = (hipStream_t)stream;
-    int st;
-    // device-side state first: its (blocking) upload of the per-pair block counts would otherwise wait for the covariance kernels enqueued below
-    // and keep the host from enqueuing the first ticks behind them
-    st = ensure_state(h);
+    const int st = ensure_state(h);
     if (st != MRS_OK) return st;
-    const bool small = h->n_pairs <= kLmWindowPairs;
-    // a second stream, two events and a pinned buffer from the context's pool for the duration of this call (small batches only)
-    AlignSide side{h->ctx, s, {}, false};
-    if (small && (st = mrs::side_acquire(h->ctx, &side.sl)) != MRS_OK) return st;
-    if ((st = covariances_first(h, small, side.sl.get(), s)) != MRS_OK) return st;
-    if (h->prm.voxel_res > 0.0) {
-        st = build_voxel_map(h, s);
-        if (st != MRS_OK) return st;
-    }
-    GicpLmBuffers& L = h->lm;
     std::vector<LmState> init(h->n_pairs);
-    for (int p = 0; p < h->n_pairs; ++p) {
-        LmState& S = init[p];
-        memset(&S, 0, sizeof(S));
-        for (int i = 0; i < 16; ++i) {
-            const double g = h_guess ? h_guess[(size_t)p * 16 + i] : (i % 5 == 0 ? 1.0 : 0.0);
-            S.x[i] = S.xi[i] = (double)(float)g;  // the reference passes an Eigen::Matrix4f guess
-        }
-        S.lambda = -1.0; S.nu = 2.0; S.active = 1;
-    }
-    MRS_HIP_TRY(hipMemcpyAsync(L.state.get(), init.data(), init.size() * sizeof(LmState), hipMemcpyHostToDevice, s));
-    if (h->cert.searched) MRS_HIP_TRY(hipMemsetAsync(h->cert.searched.get(), 0, (size_t)h->n_pairs * kStatStride * sizeof(unsigned long long), s));
+    init_states(init, h_guess, true, false);
+    for (LmState& S : init) { S.lambda = -1.0; S.nu = 2.0; }
+    const bool voxel = h->prm.voxel_res > 0.0;
     const int limit = h->prm.force_iters > 0 ? h->prm.force_iters : h->prm.max_iter;
-    const long max_ticks = (long)limit * (h->prm.lm_max_iter + 1) + 1;
-    long ticks = 0, nn_ticks = 0;
-    int next[3] = {h->n_pairs, 0, h->n_pairs};   // pairs to linearise (phase 0), pairs in an LM trial (phase 1), pairs of [0] that moved far
-    int window = kLmWindow;
-    if (const char* v = mrs::dev_env("MRS_GICP_WINDOW")) window = std::max(0, std::min(kLmWindowMax, atoi(v)));
-    if (small && window > 1 && h->prm.voxel_res <= 0.0) {
-        static_assert(kLmWindowMax * 4 <= mrs::kSidePinnedInts, "the slot's pinned buffer holds a window's counters");
-        int* const h_win = side.sl->pinned.get();
-        const bool alternate = h->n_pairs == 1;
-        const long max_ticks_w = alternate ? 2 * max_ticks : max_ticks;      // a sat-out tick does no work: the bound counts work ticks
-        while (next[0] + next[1] > 0 && ticks < max_ticks_w) {
-            MRS_HIP_TRY(hipMemsetAsync(L.nactive.get(), 0, (size_t)window * 4 * sizeof(int), s));
-            for (int t = 0; t < window; ++t) {
-                // ONE pair alternates between a linearisation and (at least) one LM trial: every second tick is enqueued without its four
-                // search kernels (an empty launch still costs ~5 us on the stream: 20 us per trial tick, ~160 us per registration).  If the
-                // pair needs a linearisation on such a tick after all (it only does after a rejected trial shifted the rhythm) it sits the
-                // tick out -- k_linearize / k_lm_update leave it alone -- and takes the next one: same transitions, same bits.
-                const int trial_only = (alternate && ((ticks + t) & 1)) ? 1 : 0;
-                h->big_movers = 1;                      // the broad search gates itself on the pair's motion (k_nn_scan: gate)
-                if (!trial_only && (st = nn_pass(h, h->prm, (ticks == 0 && t == 0) ? 0 : 1, s)) != MRS_OK) return st;
-                launch_linearize(h, trial_only, s);
-                hipLaunchKernelGGL(k_lm_update, dim3(h->n_pairs), dim3(kLmThreads), 0, s, L.state.get(), L.partial.get(), L.nblocks.get(),
-                                   L.max_blocks, h->prm, L.nactive.get() + 4 * t, trial_only);
-            }
-            MRS_HIP_TRY(hipGetLastError());
-            MRS_HIP_TRY(hipMemcpyAsync(h_win, L.nactive.get(), (size_t)window * 4 * sizeof(int), hipMemcpyDeviceToHost, s));
-            MRS_HIP_TRY(hipStreamSynchronize(s));
-            for (int t = 0; t < window; ++t) nn_ticks += h_win[4 * t + 3];
-            for (int i = 0; i < 3; ++i) next[i] = h_win[4 * (window - 1) + i];
-            ticks += window;
-        }
-    }
-    while (next[0] + next[1] > 0 && ticks < max_ticks) {
-        MRS_HIP_TRY(hipMemsetAsync(L.nactive.get(), 0, 4 * sizeof(int), s));
-        if (h->prm.voxel_res > 0.0) {
+    Estimator est;
+    est.sp = h->prm;
+    est.max_ticks = (long)limit * (h->prm.lm_max_iter + 1) + 1;
+    est.covariances = true;
+    est.searches = est.may_window = !voxel;
+    est.alternate = h->n_pairs == 1;
+    est.tick = [h, voxel](int* n_next, int trial_only, hipStream_t s) {
+        if (voxel)
             launch_linearize_voxel(h, s);
-        } else {
-            if (next[0] > 0) {   // only linearisations search; LM trials score the cached correspondences
-                h->big_movers = next[2];
-                if ((st = nn_pass(h, h->prm, nn_ticks == 0 ? 0 : 1, s)) != MRS_OK) return st;
-            }
-            launch_linearize(h, 0, s);
-        }
-        if (next[0] > 0) ++nn_ticks;
-        hipLaunchKernelGGL(k_lm_update, dim3(h->n_pairs), dim3(kLmThreads), 0, s, L.state.get(), L.partial.get(), L.nblocks.get(),
-                           L.max_blocks, h->prm, L.nactive.get(), 0);
-        MRS_HIP_TRY(hipGetLastError());
-        MRS_HIP_TRY(hipMemcpyAsync(next, L.nactive.get(), 3 * sizeof(int), hipMemcpyDeviceToHost, s));
-        MRS_HIP_TRY(hipStreamSynchronize(s));
-        ++ticks;
-    }
-    if ((st = record_search_stats(h, nn_ticks)) != MRS_OK) return st;
-    MRS_HIP_TRY(hipMemcpy(init.data(), L.state.get(), init.size() * sizeof(LmState), hipMemcpyDeviceToHost));
-    for (int p = 0; p < h->n_pairs; ++p) {
-        const LmState& S = init[p];
-        for (int i = 0; i < 16; ++i) h_final[(size_t)p * 16 + i] = (double)(float)S.x[i];  // final_transformation_ is float
-        if (h_converged) h_converged[p] = S.converged;
-        if (h_iterations) h_iterations[p] = S.outer;
-        if (h_hessian) memcpy(h_hessian + (size_t)p * 36, S.final_H, sizeof(S.final_H));
-    }
-    side.completed = true;
-    return MRS_OK;
+        else
+            launch_linearize(h, trial_only, s);
+        launch_lm_update(h, n_next, trial_only, s);
+    };
+    return run_alignment(h, est, init,AlignOut{h_final, h_converged, h_iterations, nullptr, h_hessian}, (hipStream_t)stream);
 }
 
 /* ---- point-to-point ICP (row G9; kernels: icp_device.hpp) ---- */
@@ -1151,31 +1335,6 @@ GicpParams icp_search_params(const mrs_gicp_batch* h, const mrs_icp_params* p)
     return sp;
 }
 
-void launch_icp_plane_sums(mrs_gicp_batch* h, hipStream_t s)
-{
-    const GicpCloud &S = h->side[0], &T = h->side[1];
-    GicpLmBuffers& L = h->lm;
-    hipLaunchKernelGGL(k_icp_plane_sums, dim3(L.max_blocks, h->n_pairs), dim3(kNNThreads), 0, s, S.pts.get(), S.d_offs.get(), T.pts.get(),
-                       T.nrm.get(), T.d_offs.get(), L.state.get(), L.corr.get(), L.partial.get(), L.max_blocks);
-}
-
-// one iteration's sums and update; plane: point-to-plane (row G12) instead of point-to-point (row G9)
-void launch_icp_tick(mrs_gicp_batch* h, bool plane, const IcpParams& dp, int* n_next, hipStream_t s)
-{
-    const GicpCloud &S = h->side[0], &T = h->side[1];
-    GicpLmBuffers& L = h->lm;
-    if (plane) {
-        launch_icp_plane_sums(h, s);
-        hipLaunchKernelGGL(k_icp_plane_update, dim3(h->n_pairs), dim3(kLmThreads), 0, s, L.state.get(), L.partial.get(), L.nblocks.get(),
-                           L.max_blocks, dp, n_next);
-        return;
-    }
-    hipLaunchKernelGGL(k_icp_sums, dim3(L.max_blocks, h->n_pairs), dim3(kNNThreads), 0, s, S.pts.get(), S.d_offs.get(), T.pts.get(), T.d_offs.get(),
-                       L.state.get(), L.corr.get(), L.partial.get(), L.max_blocks);
-    hipLaunchKernelGGL(k_icp_update, dim3(h->n_pairs), dim3(kLmThreads), 0, s, L.state.get(), L.partial.get(), L.nblocks.get(), L.max_blocks, dp,
-                       n_next);
-}
-
 // state, block counts and a partial buffer for the terms of the estimator at hand (29 for point-to-plane: one more than GICP's 28)
 int icp_ensure_state(mrs_gicp_batch* h, bool plane)
 {
@@ -1205,84 +1364,23 @@ mrs_icp_params icp_params_of(const mrs_icp_plane_params* p)
     return q;
 }
 
-/* The tick loop of mrs_gicp_batch_align with one kind of tick: search, sums, update.  No covariances, no voxel map. */
 int icp_align(mrs_gicp_batch* h, const mrs_icp_params* p, bool plane, const double* h_guess, double* h_final, int32_t* h_converged,
               int32_t* h_iterations, int32_t* h_state, mrs_stream stream)
 {
-    int st;
     MRS_HIP_TRY(hipSetDevice(h->ctx->device));
-    hipStream_t s = (hipStream_t)stream;
-    if ((st = icp_ensure_state(h, plane)) != MRS_OK) return st;
+    const int st = icp_ensure_state(h, plane);
+    if (st != MRS_OK) return st;
     const IcpParams dp = icp_device_params(h, p);
-    const GicpParams sp = icp_search_params(h, p);
-    GicpLmBuffers& L = h->lm;
-    const int P = h->n_pairs;
-    std::vector<LmState> init(P);
-    for (int q = 0; q < P; ++q) {
-        LmState& S = init[q];
-        memset(&S, 0, sizeof(S));
-        for (int i = 0; i < 16; ++i) {
-            const double g = h_guess ? h_guess[(size_t)q * 16 + i] : (i % 5 == 0 ? 1.0 : 0.0);
-            S.x[i] = S.xi[i] = (double)(float)g;     // pcl::Registration::align takes a Matrix4f guess
-        }
-        S.y0 = DBL_MAX; S.active = 1;
-    }
-    MRS_HIP_TRY(hipMemcpyAsync(L.state.get(), init.data(), init.size() * sizeof(LmState), hipMemcpyHostToDevice, s));
-    if (h->cert.searched) MRS_HIP_TRY(hipMemsetAsync(h->cert.searched.get(), 0, (size_t)P * kStatStride * sizeof(unsigned long long), s));
-    const long max_ticks = p->force_iterations > 0 ? p->force_iterations : p->max_iterations;     // one iteration per tick
-    long ticks = 0, nn_ticks = 0;
-    int next[4] = {P, 0, P, 0};
-    int window = kLmWindow;
-    if (const char* v = mrs::dev_env("MRS_GICP_WINDOW")) window = std::max(0, std::min(kLmWindowMax, atoi(v)));
-    if (P <= kLmWindowPairs && window > 1) {
-        // the pinned buffer of a context slot receives a window's counters (its stream and events are not used here)
-        struct Side {
-            mrs_ctx* ctx; hipStream_t s; std::unique_ptr<mrs::SideSlot> sl; bool completed;
-            ~Side()
-            {
-                if (!completed && sl) (void)hipStreamSynchronize(s);
-                mrs::side_release(ctx, std::move(sl));
-            }
-        } side{h->ctx, s, {}, false};
-        if ((st = mrs::side_acquire(h->ctx, &side.sl)) != MRS_OK) return st;
-        int* const h_win = side.sl->pinned.get();
-        while (next[0] > 0 && ticks < max_ticks) {
-            MRS_HIP_TRY(hipMemsetAsync(L.nactive.get(), 0, (size_t)window * 4 * sizeof(int), s));
-            for (int t = 0; t < window; ++t) {
-                h->big_movers = 1;                      // the broad search gates itself on the pair's motion (k_nn_scan: gate)
-                if ((st = nn_pass(h, sp, (ticks == 0 && t == 0) ? 0 : 1, s)) != MRS_OK) return st;
-                launch_icp_tick(h, plane, dp, L.nactive.get() + 4 * t, s);
-            }
-            MRS_HIP_TRY(hipGetLastError());
-            MRS_HIP_TRY(hipMemcpyAsync(h_win, L.nactive.get(), (size_t)window * 4 * sizeof(int), hipMemcpyDeviceToHost, s));
-            MRS_HIP_TRY(hipStreamSynchronize(s));
-            for (int t = 0; t < window; ++t) nn_ticks += h_win[4 * t + 3];
-            for (int i = 0; i < 3; ++i) next[i] = h_win[4 * (window - 1) + i];
-            ticks += window;
-        }
-        side.completed = true;
-    }
-    while (next[0] > 0 && ticks < max_ticks) {
-        MRS_HIP_TRY(hipMemsetAsync(L.nactive.get(), 0, 4 * sizeof(int), s));
-        h->big_movers = next[2];
-        if ((st = nn_pass(h, sp, nn_ticks == 0 ? 0 : 1, s)) != MRS_OK) return st;
-        launch_icp_tick(h, plane, dp, L.nactive.get(), s);
-        ++nn_ticks;
-        MRS_HIP_TRY(hipGetLastError());
-        MRS_HIP_TRY(hipMemcpyAsync(next, L.nactive.get(), 3 * sizeof(int), hipMemcpyDeviceToHost, s));
-        MRS_HIP_TRY(hipStreamSynchronize(s));
-        ++ticks;
-    }
-    if ((st = record_search_stats(h, nn_ticks)) != MRS_OK) return st;
-    MRS_HIP_TRY(hipMemcpy(init.data(), L.state.get(), init.size() * sizeof(LmState), hipMemcpyDeviceToHost));
-    for (int q = 0; q < P; ++q) {
-        const LmState& S = init[q];
-        for (int i = 0; i < 16; ++i) h_final[(size_t)q * 16 + i] = (double)(float)S.x[i];  // final_transformation_ is float
-        if (h_converged) h_converged[q] = S.converged;
-        if (h_iterations) h_iterations[q] = S.outer;
-        if (h_state) h_state[q] = S.inner;
-    }
-    return MRS_OK;
+    Estimator est;              // one kind of tick, one iteration each: search, sums, update.  No covariances, no voxel map.
+    est.sp = icp_search_params(h, p);
+    est.max_ticks = p->force_iterations > 0 ? p->force_iterations : p->max_iterations;
+    est.tick = [h, plane, &dp](int* n_next, int, hipStream_t s) {
+        launch_icp_sums(h, plane, s);
+        launch_icp_update(h, plane, dp, n_next, s);
+    };
+    std::vector<LmState> init(h->n_pairs);
+    init_states(init, h_guess, true, true);
+    return run_alignment(h, est, init, AlignOut{h_final, h_converged, h_iterations, h_state, nullptr}, (hipStream_t)stream);
 }
 
 int icp_step(mrs_gicp_batch* h, const mrs_icp_params* p, bool plane, const double* h_poses, double* h_sums, double* h_delta, int32_t* h_state,
@@ -1291,8 +1389,6 @@ int icp_step(mrs_gicp_batch* h, const mrs_icp_params* p, bool plane, const doubl
     int st;
     MRS_HIP_TRY(hipSetDevice(h->ctx->device));
     hipStream_t s = (hipStream_t)stream;
-    const GicpCloud &S = h->side[0], &T = h->side[1];
-    GicpLmBuffers& L = h->lm;
     const int terms = plane ? kIcpPlaneTerms : kIcpTerms;
     if ((st = icp_ensure_state(h, plane)) != MRS_OK) return st;
     IcpParams dp = icp_device_params(h, p);
@@ -1300,20 +1396,11 @@ int icp_step(mrs_gicp_batch* h, const mrs_icp_params* p, bool plane, const doubl
     dp.crit.force_iters = 0;
     const GicpParams sp = icp_search_params(h, p);
     std::vector<LmState> init(h->n_pairs);
-    for (int q = 0; q < h->n_pairs; ++q) {
-        memset(&init[q], 0, sizeof(LmState));
-        for (int i = 0; i < 16; ++i) init[q].x[i] = init[q].xi[i] = h_poses[(size_t)q * 16 + i];
-        init[q].y0 = DBL_MAX; init[q].active = 1;
-    }
-    MRS_HIP_TRY(hipMemcpyAsync(L.state.get(), init.data(), init.size() * sizeof(LmState), hipMemcpyHostToDevice, s));
-    MRS_HIP_TRY(hipMemsetAsync(L.nactive.get(), 0, 4 * sizeof(int), s));
-    if ((st = nn_pass(h, sp, 2, s)) != MRS_OK) return st;
-    launch_icp_tick(h, plane, dp, L.nactive.get(), s);
-    if (d_corr)
-        hipLaunchKernelGGL(k_corr_to_original, dim3(64, h->n_pairs), dim3(256), 0, s, S.pts.get(), S.d_offs.get(), T.pts.get(), T.d_offs.get(),
-                           L.corr.get(), d_corr);
-    MRS_HIP_TRY(hipGetLastError());
-    MRS_HIP_TRY(hipMemcpyAsync(init.data(), L.state.get(), init.size() * sizeof(LmState), hipMemcpyDeviceToHost, s));
+    init_states(init, h_poses, false, true);
+    if ((st = step_prelude(h, init, &sp, s)) != MRS_OK) return st;
+    launch_icp_sums(h, plane, s);
+    launch_icp_update(h, plane, dp, h->lm.nactive.get(), s);
+    if ((st = step_epilogue(h, d_corr, &init, s)) != MRS_OK) return st;
     MRS_HIP_TRY(hipStreamSynchronize(s));
     for (int q = 0; q < h->n_pairs; ++q) {
         memcpy(h_sums + (size_t)q * terms, init[q].H, terms * sizeof(double));
@@ -1451,38 +1538,9 @@ int pcl_ensure_state(mrs_gicp_batch* h)
     return h->lm.partial.reserve(need, need);
 }
 
-void launch_pcl_sums(mrs_gicp_batch* h, hipStream_t s)
-{
-    const GicpCloud &S = h->side[0], &T = h->side[1];
-    GicpLmBuffers& L = h->lm;
-    // one launch over all 74 terms: it has no scratch at 2 waves per SIMD (DESIGN.md 4.15), so the two-range form is not needed
-    hipLaunchKernelGGL((k_pclgicp_sums<0, kPclTerms>), dim3(L.max_blocks, h->n_pairs), dim3(kNNThreads), 0, s, S.pts.get(), S.d_offs.get(),
-                       S.cov.get(), T.pts.get(), T.d_offs.get(), T.cov.get(), T.bbox.get(), L.state.get(), L.corr.get(), L.partial.get(), L.max_blocks);
-}
-
-void launch_pcl_update(mrs_gicp_batch* h, const PclGicpParams& dp, int* n_next, hipStream_t s)
-{
-    GicpLmBuffers& L = h->lm;
-    hipLaunchKernelGGL(k_pclgicp_update, dim3(h->n_pairs), dim3(kLmThreads), 0, s, L.state.get(), L.partial.get(), L.nblocks.get(), L.max_blocks,
-                       h->side[1].bbox.get(), dp, n_next);
-}
-
-void pcl_init_states(std::vector<LmState>& init, const double* h_poses, bool narrow)
-{
-    for (size_t q = 0; q < init.size(); ++q) {
-        LmState& S = init[q];
-        memset(&S, 0, sizeof(S));
-        for (int i = 0; i < 16; ++i) {
-            const double g = h_poses ? h_poses[q * 16 + i] : (i % 5 == 0 ? 1.0 : 0.0);
-            S.x[i] = S.xi[i] = narrow ? (double)(float)g : g;     // pcl::Registration::align takes a Matrix4f guess
-        }
-        S.active = 1;
-    }
-}
-
 }  // namespace
 
-/* The tick loop of mrs_gicp_batch_align_icp (one kind of tick: search, sums, update) behind the covariances of mrs_gicp_batch_align. */
+/* ICP's kind of tick (search, sums, update: one iteration each) behind the covariances of mrs_gicp_batch_align. */
 int mrs_gicp_batch_align_pcl(mrs_gicp_batch* h, const mrs_pclgicp_params* p, const double* h_guess, double* h_final, int32_t* h_converged,
                              int32_t* h_iterations, int32_t* h_state, mrs_stream stream)
 {
@@ -1492,67 +1550,19 @@ int mrs_gicp_batch_align_pcl(mrs_gicp_batch* h, const mrs_pclgicp_params* p, con
     int st = pcl_check_params(p);
     if (st != MRS_OK) return st;
     MRS_HIP_TRY(hipSetDevice(h->ctx->device));
-    hipStream_t s = (hipStream_t)stream;
     if ((st = pcl_ensure_state(h)) != MRS_OK) return st;
     const PclGicpParams dp = pcl_device_params(h, p);
-    const GicpParams sp = pcl_search_params(h, p);
-    GicpLmBuffers& L = h->lm;
-    const int P = h->n_pairs;
-    const bool small = P <= kLmWindowPairs;
-    AlignSide side{h->ctx, s, {}, false};
-    if (small && (st = mrs::side_acquire(h->ctx, &side.sl)) != MRS_OK) return st;
-    if ((st = covariances_first(h, small, side.sl.get(), s)) != MRS_OK) return st;
-    std::vector<LmState> init(P);
-    pcl_init_states(init, h_guess, true);
-    MRS_HIP_TRY(hipMemcpyAsync(L.state.get(), init.data(), init.size() * sizeof(LmState), hipMemcpyHostToDevice, s));
-    if (h->cert.searched) MRS_HIP_TRY(hipMemsetAsync(h->cert.searched.get(), 0, (size_t)P * kStatStride * sizeof(unsigned long long), s));
-    const long max_ticks = p->force_iterations > 0 ? p->force_iterations : p->max_iterations;     // one iteration per tick
-    long ticks = 0, nn_ticks = 0;
-    int next[4] = {P, 0, P, 0};
-    int window = kLmWindow;
-    if (const char* v = mrs::dev_env("MRS_GICP_WINDOW")) window = std::max(0, std::min(kLmWindowMax, atoi(v)));
-    if (small && window > 1) {
-        int* const h_win = side.sl->pinned.get();
-        while (next[0] > 0 && ticks < max_ticks) {
-            MRS_HIP_TRY(hipMemsetAsync(L.nactive.get(), 0, (size_t)window * 4 * sizeof(int), s));
-            for (int t = 0; t < window; ++t) {
-                h->big_movers = 1;                      // the broad search gates itself on the pair's motion (k_nn_scan: gate)
-                if ((st = nn_pass(h, sp, (ticks == 0 && t == 0) ? 0 : 1, s)) != MRS_OK) return st;
-                launch_pcl_sums(h, s);
-                launch_pcl_update(h, dp, L.nactive.get() + 4 * t, s);
-            }
-            MRS_HIP_TRY(hipGetLastError());
-            MRS_HIP_TRY(hipMemcpyAsync(h_win, L.nactive.get(), (size_t)window * 4 * sizeof(int), hipMemcpyDeviceToHost, s));
-            MRS_HIP_TRY(hipStreamSynchronize(s));
-            for (int t = 0; t < window; ++t) nn_ticks += h_win[4 * t + 3];
-            for (int i = 0; i < 3; ++i) next[i] = h_win[4 * (window - 1) + i];
-            ticks += window;
-        }
-    }
-    while (next[0] > 0 && ticks < max_ticks) {
-        MRS_HIP_TRY(hipMemsetAsync(L.nactive.get(), 0, 4 * sizeof(int), s));
-        h->big_movers = next[2];
-        if ((st = nn_pass(h, sp, nn_ticks == 0 ? 0 : 1, s)) != MRS_OK) return st;
+    Estimator est;
+    est.sp = pcl_search_params(h, p);
+    est.max_ticks = p->force_iterations > 0 ? p->force_iterations : p->max_iterations;
+    est.covariances = true;
+    est.tick = [h, &dp](int* n_next, int, hipStream_t s) {
         launch_pcl_sums(h, s);
-        launch_pcl_update(h, dp, L.nactive.get(), s);
-        ++nn_ticks;
-        MRS_HIP_TRY(hipGetLastError());
-        MRS_HIP_TRY(hipMemcpyAsync(next, L.nactive.get(), 3 * sizeof(int), hipMemcpyDeviceToHost, s));
-        MRS_HIP_TRY(hipStreamSynchronize(s));
-        ++ticks;
-    }
-    MRS_HIP_TRY(hipStreamSynchronize(s));
-    side.completed = true;
-    if ((st = record_search_stats(h, nn_ticks)) != MRS_OK) return st;
-    MRS_HIP_TRY(hipMemcpy(init.data(), L.state.get(), init.size() * sizeof(LmState), hipMemcpyDeviceToHost));
-    for (int q = 0; q < P; ++q) {
-        const LmState& S = init[q];
-        for (int i = 0; i < 16; ++i) h_final[(size_t)q * 16 + i] = (double)(float)S.x[i];  // final_transformation_ is float
-        if (h_converged) h_converged[q] = S.converged;
-        if (h_iterations) h_iterations[q] = S.outer;
-        if (h_state) h_state[q] = S.inner;
-    }
-    return MRS_OK;
+        launch_pcl_update(h, dp, n_next, s);
+    };
+    std::vector<LmState> init(h->n_pairs);
+    init_states(init, h_guess, true, false);
+    return run_alignment(h, est, init, AlignOut{h_final, h_converged, h_iterations, h_state, nullptr}, (hipStream_t)stream);
 }
 
 int mrs_gicp_batch_pcl_step(mrs_gicp_batch* h, const mrs_pclgicp_params* p, const double* h_poses, double* h_sums, double* h_next,
@@ -1565,28 +1575,20 @@ int mrs_gicp_batch_pcl_step(mrs_gicp_batch* h, const mrs_pclgicp_params* p, cons
     if (st != MRS_OK) return st;
     MRS_HIP_TRY(hipSetDevice(h->ctx->device));
     hipStream_t s = (hipStream_t)stream;
-    const GicpCloud &S = h->side[0], &T = h->side[1];
     GicpLmBuffers& L = h->lm;
     if ((st = pcl_ensure_state(h)) != MRS_OK) return st;
-    for (int w = 0; w < 2; ++w)
-        if (!h->side[w].cov_valid) { st = mrs_gicp_batch_compute_covariances(h, w, nullptr, stream); if (st != MRS_OK) return st; }
+    if ((st = covariances_first(h, nullptr, s)) != MRS_OK) return st;
     PclGicpParams dp = pcl_device_params(h, p);
     dp.crit.max_iter = 1;           // one iteration, then the pair stops whatever the rule says
     dp.crit.force_iters = 0;
     const GicpParams sp = pcl_search_params(h, p);
     const int P = h->n_pairs;
     std::vector<LmState> init(P);
-    pcl_init_states(init, h_poses, false);
-    MRS_HIP_TRY(hipMemcpyAsync(L.state.get(), init.data(), init.size() * sizeof(LmState), hipMemcpyHostToDevice, s));
-    MRS_HIP_TRY(hipMemsetAsync(L.nactive.get(), 0, 4 * sizeof(int), s));
-    if ((st = nn_pass(h, sp, 2, s)) != MRS_OK) return st;
+    init_states(init, h_poses, false, false);
+    if ((st = step_prelude(h, init, &sp, s)) != MRS_OK) return st;
     launch_pcl_sums(h, s);
     launch_pcl_update(h, dp, L.nactive.get(), s);
-    if (d_corr)
-        hipLaunchKernelGGL(k_corr_to_original, dim3(64, P), dim3(256), 0, s, S.pts.get(), S.d_offs.get(), T.pts.get(), T.d_offs.get(),
-                           L.corr.get(), d_corr);
-    MRS_HIP_TRY(hipGetLastError());
-    MRS_HIP_TRY(hipMemcpyAsync(init.data(), L.state.get(), init.size() * sizeof(LmState), hipMemcpyDeviceToHost, s));
+    if ((st = step_epilogue(h, d_corr, &init, s)) != MRS_OK) return st;
     for (int q = 0; q < P; ++q)
         MRS_HIP_TRY(hipMemcpyAsync(h_sums + (size_t)q * kPclTerms, L.partial.get() + ((size_t)q * (L.max_blocks + 1) + L.max_blocks) * kPclTerms,
                                    kPclTerms * sizeof(double), hipMemcpyDeviceToHost, s));
@@ -1616,29 +1618,16 @@ int mrs_gicp_batch_pcl_profile(mrs_gicp_batch* h, const mrs_pclgicp_params* p, c
     hipStream_t s = (hipStream_t)stream;
     GicpLmBuffers& L = h->lm;
     if ((st = pcl_ensure_state(h)) != MRS_OK) return st;
-    for (int w = 0; w < 2; ++w)
-        if (!h->side[w].cov_valid) { st = mrs_gicp_batch_compute_covariances(h, w, nullptr, stream); if (st != MRS_OK) return st; }
+    if ((st = covariances_first(h, nullptr, s)) != MRS_OK) return st;
     PclGicpParams dp = pcl_device_params(h, p);
     dp.crit.max_iter = INT32_MAX;       // the update kernel is timed on pairs that stay active: no rule may end them
     dp.crit.force_iters = INT32_MAX;
-    const GicpParams sp = pcl_search_params(h, p);
     std::vector<LmState> init(h->n_pairs);
-    pcl_init_states(init, h_poses, false);
-    MRS_HIP_TRY(hipMemcpyAsync(L.state.get(), init.data(), init.size() * sizeof(LmState), hipMemcpyHostToDevice, s));
-    MRS_HIP_TRY(hipStreamSynchronize(s));
+    init_states(init, h_poses, false, false);
     mrs::RepTimer timer;
-    MRS_TRY(timer.create());
-    int nn_st = MRS_OK;
-    if ((st = timer.timed(out_ms[0], reps, s, [&]() { const int r = nn_pass(h, sp, 2, s); if (r != MRS_OK) nn_st = r; })) != MRS_OK) return st;
-    if (nn_st != MRS_OK) return nn_st;
+    if ((st = profile_prelude(h, init, pcl_search_params(h, p), timer, reps, out_ms[0], s)) != MRS_OK) return st;
     if ((st = timer.timed(out_ms[1], reps, s, [&]() { launch_pcl_sums(h, s); })) != MRS_OK) return st;
-    {
-        std::vector<int> corr(L.n_seed);
-        MRS_HIP_TRY(hipMemcpy(corr.data(), L.corr.get(), corr.size() * sizeof(int), hipMemcpyDeviceToHost));
-        int64_t c = 0;
-        for (int v : corr) c += v >= 0;
-        out_counts[0] = (int64_t)L.n_seed; out_counts[1] = c;
-    }
+    if ((st = count_correspondences(h, out_counts)) != MRS_OK) return st;
     MRS_HIP_TRY(hipMemsetAsync(L.nactive.get(), 0, 4 * sizeof(int), s));
     // every launch starts from the given poses (a device-to-device copy of the states, part of the time): the inner minimisation timed is
     // that of the sums at hand, not of a pose already at their minimum
@@ -1660,33 +1649,23 @@ int mrs_gicp_batch_linearize(mrs_gicp_batch* h, const double* h_poses, double* h
     MRS_REQUIRE(h->clouds_set(), "set source and target clouds first");
     MRS_HIP_TRY(hipSetDevice(h->ctx->device));
     hipStream_t s = (hipStream_t)stream;
-    const GicpCloud &S = h->side[0], &T = h->side[1];
+    const GicpCloud& S = h->side[0];
     GicpLmBuffers& L = h->lm;
+    const bool voxel = h->prm.voxel_res > 0.0;
     int st;
-    for (int w = 0; w < 2; ++w)
-        if (!h->side[w].cov_valid) { st = mrs_gicp_batch_compute_covariances(h, w, nullptr, stream); if (st != MRS_OK) return st; }
-    st = ensure_state(h);
-    if (st != MRS_OK) return st;
+    if ((st = covariances_first(h, nullptr, s)) != MRS_OK) return st;
+    if ((st = ensure_state(h)) != MRS_OK) return st;
     std::vector<LmState> init(h->n_pairs);
-    for (int p = 0; p < h->n_pairs; ++p) {
-        memset(&init[p], 0, sizeof(LmState));
-        for (int i = 0; i < 16; ++i) init[p].x[i] = init[p].xi[i] = h_poses[(size_t)p * 16 + i];
-        init[p].active = 1;
-    }
-    MRS_HIP_TRY(hipMemcpyAsync(L.state.get(), init.data(), init.size() * sizeof(LmState), hipMemcpyHostToDevice, s));
-    if (h->prm.voxel_res > 0.0) {
-        st = build_voxel_map(h, s);
-        if (st != MRS_OK) return st;
+    init_states(init, h_poses, false, false);       // y0 stays 0: k_linearize does not read it
+    if ((st = step_prelude(h, init, voxel ? nullptr : &h->prm, s)) != MRS_OK) return st;
+    if (voxel) {
+        if ((st = build_voxel_map(h, s)) != MRS_OK) return st;
         MRS_REQUIRE(d_corr == nullptr, "per-point correspondences are not defined for the voxelised variant");
         launch_linearize_voxel(h, s);
     } else {
-        if ((st = nn_pass(h, h->prm, 2, s)) != MRS_OK) return st;
         launch_linearize(h, 0, s);
     }
-    if (d_corr)
-        hipLaunchKernelGGL(k_corr_to_original, dim3(64, h->n_pairs), dim3(256), 0, s, S.pts.get(), S.d_offs.get(), T.pts.get(), T.d_offs.get(),
-                           L.corr.get(), d_corr);
-    MRS_HIP_TRY(hipGetLastError());
+    if ((st = step_epilogue(h, d_corr, nullptr, s)) != MRS_OK) return st;
     std::vector<double> part((size_t)h->n_pairs * L.max_blocks * kTerms);
     MRS_HIP_TRY(hipMemcpyAsync(part.data(), L.partial.get(), part.size() * sizeof(double), hipMemcpyDeviceToHost, s));
     MRS_HIP_TRY(hipStreamSynchronize(s));
@@ -1719,28 +1698,17 @@ static int icp_profile(mrs_gicp_batch* h, const mrs_icp_params* p, const mrs_icp
     if (st != MRS_OK) return st;
     MRS_HIP_TRY(hipSetDevice(h->ctx->device));
     hipStream_t s = (hipStream_t)stream;
-    GicpLmBuffers& L = h->lm;
     if ((st = icp_ensure_state(h, plane != nullptr)) != MRS_OK) return st;
     IcpParams dp = icp_device_params(h, p);
     dp.crit.max_iter = INT32_MAX;       // the update kernel is timed on pairs that stay active: no rule may end them
     dp.crit.force_iters = INT32_MAX;
-    const GicpParams sp = icp_search_params(h, p);
     std::vector<LmState> init(h->n_pairs);
-    for (int q = 0; q < h->n_pairs; ++q) {
-        memset(&init[q], 0, sizeof(LmState));
-        for (int i = 0; i < 16; ++i) init[q].x[i] = init[q].xi[i] = h_poses[(size_t)q * 16 + i];
-        init[q].y0 = DBL_MAX; init[q].active = 1;
-    }
-    MRS_HIP_TRY(hipMemcpyAsync(L.state.get(), init.data(), init.size() * sizeof(LmState), hipMemcpyHostToDevice, s));
-    MRS_HIP_TRY(hipStreamSynchronize(s));
+    init_states(init, h_poses, false, true);
     mrs::RepTimer timer;
-    MRS_TRY(timer.create());
-    const GicpCloud &S = h->side[0], &T = h->side[1];
-    int nn_st = MRS_OK;
-    if ((st = timer.timed(*ms_search, reps, s, [&]() { const int r = nn_pass(h, sp, 2, s); if (r != MRS_OK) nn_st = r; })) != MRS_OK) return st;
-    if (nn_st != MRS_OK) return nn_st;
+    if ((st = profile_prelude(h, init, icp_search_params(h, p), timer, reps, *ms_search, s)) != MRS_OK) return st;
     if (plane) {
         MRS_REQUIRE(plane->normal_k >= 3 && plane->normal_k <= 32, "normal_k must be in [3, 32]");
+        int nn_st = MRS_OK;
         if ((st = timer.timed(*ms_normals, reps, s, [&]() {
                  h->side[1].nrm_key = 0;            // computed again, whatever the handle holds
                  const int r = mrs_gicp_batch_compute_normals(h, 1, plane->normal_k, plane->viewpoint, stream);
@@ -1748,28 +1716,10 @@ static int icp_profile(mrs_gicp_batch* h, const mrs_icp_params* p, const mrs_icp
              })) != MRS_OK) return st;
         if (nn_st != MRS_OK) return nn_st;
     }
-    if ((st = timer.timed(*ms_sums, reps, s, [&]() {
-             if (plane) return launch_icp_plane_sums(h, s);
-             hipLaunchKernelGGL(k_icp_sums, dim3(L.max_blocks, h->n_pairs), dim3(kNNThreads), 0, s, S.pts.get(), S.d_offs.get(), T.pts.get(),
-                                T.d_offs.get(), L.state.get(), L.corr.get(), L.partial.get(), L.max_blocks);
-         })) != MRS_OK) return st;
-    {
-        std::vector<int> corr(L.n_seed);
-        MRS_HIP_TRY(hipMemcpy(corr.data(), L.corr.get(), corr.size() * sizeof(int), hipMemcpyDeviceToHost));
-        int64_t c = 0;
-        for (int v : corr) c += v >= 0;
-        out_counts[0] = (int64_t)L.n_seed; out_counts[1] = c;
-    }
-    MRS_HIP_TRY(hipMemsetAsync(L.nactive.get(), 0, 4 * sizeof(int), s));
-    if ((st = timer.timed(*ms_update, reps, s, [&]() {
-             if (plane)
-                 hipLaunchKernelGGL(k_icp_plane_update, dim3(h->n_pairs), dim3(kLmThreads), 0, s, L.state.get(), L.partial.get(), L.nblocks.get(),
-                                    L.max_blocks, dp, L.nactive.get());
-             else
-                 hipLaunchKernelGGL(k_icp_update, dim3(h->n_pairs), dim3(kLmThreads), 0, s, L.state.get(), L.partial.get(), L.nblocks.get(),
-                                    L.max_blocks, dp, L.nactive.get());
-         })) != MRS_OK) return st;
-    return MRS_OK;
+    if ((st = timer.timed(*ms_sums, reps, s, [&]() { launch_icp_sums(h, plane != nullptr, s); })) != MRS_OK) return st;
+    if ((st = count_correspondences(h, out_counts)) != MRS_OK) return st;
+    MRS_HIP_TRY(hipMemsetAsync(h->lm.nactive.get(), 0, 4 * sizeof(int), s));
+    return timer.timed(*ms_update, reps, s, [&]() { launch_icp_update(h, plane != nullptr, dp, h->lm.nactive.get(), s); });
 }
 
 int mrs_gicp_batch_icp_profile(mrs_gicp_batch* h, const mrs_icp_params* p, const double* h_poses, int32_t reps, float* out_ms, int64_t* out_counts,
@@ -1805,18 +1755,16 @@ int mrs_gicp_batch_profile(mrs_gicp_batch* h, const double* h_poses, int32_t rep
     const GicpCloud& S = h->side[0];
     GicpLmBuffers& L = h->lm;
     int st;
-    for (int w = 0; w < 2; ++w)
-        if (!h->side[w].cov_valid) { st = mrs_gicp_batch_compute_covariances(h, w, nullptr, stream); if (st != MRS_OK) return st; }
+    if ((st = covariances_first(h, nullptr, s)) != MRS_OK) return st;
     if ((st = ensure_state(h)) != MRS_OK) return st;
     const int P = h->n_pairs;
     std::vector<LmState> init(P);
     auto upload = [&](int phase, double dx) -> int {
-        for (int p = 0; p < P; ++p) {
-            memset(&init[p], 0, sizeof(LmState));
-            for (int i = 0; i < 16; ++i) init[p].x[i] = init[p].xi[i] = init[p].delta[i] = h_poses[(size_t)p * 16 + i];
-            for (int i = 0; i < 16; ++i) init[p].delta[i] = (i % 5 == 0) ? 1.0 : 0.0;      // last step: none
-            init[p].x[3] += dx; init[p].xi[3] += dx;
-            init[p].active = 1; init[p].phase = phase;
+        init_states(init, h_poses, false, false);
+        for (LmState& S : init) {
+            for (int i = 0; i < 16; ++i) S.delta[i] = (i % 5 == 0) ? 1.0 : 0.0;      // last step: none
+            S.x[3] += dx; S.xi[3] += dx;
+            S.phase = phase;
         }
         MRS_HIP_TRY(hipMemcpyAsync(L.state.get(), init.data(), init.size() * sizeof(LmState), hipMemcpyHostToDevice, s));
         MRS_HIP_TRY(hipStreamSynchronize(s));
@@ -1838,13 +1786,7 @@ int mrs_gicp_batch_profile(mrs_gicp_batch* h, const double* h_poses, int32_t rep
     if ((st = knn_dev_switches(s)) != MRS_OK) return st;
     if ((st = timer.timed(out_ms[2], reps, s, round3)) != MRS_OK) return st;
     if ((st = timer.timed(out_ms[0], reps, s, linearize)) != MRS_OK) return st;
-    {   // correspondences at the poses
-        std::vector<int> corr(L.n_seed);
-        MRS_HIP_TRY(hipMemcpy(corr.data(), L.corr.get(), corr.size() * sizeof(int), hipMemcpyDeviceToHost));
-        int64_t c = 0;
-        for (int v : corr) c += v >= 0;
-        out_counts[0] = (int64_t)L.n_seed; out_counts[1] = c;
-    }
+    if ((st = count_correspondences(h, out_counts)) != MRS_OK) return st;       // at the poses
     if ((st = timer.timed(out_ms[4], reps, s, [&]() { launch_nn_scan_g(h, h->prm, false, s); })) != MRS_OK) return st;      // leaves certificates at the poses
     launch_nn_store_pose(h, 0, s);
     if ((st = timer.timed(out_ms[3], reps, s, [&]() { launch_nn_certify(h, h->prm, s); })) != MRS_OK) return st;

@@ -201,54 +201,52 @@ class GicpBatch:
         lib.mrs_gicp_batch_get_voxel_map(self._h, n, pair, coord, mean, count, c6, stream)
         return pair, coord, mean, count, c6[:, [0, 1, 2, 1, 3, 4, 2, 4, 5]].reshape(V, 3, 3)
 
-    def align(self, guesses=None):
-        """Returns (T [P,4,4] float64, converged [P] bool, iterations [P] int32)."""
+    def _poses(self, poses):
+        return np.ascontiguousarray(np.asarray(poses, dtype=np.float64).reshape(self.n_pairs, 16))
+
+    def _corr_out(self, want_corr):
+        """one int32 per source point on the device, for a step's correspondences"""
+        return torch.empty(int(self._n[0][-1]), dtype=torch.int32, device=f"cuda:{self.device}") if want_corr else None
+
+    def _align(self, entry, params_ref, guesses, want_state, want_hessian):
+        """One of the four mrs_gicp_batch_align* entry points: (handle, [params,] guesses, T, converged, iterations, state or Hessian, stream)."""
         P = self.n_pairs
-        g = None
-        if guesses is not None:
-            g = np.ascontiguousarray(np.asarray(guesses, dtype=np.float64).reshape(P, 16))
         T = np.empty((P, 16), np.float64)
         conv = np.empty(P, np.int32)
         its = np.empty(P, np.int32)
-        self.hessian = np.empty((P, 36), np.float64)
+        state = np.empty(P, np.int32) if want_state else None
+        if want_hessian:
+            self.hessian = np.empty((P, 36), np.float64)
         lib = _lib.load()
-        lib.mrs_gicp_batch_align(self._h, g, T, conv, its, self.hessian, _lib.current_stream(self.device))
+        args = (self._h,) + (() if params_ref is None else (params_ref,)) + (None if guesses is None else self._poses(guesses), T, conv, its)
+        getattr(lib, entry)(*args, self.hessian if want_hessian else state, _lib.current_stream(self.device))
         self.nn_passes = lib.mrs_gicp_batch_last_nn_passes(self._h)
         self.searched_fraction = lib.mrs_gicp_batch_last_searched_fraction(self._h)
-        return T.reshape(P, 4, 4), conv.astype(bool), its
+        out = (T.reshape(P, 4, 4), conv.astype(bool), its)
+        return out + (state,) if want_state else out
+
+    def align(self, guesses=None):
+        """Returns (T [P,4,4] float64, converged [P] bool, iterations [P] int32)."""
+        return self._align("mrs_gicp_batch_align", None, guesses, False, True)
 
     def linearize(self, poses, want_corr=False):
-        P = self.n_pairs
-        poses = np.ascontiguousarray(np.asarray(poses, dtype=np.float64).reshape(P, 16))
+        P, poses = self.n_pairs, self._poses(poses)
         H = np.empty((P, 36), np.float64); b = np.empty((P, 6), np.float64); e = np.empty(P, np.float64)
-        corr = torch.empty(int(self._n[0][-1]), dtype=torch.int32, device=f"cuda:{self.device}") if want_corr else None
+        corr = self._corr_out(want_corr)
         _lib.load().mrs_gicp_batch_linearize(self._h, poses, H, b, e, corr, _lib.current_stream(self.device))
         return e, H.reshape(P, 6, 6), b, (corr.cpu().numpy() if want_corr else None)
 
     def align_icp(self, guesses=None, **params):
         """Point-to-point ICP (row G9, pcl::IterativeClosestPoint) on the batch's clouds; params: the fields of IcpParams (PCL's defaults
         otherwise).  Returns (T [P,4,4] float64, converged [P] bool, iterations [P] int32, state [P] int32: index into ICP_STATES)."""
-        P = self.n_pairs
-        g = None
-        if guesses is not None:
-            g = np.ascontiguousarray(np.asarray(guesses, dtype=np.float64).reshape(P, 16))
-        T = np.empty((P, 16), np.float64)
-        conv = np.empty(P, np.int32)
-        its = np.empty(P, np.int32)
-        state = np.empty(P, np.int32)
-        lib = _lib.load()
-        lib.mrs_gicp_batch_align_icp(self._h, C.byref(default_icp_params(**params)), g, T, conv, its, state, _lib.current_stream(self.device))
-        self.nn_passes = lib.mrs_gicp_batch_last_nn_passes(self._h)
-        self.searched_fraction = lib.mrs_gicp_batch_last_searched_fraction(self._h)
-        return T.reshape(P, 4, 4), conv.astype(bool), its, state
+        return self._align("mrs_gicp_batch_align_icp", C.byref(default_icp_params(**params)), guesses, True, False)
 
     def icp_step(self, poses, want_corr=False, **params):
         """One ICP iteration's correspondences, 17 sums and fitted increment at `poses` (mrs_gicp_batch_icp_step).
         Returns (sums [P,17], delta [P,4,4], corr or None)."""
-        P = self.n_pairs
-        poses = np.ascontiguousarray(np.asarray(poses, dtype=np.float64).reshape(P, 16))
+        P, poses = self.n_pairs, self._poses(poses)
         sums = np.empty((P, 17), np.float64); delta = np.empty((P, 16), np.float64)
-        corr = torch.empty(int(self._n[0][-1]), dtype=torch.int32, device=f"cuda:{self.device}") if want_corr else None
+        corr = self._corr_out(want_corr)
         _lib.load().mrs_gicp_batch_icp_step(self._h, C.byref(default_icp_params(**params)), poses, sums, delta, corr,
                                             _lib.current_stream(self.device))
         return sums, delta.reshape(P, 4, 4), (corr.cpu().numpy() if want_corr else None)
@@ -256,8 +254,7 @@ class GicpBatch:
     def icp_profile(self, poses, reps=3, **params):
         """HIP-event duration of the three stages of one ICP iteration, each launched alone at `poses` (mrs_gicp_batch_icp_profile).
         Returns (dict of ms, dict of counts)."""
-        P = self.n_pairs
-        poses = np.ascontiguousarray(np.asarray(poses, dtype=np.float64).reshape(P, 16))
+        poses = self._poses(poses)
         ms = np.zeros(3, np.float32); cnt = np.zeros(2, np.int64)
         _lib.load().mrs_gicp_batch_icp_profile(self._h, C.byref(default_icp_params(**params)), poses, int(reps), ms, cnt,
                                                _lib.current_stream(self.device))
@@ -292,28 +289,14 @@ class GicpBatch:
         """Point-to-plane ICP (row G12, pcl::IterativeClosestPointWithNormals) on the batch's clouds and the targets' normals (those the
         handle holds, else computed with normal_k and viewpoint); params: the fields of IcpPlaneParams (PCL's defaults otherwise).
         Returns (T [P,4,4] float64, converged [P] bool, iterations [P] int32, state [P] int32: index into ICP_PLANE_STATES)."""
-        P = self.n_pairs
-        g = None
-        if guesses is not None:
-            g = np.ascontiguousarray(np.asarray(guesses, dtype=np.float64).reshape(P, 16))
-        T = np.empty((P, 16), np.float64)
-        conv = np.empty(P, np.int32)
-        its = np.empty(P, np.int32)
-        state = np.empty(P, np.int32)
-        lib = _lib.load()
-        lib.mrs_gicp_batch_align_icp_plane(self._h, C.byref(default_icp_plane_params(**params)), g, T, conv, its, state,
-                                           _lib.current_stream(self.device))
-        self.nn_passes = lib.mrs_gicp_batch_last_nn_passes(self._h)
-        self.searched_fraction = lib.mrs_gicp_batch_last_searched_fraction(self._h)
-        return T.reshape(P, 4, 4), conv.astype(bool), its, state
+        return self._align("mrs_gicp_batch_align_icp_plane", C.byref(default_icp_plane_params(**params)), guesses, True, False)
 
     def icp_plane_step(self, poses, want_corr=False, **params):
         """One point-to-plane iteration's correspondences, 29 sums and fitted increment at `poses` (mrs_gicp_batch_icp_plane_step).
         Returns (sums [P,29], delta [P,4,4], state [P] int32, corr or None)."""
-        P = self.n_pairs
-        poses = np.ascontiguousarray(np.asarray(poses, dtype=np.float64).reshape(P, 16))
+        P, poses = self.n_pairs, self._poses(poses)
         sums = np.empty((P, 29), np.float64); delta = np.empty((P, 16), np.float64); state = np.empty(P, np.int32)
-        corr = torch.empty(int(self._n[0][-1]), dtype=torch.int32, device=f"cuda:{self.device}") if want_corr else None
+        corr = self._corr_out(want_corr)
         _lib.load().mrs_gicp_batch_icp_plane_step(self._h, C.byref(default_icp_plane_params(**params)), poses, sums, delta, state, corr,
                                                   _lib.current_stream(self.device))
         return sums, delta.reshape(P, 4, 4), state, (corr.cpu().numpy() if want_corr else None)
@@ -321,8 +304,7 @@ class GicpBatch:
     def icp_plane_profile(self, poses, reps=3, **params):
         """HIP-event duration of the stages of one point-to-plane iteration and of the targets' normals, each launched alone at `poses`
         (mrs_gicp_batch_icp_plane_profile).  Returns (dict of ms, dict of counts)."""
-        P = self.n_pairs
-        poses = np.ascontiguousarray(np.asarray(poses, dtype=np.float64).reshape(P, 16))
+        poses = self._poses(poses)
         ms = np.zeros(4, np.float32); cnt = np.zeros(2, np.int64)
         _lib.load().mrs_gicp_batch_icp_plane_profile(self._h, C.byref(default_icp_plane_params(**params)), poses, int(reps), ms, cnt,
                                                      _lib.current_stream(self.device))
@@ -333,27 +315,14 @@ class GicpBatch:
         """PCL-style GICP (row G11, pcl::GeneralizedIterativeClosestPoint) on the batch's clouds and covariances; params: the fields of
         PclGicpParams (PCL's defaults otherwise).  Returns (T [P,4,4] float64, converged [P] bool, iterations [P] int32, state [P] int32:
         index into ICP_STATES)."""
-        P = self.n_pairs
-        g = None
-        if guesses is not None:
-            g = np.ascontiguousarray(np.asarray(guesses, dtype=np.float64).reshape(P, 16))
-        T = np.empty((P, 16), np.float64)
-        conv = np.empty(P, np.int32)
-        its = np.empty(P, np.int32)
-        state = np.empty(P, np.int32)
-        lib = _lib.load()
-        lib.mrs_gicp_batch_align_pcl(self._h, C.byref(default_pclgicp_params(**params)), g, T, conv, its, state, _lib.current_stream(self.device))
-        self.nn_passes = lib.mrs_gicp_batch_last_nn_passes(self._h)
-        self.searched_fraction = lib.mrs_gicp_batch_last_searched_fraction(self._h)
-        return T.reshape(P, 4, 4), conv.astype(bool), its, state
+        return self._align("mrs_gicp_batch_align_pcl", C.byref(default_pclgicp_params(**params)), guesses, True, False)
 
     def pcl_step(self, poses, want_corr=False, **params):
         """One outer iteration of PCL-style GICP at `poses` (mrs_gicp_batch_pcl_step): correspondences, the 74 sums, the inner BFGS.
         Returns (sums [P,74], next pose [P,4,4], inner [P,2] int32: iterations and index into PCL_INNER_ENDS, corr or None)."""
-        P = self.n_pairs
-        poses = np.ascontiguousarray(np.asarray(poses, dtype=np.float64).reshape(P, 16))
+        P, poses = self.n_pairs, self._poses(poses)
         sums = np.empty((P, 74), np.float64); nxt = np.empty((P, 16), np.float64); inner = np.empty((P, 2), np.int32)
-        corr = torch.empty(int(self._n[0][-1]), dtype=torch.int32, device=f"cuda:{self.device}") if want_corr else None
+        corr = self._corr_out(want_corr)
         _lib.load().mrs_gicp_batch_pcl_step(self._h, C.byref(default_pclgicp_params(**params)), poses, sums, nxt, inner, corr,
                                             _lib.current_stream(self.device))
         return sums, nxt.reshape(P, 4, 4), inner, (corr.cpu().numpy() if want_corr else None)
@@ -361,8 +330,7 @@ class GicpBatch:
     def pcl_profile(self, poses, reps=3, **params):
         """HIP-event duration of the three stages of one PCL-style GICP iteration, each launched alone at `poses`
         (mrs_gicp_batch_pcl_profile).  Returns (dict of ms, dict of counts)."""
-        P = self.n_pairs
-        poses = np.ascontiguousarray(np.asarray(poses, dtype=np.float64).reshape(P, 16))
+        poses = self._poses(poses)
         ms = np.zeros(3, np.float32); cnt = np.zeros(2, np.int64)
         _lib.load().mrs_gicp_batch_pcl_profile(self._h, C.byref(default_pclgicp_params(**params)), poses, int(reps), ms, cnt,
                                                _lib.current_stream(self.device))
@@ -372,8 +340,7 @@ class GicpBatch:
     def profile(self, poses, reps=3):
         """HIP-event duration of every kernel of one outer iteration, launched alone at `poses` (mrs_gicp_batch_profile).
         Returns (dict of ms, dict of counts)."""
-        P = self.n_pairs
-        poses = np.ascontiguousarray(np.asarray(poses, dtype=np.float64).reshape(P, 16))
+        poses = self._poses(poses)
         ms = np.zeros(8, np.float32); cnt = np.zeros(3, np.int64)
         _lib.load().mrs_gicp_batch_profile(self._h, poses, int(reps), ms, cnt, _lib.current_stream(self.device))
         names = ("linearize", "linearize_error_only", "search_round3_all", "certify", "search_round4_all", "knn_select", "cov_from_knn",
@@ -381,8 +348,7 @@ class GicpBatch:
         return {n: float(v) for n, v in zip(names, ms)}, {"source_points": int(cnt[0]), "correspondences": int(cnt[1]), "worklist_queries_1mm": int(cnt[2])}
 
     def fitness(self, poses, max_range):
-        P = self.n_pairs
-        poses = np.ascontiguousarray(np.asarray(poses, dtype=np.float64).reshape(P, 16))
+        P, poses = self.n_pairs, self._poses(poses)
         out = np.empty(P, np.float64)
         _lib.load().mrs_gicp_batch_fitness(self._h, poses, max_range, out, _lib.current_stream(self.device))
         return out

@@ -1,6 +1,8 @@
 """GPU suite for the batched point-to-plane ICP and its surface normals (row G12): HIP through the C ABI against the NumPy
 restatement (tests/golden/icp_plane_restate.py) on the same clouds.  Pose tolerance from BASELINE.json north_star: 1e-4 m / 1e-4 rad.
 The fixtures are those whose conditions tests/test_icp_plane_cpu.py checks."""
+import os
+
 import numpy as np
 import pytest
 
@@ -311,11 +313,53 @@ def test_given_normals_equal_computed_normals(dev):
     assert _same(lazy.align_icp_plane(**prm), want)
 
 
+def _nine():
+    """nine pairs of unequal size (2 500 to 4 908 points): one more than the windowed schedule takes"""
+    return [K.build(50 + i, 2500 + 301 * i, (0.01 * (i % 3), -0.02, 0.03 + 0.01 * i), (0.3 + 0.05 * i, -0.2, 0.05)) for i in range(9)]
+
+
+def _with_env(env, fn):
+    old = {k: os.environ.get(k) for k in ("MRS_DEV", "MRS_GICP_WINDOW")}
+    os.environ.update(env)
+    try:
+        return fn()
+    finally:
+        for k, v in old.items():
+            if v is None:
+                os.environ.pop(k, None)
+            else:
+                os.environ[k] = v
+
+
+def test_same_bits_from_call_to_call_and_across_schedules(dev):
+    """The twin of tests/test_icp_gpu.py's schedule test: one pair (windowed by default) and nine (tick by tick), natural stopping and a forced
+    run; the default schedule, the per-tick one (MRS_GICP_WINDOW=0), windows of 3 and a second call on the warm handle give the same pose,
+    flag, iteration count, state and number of searches."""
+    def run(b, prm):
+        return b.align_icp_plane(**prm) + (b.nn_passes,)
+    nine = _nine()
+    for pairs in (nine[:1], nine):
+        srcs, tgts = [p[0] for p in pairs], [p[1] for p in pairs]
+        for prm in (PK.SETTINGS["MAPPING_890"], dict(force_iterations=6, max_correspondence_distance=5.0)):
+            b = _batch(srcs, tgts)
+            want = run(b, prm)
+            assert len(want) == 5 and want[4] == want[2].max() >= 1
+            assert _same(run(b, prm), want)                                                    # warm seeds and normals, same handle
+            for window in ("0", "3"):
+                got = _with_env({"MRS_DEV": "1", "MRS_GICP_WINDOW": window}, lambda: run(_batch(srcs, tgts), prm))
+                assert _same(got, want), (len(pairs), prm, window)
+        assert want[2].min() == 6
+
+
 def test_four_methods_share_a_handle(dev):
     """align, align_icp, align_pcl and align_icp_plane interleaved on one handle each equal a fresh handle bit for bit, and point-to-plane
-    ICP computes no covariances."""
+    ICP computes no covariances.  Two pairs (the four share the windowed loop) and nine (the per-tick loop)."""
+    for pairs in ([K.build(61, 4000), K.build(62, 3001)], _nine()):
+        _four_methods_share_a_handle(pairs)
+
+
+def _four_methods_share_a_handle(pairs):
     from mr_slam_amd import _lib
-    pairs = [K.build(61, 4000), K.build(62, 3001)]
     srcs, tgts = [p[0] for p in pairs], [p[1] for p in pairs]
     prm = PK.SETTINGS["MAPPING_890"]
 

@@ -241,6 +241,23 @@ def test_same_bits_from_call_to_call_and_across_schedules(dev):
         assert want[2].min() == 5
 
 
+def test_error_return_inside_align_pcl_leaves_handle_and_side_slot_usable(dev):
+    """The twin of tests/test_gicp_gpu.py's test: search setting 3 chosen after the clouds were set under the default one (the sources have no
+    hierarchy), so align_pcl raises after it has handed the target covariances to the borrowed side stream.  The same handle, set back to
+    the default search, and a second fresh handle that borrows the returned slot in the same thread both equal a fresh default handle bit for
+    bit."""
+    from mr_slam_amd import _lib
+    src, tgt, _ = K.build(50, 2500, (0.0, -0.02, 0.03), (0.3, -0.2, 0.05))
+    want = _batch([src], [tgt]).align_pcl(**K.MAPPING_2422)
+    b = _batch([src], [tgt])
+    b.set_search(3)
+    with pytest.raises(_lib.MrsError):
+        b.align_pcl(**K.MAPPING_2422)
+    b.set_search(1)
+    assert _same(b.align_pcl(**K.MAPPING_2422), want)
+    assert _same(_batch([src], [tgt]).align_pcl(**K.MAPPING_2422), want)
+
+
 def test_three_methods_share_a_handle(dev):
     """align -> align_pcl -> align_icp -> align_pcl -> align on one handle equals fresh handles bit for bit; align_pcl leaves the covariances of
     compute_covariances behind and the handle's own correspondence distance alone."""

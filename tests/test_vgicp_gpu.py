@@ -402,3 +402,34 @@ def test_refed_handle_equals_fresh_handles_bit_for_bit(dev, n_pairs, round_):
         _same(k20, _fresh_run(P, s0, t0, k_correspondences=20), "k 15 -> 20")
         _same(k20[4:8], first[4:8], "same voxels, means and counts")
         assert not np.array_equal(k20[8], first[8])
+
+
+@pytest.mark.parametrize("n_pairs", [2, 1])
+def test_voxel_gicp_stays_out_of_the_windows(dev, n_pairs):
+    """The voxelised variant always runs tick by tick (k_linearize_voxel does not gate itself on a pair's state, so its ticks cannot be
+    enqueued ahead): the development switch that sets the window length changes nothing, for a batch of two and for a single pair."""
+    import os
+    src, tgt, Ttrue = _scan_pair()
+    srcs = [src, _thin(src, 3001)][:n_pairs]
+    tgts = [tgt, _thin(tgt, 2999)][:n_pairs]
+    guess = Ttrue.copy()
+    guess[:3, 3] += [0.05, -0.03, 0.02]                 # 5 cm from the truth: more than one outer iteration, so more than one window's worth of ticks
+
+    def run():
+        b = _batch(n_pairs, 0.5, 1)
+        b.set_sources(srcs); b.set_targets(tgts)
+        T, conv, its = b.align(np.stack([guess] * n_pairs))
+        return T, conv, its, b.hessian.copy()
+    old = {k: os.environ.pop(k, None) for k in ("MRS_DEV", "MRS_GICP_WINDOW")}
+    try:
+        want = run()
+        assert want[2].min() >= 2
+        os.environ["MRS_DEV"] = "1"
+        for window in ("0", "3", "16"):
+            os.environ["MRS_GICP_WINDOW"] = window
+            _same(run(), want, "MRS_GICP_WINDOW=" + window)
+    finally:
+        for k, v in old.items():
+            os.environ.pop(k, None)
+            if v is not None:
+                os.environ[k] = v
