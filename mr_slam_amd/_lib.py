@@ -46,9 +46,28 @@ _ELEMENTS = {"float": ("float32", "complex64"), "double": ("float64", "complex12
              "int64_t": ("int64",), "uint8_t": ("uint8",), "uint64_t": ("uint64",)}      # void and the opaque types take any element type
 
 
+_header_text = {}
+
+
+def _header(path=None):
+    """the text of a header (HEADER when None), read once per process"""
+    path = path or HEADER
+    if path not in _header_text:
+        _header_text[path] = open(path).read()
+    return _header_text[path]
+
+
+def header_int(name):
+    """the integer of `#define name <int>` in the C ABI header"""
+    m = re.search(r"#define\s+%s\s+(\d+)" % re.escape(name), _header())
+    if m is None:
+        raise MrsError("%s does not define %s" % (HEADER, name))
+    return int(m[1])
+
+
 def parse_header(path):
     """{name: (return type, [(type, pointer depth, parameter name), ...])} of every `mrs_*` declaration in the header"""
-    src = re.sub(r"/\*.*?\*/|//[^\n]*", "", open(path).read(), flags=re.S)
+    src = re.sub(r"/\*.*?\*/|//[^\n]*", "", _header(path), flags=re.S)
     protos = {}
     for ret, name, params in re.findall(r"^\s*(?:const\s+)?(\w+\s*\**)\s*(mrs_\w+)\s*\(([^)]*)\)\s*;", src, flags=re.M):
         args = []
@@ -158,7 +177,7 @@ def load():
                 cdll = C.CDLL(LIB_PATH)
                 api = types.SimpleNamespace(**{n: _bind(cdll, n, r, p) for n, (r, p) in parse_header(HEADER).items()})
                 _status_str, _last_error = cdll.mrs_status_str, cdll.mrs_last_error
-                want = int(re.search(r"#define\s+MRS_ABI_VERSION\s+(\d+)", open(HEADER).read())[1])
+                want = header_int("MRS_ABI_VERSION")
                 if api.mrs_abi_version() != want:
                     raise MrsError("%s has ABI version %d, %s declares %d: rebuild it" % (LIB_PATH, api.mrs_abi_version(), HEADER, want))
                 _lib = api
@@ -187,3 +206,70 @@ def device_of(t):
 def current_stream(device):
     import torch
     return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+
+
+class Handle:
+    """Owner of one C handle: `_h` is a plain c_void_p to pass to the C ABI; a subclass names its destroy function in `_destroy` and opens
+    with `self._create("mrs_x_create", ...)`."""
+    _destroy = None
+
+    def _create(self, fn_name, *args):
+        self._h = C.c_void_p()               # before the call: a create that raises leaves a null handle, which __del__ skips
+        getattr(load(), fn_name)(*args, C.byref(self._h))
+
+    def __del__(self):
+        try:                                 # silent: at interpreter shutdown the library or this module may be gone already
+            h = getattr(self, "_h", None)
+            if h:
+                self._h = None
+                getattr(load(), self._destroy)(h)
+        except Exception:
+            pass
+
+
+def in_range(name, value, hi):
+    """int(value) if 1 <= value <= hi, else ValueError("<name> in 1..<hi>")"""
+    value = int(value)
+    if not 1 <= value <= hi:
+        raise ValueError("%s in 1..%d" % (name, hi))
+    return value
+
+
+def ragged(points, offsets, *, dtype=None, exact=False):
+    """The leading arguments of a ragged-batch call: packed points [N, stride >= 3] on the device, cloud b = points[offsets[b]:offsets[b + 1]].
+    -> (device index, contiguous points, (h_off, d_off, B)) with int64 offsets on the host and on the points' device.
+    offsets: a tensor on either side, an array or a list (copied to the side it is not on), or a (host, device) pair of tensors, used as
+    it is.  dtype: the points are cast to it; None keeps float32 / float64 and widens anything else to float64.  The last offset may
+    stay below N unless exact, which also wants the first to be 0."""
+    import torch
+    d = device_of(points)
+    p = points.detach()
+    assert p.dim() == 2 and p.shape[1] >= 3, tuple(p.shape)
+    if dtype is not None:
+        p = p.to(dtype)
+    elif p.dtype not in (torch.float32, torch.float64):
+        p = p.to(torch.float64)
+    p = p.contiguous()
+    if isinstance(offsets, (tuple, list)) and len(offsets) == 2 and isinstance(offsets[0], torch.Tensor):
+        h_off, d_off = offsets
+    else:
+        h_off = d_off = offsets if isinstance(offsets, torch.Tensor) else torch.as_tensor(np.asarray(offsets, np.int64))
+    h_off = h_off.detach().to("cpu", torch.int64).contiguous()
+    d_off = d_off.detach().to(p.device, torch.int64).contiguous()
+    B, last = h_off.numel() - 1, int(h_off[-1])
+    if exact:
+        assert B >= 1 and int(h_off[0]) == 0 and last == p.shape[0], (h_off.tolist()[:4], p.shape[0])
+    else:
+        assert B >= 1 and last <= p.shape[0], (B, last, p.shape[0])
+    return d, p, (h_off, d_off, B)
+
+
+def one_cloud(cloud, device):
+    """one cloud [n, >= 3] of any origin (device tensor, host tensor or array) -> ([n, s] device tensor, host offsets [0, n])"""
+    import torch
+    if not isinstance(cloud, torch.Tensor):
+        cloud = torch.from_numpy(np.ascontiguousarray(cloud))
+    if not cloud.is_cuda:
+        cloud = cloud.to(device)
+    cloud = cloud.reshape(-1, cloud.shape[-1] if cloud.dim() == 2 else 3)
+    return cloud, torch.tensor([0, cloud.shape[0]], dtype=torch.int64)

@@ -14,6 +14,7 @@ import numpy as np
 import torch
 
 from .. import fpfh as _fpfh
+from .util import upload
 
 _DEVICE = "cuda:0"
 point_cloud_normals = None
@@ -27,8 +28,7 @@ def _state(point_cloud, nearest_idx, B):
     c = _cache
     if c is not None and c[0] is point_cloud and c[1] is nearest_idx and c[2] is point_cloud_normals and c[3] == int(B):
         return c[4]
-    pts = torch.from_numpy(np.ascontiguousarray(np.asarray(point_cloud)[:, :3], dtype=np.float32)).to(_DEVICE)
-    nrm = torch.from_numpy(np.ascontiguousarray(np.asarray(point_cloud_normals)[:, :3], dtype=np.float32)).to(_DEVICE)
+    pts, nrm = upload(point_cloud, np.float32, 3, _DEVICE), upload(point_cloud_normals, np.float32, 3, _DEVICE)
     offsets = torch.tensor([0, pts.shape[0]], dtype=torch.int64)
     rows = _fpfh.rows_from_lists(nearest_idx, device=_DEVICE)
     _, s = _fpfh.spfh(pts, nrm, offsets, rows, int(B), from_neighbors=True)

@@ -8,6 +8,7 @@ import numpy as np
 import torch
 
 from .. import fpfh as _fpfh
+from .util import upload
 
 _DEVICE = "cuda:0"
 salient_radius = None
@@ -20,6 +21,6 @@ def iss(points, salient_radius=None, non_max_radius=None, gamma21=0.975, gamma32
     nr = non_max_radius if non_max_radius is not None else globals()["non_max_radius"]
     if sr is None or nr is None:
         raise ValueError("iss needs salient_radius and non_max_radius (arguments, or the globals ISS.salient_radius / ISS.non_max_radius)")
-    pts = torch.from_numpy(np.ascontiguousarray(np.asarray(points)[:, :3], dtype=np.float32)).to(_DEVICE)
+    pts = upload(points, np.float32, 3, _DEVICE)
     keypoints, _ = _fpfh.iss_keypoints(pts, torch.tensor([0, pts.shape[0]], dtype=torch.int64), sr, nr, gamma21, gamma32, min_neighbors)
     return keypoints[0].cpu().numpy()

@@ -10,12 +10,13 @@ import numpy as np
 import torch
 
 from .. import scancontext as _sc
+from .util import upload
 
 _DEVICE = "cuda:0"
 
 
 def _t(x):
-    return torch.from_numpy(np.ascontiguousarray(np.asarray(x, dtype=np.float32))).to(_DEVICE)
+    return upload(x, np.float32, None, _DEVICE)
 
 
 def make_ringkey(sc):

@@ -15,9 +15,9 @@ def downsample(points, resolution, approximate=True, device="cuda:0"):
     order, float centroids, flush order) on the GPU (mrs_voxel_downsample_approx), bit-identical to the sequential filter
     as restated in oracle/voxel_oracle.c.  approximate=False is the exact voxel-grid centroid filter
     (mrs_voxel_downsample, one centroid per occupied voxel)."""
-    import torch
     from .. import preprocess
-    p = torch.from_numpy(np.ascontiguousarray(np.asarray(points, dtype=np.float64)[:, :3])).to(device)
+    from .util import upload
+    p = upload(points, np.float64, 3, device)
     if p.shape[0] == 0:
         return np.zeros((0, 3), np.float64)
     out = preprocess.approx_voxel_grid(p, float(resolution)) if approximate else preprocess.voxel_down_sample(p, float(resolution))

@@ -12,6 +12,12 @@ from ..ring import (fast_corr, fast_corr_RINGplusplus, forward_row_fft, generate
 device = torch.device("cuda:0")                                    # util.py:23 (there is no CPU path behind these names)
 
 
+def upload(x, dtype, cols=None, device=device):
+    """host array -> contiguous device tensor of `dtype` from its first `cols` columns (every column when None); the shims' way in"""
+    a = np.asarray(x)
+    return torch.from_numpy(np.ascontiguousarray(a if cols is None else a[:, :cols], dtype=dtype)).to(device)
+
+
 def euler2rot(roll, pitch, yaw):
     """util.py:51-75: R = Rz(yaw) Ry(pitch) Rx(roll)"""
     cr, sr, cp, sp, cy, sy = np.cos(roll), np.sin(roll), np.cos(pitch), np.sin(pitch), np.cos(yaw), np.sin(yaw)

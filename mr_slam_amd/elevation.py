@@ -1,7 +1,5 @@
 """Elevation mapping over the C ABI (row N3): host-side mirror of the reference's libgpu.so functions
 (Mapping/src/elevation_mapping_periodical/elevation_mapping/cuda/gpu_process.cu:938-1312)."""
-import ctypes as C
-
 import numpy as np
 
 from . import _lib
@@ -15,18 +13,12 @@ def _i(a):
     return np.ascontiguousarray(a, dtype=np.int32)
 
 
-class ElevationMap:
+class ElevationMap(_lib.Handle):
+    _destroy = "mrs_elev_destroy"
+
     def __init__(self, length, resolution, mahalanobis_threshold=2.0, obstacle_threshold=0.6, device=0):
         self.L = int(length)
-        self._h = C.c_void_p()
-        _lib.load().mrs_elev_create(_lib.ctx(device), self.L, resolution, mahalanobis_threshold, obstacle_threshold, C.byref(self._h))
-
-    def __del__(self):
-        try:
-            if getattr(self, "_h", None):
-                _lib.load().mrs_elev_destroy(self._h)
-        except Exception:
-            pass
+        self._create("mrs_elev_create", _lib.ctx(device), self.L, resolution, mahalanobis_threshold, obstacle_threshold)
 
     def move(self, position3):
         p = _f(position3); c = np.zeros(2, np.float32); s = np.zeros(2, np.int32); a = np.zeros(2, np.float32)

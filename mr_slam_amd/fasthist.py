@@ -6,27 +6,23 @@ is computed, so the contract is `statisticsOnRange(cloud.astype(np.float64), bin
 above the last edge, an empty cloud, non-finite points) are in DESIGN.md 4.17.
 """
 import ctypes as C
-import re
 
 import numpy as np
 import torch
 
 from . import _lib
+from .loopdb import VectorLoopDb
 
 DEFAULT_BINS = 100
 KIND_FH = 5
 MAX_K = 32
-_HEADER = open(_lib.HEADER).read()
 # points per workgroup of the range and bin kernels, and the largest bucket count (MRS_FH_TILE_POINTS / MRS_FH_MAX_BINS of the C ABI header)
-TILE_POINTS = int(re.search(r"#define\s+MRS_FH_TILE_POINTS\s+(\d+)", _HEADER)[1])
-MAX_BINS = int(re.search(r"#define\s+MRS_FH_MAX_BINS\s+(\d+)", _HEADER)[1])
+TILE_POINTS = _lib.header_int("MRS_FH_TILE_POINTS")
+MAX_BINS = _lib.header_int("MRS_FH_MAX_BINS")
 
 
 def _check_bins(bins):
-    bins = int(bins)
-    if not 1 <= bins <= MAX_BINS:
-        raise ValueError("bins in 1..%d" % MAX_BINS)
-    return bins
+    return _lib.in_range("bins", bins, MAX_BINS)
 
 
 def range_histogram_batch(points, offsets, bins=DEFAULT_BINS):
@@ -35,17 +31,7 @@ def range_histogram_batch(points, offsets, bins=DEFAULT_BINS):
     cloud gives zeros.  offsets: an int64 [B + 1] tensor on either side (it is copied to the other), or a (host, device) pair of the same
     offsets, which costs no copy"""
     bins = _check_bins(bins)
-    d = _lib.device_of(points)
-    p = points.detach()
-    if p.dtype not in (torch.float32, torch.float64):
-        p = p.to(torch.float64)
-    assert p.dim() == 2 and p.shape[1] >= 3, tuple(p.shape)
-    p = p.contiguous()
-    h_off, d_off = offsets if isinstance(offsets, (tuple, list)) else (offsets, offsets)
-    h_off = h_off.detach().to("cpu", torch.int64).contiguous()
-    d_off = d_off.detach().to(p.device, torch.int64).contiguous()
-    B = h_off.numel() - 1
-    assert B >= 1 and int(h_off[-1]) <= p.shape[0], (B, int(h_off[-1]), p.shape[0])
+    d, p, (h_off, d_off, B) = _lib.ragged(points, offsets)
     hist = torch.empty((B, bins), dtype=torch.float64, device=p.device)
     counts = torch.empty((B, bins), dtype=torch.int32, device=p.device)
     max_range = torch.empty(B, dtype=torch.float64, device=p.device)
@@ -57,58 +43,26 @@ def range_histogram_batch(points, offsets, bins=DEFAULT_BINS):
 
 def range_histogram(cloud, bins=DEFAULT_BINS, device="cuda:0"):
     """one cloud [n, >= 3] (device tensor, host tensor or array) -> (hist [bins], counts [bins], max_range, unbound) device tensors"""
-    if not isinstance(cloud, torch.Tensor):
-        cloud = torch.from_numpy(np.ascontiguousarray(cloud))
-    if not cloud.is_cuda:
-        cloud = cloud.to(device)
-    cloud = cloud.reshape(-1, cloud.shape[-1] if cloud.dim() == 2 else 3)
-    hist, counts, max_range, unbound = range_histogram_batch(cloud, torch.tensor([0, cloud.shape[0]], dtype=torch.int64), bins)
+    hist, counts, max_range, unbound = range_histogram_batch(*_lib.one_cloud(cloud, device), bins)
     return hist[0], counts[0], max_range[0], unbound[0]
 
 
-class FastHistogramDatabase:
+class FastHistogramDatabase(VectorLoopDb):
     """Device-resident list of range histograms of one robot (mrs_loopdb, kind FH; entries are kept in float64 as they come): `append(hist)`;
     `query(hist, k)` = the k nearest entries by getEMD, ascending, ties to the lower index; `distances(hist)` = getEMD to every entry.  The
     distances carry the reference's bits: |G_i - H_i| added in index order in float64, divided by bins."""
 
     def __init__(self, device=0, capacity=1024, bins=DEFAULT_BINS):
-        self.device = int(device)
         self.bins = _check_bins(bins)
-        self._h = C.c_void_p()
-        _lib.load().mrs_loopdb_create(_lib.ctx(self.device), KIND_FH, self.bins, int(capacity), C.byref(self._h))
-
-    def __del__(self):
-        try:
-            if getattr(self, "_h", None):
-                _lib.load().mrs_loopdb_destroy(self._h)
-        except Exception:
-            pass
-
-    def __len__(self):
-        n = C.c_int32(0)
-        _lib.load().mrs_loopdb_size(self._h, C.byref(n))
-        return n.value
-
-    def _arg(self, hist):
-        """(histogram, on_device, stream) of one [bins] histogram (torch host / device tensor or numpy array)"""
-        if isinstance(hist, torch.Tensor):
-            t = hist.detach().to(torch.float64).contiguous()
-            assert t.numel() == self.bins, tuple(t.shape)
-            if t.is_cuda:
-                return t, 1, _lib.current_stream(t.device.index or 0)
-            return t, 0, None
-        a = np.ascontiguousarray(hist, dtype=np.float64)
-        assert a.size == self.bins, a.shape
-        return a, 0, None
+        self._elem = (torch.float64, np.float64, self.bins)
+        super().__init__(KIND_FH, self.bins, device, capacity)
 
     def append(self, hist):
         _lib.load().mrs_loopdb_append_fh(self._h, *self._arg(hist))
 
     def query(self, hist, k=1):
         """-> (indices int32, distances float64) as numpy arrays of length min(k, len(self)), nearest first"""
-        k = int(k)
-        if not 1 <= k <= MAX_K:
-            raise ValueError("k in 1..%d" % MAX_K)
+        k = _lib.in_range("k", k, MAX_K)
         t, dev, stream = self._arg(hist)
         idx, dist = np.full(k, -1, np.int32), np.full(k, np.inf, np.float64)
         cnt = C.c_int32(0)

@@ -9,7 +9,6 @@ deviations from the reference (a neighbour at distance 0, an empty histogram, a 
 RANSAC contract (draw, pre-rejection, scoring, refit) is in DESIGN.md 4.22.
 """
 import ctypes as C
-import re
 
 import numpy as np
 import torch
@@ -17,9 +16,9 @@ import torch
 from . import _lib
 
 DEFAULT_BINS = 5
-MAX_BINS = int(re.search(r"#define\s+MRS_FPFH_MAX_BINS\s+(\d+)", open(_lib.HEADER).read())[1])
+MAX_BINS = _lib.header_int("MRS_FPFH_MAX_BINS")
 MATCH_MAX_K = 32
-RANSAC_MAX_HYPOTHESES = int(re.search(r"#define\s+MRS_RANSAC_MAX_HYPOTHESES\s+(\d+)", open(_lib.HEADER).read())[1])
+RANSAC_MAX_HYPOTHESES = _lib.header_int("MRS_RANSAC_MAX_HYPOTHESES")
 
 
 class RansacParams(C.Structure):
@@ -29,29 +28,12 @@ class RansacParams(C.Structure):
 
 
 def _check_bins(bins):
-    bins = int(bins)
-    if not 1 <= bins <= MAX_BINS:
-        raise ValueError("bins in 1..%d" % MAX_BINS)
-    return bins
+    return _lib.in_range("bins", bins, MAX_BINS)
 
 
-def _points(points):
-    d = _lib.device_of(points)
-    p = points.detach()
-    assert p.dim() == 2 and p.shape[1] >= 3, tuple(p.shape)
-    return d, p.to(torch.float32).contiguous()
-
-
-def _offsets(offsets, p):
-    """(host, device) int64 offsets from a tensor / array / list on either side, or from a (host, device) pair (no copy then)"""
-    if isinstance(offsets, tuple):
-        h_off, d_off = offsets
-    else:
-        h_off = d_off = offsets if isinstance(offsets, torch.Tensor) else torch.as_tensor(np.asarray(offsets, np.int64))
-    h_off = h_off.detach().to("cpu", torch.int64).contiguous()
-    d_off = d_off.detach().to(p.device, torch.int64).contiguous()
-    assert h_off.numel() >= 2 and int(h_off[0]) == 0 and int(h_off[-1]) == p.shape[0], (h_off.tolist()[:4], p.shape[0])
-    return h_off, d_off
+def _ragged(points, offsets):
+    """float32 points and offsets that start at 0 and end at N (a (host, device) pair of offsets costs no copy)"""
+    return _lib.ragged(points, offsets, dtype=torch.float32, exact=True)
 
 
 def _rows(rows, p):
@@ -65,9 +47,8 @@ def _rows(rows, p):
 def radius_neighbors(points, offsets, radius):
     """every j != i of the same cloud with d2(i, j) <= radius^2 (fp64 on the widened coordinates; coincident points included) ->
     (row_start int64 [N + 1], index int32 [total]) device tensors.  Two calls: counts and total, then the fill.  Blocking."""
-    d, p = _points(points)
-    h_off, d_off = _offsets(offsets, p)
-    B, n = h_off.numel() - 1, p.shape[0]
+    d, p, (h_off, d_off, B) = _ragged(points, offsets)
+    n = p.shape[0]
     row_start = torch.empty(n + 1, dtype=torch.int64, device=p.device)
     total = np.zeros(1, np.int64)
     lib, ctx, stream = _lib.load(), _lib.ctx(d), _lib.current_stream(d)
@@ -92,17 +73,16 @@ def spfh(points, normals, offsets, rows, bins=DEFAULT_BINS, from_neighbors=False
     """-> (counts int32 [N, 3 bins], spfh float64 [N, 3 bins]): the alpha, phi and theta histograms of every point over its row, each third
     divided by its own sum.  from_neighbors=True is for rows the caller made: they are checked (an entry outside its cloud raises)."""
     bins = _check_bins(bins)
-    d, p = _points(points)
+    d, p, (h_off, d_off, B) = _ragged(points, offsets)
     nrm = normals.detach().to(p.device, torch.float32).contiguous()
     assert nrm.shape == (p.shape[0], 3), tuple(nrm.shape)
-    h_off, d_off = _offsets(offsets, p)
     row_start, index = _rows(rows, p)
     n = p.shape[0]
     counts = torch.empty((n, 3 * bins), dtype=torch.int32, device=p.device)
     out = torch.empty((n, 3 * bins), dtype=torch.float64, device=p.device)
     lib = _lib.load()
     fn = lib.mrs_fpfh_spfh_from_neighbors if from_neighbors else lib.mrs_fpfh_spfh
-    fn(_lib.ctx(d), p, p.shape[1], nrm, d_off, h_off.numel() - 1, n, row_start, index, index.numel(), bins, counts, out, _lib.current_stream(d))
+    fn(_lib.ctx(d), p, p.shape[1], nrm, d_off, B, n, row_start, index, index.numel(), bins, counts, out, _lib.current_stream(d))
     return counts, out
 
 
@@ -119,15 +99,14 @@ def describe(points, offsets, rows, spfh_all, bins=DEFAULT_BINS, keypoints=None)
     """FPFH [K, 3 bins] float64 of the keypoints (every point when None) from the SPFH of all points: f = spfh_i + (1 / k) sum_j spfh_j /
     |p_j - p_i| over row i in row order, then f / |f|"""
     bins = _check_bins(bins)
-    d, p = _points(points)
-    h_off, d_off = _offsets(offsets, p)
+    d, p, (h_off, d_off, B) = _ragged(points, offsets)
     row_start, index = _rows(rows, p)
     n = p.shape[0]
     assert spfh_all.shape == (n, 3 * bins) and spfh_all.dtype == torch.float64 and spfh_all.is_contiguous(), tuple(spfh_all.shape)
     kp = None if keypoints is None else _keypoints(keypoints, h_off, p.device)
     K = n if kp is None else kp.numel()
     out = torch.empty((K, 3 * bins), dtype=torch.float64, device=p.device)
-    _lib.load().mrs_fpfh_describe(_lib.ctx(d), p, p.shape[1], d_off, h_off.numel() - 1, n, row_start, index, index.numel(), bins, spfh_all, kp, K,
+    _lib.load().mrs_fpfh_describe(_lib.ctx(d), p, p.shape[1], d_off, B, n, row_start, index, index.numel(), bins, spfh_all, kp, K,
                                   out, _lib.current_stream(d))
     return out
 
@@ -144,9 +123,8 @@ def fpfh(points, normals, offsets, radius, bins=DEFAULT_BINS, keypoints=None, re
 def iss_keypoints(points, offsets, salient_radius, non_max_radius, gamma21=0.975, gamma32=0.975, min_neighbors=5):
     """ISS keypoints (parity unpinned: the reference imports an ISS module it does not ship; this is the published method)
     -> (list of ascending cloud-local int64 index tensors, one per cloud; saliency float64 [N])"""
-    d, p = _points(points)
-    h_off, d_off = _offsets(offsets, p)
-    B, n = h_off.numel() - 1, p.shape[0]
+    d, p, (h_off, d_off, B) = _ragged(points, offsets)
+    n = p.shape[0]
     lib, ctx, stream = _lib.load(), _lib.ctx(d), _lib.current_stream(d)
     rs, idx = radius_neighbors(p, (h_off, d_off), salient_radius)
     sal = torch.empty(n, dtype=torch.float64, device=p.device)
@@ -163,9 +141,7 @@ def iss_keypoints(points, offsets, salient_radius, non_max_radius, gamma21=0.975
 def match(a, b, k=1):
     """the k nearest rows of b for every row of a by squared L2 distance over the float32-rounded descriptors (mrs_signature_knn: ascending,
     ties to the lower index) -> (index int32 [len(a), k], dist2 float32 [len(a), k]); slots past len(b) hold -1 / +inf"""
-    k = int(k)
-    if not 1 <= k <= MATCH_MAX_K:
-        raise ValueError("k in 1..%d" % MATCH_MAX_K)
+    k = _lib.in_range("k", k, MATCH_MAX_K)
     d = _lib.device_of(a)
     qa = a.detach().to(torch.float32).contiguous()
     qb = b.detach().to(a.device, torch.float32).contiguous()
@@ -199,11 +175,9 @@ def ransac_pose(src, dst, offsets, max_distance, seeds=None, hypotheses=4096, ed
     [total]]) on the device.  A pair without a pose (fewer than 3 correspondences, every triple rejected) gets the identity and
     info = (0, -1, valid, 0).  Enqueued on the current stream; a pair's result does not depend on the batch it is in.
     profile=True (measurements; blocking) appends the milliseconds of the three stages (models, score, refit) to the result."""
-    d, p = _points(src)
+    d, p, (h_off, d_off, P) = _ragged(src, offsets)
     q = dst.detach().to(p.device, torch.float32).contiguous()
     assert q.shape == p.shape, (tuple(p.shape), tuple(q.shape))
-    h_off, d_off = _offsets(offsets, p)
-    P = h_off.numel() - 1
     h_seeds = np.arange(P, dtype=np.uint64) if seeds is None else np.ascontiguousarray(np.asarray(seeds).astype(np.uint64)).reshape(-1)
     assert h_seeds.size == P, (h_seeds.size, P)
     par = RansacParams(int(hypotheses), int(refine_iters), float(max_distance), float(edge_similarity), float(min_sin2))

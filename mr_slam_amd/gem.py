@@ -46,24 +46,17 @@ def _poses(p, what):
     return p
 
 
-class ElevationSubmaps:
+class ElevationSubmaps(_lib.Handle):
     """The submap store of one robot.  `append_cells` / `append_leaving` fill the open submap, `close_submap(pose, centre)` makes it
     submap K, `update_global(opt_poses)` moves and fuses the closed ones, `submap(i)` / `compose()` read them back; `dropped` and
     `matched` are the counts of the last `update_global`."""
+    _destroy = "mrs_gem_destroy"
 
     def __init__(self, resolution=0.2, rule=WEIGHTED, radius=15.0, min_neighbours=3, device=0):
         self.device = int(device)
         self.resolution = float(resolution)
         self.rule = int(rule)
-        self._h = C.c_void_p()
-        _lib.load().mrs_gem_create(_lib.ctx(self.device), self.resolution, self.rule, float(radius), int(min_neighbours), C.byref(self._h))
-
-    def __del__(self):
-        try:
-            if getattr(self, "_h", None):
-                _lib.load().mrs_gem_destroy(self._h)
-        except Exception:
-            pass
+        self._create("mrs_gem_create", _lib.ctx(self.device), self.resolution, self.rule, float(radius), int(min_neighbours))
 
     def _counts(self):
         k, n, o = C.c_int32(0), C.c_int64(0), C.c_int64(0)

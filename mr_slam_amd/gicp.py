@@ -93,23 +93,16 @@ def _staging(points):
     return buf
 
 
-class GicpBatch:
+class GicpBatch(_lib.Handle):
     """n_pairs independent (source, target) registrations advanced together on one GPU."""
+    _destroy = "mrs_gicp_batch_destroy"
 
     def __init__(self, n_pairs, device=0):
         self.n_pairs = int(n_pairs)
         self.device = device
-        self._h = C.c_void_p()
-        _lib.load().mrs_gicp_batch_create(_lib.ctx(device), self.n_pairs, C.byref(self._h))
+        self._create("mrs_gicp_batch_create", _lib.ctx(device), self.n_pairs)
         self.params = default_params()
         self._n = [None, None]
-
-    def __del__(self):
-        try:
-            if getattr(self, "_h", None):
-                _lib.load().mrs_gicp_batch_destroy(self._h)
-        except Exception:
-            pass
 
     def set_params(self, **kw):
         for k, v in kw.items():

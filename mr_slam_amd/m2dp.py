@@ -6,32 +6,23 @@ Thin host logic over the C ABI (mrs_m2dp_*, mrs_loopdb_*_m2dp); there is no CPU 
 float32 cloud is widened to float64 before anything is computed, so the contract is `M2DP(cloud.astype(np.float64))`.
 """
 import ctypes as C
-import re
 
 import numpy as np
 import torch
 
 from . import _lib
+from .loopdb import VectorLoopDb
 
 NUM_PLANES, NUM_BINS, DESC_DIM = 64, 128, 192
 KIND_M2DP = 4
 MAX_K = 32
 # points per workgroup of the signature-matrix kernel (MRS_M2DP_TILE_POINTS of the C ABI header)
-TILE_POINTS = int(re.search(r"#define\s+MRS_M2DP_TILE_POINTS\s+(\d+)", open(_lib.HEADER).read())[1])
+TILE_POINTS = _lib.header_int("MRS_M2DP_TILE_POINTS")
 
 
 def _args(points, offsets):
-    """([total, stride >= 3] float32 / float64 device tensor, int64 offsets [B + 1] on either side) -> the C ABI's leading arguments"""
-    d = _lib.device_of(points)
-    p = points.detach()
-    if p.dtype not in (torch.float32, torch.float64):
-        p = p.to(torch.float64)
-    assert p.dim() == 2 and p.shape[1] >= 3, tuple(p.shape)
-    p = p.contiguous()
-    h_off = offsets.detach().to("cpu", torch.int64).contiguous()
-    d_off = offsets.detach().to(p.device, torch.int64).contiguous()
-    B = h_off.numel() - 1
-    assert B >= 1 and int(h_off[-1]) <= p.shape[0], (B, int(h_off[-1]), p.shape[0])
+    """([total, stride >= 3] float32 / float64 device tensor, offsets [B + 1] in any form _lib.ragged takes) -> the C ABI's leading arguments"""
+    d, p, (h_off, d_off, B) = _lib.ragged(points, offsets)
     return d, p, (_lib.ctx(d), p, p.dtype == torch.float64, p.shape[1], d_off, h_off, B)
 
 
@@ -56,56 +47,24 @@ def pca_batch(points, offsets):
 
 def m2dp(cloud, device="cuda:0"):
     """one cloud [n, >= 3] (device tensor, host tensor or array) -> (desc [192], A [64, 128]) float64 device tensors"""
-    if not isinstance(cloud, torch.Tensor):
-        cloud = torch.from_numpy(np.ascontiguousarray(cloud))
-    if not cloud.is_cuda:
-        cloud = cloud.to(device)
-    cloud = cloud.reshape(-1, cloud.shape[-1] if cloud.dim() == 2 else 3)
-    desc, A = m2dp_batch(cloud, torch.tensor([0, cloud.shape[0]], dtype=torch.int64))
+    desc, A = m2dp_batch(*_lib.one_cloud(cloud, device))
     return desc[0], A[0]
 
 
-class M2DPDatabase:
+class M2DPDatabase(VectorLoopDb):
     """Device-resident list of M2DP descriptors of one robot (mrs_loopdb, kind M2DP; entries are kept as float32 [192]): `append(desc)`;
     `query(desc, k)` = the k nearest entries by squared L2 distance, ascending, ties to the lower index."""
+    _elem = (torch.float64, np.float64, DESC_DIM)
 
     def __init__(self, device=0, capacity=1024):
-        self.device = int(device)
-        self._h = C.c_void_p()
-        _lib.load().mrs_loopdb_create(_lib.ctx(self.device), KIND_M2DP, 1, int(capacity), C.byref(self._h))
-
-    def __del__(self):
-        try:
-            if getattr(self, "_h", None):
-                _lib.load().mrs_loopdb_destroy(self._h)
-        except Exception:
-            pass
-
-    def __len__(self):
-        n = C.c_int32(0)
-        _lib.load().mrs_loopdb_size(self._h, C.byref(n))
-        return n.value
-
-    def _arg(self, desc):
-        """(descriptor, on_device, stream) of one [192] descriptor (torch host / device tensor or numpy array)"""
-        if isinstance(desc, torch.Tensor):
-            t = desc.detach().to(torch.float64).contiguous()
-            assert t.numel() == DESC_DIM, tuple(t.shape)
-            if t.is_cuda:
-                return t, 1, _lib.current_stream(t.device.index or 0)
-            return t, 0, None
-        a = np.ascontiguousarray(desc, dtype=np.float64)
-        assert a.size == DESC_DIM, a.shape
-        return a, 0, None
+        super().__init__(KIND_M2DP, 1, device, capacity)
 
     def append(self, desc):
         _lib.load().mrs_loopdb_append_m2dp(self._h, *self._arg(desc))
 
     def query(self, desc, k=1):
         """-> (indices, squared distances) as numpy arrays of length min(k, len(self)), nearest first"""
-        k = int(k)
-        if not 1 <= k <= MAX_K:
-            raise ValueError("k in 1..%d" % MAX_K)
+        k = _lib.in_range("k", k, MAX_K)
         t, dev, stream = self._arg(desc)
         idx, d2 = np.full(k, -1, np.int32), np.full(k, np.inf, np.float32)
         cnt = C.c_int32(0)

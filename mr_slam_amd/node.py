@@ -22,6 +22,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from .loopdb import LoopDb, query_grown
 
 KIND = {"ring": 0, "ringpp": 1, "disco": 2}
 FORM_HOST, FORM_DEVICE, FORM_DEVICE_SPEC = 0, 1, 2
@@ -45,7 +46,7 @@ def _on_device(x):
     return isinstance(x, torch.Tensor) and x.is_cuda
 
 
-class LoopDatabase:
+class LoopDatabase(LoopDb):
     """Device-resident descriptor list of one robot (mrs_loopdb).
 
     kind "ring"  : entries = what generate_RING returns as pc_TIRING (complex64 [1,120,120], util.py:198) or half spectra [1,61,120];
@@ -56,22 +57,9 @@ class LoopDatabase:
 
     def __init__(self, kind="ring", channels=None, device=0, capacity=1024):
         assert kind in ("ring", "ringpp")
-        self.kind, self.device = kind, int(device)
+        self.kind = kind
         self.channels = 1 if kind == "ring" else int(channels or 6)
-        self._h = C.c_void_p()
-        _lib.load().mrs_loopdb_create(_lib.ctx(self.device), KIND[kind], self.channels, int(capacity), C.byref(self._h))
-
-    def __del__(self):
-        try:
-            if getattr(self, "_h", None):
-                _lib.load().mrs_loopdb_destroy(self._h)
-        except Exception:
-            pass
-
-    def __len__(self):
-        n = C.c_int32(0)
-        _lib.load().mrs_loopdb_size(self._h, C.byref(n))
-        return n.value
+        super().__init__(KIND[kind], self.channels, device, capacity)
 
     def _descriptor(self, x):
         """(descriptor, form)"""
@@ -105,21 +93,19 @@ class LoopDatabase:
         ctypes drops the GIL during the call, so every call owns its output arrays; the entries scored are the n the C side reports (an
         append from another thread between sizing the arrays and the sweep can neither overflow nor truncate them silently)."""
         t, form = self._descriptor(descriptor)
-        lib = _lib.load()
-        cap = max(len(self), 1) + 64                       # room for entries another thread appends before the sweep runs
-        while True:
+        lib, stream = _lib.load(), self._stream(form)
+
+        def sweep(cap):
             idx, dist, ang = np.empty(cap, np.int32), np.empty(cap, np.float32), np.empty(cap, np.int32)
             alld = np.empty(cap, np.float32) if want_all else None
             alla = np.empty(cap, np.int32) if want_all else None
             cnt, n = C.c_int32(0), C.c_int32(0)
             lib.mrs_loopdb_query(self._h, t, form, threshold, cap, idx, dist, ang, C.byref(cnt), cap if want_all else 0, alld, alla,
-                                 C.byref(n), self._stream(form))
-            if cnt.value <= cap and n.value <= cap:
-                break
-            cap = max(cnt.value, n.value) + 64             # the list grew by more than the slack meanwhile: once more, with room
-        m = cnt.value
-        out = (idx[:m], dist[:m], ang[:m])
-        return out + (alld[:n.value], alla[:n.value]) if want_all else out
+                                 C.byref(n), stream)
+            m, n = cnt.value, n.value
+            out = (idx[:m], dist[:m], ang[:m])
+            return max(m, n), (out + (alld[:n], alla[:n]) if want_all else out)
+        return query_grown(sweep, max(len(self), 1) + 64, 64)     # + 64: room for entries another thread appends before the sweep runs
 
     def query_multi(self, descriptors):
         """Several new descriptors against every entry in ONE sweep (mrs_loopdb_query_multi): `descriptors` = a list / stacked tensor of
@@ -142,35 +128,27 @@ class LoopDatabase:
             t = q.to(torch.float32).contiguous()
             assert t.numel() == nq * self.channels * 120 * 120
             form = FORM_DEVICE if t.is_cuda else FORM_HOST
-        lib = _lib.load()
-        cap = max(len(self), 1) + 64
-        while True:
+        lib, stream = _lib.load(), self._stream(form)
+
+        def sweep(cap):
             alld, alla = np.empty((nq, cap), np.float32), np.empty((nq, cap), np.int32)
             n = C.c_int32(0)
-            lib.mrs_loopdb_query_multi(self._h, t, form, nq, cap, alld, alla, C.byref(n), self._stream(form))
-            if n.value <= cap:
-                break
-            cap = n.value + 64
-        return alld[:, :n.value], alla[:, :n.value]
+            lib.mrs_loopdb_query_multi(self._h, t, form, nq, cap, alld, alla, C.byref(n), stream)
+            return n.value, (alld[:, :n.value], alla[:, :n.value])
+        return query_grown(sweep, max(len(self), 1) + 64, 64)
 
     def device_entries(self):
         """(device pointer, n, floats per entry) of the stored entries (tests)"""
-        p, n, ef = C.c_void_p(), C.c_int32(0), C.c_int64(0)
-        _lib.load().mrs_loopdb_device_entries(self._h, C.byref(p), None, C.byref(n), C.byref(ef))
-        return p.value, n.value, ef.value
+        p, _, n, ef = super().device_entries()
+        return p, n, ef
 
 
-class DiscoDatabase:
+class DiscoDatabase(LoopDb):
     """DiSCO twin: `DiSCO<k>` (1024-d signatures) + `FFT<k>` (complex64 [1,1,40,120] spectra) of one robot on the device;
     `query(signature, spectrum)` = disco_ros/main.py:284-291 (nearest signature + phase_corr of the winner) in two launches."""
 
     def __init__(self, device=0, capacity=1024):
-        self.device = int(device)
-        self._h = C.c_void_p()
-        _lib.load().mrs_loopdb_create(_lib.ctx(self.device), KIND["disco"], 1, int(capacity), C.byref(self._h))
-
-    __del__ = LoopDatabase.__del__
-    __len__ = LoopDatabase.__len__
+        super().__init__(KIND["disco"], 1, device, capacity)
 
     def _args(self, signature, spectrum):
         sig = _as_arg(torch.as_tensor(signature).reshape(-1), torch.float32, (1024,))

@@ -6,15 +6,13 @@ Thin host logic over the C ABI (mrs_pcm_*); there is no CPU fallback.  The consi
 its two reproduced quirks and its three fixes are in DESIGN.md 4.18.
 """
 import ctypes as C
-import re
 
 import numpy as np
 
 from . import _lib
 
-MAX_LOOPS = int(re.search(r"#define\s+MRS_PCM_MAX_LOOPS\s+(\d+)", open(_lib.HEADER).read())[1])
-EXACT_DEFAULT_NODES, EXACT_OVERSHOOT = (int(re.search(r"#define\s+MRS_PCM_EXACT_%s\s+(\d+)" % k, open(_lib.HEADER).read())[1])
-                                        for k in ("DEFAULT_NODES", "OVERSHOOT"))
+MAX_LOOPS = _lib.header_int("MRS_PCM_MAX_LOOPS")
+EXACT_DEFAULT_NODES, EXACT_OVERSHOOT = _lib.header_int("MRS_PCM_EXACT_DEFAULT_NODES"), _lib.header_int("MRS_PCM_EXACT_OVERSHOOT")
 # getChiSquaredThreshold for 6 degrees of freedom (pairwise_consistency.cpp:7-38), keyed by round(100 p)
 _CHI2 = {1: 0.872, 5: 1.635, 10: 2.204, 25: 3.455, 50: 5.348, 75: 7.840}
 
@@ -59,12 +57,13 @@ def _poses(a, what):
     return a
 
 
-class PcmGraph:
+class PcmGraph(_lib.Handle):
     """The loops of one robot pair on the device: `set_trajectories(XA, XB)`, `add_loops(ia, kb, Z)` (vertex numbers follow the order of
     addition; pass them in `reference_order` to number them as the reference does), `solve()` -> (member list in the reference's order,
     number of rejected loops).  `matrix()` / `distances()` read the consistency matrix and the distances behind it; `set_matrix(A)` puts a
     given adjacency in place of the loops, for the clique stage alone.  `rounds` is the number of rounds the last solve took.
     `solve_exact()` -> (a MAXIMUM clique in ascending order, number of rejected loops) with `proof` and `nodes`."""
+    _destroy = "mrs_pcm_destroy"
 
     def __init__(self, capacity=MAX_LOOPS, p=0.01, threshold=None, device=0):
         self.device = int(device)
@@ -72,15 +71,7 @@ class PcmGraph:
         self.threshold = chi2_threshold(p) if threshold is None else float(threshold)
         self.rounds = 0
         self.proof, self.nodes, self.launches = 0, 0, 0
-        self._h = C.c_void_p()
-        _lib.load().mrs_pcm_create(_lib.ctx(self.device), self.capacity, self.threshold, C.byref(self._h))
-
-    def __del__(self):
-        try:
-            if getattr(self, "_h", None):
-                _lib.load().mrs_pcm_destroy(self._h)
-        except Exception:
-            pass
+        self._create("mrs_pcm_create", _lib.ctx(self.device), self.capacity, self.threshold)
 
     def __len__(self):
         n = C.c_int32(0)

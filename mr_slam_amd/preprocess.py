@@ -31,13 +31,11 @@ def voxel_down_sample_batch(points, raw_offsets, voxel_size):
     Returns (centroids float64 device [M,3], offsets int64 device [B+1]).  A batch without a single point gives an empty [0,3] result and
     all-zero offsets without a launch; the C ABI itself refuses a total of 0."""
     assert points.dtype in (torch.float32, torch.float64)
-    d = _lib.device_of(points)
-    p = points.contiguous()
+    _lib.device_of(points)
     h_off = np.ascontiguousarray(raw_offsets, dtype=np.int64)
     if h_off[-1] == 0:
-        return torch.empty((0, 3), dtype=torch.float64, device=p.device), torch.zeros(h_off.size, dtype=torch.int64, device=p.device)
-    d_off = torch.from_numpy(h_off).to(p.device)
-    B = h_off.size - 1
+        return torch.empty((0, 3), dtype=torch.float64, device=points.device), torch.zeros(h_off.size, dtype=torch.int64, device=points.device)
+    d, p, (h_off, d_off, B) = _lib.ragged(points, h_off)
     out = torch.empty((int(h_off[-1]), 3), dtype=torch.float64, device=p.device)
     offs = torch.empty(B + 1, dtype=torch.int64, device=p.device)
     _lib.load().mrs_voxel_downsample_batch(_lib.ctx(d), p, p.dtype == torch.float64, p.shape[1], d_off, h_off, B, voxel_size, out, offs,
@@ -70,13 +68,11 @@ def load_pc_infer_batch(points, raw_offsets):
     pointer to hand to the C ABI) gives all-zero offsets without a launch; xyz_soa keeps its minimum length of 3, zeroed, so that
     what consumes it still gets a buffer."""
     assert points.dtype in (torch.float32, torch.float64)
-    d = _lib.device_of(points)
-    p = points.contiguous()
+    _lib.device_of(points)
     h_off = np.ascontiguousarray(raw_offsets, dtype=np.int64)
     if h_off[-1] == 0:
-        return torch.zeros(3, dtype=torch.float32, device=p.device), torch.zeros(h_off.size, dtype=torch.int64, device=p.device)
-    d_off = torch.from_numpy(h_off).to(p.device)
-    B = h_off.size - 1
+        return torch.zeros(3, dtype=torch.float32, device=points.device), torch.zeros(h_off.size, dtype=torch.int64, device=points.device)
+    d, p, (h_off, d_off, B) = _lib.ragged(points, h_off)
     out = torch.empty(3 * max(1, int(h_off[-1])), dtype=torch.float32, device=p.device)
     offs = torch.empty(B + 1, dtype=torch.int64, device=p.device)
     _lib.load().mrs_crop_scale_batch(_lib.ctx(d), p, p.dtype == torch.float64, p.shape[1], d_off, h_off, B, out, offs, _lib.current_stream(d))

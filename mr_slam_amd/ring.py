@@ -19,22 +19,15 @@ MAX_LENGTH = 1
 MAX_HEIGHT = 1
 
 
-class RadonPlan:
+class RadonPlan(_lib.Handle):
     """Parallel-beam geometry bound to one device (C ABI mrs_radon_plan_*)."""
+    _destroy = "mrs_radon_plan_destroy"
 
     def __init__(self, det_count, angles, det_spacing, height, width, device=0):
         ang = np.ascontiguousarray(np.asarray(angles, dtype=np.float32))
         self.n_angles, self.det, self.h, self.w = int(ang.size), int(det_count), int(height), int(width)
         self.device = device
-        self._h = C.c_void_p()
-        _lib.load().mrs_radon_plan_create(_lib.ctx(device), ang, self.n_angles, self.det, det_spacing, self.h, self.w, C.byref(self._h))
-
-    def __del__(self):
-        try:
-            if getattr(self, "_h", None):
-                _lib.load().mrs_radon_plan_destroy(self._h)
-        except Exception:
-            pass
+        self._create("mrs_radon_plan_create", _lib.ctx(device), ang, self.n_angles, self.det, det_spacing, self.h, self.w)
 
     def degenerate_count(self, reset=True):
         """Sinograms whose fused normalisation met std == 0 (blank / constant image) since the last reset: the reference

@@ -12,6 +12,7 @@ import numpy as np
 import torch
 
 from . import _lib, bev
+from .loopdb import VectorLoopDb, query_grown
 
 NUM_RING = NUM_SECTOR = 120
 KIND_SC = 3
@@ -112,48 +113,22 @@ def distance_sc(sc1, sc2):
     return _pairs("mrs_sc_distance_pairs", sc1, sc2)
 
 
-class ScanContextDatabase:
+class ScanContextDatabase(VectorLoopDb):
     """Device-resident SC<k> + RingkeyPC<k> of one robot (mrs_loopdb, kind SC): `append(sc)` stores a [120, 120] descriptor with its keys;
     `query(sc, num_candidates, search_ratio)` = main_SC.py:159-167 (the nearest ring keys, then dist_align_sc(candidate, current));
-    `query_all(sc, search_ratio)` aligns the query against every entry."""
+    `query_all(sc, search_ratio)` aligns the query against every entry; `device_entries()` = (packed entries [n, entry_floats], ring
+    keys [n, 120], n, entry_floats)."""
+    _elem = (torch.float32, np.float32, NUM_RING * NUM_SECTOR)
 
     def __init__(self, device=0, capacity=1024):
-        self.device = int(device)
-        self._h = C.c_void_p()
-        _lib.load().mrs_loopdb_create(_lib.ctx(self.device), KIND_SC, 1, int(capacity), C.byref(self._h))
-
-    def __del__(self):
-        try:
-            if getattr(self, "_h", None):
-                _lib.load().mrs_loopdb_destroy(self._h)
-        except Exception:
-            pass
-
-    def __len__(self):
-        n = C.c_int32(0)
-        _lib.load().mrs_loopdb_size(self._h, C.byref(n))
-        return n.value
-
-    def _arg(self, sc):
-        """(descriptor, on_device, stream) of one [120, 120] descriptor (torch host / device tensor or numpy array)"""
-        if isinstance(sc, torch.Tensor):
-            t = sc.detach().to(torch.float32).contiguous()
-            assert t.numel() == NUM_RING * NUM_SECTOR, tuple(t.shape)
-            if t.is_cuda:
-                return t, 1, _lib.current_stream(t.device.index or 0)
-            return t, 0, None
-        a = np.ascontiguousarray(sc, dtype=np.float32)
-        assert a.size == NUM_RING * NUM_SECTOR, a.shape
-        return a, 0, None
+        super().__init__(KIND_SC, 1, device, capacity)
 
     def append(self, sc):
         _lib.load().mrs_loopdb_append_sc(self._h, *self._arg(sc))
 
     def query(self, sc, num_candidates=1, search_ratio=0.1):
         """-> (indices, ring-key distances, dists, shifts) as numpy arrays of length min(num_candidates, len(self)), nearest key first"""
-        k = int(num_candidates)
-        if not 1 <= k <= MAX_CANDIDATES:
-            raise ValueError("num_candidates in 1..%d" % MAX_CANDIDATES)
+        k = _lib.in_range("num_candidates", num_candidates, MAX_CANDIDATES)
         t, dev, stream = self._arg(sc)
         idx, kd = np.full(k, -1, np.int32), np.zeros(k, np.float32)
         dist, shift = np.zeros(k, np.float32), np.zeros(k, np.int32)
@@ -166,16 +141,10 @@ class ScanContextDatabase:
         """-> (dists [n], shifts [n], index of the first smallest dist or -1): dist_align_sc(entry, sc) for every entry"""
         t, dev, stream = self._arg(sc)
         lib = _lib.load()
-        while True:
-            cap = len(self)
+
+        def sweep(cap):
             dist, shift = np.zeros(max(cap, 1), np.float32), np.zeros(max(cap, 1), np.int32)
             best, n = C.c_int32(-1), C.c_int32(0)
             lib.mrs_loopdb_query_sc_all(self._h, t, dev, search_ratio, cap, dist, shift, C.byref(best), C.byref(n), stream)
-            if n.value <= cap:        # another thread may have appended since len(): ask again with larger arrays
-                return dist[:n.value], shift[:n.value], best.value
-
-    def device_entries(self):
-        """(packed entries [n, entry_floats], ring keys [n, 120]) as device tensors viewing the handle's memory (valid until it grows)"""
-        pe, ps, n, ef = C.c_void_p(), C.c_void_p(), C.c_int32(0), C.c_int64(0)
-        _lib.load().mrs_loopdb_device_entries(self._h, C.byref(pe), C.byref(ps), C.byref(n), C.byref(ef))
-        return pe.value, ps.value, n.value, ef.value
+            return n.value, (dist[:n.value], shift[:n.value], best.value)
+        return query_grown(sweep, len(self))          # exact: another thread may have appended since len()

@@ -325,12 +325,13 @@ class OwnerRescorer:
         return out_d, out_a
 
 
-class Exchange:
+class Exchange(_lib.Handle):
     """The exchange step behind the C ABI (include/mrslam_hip.h: mrs_exchange_*, RCCL looked up at run time): what a C++ host would call,
     usable from here as well.  The communicator is created by the library from a unique id that rank 0 makes and torch.distributed (any
     backend) hands to the others; without an initialised process group the world is this one process.
       allgather(local)              -> [world * n, ...]: every rank's `local` ([n, ...], the same n everywhere), in rank order
       fetch_rows(local_db, rows)    -> local_db-shaped rows by GLOBAL index (rank r owns rows [r * n, (r + 1) * n)), in request order"""
+    _destroy = "mrs_exchange_destroy"
 
     def __init__(self, device=0, group=None):
         lib = _lib.load()
@@ -345,15 +346,7 @@ class Exchange:
             box = [bytes(ident)]
             dist.broadcast_object_list(box, src=0, group=group)
             ident = (C.c_uint8 * 128).from_buffer_copy(box[0])
-        self._h = C.c_void_p()
-        lib.mrs_exchange_create(_lib.ctx(self.device), self.world, self.rank, ident, C.byref(self._h))
-
-    def __del__(self):
-        try:
-            if getattr(self, "_h", None):
-                _lib.load().mrs_exchange_destroy(self._h)
-        except Exception:
-            pass
+        self._create("mrs_exchange_create", _lib.ctx(self.device), self.world, self.rank, ident)
 
     def allgather(self, local):
         x = local.contiguous()
@@ -387,10 +380,11 @@ class Exchange:
         return out
 
 
-class PlannedFetch:
+class PlannedFetch(_lib.Handle):
     """RowFetchPlan's counterpart behind the C ABI (mrs_exchange_fetch_plan_*): the candidate rows a rank will ask for are registered once
     (one all-gather of the requests, one host synchronisation), every fetch() afterwards is gather -> grouped RCCL send / receive -> scatter,
     enqueued on a stream without touching the host.  Same interface as RowFetchPlan.fetch(async_op=True): (work, finish)."""
+    _destroy = "mrs_exchange_fetch_plan_destroy"
 
     class _Work:
         def __init__(self, event):
@@ -404,19 +398,10 @@ class PlannedFetch:
         rows = global_rows.to(torch.int64).reshape(-1).contiguous()
         assert rows.numel() > 0
         self.n, self.rows_per_rank = int(rows.numel()), int(rows_per_rank)
-        self._h = C.c_void_p()
-        _lib.load().mrs_exchange_fetch_plan_create(exchange._h, self.rows_per_rank, rows, self.n, _lib.current_stream(exchange.device),
-                                                   C.byref(self._h))
+        self._create("mrs_exchange_fetch_plan_create", exchange._h, self.rows_per_rank, rows, self.n, _lib.current_stream(exchange.device))
         sent, recv = C.c_int64(0), C.c_int64(0)
         _lib.load().mrs_exchange_fetch_plan_counts(self._h, C.byref(sent), C.byref(recv))
         self.rows_from_peers, self.rows_to_peers = int(recv.value), int(sent.value)
-
-    def __del__(self):
-        try:
-            if getattr(self, "_h", None):
-                _lib.load().mrs_exchange_fetch_plan_destroy(self._h)
-        except Exception:
-            pass
 
     def bytes_in(self, row_bytes, rank_local_too=False):
         return row_bytes * (self.n if rank_local_too else self.rows_from_peers)

@@ -40,21 +40,14 @@ def relative_transform(center_pose, near_pose):
     return T
 
 
-class KeyframeStore:
+class KeyframeStore(_lib.Handle):
     """One robot's keyframes (thisRobotHandle->keyframes / ->trajectory) resident on one GPU."""
+    _destroy = "mrs_keyframes_destroy"
 
     def __init__(self, device=0, capacity_hint=1 << 20):
         self.device = device
-        self._h = C.c_void_p()
         self._counts = []
-        _lib.load().mrs_keyframes_create(_lib.ctx(device), int(capacity_hint), C.byref(self._h))
-
-    def __del__(self):
-        try:
-            if getattr(self, "_h", None):
-                _lib.load().mrs_keyframes_destroy(self._h)
-        except Exception:
-            pass
+        self._create("mrs_keyframes_create", _lib.ctx(device), int(capacity_hint))
 
     def __len__(self):
         return len(self._counts)
