@@ -894,11 +894,11 @@ int mrs_loopdb_append_sc(mrs_loopdb* db, const float* sc, int32_t on_device, mrs
  * dist_align_sc(SC_candidate, SC_current, search_ratio) (pr_methods/ScanContext.py:128-142) for each.  h_index / h_key_dist / h_dist /
  * h_shift [num_candidates]; *h_count = min(k, n).  The shift is the reference's: in [-S, S), the roll applied to SC_current.  Blocking;
  * an empty database returns *h_count = 0 and index -1 without device work. */
-int mrs_loopdb_query_sc(mrs_loopdb* db, const float* sc, int32_t on_device, int32_t num_candidates, float search_ratio, int32_t* h_index,
+int mrs_loopdb_query_sc(mrs_loopdb* db, const float* sc, int32_t on_device, int32_t num_candidates, double search_ratio, int32_t* h_index,
                         float* h_key_dist, float* h_dist, int32_t* h_shift, int32_t* h_count, mrs_stream stream);
 /* dist_align_sc(entry, sc, search_ratio) against EVERY entry in one launch: h_all_dist / h_all_shift receive the first min(n, all_capacity)
  * results, *h_best the index of the first smallest dist over all n (-1 when empty), *h_n = n.  Blocking. */
-int mrs_loopdb_query_sc_all(mrs_loopdb* db, const float* sc, int32_t on_device, float search_ratio, int32_t all_capacity, float* h_all_dist,
+int mrs_loopdb_query_sc_all(mrs_loopdb* db, const float* sc, int32_t on_device, double search_ratio, int32_t all_capacity, float* h_all_dist,
                             int32_t* h_all_shift, int32_t* h_best, int32_t* h_n, mrs_stream stream);
 /* M2DP (MRS_LOOPDB_M2DP): the list of 192-d descriptors a node would keep per robot and search by Euclidean distance (the M2DP paper's
  * matching rule; the reference ships the descriptor, RING_ros/pr_methods/M2DP.py, without a node of its own).  desc = double [192] as
@@ -947,7 +947,7 @@ int mrs_sc_dist_direct_pairs(mrs_ctx* ctx, const float* d_sc1, const float* d_sc
 /* dist_align_sc(sc1, sc2, search_ratio) (ScanContext.py:128-142): sector-key pre-alignment s*, then the window
  * [max(-S, s* - r), min(S, s* + r + 1)) with r = round(0.5 search_ratio S), first minimum; d_shift may be negative. */
 int mrs_sc_dist_align_pairs(mrs_ctx* ctx, const float* d_sc1, const float* d_sc2, int32_t n_pairs, int32_t num_ring, int32_t num_sector,
-                            float search_ratio, float* d_dist, int32_t* d_shift, mrs_stream stream);
+                            double search_ratio, float* d_dist, int32_t* d_shift, mrs_stream stream);
 /* distance_sc(sc1, sc2) (ScanContext.py:34-69): all num_sector shifts of sc1, mean cosine over the engaged columns (0 if none);
  * d_dist = 1 - max, d_yaw = argmax + 1 (the reference's convention). */
 int mrs_sc_distance_pairs(mrs_ctx* ctx, const float* d_sc1, const float* d_sc2, int32_t n_pairs, int32_t num_ring, int32_t num_sector, float* d_dist,

@@ -287,7 +287,7 @@ namespace mrs {
 // Scan Context building blocks (scancontext.hip), shared with the MRS_LOOPDB_SC database of loopdb.hip.  An entry is a header (sector keys,
 // column norms) followed by the [R][S] descriptor; sc_entry_floats(R, S) floats from one entry to the next.
 size_t sc_entry_floats(int R, int S);
-int sc_search_radius(float search_ratio, int S);
+int sc_search_radius(double search_ratio, int S);
 int sc_pack(const float* d_sc, int n, int R, int S, float* d_entries, size_t entry_stride, float* d_ring, float* d_sector, hipStream_t s);
 int sc_nearest(const float* d_q, const float* d_keys, int n, int R, int k, int* d_idx, double* d_d2, hipStream_t s);
 // mode 0: dist_align_sc(F, Q) with the given search radius; 1: distance_sc(Q, F); 2: dist_direct_sc(F, Q)

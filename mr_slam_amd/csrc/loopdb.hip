@@ -701,13 +701,13 @@ int mrs_loopdb_append_sc(mrs_loopdb* db, const float* sc, int32_t on_device, mrs
     return MRS_OK;
 }
 
-int mrs_loopdb_query_sc(mrs_loopdb* db, const float* sc, int32_t on_device, int32_t num_candidates, float search_ratio, int32_t* h_index,
+int mrs_loopdb_query_sc(mrs_loopdb* db, const float* sc, int32_t on_device, int32_t num_candidates, double search_ratio, int32_t* h_index,
                         float* h_key_dist, float* h_dist, int32_t* h_shift, int32_t* h_count, mrs_stream stream)
 {
     MRS_REQUIRE(db && sc && h_index && h_key_dist && h_dist && h_shift && h_count, "null pointer");
     MRS_TRY(require_kind(db, kWantSc));
     MRS_REQUIRE(num_candidates >= 1 && num_candidates <= kScMaxK, "num_candidates in 1..64");
-    MRS_REQUIRE(std::isfinite(search_ratio) && search_ratio >= 0.0f, "search_ratio >= 0");
+    MRS_REQUIRE(std::isfinite(search_ratio) && search_ratio >= 0.0, "search_ratio >= 0");
     MRS_HIP_TRY(hipSetDevice(db->ctx->device));
     std::lock_guard<std::mutex> lk(db->mu);
     const int k = num_candidates;
@@ -736,12 +736,12 @@ int mrs_loopdb_query_sc(mrs_loopdb* db, const float* sc, int32_t on_device, int3
     return MRS_OK;
 }
 
-int mrs_loopdb_query_sc_all(mrs_loopdb* db, const float* sc, int32_t on_device, float search_ratio, int32_t all_capacity, float* h_all_dist,
+int mrs_loopdb_query_sc_all(mrs_loopdb* db, const float* sc, int32_t on_device, double search_ratio, int32_t all_capacity, float* h_all_dist,
                             int32_t* h_all_shift, int32_t* h_best, int32_t* h_n, mrs_stream stream)
 {
     MRS_REQUIRE(db && sc && h_best && h_n, "null pointer");
     MRS_TRY(require_kind(db, kWantSc));
-    MRS_REQUIRE(std::isfinite(search_ratio) && search_ratio >= 0.0f, "search_ratio >= 0");
+    MRS_REQUIRE(std::isfinite(search_ratio) && search_ratio >= 0.0, "search_ratio >= 0");
     MRS_REQUIRE(all_capacity >= 0 && (all_capacity == 0 || (h_all_dist && h_all_shift)), "all_capacity without arrays");
     MRS_HIP_TRY(hipSetDevice(db->ctx->device));
     std::lock_guard<std::mutex> lk(db->mu);

@@ -360,10 +360,10 @@ int sc_pack(const float* d_sc, int n, int R, int S, float* d_entries, size_t ent
     return MRS_OK;
 }
 
-int sc_search_radius(float search_ratio, int S)
+int sc_search_radius(double search_ratio, int S)
 {
     // round(0.5 * search_ratio * num_sector) (Python's round: half to even); the window is clipped to [-S, S) anyway
-    const double r = std::nearbyint(0.5 * (double)search_ratio * (double)S);
+    const double r = std::nearbyint(0.5 * search_ratio * (double)S);
     return (int)std::min(std::max(r, 0.0), 2.0 * S);
 }
 
@@ -470,9 +470,9 @@ int mrs_sc_dist_direct_pairs(mrs_ctx* ctx, const float* d_sc1, const float* d_sc
 }
 
 int mrs_sc_dist_align_pairs(mrs_ctx* ctx, const float* d_sc1, const float* d_sc2, int32_t n_pairs, int32_t num_ring, int32_t num_sector,
-                            float search_ratio, float* d_dist, int32_t* d_shift, mrs_stream stream)
+                            double search_ratio, float* d_dist, int32_t* d_shift, mrs_stream stream)
 {
-    MRS_REQUIRE(std::isfinite(search_ratio) && search_ratio >= 0.0f, "search_ratio >= 0");
+    MRS_REQUIRE(std::isfinite(search_ratio) && search_ratio >= 0.0, "search_ratio >= 0");
     return pairs_common(ctx, d_sc1, d_sc2, n_pairs, num_ring, num_sector, kModeAlign, mrs::sc_search_radius(search_ratio, num_sector), false,
                         d_dist, d_shift, (hipStream_t)stream);
 }

@@ -105,7 +105,7 @@ def dist_direct_sc(sc1, sc2):
 
 def dist_align_sc(sc1, sc2, search_ratio=0.1):
     """ScanContext.py:128-142: (dist, shift); the shift rolls sc2 and may be negative.  Batched over a leading axis."""
-    return _pairs("mrs_sc_dist_align_pairs", sc1, sc2, search_ratio)
+    return _pairs("mrs_sc_dist_align_pairs", sc1, sc2, float(search_ratio))
 
 
 def distance_sc(sc1, sc2):
@@ -133,7 +133,7 @@ class ScanContextDatabase(VectorLoopDb):
         idx, kd = np.full(k, -1, np.int32), np.zeros(k, np.float32)
         dist, shift = np.zeros(k, np.float32), np.zeros(k, np.int32)
         cnt = C.c_int32(0)
-        _lib.load().mrs_loopdb_query_sc(self._h, t, dev, k, search_ratio, idx, kd, dist, shift, C.byref(cnt), stream)
+        _lib.load().mrs_loopdb_query_sc(self._h, t, dev, k, float(search_ratio), idx, kd, dist, shift, C.byref(cnt), stream)
         c = cnt.value
         return idx[:c], kd[:c], dist[:c], shift[:c]
 
@@ -145,6 +145,6 @@ class ScanContextDatabase(VectorLoopDb):
         def sweep(cap):
             dist, shift = np.zeros(max(cap, 1), np.float32), np.zeros(max(cap, 1), np.int32)
             best, n = C.c_int32(-1), C.c_int32(0)
-            lib.mrs_loopdb_query_sc_all(self._h, t, dev, search_ratio, cap, dist, shift, C.byref(best), C.byref(n), stream)
+            lib.mrs_loopdb_query_sc_all(self._h, t, dev, float(search_ratio), cap, dist, shift, C.byref(best), C.byref(n), stream)
             return n.value, (dist[:n.value], shift[:n.value], best.value)
         return query_grown(sweep, len(self))          # exact: another thread may have appended since len()

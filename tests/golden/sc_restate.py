@@ -24,12 +24,22 @@ def sector_norms(k1, k2):
     return np.sqrt(((np.asarray(k1, np.float64)[None, :] - np.asarray(k2, np.float64)[idx]) ** 2).sum(1))
 
 
+def _nonempty(sc, norm64):
+    """the columns that count: the reference tests np.linalg.norm(column) > 0 in the descriptor's own type, and in float32 the squares
+    of values below 2^-75 underflow to 0, so such a column is empty although its fp64 norm is not"""
+    a = np.asarray(sc)
+    if a.dtype != np.float32:
+        return norm64 > 0
+    a = a.reshape(a.shape[-2:])
+    return (a * a).sum(0, dtype=np.float32) > 0
+
+
 def _cos(sc1, sc2):
     """[j, c]: cosine of column j of sc1 and column c of sc2 (0 where a norm is 0), and the engaged mask"""
     a = np.asarray(sc1, np.float64).reshape(np.shape(sc1)[-2:])
     b = np.asarray(sc2, np.float64).reshape(np.shape(sc2)[-2:])
     na, nb = np.sqrt((a * a).sum(0)), np.sqrt((b * b).sum(0))
-    eng = (na[:, None] > 0) & (nb[None, :] > 0)
+    eng = _nonempty(sc1, na)[:, None] & _nonempty(sc2, nb)[None, :]
     g = a.T @ b
     with np.errstate(invalid="ignore", divide="ignore"):
         c = np.where(eng, g / (na[:, None] * nb[None, :]), 0.0)
