@@ -1,0 +1,102 @@
+// mrslam/posegraph.hpp -- C++ host-side pose-graph optimisation for the Mapping workspace.
+//
+// Stands where GlobalManager calls evaluation_utils::centralizedGNEstimation (Mapping/src/global_manager/src/global_manager.cpp:1354;
+// distributed_mapper/evaluation_utils.cpp:273-329): the rotations by chordal relaxation, then Gauss-Newton on BetweenChordalFactor errors.
+// All arithmetic happens in libmrslam_hip.so through the C ABI (mrs_pgo_*); this header only adapts types.  Plain arrays
+// in, std::vector<double> out: no gtsam and no Eigen.  A pose is 16 doubles, the row-major 4x4 (gtsam: pose.matrix(), copied row by row).
+//
+// Poses are numbered chain after chain (robot after robot); a factor (i, j, Z) measures the pose of j in the frame of i.
+#pragma once
+#include <cstdint>
+#include <numeric>
+#include <stdexcept>
+#include <string>
+#include <vector>
+
+#include "mrslam_hip.h"
+
+namespace mrslam {
+
+class PoseGraph {
+public:
+    struct Result {
+        std::vector<double> poses;       // [poses][16]
+        int iterations = 0;
+        bool converged = false;
+        double max_delta = 0.0;          // the last Gauss-Newton step's largest component
+        double error_initial = 0.0;      // 0.5 sum |e|^2 at the chordal start: the reference's "Initial Error"
+        double error_final = 0.0;        // and at the result: its "GN Error"
+        int separators = 0;
+    };
+
+    explicit PoseGraph(const std::vector<int32_t>& chain_lengths, int device = 0)
+        : poses_(std::accumulate(chain_lengths.begin(), chain_lengths.end(), 0))
+    {
+        check(mrs_ctx_create(device, &ctx_), "mrs_ctx_create");
+        const int st = mrs_pgo_create(ctx_, static_cast<int32_t>(chain_lengths.size()), chain_lengths.data(), &h_);
+        if (st != MRS_OK) {
+            const std::string why = std::string(mrs_status_str(st)) + ": " + mrs_last_error();
+            mrs_ctx_destroy(ctx_);
+            throw std::runtime_error("mrs_pgo_create: " + why);
+        }
+    }
+    ~PoseGraph()
+    {
+        mrs_pgo_destroy(h_);
+        mrs_ctx_destroy(ctx_);
+    }
+    PoseGraph(const PoseGraph&) = delete;
+    PoseGraph& operator=(const PoseGraph&) = delete;
+
+    int poses() const { return poses_; }
+    // one between-pose per consecutive pair of a chain, chain after chain: Z [n][16]
+    void setOdometry(const double* Z, int n) { check(mrs_pgo_set_odometry(h_, Z, n), "mrs_pgo_set_odometry"); }
+    // n loop factors: Z [n][16], the measured pose of j[u] in the frame of i[u]
+    void addLoops(const int32_t* i, const int32_t* j, const double* Z, int n) { check(mrs_pgo_add_loops(h_, i, j, Z, n), "mrs_pgo_add_loops"); }
+    void clearLoops() { check(mrs_pgo_clear_loops(h_), "mrs_pgo_clear_loops"); }
+    int loops() const
+    {
+        int32_t n = 0;
+        check(mrs_pgo_count(h_, &n), "mrs_pgo_count");
+        return n;
+    }
+    void setPrior(const double* T) { check(mrs_pgo_set_prior(h_, T), "mrs_pgo_set_prior"); }
+    void setSegmentLength(int length) { check(mrs_pgo_set_segment_length(h_, length), "mrs_pgo_set_segment_length"); }
+
+    // stage 1 alone: the relaxed rotations projected to SO(3), zero translations, [poses][16]
+    std::vector<double> initialize()
+    {
+        std::vector<double> T(static_cast<size_t>(poses_) * 16);
+        check(mrs_pgo_initialize(h_, T.data()), "mrs_pgo_initialize");
+        return T;
+    }
+
+    // centralizedGNEstimation with a stop rule: eps = 0 and max_iterations = 200 is the reference's loop, max_iterations = 1 is
+    // centralizedEstimation
+    Result optimize(double eps = 1e-9, int max_iterations = MRS_PGO_DEFAULT_MAX_ITERATIONS)
+    {
+        Result r;
+        r.poses.resize(static_cast<size_t>(poses_) * 16);
+        double info[MRS_PGO_INFO_DOUBLES] = {};
+        check(mrs_pgo_optimize(h_, eps, max_iterations, r.poses.data(), info), "mrs_pgo_optimize");
+        r.iterations = static_cast<int>(info[0]);
+        r.converged = info[1] != 0.0;
+        r.max_delta = info[2];
+        r.error_initial = info[3];
+        r.error_final = info[4];
+        r.separators = static_cast<int>(info[5]);
+        return r;
+    }
+
+private:
+    static void check(int st, const char* what)
+    {
+        if (st != MRS_OK) throw std::runtime_error(std::string(what) + ": " + mrs_status_str(st) + ": " + mrs_last_error());
+    }
+
+    mrs_ctx* ctx_ = nullptr;
+    mrs_pgo* h_ = nullptr;
+    int poses_ = 0;
+};
+
+}  // namespace mrslam

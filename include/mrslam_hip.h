@@ -1271,6 +1271,63 @@ int mrs_ransac_pose_batch_profile(mrs_ctx* ctx, const float* d_src, const float*
                                   const int64_t* h_offsets, int32_t n_pairs, const uint64_t* h_seeds, const mrs_ransac_params* params,
                                   double* d_T, int32_t* d_info, uint8_t* d_mask, float* h_stage_ms, mrs_stream stream);
 
+/* ------------------------------------------------------------------------------------
+ * Pose-graph optimisation: what evaluation_utils::centralizedGNEstimation computes
+ * (Mapping/src/global_manager/src/distributed_mapper/evaluation_utils.cpp:273-329, called at global_manager.cpp:1354): the rotations by
+ * chordal relaxation, then Gauss-Newton on BetweenChordalFactor errors (between_chordal_factor.h:97-144) with unit weights and pose 0
+ * held at its initial value.  All arithmetic is fp64.  The graph is `nr` odometry chains, poses numbered chain after chain, plus loop
+ * factors between any two poses.  Host arrays in and out; every call is blocking and works on the legacy default stream.  One caller
+ * at a time per handle.  Results are the same bits from run to run and do not depend on how the loops were split over calls.
+ * ---------------------------------------------------------------------------------- */
+typedef struct mrs_pgo mrs_pgo;
+
+#define MRS_PGO_MAX_CHAINS 16
+#define MRS_PGO_MAX_POSES 65536
+#define MRS_PGO_MAX_LOOPS 8192
+/* most separators of the Gauss-Newton system: the poses a loop touches (pose 0 apart) and the cut poses that bound a segment's length */
+#define MRS_PGO_MAX_SEPARATORS 1024
+/* longest run of poses one segment walk eliminates unless mrs_pgo_set_segment_length says otherwise (0: unbounded) */
+#define MRS_PGO_DEFAULT_SEGMENT_LENGTH 64
+/* panel width of the dense Cholesky of the reduced system (the tests place their reduced orders around its multiples) */
+#define MRS_PGO_PANEL_WIDTH 24
+#define MRS_PGO_DEFAULT_MAX_ITERATIONS 200
+/* doubles of mrs_pgo_optimize's h_info: iterations done, converged (0 / 1), the last max|delta|, 0.5 sum |e|^2 at the stage-1 values and
+ * at the result, the separator count */
+#define MRS_PGO_INFO_DOUBLES 6
+
+/* nr in 1 .. MRS_PGO_MAX_CHAINS chains of h_chain_lengths[r] >= 1 poses, MRS_PGO_MAX_POSES in all at most (more: MRS_ERR_UNSUPPORTED) */
+int mrs_pgo_create(mrs_ctx* ctx, int32_t nr, const int32_t* h_chain_lengths, mrs_pgo** out);
+int mrs_pgo_destroy(mrs_pgo* pgo);
+/* The odometry factors, chain after chain: h_Z double [n][4][4] row-major, the measured pose of pose p + 1 in the frame of pose p.
+ * n must be (poses - nr), and every entry finite: MRS_ERR_ARG otherwise, the handle unchanged. */
+int mrs_pgo_set_odometry(mrs_pgo* pgo, const double* h_Z, int32_t n);
+/* Appends n loop factors (h_i[u], h_j[u], h_Z[u]): h_Z double [n][4][4] is the measured pose of j in the frame of i.  Any two different
+ * poses, in either order; repeated pairs, consecutive poses and pose 0 are allowed.  i == j, an index outside the graph or a pose that is
+ * not finite: MRS_ERR_ARG.  More than MRS_PGO_MAX_LOOPS loops or MRS_PGO_MAX_SEPARATORS separators: MRS_ERR_UNSUPPORTED.  Nothing is
+ * added then. */
+int mrs_pgo_add_loops(mrs_pgo* pgo, const int32_t* h_i, const int32_t* h_j, const double* h_Z, int32_t n);
+int mrs_pgo_clear_loops(mrs_pgo* pgo);
+/* the number of loop factors */
+int mrs_pgo_count(mrs_pgo* pgo, int32_t* h_count);
+/* The prior on pose 0, double [4][4] (the identity until set): stage 1 ties pose 0's rotation to its rotation; the translation of
+ * pose 0 is zero whatever it says, as pose3WithZeroTranslation leaves it. */
+int mrs_pgo_set_prior(mrs_pgo* pgo, const double* h_T);
+/* No run of poses between two separators is longer than `length` (0: unbounded).  Negative: MRS_ERR_ARG; a length that needs more than
+ * MRS_PGO_MAX_SEPARATORS separators: MRS_ERR_UNSUPPORTED, the setting unchanged.  A setting's results do not depend on earlier ones. */
+int mrs_pgo_set_segment_length(mrs_pgo* pgo, int32_t length);
+/* Stage 1 alone: h_T double [poses][4][4] receives the relaxed rotations projected to SO(3), with zero translations.  A chain that no
+ * loop factors connect to chain 0, or odometry not set: MRS_ERR_ARG.  A pivot block that is not positive definite:
+ * MRS_ERR_NOT_CONVERGED with the pose in mrs_last_error(). */
+int mrs_pgo_initialize(mrs_pgo* pgo, double* h_T);
+/* Both stages: Gauss-Newton from the stage-1 values until max|delta| < eps or max_iterations steps are done (eps = 0: exactly
+ * max_iterations, what the reference does with 200; max_iterations = 1: centralizedEstimation).  eps >= 0, max_iterations >= 1.
+ * h_T double [poses][4][4]; h_info double [MRS_PGO_INFO_DOUBLES].  Errors as mrs_pgo_initialize; the handle's graph is never changed. */
+int mrs_pgo_optimize(mrs_pgo* pgo, double eps, int32_t max_iterations, double* h_T, double* h_info);
+/* The last mrs_pgo_optimize between events (for measurements): h_ms float [6] = milliseconds of stage 1, and of the linearisation with
+ * the gather, the segment walks (both directions), the assembly, the dense factorisation with its solves, and the retraction, each
+ * summed over the iterations.  Zeros unless MRS_DEV=1 and MRS_PGO_TIMING=1 were set when the call ran. */
+int mrs_pgo_last_stage_ms(mrs_pgo* pgo, float* h_ms);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,1231 @@
+// posegraph.hip -- pose-graph optimisation of the Mapping back end (C ABI mrs_pgo_*).
+//
+// What it replaces: evaluation_utils::centralizedGNEstimation (distributed_mapper/evaluation_utils.cpp:273-329, called at
+// global_manager.cpp:1354 after every accepted loop closure): a chordal-relaxation solve for all rotations and then 200 unconditional
+// Gauss-Newton iterations, each a re-linearisation of every factor and a sparse elimination on one host thread.  Here both stages go
+// through one direct solver, templated on the block size B and the number of right-hand sides NR (3 and 3 for the rotations, 6 and 1 for
+// Gauss-Newton), that uses the structure of the workload: a few odometry chains plus a comparatively small set of loop factors.
+//   separators : every pose a loop factor touches, and cut poses so that no run of other poses is longer than the segment length.  The
+//                runs between them (segments) are block-tridiagonal and independent of each other;
+//   linearize  : k_pgo_linearize, a thread per factor: e, Hi^T Hi, Hi^T Hj, -Hi^T e, -Hj^T e (posegraph_factor.hpp), factor-major;
+//                k_pgo_gather, a thread per pose, sums them in ascending factor order through a CSR.  No float atomics anywhere;
+//   eliminate  : k_pgo_eliminate, a lane per segment walks its run: a B x B Cholesky of the pivot block per pose, the fill towards the
+//                left separator carried along, the Schur contributions to the bounding separators left per segment, the per-pose factors
+//                left for the way back;
+//   reduced    : k_pgo_assemble sums, per block of the dense lower system of order B E, the separator's own block, the loop blocks and
+//                the segment contributions in a fixed order (a list per block, built on the host).  The right-hand sides are appended as
+//                NR extra rows, so that the blocked right-looking Cholesky (k_pgo_chol_panel on one workgroup, k_pgo_chol_trail over a
+//                grid, per panel of kNB columns) performs the forward substitution on its way; k_pgo_chol_back is the other solve;
+//   backsolve  : k_pgo_backsolve, a lane per segment, from its right separator down; k_pgo_scatter copies the separators' solutions;
+//   retract    : k_pgo_retract, a thread per pose; max|delta| by an integer atomicMax on the bits of a non-negative double;
+//   error      : 0.5 sum |e|^2 by a fixed two-level tree (k_pgo_sum1, k_pgo_sum2);
+//   project    : k_pgo_project, stage 1: the closest rotation of each solved 3x3.
+// No kernel waits for another workgroup, every device loop is bounded by a size known at launch, and a pivot block that is not positive
+// definite becomes a status word (the walk goes on with a unit pivot; the host ends the call).  The host reads 16 bytes per iteration.
+#include "common.hpp"
+#include "posegraph_factor.hpp"
+
+#include <algorithm>
+#include <cmath>
+#include <map>
+#include <utility>
+#include <vector>
+
+namespace {
+
+using u64 = unsigned long long;
+constexpr int kThreads = 256;
+constexpr int kMaxChains = MRS_PGO_MAX_CHAINS, kMaxPoses = MRS_PGO_MAX_POSES, kMaxLoops = MRS_PGO_MAX_LOOPS, kMaxSep = MRS_PGO_MAX_SEPARATORS;
+constexpr int kNB = MRS_PGO_PANEL_WIDTH;  // panel width of the dense Cholesky: a multiple of both block sizes
+constexpr int kTile = 32;                // the trailing update works on kTile x kTile tiles
+constexpr int kBig = 1 << 30;            // a failed pivot is recorded as kBig - index by atomicMax: the lowest index wins, 0 = none
+constexpr int kTypeShift = 24;           // a contribution is type << 24 | index
+static_assert(kMaxPoses + kMaxLoops + 2 < (1 << kTypeShift), "a contribution's index must fit below its type");
+enum : int { kNodeDiag = 0, kFactor = 1, kFactorT = 2, kSegLL = 3, kSegRR = 4, kSegRL = 5, kSegRLT = 6 };
+
+struct Status {
+    u64 max_delta;       // bits of max|delta|
+    int seg_fail;        // kBig - pose of the lowest pose whose pivot block failed in a segment walk
+    int dense_fail;      // kBig - row of the lowest failed pivot of the dense factorisation
+};
+static_assert(sizeof(Status) == 16, "the host reads 16 bytes per iteration");
+
+inline unsigned blocks_for(long long items, int per_block) { return (unsigned)((items + per_block - 1) / per_block); }
+
+// ------------------------------------------------------------------ small dense pieces, row-major B x B in registers
+
+// lower Cholesky in place (only the lower triangle is read); a pivot that is not positive and finite is replaced by 1 -> false
+template <int B>
+__device__ __forceinline__ bool chol_inplace(double* D)
+{
+    bool ok = true;
+#pragma unroll
+    for (int j = 0; j < B; ++j) {
+        double d = D[j * B + j];
+#pragma unroll
+        for (int k = 0; k < j; ++k) d -= D[j * B + k] * D[j * B + k];
+        if (!(d > 0.0) || !isfinite(d)) {
+            ok = false;
+            d = 1.0;
+        }
+        d = sqrt(d);
+        D[j * B + j] = d;
+#pragma unroll
+        for (int i = j + 1; i < B; ++i) {
+            double s = D[i * B + j];
+#pragma unroll
+            for (int k = 0; k < j; ++k) s -= D[i * B + k] * D[j * B + k];
+            D[i * B + j] = s / d;
+        }
+    }
+    return ok;
+}
+
+// M <- L^-1 M for M [B][C]
+template <int B, int C>
+__device__ __forceinline__ void lower_solve(const double* L, double* M)
+{
+#pragma unroll
+    for (int c = 0; c < C; ++c)
+#pragma unroll
+        for (int i = 0; i < B; ++i) {
+            double s = M[i * C + c];
+#pragma unroll
+            for (int k = 0; k < i; ++k) s -= L[i * B + k] * M[k * C + c];
+            M[i * C + c] = s / L[i * B + i];
+        }
+}
+
+// v <- L^-T v
+template <int B>
+__device__ __forceinline__ void upper_solve(const double* L, double* v)
+{
+#pragma unroll
+    for (int i = B - 1; i >= 0; --i) {
+        double s = v[i];
+#pragma unroll
+        for (int k = i + 1; k < B; ++k) s -= L[k * B + i] * v[k];
+        v[i] = s / L[i * B + i];
+    }
+}
+
+// ------------------------------------------------------------------ linearisation
+
+// stage 2: a thread per factor
+__global__ __launch_bounds__(kThreads) void k_pgo_linearize(const double* __restrict__ T, const int* __restrict__ fi, const int* __restrict__ fj,
+                                                            const double* __restrict__ Z, int F, double* __restrict__ Hii, double* __restrict__ Hij,
+                                                            double* __restrict__ gi, double* __restrict__ gj, double* __restrict__ err)
+{
+    const int f = blockIdx.x * kThreads + threadIdx.x;
+    if (f >= F) return;
+    double Ti[12], Tj[12], z[12], e[12], hii[36], hij[36], a[6], b[6];
+    const int i = fi[f], j = fj[f];
+#pragma unroll
+    for (int k = 0; k < 12; ++k) {
+        Ti[k] = T[(size_t)i * 12 + k];
+        Tj[k] = T[(size_t)j * 12 + k];
+        z[k] = Z[(size_t)f * 12 + k];
+    }
+    mrs::pgo::factor_normal(Ti, Tj, z, e, hii, hij, a, b);
+#pragma unroll
+    for (int k = 0; k < 36; ++k) {
+        Hii[(size_t)f * 36 + k] = hii[k];
+        Hij[(size_t)f * 36 + k] = hij[k];
+    }
+#pragma unroll
+    for (int k = 0; k < 6; ++k) {
+        gi[(size_t)f * 6 + k] = a[k];
+        gj[(size_t)f * 6 + k] = b[k];
+    }
+    err[f] = mrs::pgo::factor_half_sq(e);
+}
+
+// the error alone
+__global__ __launch_bounds__(kThreads) void k_pgo_error(const double* __restrict__ T, const int* __restrict__ fi, const int* __restrict__ fj,
+                                                        const double* __restrict__ Z, int F, double* __restrict__ err)
+{
+    const int f = blockIdx.x * kThreads + threadIdx.x;
+    if (f >= F) return;
+    double Ti[12], Tj[12], z[12], e[12], RiRij[9];
+    const int i = fi[f], j = fj[f];
+#pragma unroll
+    for (int k = 0; k < 12; ++k) {
+        Ti[k] = T[(size_t)i * 12 + k];
+        Tj[k] = T[(size_t)j * 12 + k];
+        z[k] = Z[(size_t)f * 12 + k];
+    }
+    mrs::pgo::factor_error(Ti, Tj, z, RiRij, e);
+    err[f] = mrs::pgo::factor_half_sq(e);
+}
+
+// stage 1: the residual of factor (i, j) is Rij x_j - x_i per row of the rotations, so Hi^T Hj = -Rij and both diagonal blocks are I
+__global__ __launch_bounds__(kThreads) void k_pgo_linearize_rot(const double* __restrict__ Z, int F1, double* __restrict__ Hij)
+{
+    const int f = blockIdx.x * kThreads + threadIdx.x;
+    if (f >= F1) return;
+#pragma unroll
+    for (int r = 0; r < 3; ++r)
+#pragma unroll
+        for (int c = 0; c < 3; ++c) Hij[(size_t)f * 9 + 3 * r + c] = -Z[(size_t)f * 12 + 4 * r + c];
+}
+
+// stage 2: Hpp [36] and g [6] of pose p from its factors in ascending order; an entry of the CSR is factor << 1 | (1 if p is the factor's j)
+__global__ __launch_bounds__(kThreads) void k_pgo_gather(const int* __restrict__ ptr, const int* __restrict__ ent, int N, int F,
+                                                         const double* __restrict__ Hii, const double* __restrict__ gi, const double* __restrict__ gj,
+                                                         double* __restrict__ Hpp, double* __restrict__ g)
+{
+    const int p = blockIdx.x * kThreads + threadIdx.x;
+    if (p >= N) return;
+    double H[36], v[6];
+#pragma unroll
+    for (int k = 0; k < 36; ++k) H[k] = 0.0;
+#pragma unroll
+    for (int k = 0; k < 6; ++k) v[k] = 0.0;
+    const int u1 = ptr[p + 1];
+    for (int u = ptr[p]; u < u1; ++u) {
+        const int f = ent[u] >> 1;
+        if (f >= F) continue;                                    // the anchor's factor belongs to stage 1
+        if (ent[u] & 1) {
+#pragma unroll
+            for (int k = 0; k < 6; ++k) {
+                H[7 * k] += mrs::pgo::hjj_diagonal(k);
+                v[k] += gj[(size_t)f * 6 + k];
+            }
+        } else {
+#pragma unroll
+            for (int k = 0; k < 36; ++k) H[k] += Hii[(size_t)f * 36 + k];
+#pragma unroll
+            for (int k = 0; k < 6; ++k) v[k] += gi[(size_t)f * 6 + k];
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < 36; ++k) Hpp[(size_t)p * 36 + k] = H[k];
+#pragma unroll
+    for (int k = 0; k < 6; ++k) g[(size_t)p * 6 + k] = v[k];
+}
+
+// stage 1: Hpp = (number of factors) I, plus I for the anchor's own prior, whose right-hand sides are the rows of the identity
+__global__ __launch_bounds__(kThreads) void k_pgo_gather_rot(const int* __restrict__ ptr, int N, double* __restrict__ Hpp, double* __restrict__ g)
+{
+    const int p = blockIdx.x * kThreads + threadIdx.x;
+    if (p > N) return;                                           // node N is the anchor
+    const double d = (double)(ptr[p + 1] - ptr[p]) + (p == N ? 1.0 : 0.0);
+#pragma unroll
+    for (int r = 0; r < 3; ++r)
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            Hpp[(size_t)p * 9 + 3 * r + c] = r == c ? d : 0.0;
+            g[(size_t)p * 9 + 3 * r + c] = (p == N && r == c) ? 1.0 : 0.0;
+        }
+}
+
+// ------------------------------------------------------------------ segments
+
+struct SegView {
+    int n;
+    const int *first, *len, *chain, *left, *right;      // left / right: reduced index of the bounding separator, or -1
+};
+
+// the odometry factor between poses p and p + 1 of chain c is factor p - c
+template <int B, int NR>
+__global__ __launch_bounds__(64) void k_pgo_eliminate(SegView sv, const double* __restrict__ Hpp, const double* __restrict__ g,
+                                                      const double* __restrict__ Hij, double* __restrict__ Lk, double* __restrict__ Ak,
+                                                      double* __restrict__ Wk, double* __restrict__ yk, double* __restrict__ Sll,
+                                                      double* __restrict__ Srr, double* __restrict__ Srl, double* __restrict__ gl,
+                                                      double* __restrict__ gr, Status* st)
+{
+    constexpr int BB = B * B, BV = B * NR;
+    const int s = blockIdx.x * 64 + threadIdx.x;
+    if (s >= sv.n) return;
+    const int first = sv.first[s], m = sv.len[s], chain = sv.chain[s], left = sv.left[s], right = sv.right[s];
+    double Ct[BB], D[BB], W[BB], A[BB], y[BV], cD[BB], cy[BV], sll[BB], sgl[BV];
+#pragma unroll
+    for (int k = 0; k < BB; ++k) {
+        cD[k] = 0.0;
+        sll[k] = 0.0;
+        Ct[k] = 0.0;
+    }
+#pragma unroll
+    for (int k = 0; k < BV; ++k) {
+        cy[k] = 0.0;
+        sgl[k] = 0.0;
+    }
+    if (left >= 0) {                                             // H(left, first) is the block of factor first - 1 - chain: Ct is its transpose
+        const double* h = Hij + (size_t)(first - 1 - chain) * BB;
+#pragma unroll
+        for (int r = 0; r < B; ++r)
+#pragma unroll
+            for (int c = 0; c < B; ++c) Ct[r * B + c] = h[c * B + r];
+    }
+    for (int k = 0; k < m; ++k) {
+        const int p = first + k;
+#pragma unroll
+        for (int e = 0; e < BB; ++e) D[e] = Hpp[(size_t)p * BB + e] - cD[e];
+#pragma unroll
+        for (int e = 0; e < BV; ++e) y[e] = g[(size_t)p * BV + e] - cy[e];
+        if (!chol_inplace<B>(D)) atomicMax(&st->seg_fail, kBig - p);
+        const bool has_next = k + 1 < m || right >= 0;
+#pragma unroll
+        for (int e = 0; e < BB; ++e) {
+            W[e] = has_next ? Hij[(size_t)(p - chain) * BB + e] : 0.0;
+            A[e] = Ct[e];
+        }
+        lower_solve<B, B>(D, W);
+        lower_solve<B, B>(D, A);
+#pragma unroll
+        for (int q = 0; q < NR; ++q) lower_solve<B, 1>(D, y + q * B);
+#pragma unroll
+        for (int a = 0; a < B; ++a)
+#pragma unroll
+            for (int b = 0; b < B; ++b) {
+                double aa = 0.0, ww = 0.0, wa = 0.0;
+#pragma unroll
+                for (int i = 0; i < B; ++i) {
+                    aa += A[i * B + a] * A[i * B + b];
+                    ww += W[i * B + a] * W[i * B + b];
+                    wa += W[i * B + a] * A[i * B + b];
+                }
+                sll[a * B + b] += aa;
+                cD[a * B + b] = ww;
+                Ct[a * B + b] = -wa;
+            }
+#pragma unroll
+        for (int q = 0; q < NR; ++q)
+#pragma unroll
+            for (int a = 0; a < B; ++a) {
+                double ay = 0.0, wy = 0.0;
+#pragma unroll
+                for (int i = 0; i < B; ++i) {
+                    ay += A[i * B + a] * y[q * B + i];
+                    wy += W[i * B + a] * y[q * B + i];
+                }
+                sgl[q * B + a] += ay;
+                cy[q * B + a] = wy;
+            }
+#pragma unroll
+        for (int e = 0; e < BB; ++e) {
+            Lk[(size_t)p * BB + e] = D[e];
+            Ak[(size_t)p * BB + e] = A[e];
+            Wk[(size_t)p * BB + e] = W[e];
+        }
+#pragma unroll
+        for (int e = 0; e < BV; ++e) yk[(size_t)p * BV + e] = y[e];
+    }
+#pragma unroll
+    for (int e = 0; e < BB; ++e) {
+        Sll[(size_t)s * BB + e] = -sll[e];
+        Srr[(size_t)s * BB + e] = -cD[e];
+        Srl[(size_t)s * BB + e] = Ct[e];                         // rows of the right separator, columns of the left one
+    }
+#pragma unroll
+    for (int e = 0; e < BV; ++e) {
+        gl[(size_t)s * BV + e] = -sgl[e];
+        gr[(size_t)s * BV + e] = -cy[e];
+    }
+}
+
+// xr: the solved right-hand-side rows of the reduced system, row q at xr + q * ld
+template <int B, int NR>
+__global__ __launch_bounds__(64) void k_pgo_backsolve(SegView sv, const double* __restrict__ Lk, const double* __restrict__ Ak,
+                                                      const double* __restrict__ Wk, const double* __restrict__ yk, const double* __restrict__ xr,
+                                                      size_t ld, double* __restrict__ delta)
+{
+    constexpr int BB = B * B, BV = B * NR;
+    const int s = blockIdx.x * 64 + threadIdx.x;
+    if (s >= sv.n) return;
+    const int first = sv.first[s], m = sv.len[s], left = sv.left[s], right = sv.right[s];
+    double xl[BV], xn[BV], L[BB], v[B];
+#pragma unroll
+    for (int q = 0; q < NR; ++q)
+#pragma unroll
+        for (int i = 0; i < B; ++i) {
+            xl[q * B + i] = left >= 0 ? xr[q * ld + (size_t)B * left + i] : 0.0;
+            xn[q * B + i] = right >= 0 ? xr[q * ld + (size_t)B * right + i] : 0.0;
+        }
+    for (int k = m - 1; k >= 0; --k) {
+        const int p = first + k;
+#pragma unroll
+        for (int e = 0; e < BB; ++e) L[e] = Lk[(size_t)p * BB + e];
+#pragma unroll
+        for (int q = 0; q < NR; ++q) {
+#pragma unroll
+            for (int i = 0; i < B; ++i) {
+                double t = yk[(size_t)p * BV + q * B + i];
+#pragma unroll
+                for (int c = 0; c < B; ++c) t -= Ak[(size_t)p * BB + i * B + c] * xl[q * B + c];
+#pragma unroll
+                for (int c = 0; c < B; ++c) t -= Wk[(size_t)p * BB + i * B + c] * xn[q * B + c];
+                v[i] = t;
+            }
+            upper_solve<B>(L, v);
+#pragma unroll
+            for (int i = 0; i < B; ++i) {
+                xn[q * B + i] = v[i];
+                delta[(size_t)p * BV + q * B + i] = v[i];
+            }
+        }
+    }
+}
+
+template <int B, int NR>
+__global__ __launch_bounds__(kThreads) void k_pgo_scatter(const int* __restrict__ sep_node, int E, const double* __restrict__ xr, size_t ld,
+                                                          double* __restrict__ delta)
+{
+    const int t = blockIdx.x * kThreads + threadIdx.x;
+    if (t >= E * B * NR) return;
+    const int a = t / (B * NR), q = (t / B) % NR, i = t % B;
+    delta[(size_t)sep_node[a] * (B * NR) + q * B + i] = xr[q * ld + (size_t)B * a + i];
+}
+
+// ------------------------------------------------------------------ the reduced system: S [n + NR][ld], lower, the right-hand sides as rows n ..
+
+struct Parts {
+    const double *Hpp, *g, *Hij, *Sll, *Srr, *Srl, *gl, *gr;
+};
+
+// a thread per (block, entry): the block's contributions in their listed order
+template <int B>
+__global__ __launch_bounds__(kThreads) void k_pgo_assemble(const int* __restrict__ tgt_a, const int* __restrict__ tgt_b, const int* __restrict__ tgt_ptr,
+                                                           const int* __restrict__ contrib, int n_tgt, Parts P, double* __restrict__ S, size_t ld)
+{
+    constexpr int BB = B * B;
+    const int t = blockIdx.x * kThreads + threadIdx.x;
+    if (t >= n_tgt * BB) return;
+    const int blk = t / BB, e = t % BB, r = e / B, c = e % B, et = c * B + r;
+    double sum = 0.0;
+    const int u1 = tgt_ptr[blk + 1];
+    for (int u = tgt_ptr[blk]; u < u1; ++u) {
+        const int type = contrib[u] >> kTypeShift;
+        const size_t idx = (size_t)(contrib[u] & ((1 << kTypeShift) - 1)) * BB;
+        double v = 0.0;
+        if (type == kNodeDiag) v = P.Hpp[idx + e];
+        else if (type == kFactor) v = P.Hij[idx + e];
+        else if (type == kFactorT) v = P.Hij[idx + et];
+        else if (type == kSegLL) v = P.Sll[idx + e];
+        else if (type == kSegRR) v = P.Srr[idx + e];
+        else if (type == kSegRL) v = P.Srl[idx + e];
+        else if (type == kSegRLT) v = P.Srl[idx + et];
+        sum += v;
+    }
+    S[((size_t)B * tgt_a[blk] + r) * ld + (size_t)B * tgt_b[blk] + c] = sum;
+}
+
+// a thread per (separator, right-hand side, row): the first E blocks are the diagonal ones, in the separators' order
+template <int B, int NR>
+__global__ __launch_bounds__(kThreads) void k_pgo_assemble_rhs(const int* __restrict__ tgt_ptr, const int* __restrict__ contrib, int E, Parts P,
+                                                               double* __restrict__ rhs, size_t ld)
+{
+    constexpr int BV = B * NR;
+    const int t = blockIdx.x * kThreads + threadIdx.x;
+    if (t >= E * BV) return;
+    const int a = t / BV, e = t % BV, q = e / B, i = e % B;
+    double sum = 0.0;
+    const int u1 = tgt_ptr[a + 1];
+    for (int u = tgt_ptr[a]; u < u1; ++u) {
+        const int type = contrib[u] >> kTypeShift;
+        const size_t idx = (size_t)(contrib[u] & ((1 << kTypeShift) - 1)) * BV;
+        double v = 0.0;
+        if (type == kNodeDiag) v = P.g[idx + e];
+        else if (type == kSegLL) v = P.gl[idx + e];
+        else if (type == kSegRR) v = P.gr[idx + e];
+        sum += v;
+    }
+    rhs[q * ld + (size_t)B * a + i] = sum;
+}
+
+// One panel: the Cholesky of the diagonal block [k0, k0 + nb) in LDS, then every row below it (the right-hand-side rows included) times the
+// inverse transpose of that factor.  One workgroup.
+__global__ __launch_bounds__(kThreads) void k_pgo_chol_panel(double* __restrict__ S, int n, int nt, size_t ld, int k0, Status* st)
+{
+    __shared__ double Ls[kNB][kNB + 1];
+    const int tid = threadIdx.x, nb = min(kNB, n - k0);
+    for (int e = tid; e < nb * nb; e += kThreads) {
+        const int r = e / nb, c = e % nb;
+        Ls[r][c] = c <= r ? S[(size_t)(k0 + r) * ld + k0 + c] : 0.0;
+    }
+    __syncthreads();
+    for (int j = 0; j < nb; ++j) {
+        if (tid == 0) {
+            double d = Ls[j][j];
+            if (!(d > 0.0) || !isfinite(d)) {
+                atomicMax(&st->dense_fail, kBig - (k0 + j));
+                d = 1.0;
+            }
+            Ls[j][j] = sqrt(d);
+        }
+        __syncthreads();
+        if (tid > j && tid < nb) Ls[tid][j] /= Ls[j][j];
+        __syncthreads();
+        for (int e = tid; e < nb * nb; e += kThreads) {
+            const int r = e / nb, c = e % nb;
+            if (c > j && c <= r) Ls[r][c] -= Ls[r][j] * Ls[c][j];
+        }
+        __syncthreads();
+    }
+    for (int e = tid; e < nb * nb; e += kThreads) {
+        const int r = e / nb, c = e % nb;
+        if (c <= r) S[(size_t)(k0 + r) * ld + k0 + c] = Ls[r][c];
+    }
+    for (int r = k0 + nb + tid; r < nt; r += kThreads) {
+        double x[kNB];
+        double* row = S + (size_t)r * ld + k0;
+#pragma unroll
+        for (int c = 0; c < kNB; ++c) {
+            if (c < nb) {
+                double s = row[c];
+#pragma unroll
+                for (int d = 0; d < c; ++d) s -= x[d] * Ls[c][d];
+                x[c] = s / Ls[c][c];
+            } else {
+                x[c] = 0.0;
+            }
+        }
+#pragma unroll
+        for (int c = 0; c < kNB; ++c)
+            if (c < nb) row[c] = x[c];
+    }
+}
+
+// the trailing update of one panel: S[i][j] -= sum_c S[i][k0 + c] S[j][k0 + c] for k0 + nb <= j <= i, j < n, i < nt; a workgroup per tile of
+// the lower triangle
+__global__ __launch_bounds__(kThreads) void k_pgo_chol_trail(double* __restrict__ S, int n, int nt, size_t ld, int k0, int nb)
+{
+    __shared__ double Lr[kTile][kNB + 1], Lc[kTile][kNB + 1];
+    if (blockIdx.x > blockIdx.y) return;
+    const int k1 = k0 + nb, i0 = k1 + blockIdx.y * kTile, j0 = k1 + blockIdx.x * kTile, tid = threadIdx.x;
+    if (j0 >= n || i0 >= nt) return;
+    for (int e = tid; e < kTile * kNB; e += kThreads) {
+        const int r = e / kNB, c = e % kNB;
+        Lr[r][c] = (i0 + r < nt && c < nb) ? S[(size_t)(i0 + r) * ld + k0 + c] : 0.0;
+        Lc[r][c] = (j0 + r < n && c < nb) ? S[(size_t)(j0 + r) * ld + k0 + c] : 0.0;
+    }
+    __syncthreads();
+    const int tx = tid % kTile, j = j0 + tx;
+    for (int rr = tid / kTile; rr < kTile; rr += kThreads / kTile) {
+        const int i = i0 + rr;
+        if (i < nt && j < n && j <= i) {
+            double s = 0.0;
+#pragma unroll
+            for (int c = 0; c < kNB; ++c) s += Lr[rr][c] * Lc[tx][c];
+            S[(size_t)i * ld + j] -= s;
+        }
+    }
+}
+
+// L^T x = y on the nr right-hand-side rows, in place, panel after panel from the last; one workgroup
+__global__ __launch_bounds__(kThreads) void k_pgo_chol_back(double* __restrict__ S, int n, size_t ld, int nr)
+{
+    __shared__ double Ls[kNB][kNB + 1];
+    __shared__ double xs[3][kNB];
+    const int tid = threadIdx.x;
+    double* rhs = S + (size_t)n * ld;
+    for (int blk = (n + kNB - 1) / kNB - 1; blk >= 0; --blk) {
+        const int c0 = blk * kNB, nb = min(kNB, n - c0);
+        for (int e = tid; e < nb * nb; e += kThreads) {
+            const int r = e / nb, c = e % nb;
+            Ls[r][c] = c <= r ? S[(size_t)(c0 + r) * ld + c0 + c] : 0.0;
+        }
+        __syncthreads();
+        if (tid < nr) {
+            for (int c = nb - 1; c >= 0; --c) {
+                double s = rhs[(size_t)tid * ld + c0 + c];
+                for (int d = c + 1; d < nb; ++d) s -= Ls[d][c] * xs[tid][d];
+                s /= Ls[c][c];
+                xs[tid][c] = s;
+                rhs[(size_t)tid * ld + c0 + c] = s;
+            }
+        }
+        __syncthreads();
+        for (int r = tid; r < c0; r += kThreads)
+            for (int q = 0; q < nr; ++q) {
+                double s = rhs[(size_t)q * ld + r];
+                for (int c = 0; c < nb; ++c) s -= S[(size_t)(c0 + c) * ld + r] * xs[q][c];
+                rhs[(size_t)q * ld + r] = s;
+            }
+        __syncthreads();
+    }
+}
+
+// ------------------------------------------------------------------ per pose
+
+__global__ __launch_bounds__(kThreads) void k_pgo_retract(double* __restrict__ T, const double* __restrict__ delta, int N, Status* st)
+{
+    const int p = blockIdx.x * kThreads + threadIdx.x;
+    if (p >= N) return;
+    double t[12], d[6], m = 0.0;
+#pragma unroll
+    for (int k = 0; k < 12; ++k) t[k] = T[(size_t)p * 12 + k];
+#pragma unroll
+    for (int k = 0; k < 6; ++k) {
+        d[k] = delta[(size_t)p * 6 + k];
+        const double a = fabs(d[k]);
+        m = (a > m || a != a) ? a : m;                            // a NaN stays: its bits are above every finite value's
+    }
+    mrs::pgo::retract(t, d, t);
+#pragma unroll
+    for (int k = 0; k < 12; ++k) T[(size_t)p * 12 + k] = t[k];
+    atomicMax(&st->max_delta, (u64)__double_as_longlong(m));      // m >= 0 or NaN with a clear sign: the order of the bits is the order of the values
+}
+
+// stage 1: T [p] = [closest rotation of the solved 3x3 | 0]
+__global__ __launch_bounds__(kThreads) void k_pgo_project(const double* __restrict__ X, int N, double* __restrict__ T)
+{
+    const int p = blockIdx.x * kThreads + threadIdx.x;
+    if (p >= N) return;
+    double x[9], R[9];
+#pragma unroll
+    for (int k = 0; k < 9; ++k) x[k] = X[(size_t)p * 9 + k];
+    mrs::pgo::closest_rotation(x, R);
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+        T[(size_t)p * 12 + 4 * r] = R[3 * r];
+        T[(size_t)p * 12 + 4 * r + 1] = R[3 * r + 1];
+        T[(size_t)p * 12 + 4 * r + 2] = R[3 * r + 2];
+        T[(size_t)p * 12 + 4 * r + 3] = 0.0;
+    }
+}
+
+// ------------------------------------------------------------------ the error sum: a fixed two-level tree
+
+__device__ __forceinline__ double block_tree_sum(double v, double* sh)
+{
+    sh[threadIdx.x] = v;
+    __syncthreads();
+    for (int o = kThreads / 2; o > 0; o >>= 1) {
+        if ((int)threadIdx.x < o) sh[threadIdx.x] += sh[threadIdx.x + o];
+        __syncthreads();
+    }
+    return sh[0];
+}
+
+__global__ __launch_bounds__(kThreads) void k_pgo_sum1(const double* __restrict__ v, int n, double* __restrict__ partial)
+{
+    __shared__ double sh[kThreads];
+    const int i = blockIdx.x * kThreads + threadIdx.x;
+    const double s = block_tree_sum(i < n ? v[i] : 0.0, sh);
+    if (threadIdx.x == 0) partial[blockIdx.x] = s;
+}
+
+__global__ __launch_bounds__(kThreads) void k_pgo_sum2(const double* __restrict__ partial, int n, double* __restrict__ out)
+{
+    __shared__ double sh[kThreads];
+    double s = 0.0;
+    for (int i = threadIdx.x; i < n; i += kThreads) s += partial[i];
+    s = block_tree_sum(s, sh);
+    if (threadIdx.x == 0) *out = s;
+}
+
+// ------------------------------------------------------------------ host: the topology of one stage
+
+struct Topology {
+    int n_nodes = 0, E = 0;
+    std::vector<int> sep_node;                                   // [E] ascending; the anchor, where there is one, is last
+    std::vector<int> seg_first, seg_len, seg_chain, seg_left, seg_right;
+    std::vector<int> tgt_a, tgt_b, tgt_ptr, contrib;             // the first E blocks are the diagonal ones
+};
+
+struct Graph {
+    int nr = 0, N = 0;
+    std::vector<int> start;                                      // [nr + 1]
+    std::vector<int> li, lj;                                     // the loops
+};
+
+// is_sep [N] for the loops given: the touched poses (pose 0 too) and the cuts.  Pose 0 ends a run in both stages, so both have the same cuts.
+void mark_separators(const Graph& g, int seglen, std::vector<char>* is_sep)
+{
+    is_sep->assign(g.N, 0);
+    for (size_t u = 0; u < g.li.size(); ++u) (*is_sep)[g.li[u]] = (*is_sep)[g.lj[u]] = 1;
+    (*is_sep)[0] = 1;
+    for (int c = 0; c < g.nr; ++c) {
+        int run = 0;
+        for (int p = g.start[c]; p < g.start[c + 1]; ++p) {
+            if ((*is_sep)[p]) {
+                run = 0;
+            } else if (seglen > 0 && run == seglen) {
+                (*is_sep)[p] = 1;
+                run = 0;
+            } else {
+                ++run;
+            }
+        }
+    }
+}
+
+// the separators of stage 2: pose 0 is held and does not count
+int count_separators(const Graph& g, int seglen)
+{
+    std::vector<char> is_sep;
+    mark_separators(g, seglen, &is_sep);
+    return (int)std::count(is_sep.begin(), is_sep.end(), 1) - 1;
+}
+
+// stage 1: the nodes are the poses and the anchor (node N), factor F is anchor -> pose 0; stage 2: pose 0 is held and drops out
+void build_topology(const Graph& g, int seglen, int stage, Topology* t)
+{
+    const int N = g.N, F = N - g.nr + (int)g.li.size();
+    std::vector<char> is_sep;
+    mark_separators(g, seglen, &is_sep);
+    const bool rot = stage == 1;
+    *t = Topology();
+    t->n_nodes = rot ? N + 1 : N;
+    std::vector<int> sep_of(N + 1, -1);
+    for (int p = rot ? 0 : 1; p < N; ++p)
+        if (is_sep[p]) {
+            sep_of[p] = (int)t->sep_node.size();
+            t->sep_node.push_back(p);
+        }
+    if (rot) {
+        sep_of[N] = (int)t->sep_node.size();
+        t->sep_node.push_back(N);
+    }
+    const int E = t->E = (int)t->sep_node.size();
+    for (int c = 0; c < g.nr; ++c) {
+        int p = g.start[c];
+        const int end = g.start[c + 1];
+        while (p < end) {
+            if (is_sep[p]) {
+                ++p;
+                continue;
+            }
+            int q = p;
+            while (q < end && !is_sep[q]) ++q;
+            t->seg_first.push_back(p);
+            t->seg_len.push_back(q - p);
+            t->seg_chain.push_back(c);
+            t->seg_left.push_back(p > g.start[c] ? sep_of[p - 1] : -1);       // -1 too when the pose before is the held pose 0
+            t->seg_right.push_back(q < end ? sep_of[q] : -1);
+            p = q;
+        }
+    }
+    std::vector<std::vector<int>> diag(E);
+    std::map<std::pair<int, int>, std::vector<int>> off;
+    for (int a = 0; a < E; ++a) diag[a].push_back(kNodeDiag << kTypeShift | t->sep_node[a]);
+    const auto factor = [&](int f, int i, int j) {
+        const int a = sep_of[i], b = sep_of[j];
+        if (a < 0 || b < 0) return;
+        if (a > b) off[{a, b}].push_back(kFactor << kTypeShift | f);
+        else off[{b, a}].push_back(kFactorT << kTypeShift | f);
+    };
+    for (int c = 0; c < g.nr; ++c)
+        for (int p = g.start[c]; p + 1 < g.start[c + 1]; ++p) factor(p - c, p, p + 1);
+    for (size_t u = 0; u < g.li.size(); ++u) factor(N - g.nr + (int)u, g.li[u], g.lj[u]);
+    if (rot) factor(F, N, 0);
+    for (size_t s = 0; s < t->seg_first.size(); ++s) {
+        const int l = t->seg_left[s], r = t->seg_right[s];
+        if (l >= 0) diag[l].push_back(kSegLL << kTypeShift | (int)s);
+        if (r >= 0) diag[r].push_back(kSegRR << kTypeShift | (int)s);
+        if (l >= 0 && r >= 0) {
+            if (r > l) off[{r, l}].push_back(kSegRL << kTypeShift | (int)s);
+            else off[{l, r}].push_back(kSegRLT << kTypeShift | (int)s);
+        }
+    }
+    t->tgt_ptr.push_back(0);
+    for (int a = 0; a < E; ++a) {
+        t->tgt_a.push_back(a);
+        t->tgt_b.push_back(a);
+        t->contrib.insert(t->contrib.end(), diag[a].begin(), diag[a].end());
+        t->tgt_ptr.push_back((int)t->contrib.size());
+    }
+    for (const auto& kv : off) {
+        t->tgt_a.push_back(kv.first.first);
+        t->tgt_b.push_back(kv.first.second);
+        t->contrib.insert(t->contrib.end(), kv.second.begin(), kv.second.end());
+        t->tgt_ptr.push_back((int)t->contrib.size());
+    }
+}
+
+// one stage's topology on the device: a single int buffer
+struct DeviceTopology {
+    mrs::DeviceBuffer<int> ints;
+    int E = 0, n_tgt = 0;
+    SegView sv = {};
+    const int *sep_node = nullptr, *tgt_a = nullptr, *tgt_b = nullptr, *tgt_ptr = nullptr, *contrib = nullptr;
+
+    int upload(const Topology& t)
+    {
+        std::vector<int> h;
+        const auto put = [&](const std::vector<int>& v) {
+            const size_t at = h.size();
+            h.insert(h.end(), v.begin(), v.end());
+            return at;
+        };
+        const size_t o_sep = put(t.sep_node), o_f = put(t.seg_first), o_l = put(t.seg_len), o_c = put(t.seg_chain), o_sl = put(t.seg_left),
+                     o_sr = put(t.seg_right), o_a = put(t.tgt_a), o_b = put(t.tgt_b), o_p = put(t.tgt_ptr), o_k = put(t.contrib);
+        h.push_back(0);                                           // never empty
+        MRS_TRY(ints.reserve(h.size(), h.size() + h.size() / 4));
+        MRS_HIP_TRY(hipMemcpy(ints.get(), h.data(), h.size() * sizeof(int), hipMemcpyHostToDevice));
+        const int* d = ints.get();
+        E = t.E;
+        n_tgt = (int)t.tgt_a.size();
+        sv = SegView{(int)t.seg_first.size(), d + o_f, d + o_l, d + o_c, d + o_sl, d + o_sr};
+        sep_node = d + o_sep; tgt_a = d + o_a; tgt_b = d + o_b; tgt_ptr = d + o_p; contrib = d + o_k;
+        return MRS_OK;
+    }
+};
+
+bool finite16(const double* m)
+{
+    for (int k = 0; k < 16; ++k)
+        if (!std::isfinite(m[k])) return false;
+    return true;
+}
+
+}  // namespace
+
+struct mrs_pgo {
+    mrs_ctx* ctx = nullptr;
+    Graph g;
+    int seglen = MRS_PGO_DEFAULT_SEGMENT_LENGTH;
+    bool odometry_set = false;
+    std::vector<double> odom, loopZ;                             // [.][16] as given
+    double prior[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
+    bool dirty = true;                                           // the device copy of the graph and of the topologies is behind
+    bool init_valid = false;                                     // T0 holds stage 1 of the current graph
+    Topology topo[2];                                            // stage 1, stage 2
+    DeviceTopology dtopo[2];
+    int F = 0;                                                   // factors without the anchor's
+    mrs::DeviceBuffer<int> fints;                                // fi [F + 1] | fj [F + 1] | csr ptr [N + 2] | csr entries [2 (F + 1)]
+    mrs::DeviceBuffer<double> Z, T0, T, delta, Hii, Hij, gi, gj, err, partial, Hpp, gp, Lk, Ak, Wk, yk, seg, S;
+    mrs::DeviceBuffer<Status> status;
+    mrs::DeviceBuffer<double> err_out;
+    float stage_ms[6] = {0, 0, 0, 0, 0, 0};
+};
+
+namespace {
+
+int pgo_chain_of(const Graph& g, int p) { return (int)(std::upper_bound(g.start.begin(), g.start.end(), p) - g.start.begin()) - 1; }
+
+bool pgo_connected(const Graph& g)
+{
+    std::vector<int> root(g.nr);
+    for (int c = 0; c < g.nr; ++c) root[c] = c;
+    const auto find = [&](int c) {
+        while (root[c] != c) c = root[c] = root[root[c]];
+        return c;
+    };
+    for (size_t u = 0; u < g.li.size(); ++u) {
+        const int a = find(pgo_chain_of(g, g.li[u])), b = find(pgo_chain_of(g, g.lj[u]));
+        if (a != b) root[std::max(a, b)] = std::min(a, b);
+    }
+    for (int c = 0; c < g.nr; ++c)
+        if (find(c) != 0) return false;
+    return true;
+}
+
+// the graph, both topologies and the workspace they need, on the device
+int pgo_sync(mrs_pgo* h)
+{
+    if (!h->dirty) return MRS_OK;
+    const Graph& g = h->g;
+    const int N = g.N, L = (int)g.li.size(), F = N - g.nr + L, F1 = F + 1;
+    h->F = F;
+    h->init_valid = false;
+    build_topology(g, h->seglen, 1, &h->topo[0]);
+    build_topology(g, h->seglen, 2, &h->topo[1]);
+    MRS_TRY(h->dtopo[0].upload(h->topo[0]));
+    MRS_TRY(h->dtopo[1].upload(h->topo[1]));
+    // factors and the CSR of factors per node, ascending (the anchor's factor F is the last of pose 0 and the only one of node N)
+    std::vector<int> ints((size_t)2 * F1 + (N + 2) + 2 * (size_t)F1);
+    int *fi = ints.data(), *fj = fi + F1, *ptr = fj + F1, *ent = ptr + N + 2;
+    std::vector<double> Z((size_t)F1 * 12);
+    int f = 0;
+    for (int c = 0; c < g.nr; ++c)
+        for (int p = g.start[c]; p + 1 < g.start[c + 1]; ++p, ++f) {
+            fi[f] = p;
+            fj[f] = p + 1;
+            std::copy(h->odom.begin() + (size_t)f * 16, h->odom.begin() + (size_t)f * 16 + 12, Z.begin() + (size_t)f * 12);
+        }
+    for (int u = 0; u < L; ++u, ++f) {
+        fi[f] = g.li[u];
+        fj[f] = g.lj[u];
+        std::copy(h->loopZ.begin() + (size_t)u * 16, h->loopZ.begin() + (size_t)u * 16 + 12, Z.begin() + (size_t)f * 12);
+    }
+    fi[F] = N;
+    fj[F] = 0;
+    std::copy(h->prior, h->prior + 12, Z.begin() + (size_t)F * 12);
+    std::vector<int> deg(N + 2, 0);
+    for (int k = 0; k < F1; ++k) {
+        ++deg[fi[k] + 1];
+        ++deg[fj[k] + 1];
+    }
+    ptr[0] = 0;
+    for (int p = 0; p <= N; ++p) ptr[p + 1] = ptr[p] + deg[p + 1];
+    std::vector<int> fill(ptr, ptr + N + 1);
+    for (int k = 0; k < F1; ++k) {
+        ent[fill[fi[k]]++] = k << 1;
+        ent[fill[fj[k]]++] = k << 1 | 1;
+    }
+    MRS_TRY(h->fints.reserve(ints.size(), ints.size() + ints.size() / 4));
+    MRS_HIP_TRY(hipMemcpy(h->fints.get(), ints.data(), ints.size() * sizeof(int), hipMemcpyHostToDevice));
+    const auto grow = [](mrs::DeviceBuffer<double>& b, size_t need) { return b.reserve(std::max<size_t>(need, 1), std::max<size_t>(need + need / 4, 16)); };
+    MRS_TRY(grow(h->Z, Z.size()));
+    MRS_HIP_TRY(hipMemcpy(h->Z.get(), Z.data(), Z.size() * sizeof(double), hipMemcpyHostToDevice));
+    const size_t nodes = (size_t)N + 1, nseg = std::max(h->topo[0].seg_first.size(), h->topo[1].seg_first.size());
+    const size_t n1 = 3 * (size_t)h->topo[0].E, n2 = 6 * (size_t)h->topo[1].E;
+    MRS_TRY(grow(h->T0, nodes * 12));
+    MRS_TRY(grow(h->T, nodes * 12));
+    MRS_TRY(grow(h->delta, nodes * 9));
+    MRS_TRY(grow(h->Hii, (size_t)F1 * 36));
+    MRS_TRY(grow(h->Hij, (size_t)F1 * 36));
+    MRS_TRY(grow(h->gi, (size_t)F1 * 6));
+    MRS_TRY(grow(h->gj, (size_t)F1 * 6));
+    MRS_TRY(grow(h->err, (size_t)F1));
+    MRS_TRY(grow(h->partial, (size_t)blocks_for(F1, kThreads)));
+    MRS_TRY(grow(h->Hpp, nodes * 36));
+    MRS_TRY(grow(h->gp, nodes * 9));
+    MRS_TRY(grow(h->Lk, nodes * 36));
+    MRS_TRY(grow(h->Ak, nodes * 36));
+    MRS_TRY(grow(h->Wk, nodes * 36));
+    MRS_TRY(grow(h->yk, nodes * 9));
+    MRS_TRY(grow(h->seg, nseg * (3 * 36 + 2 * 9)));
+    MRS_TRY(grow(h->S, std::max((n1 + 3) * n1, (n2 + 1) * n2)));
+    MRS_TRY(h->status.reserve(1, 1));
+    MRS_TRY(h->err_out.reserve(1, 1));
+    h->dirty = false;
+    return MRS_OK;
+}
+
+// One solve of the assembled per-node system (Hpp, gp, Hij) of a stage -> delta [n_nodes][NR][B]; entries of held nodes are zero.
+// `marks` (optional) gets marks base .. base + 3: after the walk, the assembly, the dense solve and the way back.
+template <int B, int NR>
+int pgo_solve(mrs_pgo* h, int stage, mrs::StageMarks* marks, int base)
+{
+    constexpr int BB = B * B, BV = B * NR;
+    const DeviceTopology& t = h->dtopo[stage - 1];
+    const int nodes = h->topo[stage - 1].n_nodes, E = t.E, n = B * E, nt = n + NR;
+    const size_t ld = (size_t)n, nseg = (size_t)t.sv.n;
+    double* seg = h->seg.get();
+    double *Sll = seg, *Srr = Sll + nseg * BB, *Srl = Srr + nseg * BB, *gl = Srl + nseg * BB, *gr = gl + nseg * BV;
+    double* S = h->S.get();
+    Status* st = h->status.get();
+    MRS_HIP_TRY(hipMemsetAsync(h->delta.get(), 0, (size_t)nodes * BV * sizeof(double), nullptr));
+    if (nseg)
+        hipLaunchKernelGGL((k_pgo_eliminate<B, NR>), dim3(blocks_for((long long)nseg, 64)), dim3(64), 0, nullptr, t.sv, h->Hpp.get(), h->gp.get(),
+                           h->Hij.get(), h->Lk.get(), h->Ak.get(), h->Wk.get(), h->yk.get(), Sll, Srr, Srl, gl, gr, st);
+    if (marks) marks->mark(base);
+    if (E) {
+        const Parts P = {h->Hpp.get(), h->gp.get(), h->Hij.get(), Sll, Srr, Srl, gl, gr};
+        MRS_HIP_TRY(hipMemsetAsync(S, 0, (size_t)nt * ld * sizeof(double), nullptr));
+        hipLaunchKernelGGL((k_pgo_assemble<B>), dim3(blocks_for((long long)t.n_tgt * BB, kThreads)), dim3(kThreads), 0, nullptr, t.tgt_a, t.tgt_b,
+                           t.tgt_ptr, t.contrib, t.n_tgt, P, S, ld);
+        hipLaunchKernelGGL((k_pgo_assemble_rhs<B, NR>), dim3(blocks_for((long long)E * BV, kThreads)), dim3(kThreads), 0, nullptr, t.tgt_ptr, t.contrib,
+                           E, P, S + (size_t)n * ld, ld);
+        if (marks) marks->mark(base + 1);
+        for (int k0 = 0; k0 < n; k0 += kNB) {
+            const int nb = std::min(kNB, n - k0), k1 = k0 + nb;
+            hipLaunchKernelGGL(k_pgo_chol_panel, dim3(1), dim3(kThreads), 0, nullptr, S, n, nt, ld, k0, st);
+            if (k1 < n) {
+                const unsigned tiles = blocks_for(nt - k1, kTile);
+                hipLaunchKernelGGL(k_pgo_chol_trail, dim3(tiles, tiles), dim3(kThreads), 0, nullptr, S, n, nt, ld, k0, nb);
+            }
+        }
+        hipLaunchKernelGGL(k_pgo_chol_back, dim3(1), dim3(kThreads), 0, nullptr, S, n, ld, NR);
+        if (marks) marks->mark(base + 2);
+        hipLaunchKernelGGL((k_pgo_scatter<B, NR>), dim3(blocks_for((long long)E * BV, kThreads)), dim3(kThreads), 0, nullptr, t.sep_node, E,
+                           S + (size_t)n * ld, ld, h->delta.get());
+    } else if (marks) {
+        marks->mark(base + 1);
+        marks->mark(base + 2);
+    }
+    if (nseg)
+        hipLaunchKernelGGL((k_pgo_backsolve<B, NR>), dim3(blocks_for((long long)nseg, 64)), dim3(64), 0, nullptr, t.sv, h->Lk.get(), h->Ak.get(),
+                           h->Wk.get(), h->yk.get(), S + (size_t)n * ld, ld, h->delta.get());
+    if (marks) marks->mark(base + 3);
+    MRS_HIP_TRY(hipGetLastError());
+    return MRS_OK;
+}
+
+// the status words of the solves since the last reset -> MRS_OK, or MRS_ERR_NOT_CONVERGED with the pose named
+int pgo_check_pivots(const mrs_pgo* h, const Status& st, int stage)
+{
+    if (st.seg_fail) {
+        mrs::set_error("stage %d: the pivot block of pose %d is not positive definite", stage, kBig - st.seg_fail);
+        return MRS_ERR_NOT_CONVERGED;
+    }
+    if (st.dense_fail) {
+        const Topology& t = h->topo[stage - 1];
+        const int row = kBig - st.dense_fail, a = row / (stage == 1 ? 3 : 6);
+        const int pose = a >= 0 && a < t.E ? t.sep_node[a] : -1;
+        if (stage == 1 && pose == h->g.N) mrs::set_error("stage 1: the pivot block of the anchor is not positive definite (row %d)", row);
+        else mrs::set_error("stage %d: the pivot block of pose %d is not positive definite (row %d of the reduced system)", stage, pose, row);
+        return MRS_ERR_NOT_CONVERGED;
+    }
+    return MRS_OK;
+}
+
+int pgo_ready(mrs_pgo* h)
+{
+    MRS_REQUIRE(h->odometry_set || h->g.N == h->g.nr, "set the odometry first");
+    if (!pgo_connected(h->g)) {
+        mrs::set_error("bad argument: a chain is not connected to chain 0 through loop factors");
+        return MRS_ERR_ARG;
+    }
+    MRS_HIP_TRY(hipSetDevice(h->ctx->device));
+    return pgo_sync(h);
+}
+
+// stage 1 into T0, unless it is there already
+int pgo_stage1(mrs_pgo* h)
+{
+    if (h->init_valid) return MRS_OK;
+    const int N = h->g.N, F1 = h->F + 1;
+    const int* ptr = h->fints.get() + 2 * (size_t)F1;
+    MRS_HIP_TRY(hipMemsetAsync(h->status.get(), 0, sizeof(Status), nullptr));
+    hipLaunchKernelGGL(k_pgo_linearize_rot, dim3(blocks_for(F1, kThreads)), dim3(kThreads), 0, nullptr, h->Z.get(), F1, h->Hij.get());
+    hipLaunchKernelGGL(k_pgo_gather_rot, dim3(blocks_for(N + 1, kThreads)), dim3(kThreads), 0, nullptr, ptr, N, h->Hpp.get(), h->gp.get());
+    MRS_TRY((pgo_solve<3, 3>(h, 1, nullptr, 0)));
+    hipLaunchKernelGGL(k_pgo_project, dim3(blocks_for(N, kThreads)), dim3(kThreads), 0, nullptr, h->delta.get(), N, h->T0.get());
+    MRS_HIP_TRY(hipGetLastError());
+    Status st;
+    MRS_HIP_TRY(hipMemcpy(&st, h->status.get(), sizeof(st), hipMemcpyDeviceToHost));
+    MRS_TRY(pgo_check_pivots(h, st, 1));
+    h->init_valid = true;
+    return MRS_OK;
+}
+
+int pgo_error_sum(mrs_pgo* h, double* out)
+{
+    const int F = h->F;
+    *out = 0.0;
+    if (F == 0) return MRS_OK;
+    const int nb = (int)blocks_for(F, kThreads);
+    hipLaunchKernelGGL(k_pgo_sum1, dim3(nb), dim3(kThreads), 0, nullptr, h->err.get(), F, h->partial.get());
+    hipLaunchKernelGGL(k_pgo_sum2, dim3(1), dim3(kThreads), 0, nullptr, h->partial.get(), nb, h->err_out.get());
+    MRS_HIP_TRY(hipGetLastError());
+    MRS_HIP_TRY(hipMemcpy(out, h->err_out.get(), sizeof(double), hipMemcpyDeviceToHost));
+    return MRS_OK;
+}
+
+// T [N][12] on the device -> h_T [N][16]
+int pgo_download(const double* d_T, int N, double* h_T)
+{
+    std::vector<double> t((size_t)N * 12);
+    MRS_HIP_TRY(hipMemcpy(t.data(), d_T, t.size() * sizeof(double), hipMemcpyDeviceToHost));
+    for (int p = 0; p < N; ++p) {
+        std::copy(t.begin() + (size_t)p * 12, t.begin() + (size_t)p * 12 + 12, h_T + (size_t)p * 16);
+        h_T[(size_t)p * 16 + 12] = h_T[(size_t)p * 16 + 13] = h_T[(size_t)p * 16 + 14] = 0.0;
+        h_T[(size_t)p * 16 + 15] = 1.0;
+    }
+    return MRS_OK;
+}
+
+// validates on a copy: the handle changes only when everything holds
+int pgo_check_separators(const Graph& g, int seglen)
+{
+    const int E = count_separators(g, seglen);
+    if (E > kMaxSep) {
+        mrs::set_error("%d separators (poses touched by loops and cut poses) exceed the %d the reduced system holds", E, kMaxSep);
+        return MRS_ERR_UNSUPPORTED;
+    }
+    return MRS_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int mrs_pgo_create(mrs_ctx* ctx, int32_t nr, const int32_t* h_chain_lengths, mrs_pgo** out)
+{
+    MRS_REQUIRE(ctx && out && h_chain_lengths, "null pointer");
+    MRS_REQUIRE(nr >= 1 && nr <= kMaxChains, "1 .. MRS_PGO_MAX_CHAINS chains");
+    long long total = 0;
+    for (int c = 0; c < nr; ++c) {
+        MRS_REQUIRE(h_chain_lengths[c] >= 1, "a chain has at least one pose");
+        total += h_chain_lengths[c];
+    }
+    if (total > kMaxPoses) {
+        mrs::set_error("%lld poses exceed the %d a pose graph holds", total, kMaxPoses);
+        return MRS_ERR_UNSUPPORTED;
+    }
+    Graph g;
+    g.nr = nr;
+    g.N = (int)total;
+    g.start.assign(1, 0);
+    for (int c = 0; c < nr; ++c) g.start.push_back(g.start.back() + h_chain_lengths[c]);
+    int seglen = MRS_PGO_DEFAULT_SEGMENT_LENGTH;
+    while (count_separators(g, seglen) > kMaxSep) seglen *= 2;    // 65 536 poses at most: ends at 64 or 128
+    MRS_HIP_TRY(hipSetDevice(ctx->device));
+    mrs_pgo* h = new mrs_pgo;
+    h->ctx = ctx;
+    h->g = g;
+    h->seglen = seglen;
+    *out = h;
+    return MRS_OK;
+}
+
+int mrs_pgo_destroy(mrs_pgo* pgo)
+{
+    if (!pgo) return MRS_OK;
+    (void)hipSetDevice(pgo->ctx->device);
+    (void)hipStreamSynchronize(nullptr);
+    delete pgo;
+    return MRS_OK;
+}
+
+int mrs_pgo_set_odometry(mrs_pgo* pgo, const double* h_Z, int32_t n)
+{
+    MRS_REQUIRE(pgo, "null pointer");
+    MRS_REQUIRE(n == pgo->g.N - pgo->g.nr, "one odometry factor per consecutive pair of a chain");
+    MRS_REQUIRE(h_Z || n == 0, "null pointer");
+    for (int k = 0; k < n; ++k) MRS_REQUIRE(finite16(h_Z + (size_t)k * 16), "an odometry pose is not finite");
+    pgo->odom.assign(h_Z, h_Z + (size_t)n * 16);
+    pgo->odometry_set = true;
+    pgo->dirty = true;
+    return MRS_OK;
+}
+
+int mrs_pgo_add_loops(mrs_pgo* pgo, const int32_t* h_i, const int32_t* h_j, const double* h_Z, int32_t n)
+{
+    MRS_REQUIRE(pgo, "null pointer");
+    MRS_REQUIRE(n >= 0, "n must not be negative");
+    if (n == 0) return MRS_OK;
+    MRS_REQUIRE(h_i && h_j && h_Z, "null pointer");
+    for (int u = 0; u < n; ++u) {
+        MRS_REQUIRE(h_i[u] >= 0 && h_i[u] < pgo->g.N && h_j[u] >= 0 && h_j[u] < pgo->g.N, "a loop names a pose outside the graph");
+        MRS_REQUIRE(h_i[u] != h_j[u], "a loop joins a pose with itself");
+        MRS_REQUIRE(finite16(h_Z + (size_t)u * 16), "a loop pose is not finite");
+    }
+    if ((long long)pgo->g.li.size() + n > kMaxLoops) {
+        mrs::set_error("%zu loops held and %d more exceed the %d a pose graph holds", pgo->g.li.size(), n, kMaxLoops);
+        return MRS_ERR_UNSUPPORTED;
+    }
+    Graph g = pgo->g;
+    g.li.insert(g.li.end(), h_i, h_i + n);
+    g.lj.insert(g.lj.end(), h_j, h_j + n);
+    MRS_TRY(pgo_check_separators(g, pgo->seglen));
+    pgo->g = std::move(g);
+    pgo->loopZ.insert(pgo->loopZ.end(), h_Z, h_Z + (size_t)n * 16);
+    pgo->dirty = true;
+    return MRS_OK;
+}
+
+int mrs_pgo_clear_loops(mrs_pgo* pgo)
+{
+    MRS_REQUIRE(pgo, "null pointer");
+    pgo->g.li.clear();
+    pgo->g.lj.clear();
+    pgo->loopZ.clear();
+    pgo->dirty = true;
+    return MRS_OK;
+}
+
+int mrs_pgo_count(mrs_pgo* pgo, int32_t* h_count)
+{
+    MRS_REQUIRE(pgo && h_count, "null pointer");
+    *h_count = (int32_t)pgo->g.li.size();
+    return MRS_OK;
+}
+
+int mrs_pgo_set_prior(mrs_pgo* pgo, const double* h_T)
+{
+    MRS_REQUIRE(pgo && h_T, "null pointer");
+    MRS_REQUIRE(finite16(h_T), "the prior is not finite");
+    std::copy(h_T, h_T + 16, pgo->prior);
+    pgo->dirty = true;
+    return MRS_OK;
+}
+
+int mrs_pgo_set_segment_length(mrs_pgo* pgo, int32_t length)
+{
+    MRS_REQUIRE(pgo, "null pointer");
+    MRS_REQUIRE(length >= 0, "the segment length must not be negative");
+    if (length == pgo->seglen) return MRS_OK;
+    MRS_TRY(pgo_check_separators(pgo->g, length));
+    pgo->seglen = length;
+    pgo->dirty = true;
+    return MRS_OK;
+}
+
+int mrs_pgo_initialize(mrs_pgo* pgo, double* h_T)
+{
+    MRS_REQUIRE(pgo && h_T, "null pointer");
+    MRS_TRY(pgo_ready(pgo));
+    MRS_TRY(pgo_stage1(pgo));
+    return pgo_download(pgo->T0.get(), pgo->g.N, h_T);
+}
+
+int mrs_pgo_optimize(mrs_pgo* pgo, double eps, int32_t max_iterations, double* h_T, double* h_info)
+{
+    MRS_REQUIRE(pgo && h_T && h_info, "null pointer");
+    MRS_REQUIRE(eps >= 0.0 && std::isfinite(eps), "eps must be finite and not negative");
+    MRS_REQUIRE(max_iterations >= 1, "max_iterations must be positive");
+    MRS_TRY(pgo_ready(pgo));
+    mrs_pgo* h = pgo;
+    const bool timing = mrs::dev_env("MRS_PGO_TIMING") != nullptr;
+    std::fill(h->stage_ms, h->stage_ms + 6, 0.0f);
+    {
+        mrs::StageMarks m1(timing && !h->init_valid, nullptr);
+        m1.mark(0);
+        MRS_TRY(pgo_stage1(h));
+        m1.mark(1);
+        if (m1) {
+            MRS_HIP_TRY(hipStreamSynchronize(nullptr));
+            h->stage_ms[0] = m1.ms(0);
+        }
+    }
+    const int N = h->g.N, F = h->F, F1 = F + 1;
+    const int *fi = h->fints.get(), *fj = fi + F1, *ptr = fj + F1, *ent = ptr + N + 2;
+    double* T = h->T.get();
+    Status* st = h->status.get();
+    MRS_HIP_TRY(hipMemcpyAsync(T, h->T0.get(), (size_t)N * 12 * sizeof(double), hipMemcpyDeviceToDevice, nullptr));
+    int its = 0, converged = 0;
+    double max_delta = 0.0, e0 = 0.0, e1 = 0.0;
+    while (its < max_iterations) {
+        mrs::StageMarks m(timing, nullptr);
+        MRS_HIP_TRY(hipMemsetAsync(st, 0, sizeof(Status), nullptr));
+        m.mark(0);
+        if (F) {
+            hipLaunchKernelGGL(k_pgo_linearize, dim3(blocks_for(F, kThreads)), dim3(kThreads), 0, nullptr, T, fi, fj, h->Z.get(), F, h->Hii.get(),
+                               h->Hij.get(), h->gi.get(), h->gj.get(), h->err.get());
+            if (its == 0) MRS_TRY(pgo_error_sum(h, &e0));
+        }
+        hipLaunchKernelGGL(k_pgo_gather, dim3(blocks_for(N, kThreads)), dim3(kThreads), 0, nullptr, ptr, ent, N, F, h->Hii.get(), h->gi.get(),
+                           h->gj.get(), h->Hpp.get(), h->gp.get());
+        m.mark(1);
+        MRS_TRY((pgo_solve<6, 1>(h, 2, &m, 2)));                  // marks 2 .. 5
+        hipLaunchKernelGGL(k_pgo_retract, dim3(blocks_for(N, kThreads)), dim3(kThreads), 0, nullptr, T, h->delta.get(), N, st);
+        m.mark(6);
+        MRS_HIP_TRY(hipGetLastError());
+        Status hs;
+        MRS_HIP_TRY(hipMemcpy(&hs, st, sizeof(hs), hipMemcpyDeviceToHost));      // the 16 bytes of this iteration
+        if (m) {
+            h->stage_ms[1] += m.ms(0);
+            h->stage_ms[2] += m.ms(1) + m.ms(4);
+            h->stage_ms[3] += m.ms(2);
+            h->stage_ms[4] += m.ms(3);
+            h->stage_ms[5] += m.ms(5);
+        }
+        ++its;
+        MRS_TRY(pgo_check_pivots(h, hs, 2));
+        std::memcpy(&max_delta, &hs.max_delta, sizeof(double));
+        if (!std::isfinite(max_delta)) {
+            mrs::set_error("Gauss-Newton iteration %d produced a step that is not finite", its);
+            return MRS_ERR_NOT_CONVERGED;
+        }
+        if (max_delta < eps) {
+            converged = 1;
+            break;
+        }
+    }
+    if (F) {
+        hipLaunchKernelGGL(k_pgo_error, dim3(blocks_for(F, kThreads)), dim3(kThreads), 0, nullptr, T, fi, fj, h->Z.get(), F, h->err.get());
+        MRS_TRY(pgo_error_sum(h, &e1));
+    }
+    MRS_TRY(pgo_download(T, N, h_T));
+    h_info[0] = its;
+    h_info[1] = converged;
+    h_info[2] = max_delta;
+    h_info[3] = e0;
+    h_info[4] = e1;
+    h_info[5] = h->topo[1].E;
+    return MRS_OK;
+}
+
+int mrs_pgo_last_stage_ms(mrs_pgo* pgo, float* h_ms)
+{
+    MRS_REQUIRE(pgo && h_ms, "null pointer");
+    std::copy(pgo->stage_ms, pgo->stage_ms + 6, h_ms);
+    return MRS_OK;
+}
+
+}  // extern "C"

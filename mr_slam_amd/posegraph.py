@@ -1,0 +1,127 @@
+"""Pose-graph optimisation for the Mapping back end (Mapping/src/global_manager/src/distributed_mapper/evaluation_utils.cpp:273-329,
+centralizedGNEstimation): rotations by chordal relaxation, then Gauss-Newton on chordal between factors, for a few odometry chains joined
+by loop factors.
+
+Thin host logic over the C ABI (mrs_pgo_*); there is no CPU fallback.  Both stages run on the GPU in fp64; `between`,
+`odometry_from_trajectory` and `correction` are the small host steps around them.  The contract and its named deviations are in
+DESIGN.md 4.23."""
+import collections
+
+import numpy as np
+
+from . import _lib
+from .pcm import _poses
+
+MAX_CHAINS, MAX_POSES = _lib.header_int("MRS_PGO_MAX_CHAINS"), _lib.header_int("MRS_PGO_MAX_POSES")
+MAX_LOOPS, MAX_SEPARATORS = _lib.header_int("MRS_PGO_MAX_LOOPS"), _lib.header_int("MRS_PGO_MAX_SEPARATORS")
+DEFAULT_SEGMENT_LENGTH = _lib.header_int("MRS_PGO_DEFAULT_SEGMENT_LENGTH")
+DEFAULT_EPS, DEFAULT_MAX_ITERATIONS = 1e-9, _lib.header_int("MRS_PGO_DEFAULT_MAX_ITERATIONS")
+_INFO = _lib.header_int("MRS_PGO_INFO_DOUBLES")
+
+Result = collections.namedtuple("Result", "T iterations converged max_delta error_initial error_final separators")
+Result.__doc__ = """T float64 [N, 4, 4]; iterations done; converged (max|delta| < eps was met); the last max|delta|; 0.5 sum |e|^2 at the
+stage-1 values and at T (the reference's "Initial Error" and "GN Error"); the separators of the Gauss-Newton system."""
+
+
+def _inverse(X):
+    Xi = np.tile(np.eye(4), (X.shape[0], 1, 1))
+    Rt = X[:, :3, :3].transpose(0, 2, 1)
+    Xi[:, :3, :3] = Rt
+    Xi[:, :3, 3] = -np.einsum("nab,nb->na", Rt, X[:, :3, 3])
+    return Xi
+
+
+def between(Xa, Xb):
+    """Xa^-1 Xb: the pose of b in the frame of a, for one pair [4, 4] or n pairs [n, 4, 4]"""
+    single = np.asarray(Xa).ndim == 2
+    Z = _inverse(_poses(Xa, "Xa")) @ _poses(Xb, "Xb")
+    return Z[0] if single else Z
+
+
+def odometry_from_trajectory(X):
+    """trajectory [n, 4, 4] -> odometry between-poses [n - 1, 4, 4]: the inverse of pcm.chain_odometry up to the first pose"""
+    X = _poses(X, "X")
+    return between(X[:-1], X[1:]) if X.shape[0] > 1 else np.zeros((0, 4, 4))
+
+
+def correction(T_opt, T_origin):
+    """optMapTF * originMapTF per pose (composeGlobalMap), float32 [n, 4, 4]: the optimised poses T_opt applied to the transforms T_origin
+    the keyframes were stored with, as GlobalMap.rebuild's segment poses and ElevationSubmaps.update_global take them.  Both are rounded to
+    float32 first, and every product and sum is rounded once in float32 in the order globalmap.pose_product documents."""
+    from .globalmap import pose_product
+    T_opt, T_origin = _poses(T_opt, "T_opt"), _poses(T_origin, "T_origin")
+    if T_opt.shape != T_origin.shape:
+        raise ValueError("T_opt and T_origin must have one pose each per entry")
+    out = np.empty(T_opt.shape, np.float32)
+    for k in range(T_opt.shape[0]):
+        out[k] = pose_product(T_opt[k].astype(np.float32), T_origin[k].astype(np.float32))
+    return out
+
+
+class PoseGraph:
+    """`nr` odometry chains on the device, poses numbered chain after chain: `set_odometry(Z)` (one factor per consecutive pair, chain
+    after chain), `add_loops(i, j, Z)` (Z[u] is the measured pose of j[u] in the frame of i[u]; any two different poses),
+    `set_prior(T)`, `set_segment_length(n)`, `initialize()` -> stage-1 poses, `optimize()` -> Result.  A refused call leaves the graph as
+    it was.
+
+    The C handle is owned by a plain `_lib.Handle` object (`_owner`, destroyed with this object by Handle's own `__del__`), not by a
+    subclass: the set of Handle subclasses of the package is pinned by tests/test_python_layer_cpu.py."""
+
+    def __init__(self, chain_lengths, device=0):
+        self.device = int(device)
+        self.chain_lengths = np.ascontiguousarray(chain_lengths, np.int32).reshape(-1)
+        self.n_poses = int(self.chain_lengths.sum())
+        self._owner = _lib.Handle()
+        self._owner._destroy = "mrs_pgo_destroy"
+        self._owner._create("mrs_pgo_create", _lib.ctx(self.device), self.chain_lengths.size, self.chain_lengths)
+
+    @property
+    def _h(self):
+        return self._owner._h
+
+    def __len__(self):
+        import ctypes as C
+        n = C.c_int32(0)
+        _lib.load().mrs_pgo_count(self._h, C.byref(n))
+        return n.value
+
+    def set_odometry(self, Z):
+        Z = _poses(Z, "Z") if np.size(Z) else np.zeros((0, 4, 4))
+        _lib.load().mrs_pgo_set_odometry(self._h, Z if Z.size else None, Z.shape[0])
+
+    def add_loops(self, i, j, Z):
+        i, j = np.ascontiguousarray(i, np.int32).reshape(-1), np.ascontiguousarray(j, np.int32).reshape(-1)
+        if not i.size:
+            return
+        Z = _poses(Z, "Z")
+        if not i.size == j.size == Z.shape[0]:
+            raise ValueError("i, j and Z must have one entry per loop")
+        _lib.load().mrs_pgo_add_loops(self._h, i, j, Z, i.size)
+
+    def clear(self):
+        _lib.load().mrs_pgo_clear_loops(self._h)
+
+    def set_prior(self, T):
+        _lib.load().mrs_pgo_set_prior(self._h, _poses(T, "T")[0].copy())
+
+    def set_segment_length(self, length):
+        _lib.load().mrs_pgo_set_segment_length(self._h, int(length))
+
+    def initialize(self):
+        """stage 1 alone -> float64 [N, 4, 4]: the relaxed rotations projected to SO(3), zero translations"""
+        T = np.zeros((self.n_poses, 4, 4))
+        _lib.load().mrs_pgo_initialize(self._h, T)
+        return T
+
+    def optimize(self, eps=DEFAULT_EPS, max_iterations=DEFAULT_MAX_ITERATIONS):
+        """both stages -> Result; eps = 0 runs exactly max_iterations steps"""
+        T, info = np.zeros((self.n_poses, 4, 4)), np.zeros(_INFO)
+        _lib.load().mrs_pgo_optimize(self._h, float(eps), int(max_iterations), T, info)
+        return Result(T, int(info[0]), bool(info[1]), float(info[2]), float(info[3]), float(info[4]), int(info[5]))
+
+    def stage_ms(self):
+        """milliseconds of the last optimize's stages (stage 1, linearise, segment walks, assembly, dense solve, retraction); zeros unless
+        the development timing switch was on"""
+        ms = np.zeros(6, np.float32)
+        _lib.load().mrs_pgo_last_stage_ms(self._h, ms)
+        return ms
