@@ -88,6 +88,60 @@ public:
         return r;
     }
 
+    // ---- per-factor noise, Levenberg-Marquardt step control, robust kernels on the loops
+    struct ResultLM {
+        std::vector<double> poses;       // [poses][16]
+        int solves = 0, accepted = 0;
+        bool converged = false;
+        double max_delta = 0.0;          // the last accepted step's largest component
+        double cost_initial = 0.0;       // sum 0.5 r^2 over the odometry factors + sum rho(r) over the loops, at the chordal start
+        double cost_final = 0.0;         // and at the result
+        int separators = 0;
+        double lambda = 0.0;
+    };
+    struct LoopState {
+        std::vector<double> weight, r2;  // per loop: the kernel's weight and e^T L e at the last result
+    };
+
+    // one Pose3 covariance (gtsam's order: rotation xyz, translation xyz) per odometry factor, C [n][36]; nullptr, 0 clears them
+    void setOdometryNoise(const double* C, int n) { check(mrs_pgo_set_odometry_noise(h_, C, n), "mrs_pgo_set_odometry_noise"); }
+    // addLoops with a covariance per loop, C [n][36]
+    void addLoops(const int32_t* i, const int32_t* j, const double* Z, const double* C, int n)
+    {
+        check(mrs_pgo_add_loops_noise(h_, i, j, Z, C, n), "mrs_pgo_add_loops_noise");
+    }
+    // MRS_PGO_KERNEL_*: in force under optimizeLM only; optimize refuses a handle with a kernel
+    void setLoopKernel(int kernel, double k = 1.0) { check(mrs_pgo_set_loop_kernel(h_, kernel, k), "mrs_pgo_set_loop_kernel"); }
+
+    ResultLM optimizeLM(double eps = 1e-9, int max_solves = MRS_PGO_DEFAULT_MAX_ITERATIONS)
+    {
+        ResultLM r;
+        r.poses.resize(static_cast<size_t>(poses_) * 16);
+        double info[MRS_PGO_LM_INFO_DOUBLES] = {};
+        check(mrs_pgo_optimize_lm(h_, eps, max_solves, r.poses.data(), info), "mrs_pgo_optimize_lm");
+        r.solves = static_cast<int>(info[0]);
+        r.accepted = static_cast<int>(info[1]);
+        r.converged = info[2] != 0.0;
+        r.max_delta = info[3];
+        r.cost_initial = info[4];
+        r.cost_final = info[5];
+        r.separators = static_cast<int>(info[6]);
+        r.lambda = info[7];
+        return r;
+    }
+
+    LoopState loopState() const
+    {
+        LoopState s;
+        const int n = loops();
+        s.weight.resize(static_cast<size_t>(n) + 1);
+        s.r2.resize(static_cast<size_t>(n) + 1);
+        check(mrs_pgo_get_loop_state(h_, s.weight.data(), s.r2.data(), n), "mrs_pgo_get_loop_state");
+        s.weight.resize(n);
+        s.r2.resize(n);
+        return s;
+    }
+
 private:
     static void check(int st, const char* what)
     {

@@ -1328,6 +1328,49 @@ int mrs_pgo_optimize(mrs_pgo* pgo, double eps, int32_t max_iterations, double* h
  * summed over the iterations.  Zeros unless MRS_DEV=1 and MRS_PGO_TIMING=1 were set when the call ran. */
 int mrs_pgo_last_stage_ms(mrs_pgo* pgo, float* h_ms);
 
+/* ---- per-factor noise, Levenberg-Marquardt step control and robust kernels on the loop factors ----
+ * A covariance is double [6][6] in gtsam's Pose3 order, rotation xyz then translation xyz, and is converted as
+ * evaluation_utils::convertToChordalNoise converts it (evaluation_utils.cpp:333-366, the reference's use_between_noise = true): weight
+ * 1 / max(C00, C11, C22) on the nine rotation rows, information Rhat (C[3:6][3:6] + 0.01 I)^-1 Rhat^T on the translation rows, Rhat the
+ * stage-1 rotation of the factor's first pose (i as given), fixed for a call; the rotation-translation blocks are ignored.  Stage 1 is
+ * not weighted.  A factor without a covariance keeps the unit model.  Refused with MRS_ERR_ARG, the handle unchanged: an entry that is
+ * not finite, max(C00, C11, C22) <= 0, a C[3:6][3:6] + 0.01 I that is not positive definite.  Both optimisers honour the noise. */
+int mrs_pgo_set_odometry_noise(mrs_pgo* pgo, const double* h_C, int32_t n);     /* n = the number of odometry factors; NULL, 0 clears */
+/* mrs_pgo_add_loops with a covariance per loop, h_C double [n][6][6] */
+int mrs_pgo_add_loops_noise(mrs_pgo* pgo, const int32_t* h_i, const int32_t* h_j, const double* h_Z, const double* h_C, int32_t n);
+
+#define MRS_PGO_KERNEL_NONE 0
+#define MRS_PGO_KERNEL_HUBER 1
+#define MRS_PGO_KERNEL_CAUCHY 2
+#define MRS_PGO_KERNEL_GEMAN_MCCLURE 3
+/* A robust kernel on every loop factor, with r = sqrt(e^T L e) over the factor's 12 rows: Huber w = 1 (r <= k) or k / r; Cauchy
+ * w = k^2 / (k^2 + r^2); Geman-McClure w = (k^2 / (k^2 + r^2))^2.  k must be positive and finite.  A kernel works only under
+ * mrs_pgo_optimize_lm; mrs_pgo_optimize on a handle with one returns MRS_ERR_ARG.  Not pinned to the reference: its chordal conversion
+ * cannot carry a Robust model. */
+int mrs_pgo_set_loop_kernel(mrs_pgo* pgo, int32_t kernel, double k);
+
+/* Levenberg-Marquardt's constants: lambda starts at gtsam's lambdaInitial and stays within [MIN, MAX]; a step whose predicted decrease
+ * is at most PRED_FLOOR times the cost is below what an fp64 cost resolves: it is accepted and its gain counts as 1 */
+#define MRS_PGO_LM_LAMBDA_INITIAL 1e-5
+#define MRS_PGO_LM_LAMBDA_MIN 1e-12
+#define MRS_PGO_LM_LAMBDA_MAX 1e12
+#define MRS_PGO_LM_PRED_FLOOR 1e-10
+/* doubles of mrs_pgo_optimize_lm's h_info: solves done, steps accepted, converged (0 / 1), the last accepted max|delta|, the cost at the
+ * stage-1 values and at the result (sum 0.5 r^2 over the odometry factors + sum rho(r) over the loops), the separator count, the final
+ * lambda */
+#define MRS_PGO_LM_INFO_DOUBLES 8
+/* Both stages with step control.  Solve 1 is the Gauss-Newton step (lambda = 0, kernel weights 1), accepted whatever it does to the
+ * cost: the linear solve for the translations from t = 0.  Later solves: (H + lambda diag H) delta = g, the loops' blocks scaled by the
+ * kernel's weight at the current poses; pred = 0.5 delta^T (lambda diag(H) delta + g), rho = (c - c_new) / pred (1 for a step below
+ * the floor); accepted iff
+ * c_new <= c or pred <= PRED_FLOOR c; then lambda *= max(1/3, 1 - (2 rho - 1)^3) and nu = 2, else lambda *= nu, nu *= 2 and the poses
+ * are restored.  Stops at an accepted step with max|delta| < eps or after max_solves solves (rejected ones count).  Errors as
+ * mrs_pgo_optimize. */
+int mrs_pgo_optimize_lm(mrs_pgo* pgo, double eps, int32_t max_solves, double* h_T, double* h_info);
+/* The kernel's weight and e^T L e of every loop at the last result of either optimiser (weights 1 without a kernel): h_w, h_r2 double
+ * [capacity], capacity >= the number of loops.  MRS_ERR_ARG when the graph changed since, or nothing was optimised. */
+int mrs_pgo_get_loop_state(mrs_pgo* pgo, double* h_w, double* h_r2, int32_t capacity);
+
 #ifdef __cplusplus
 }
 #endif

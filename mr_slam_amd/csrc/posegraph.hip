@@ -20,6 +20,10 @@
 //   retract    : k_pgo_retract, a thread per pose; max|delta| by an integer atomicMax on the bits of a non-negative double;
 //   error      : 0.5 sum |e|^2 by a fixed two-level tree (k_pgo_sum1, k_pgo_sum2);
 //   project    : k_pgo_project, stage 1: the closest rotation of each solved 3x3.
+// Beyond the reference's settings: a covariance per factor, converted as convertToChordalNoise converts it
+// (k_pgo_information after stage 1; the <true> instantiations of k_pgo_linearize, k_pgo_error and k_pgo_gather; the <false> ones keep the
+// unit model's arithmetic), Levenberg-Marquardt step control (mrs_pgo_optimize_lm: lambda enters the gather, k_pgo_predicted and the sum
+// tree give the predicted decrease, one previous copy of the poses) and robust kernels on the loop factors (weights in the linearisation).
 // No kernel waits for another workgroup, every device loop is bounded by a size known at launch, and a pivot block that is not positive
 // definite becomes a status word (the walk goes on with a unit pivot; the host ends the call).  The host reads 16 bytes per iteration.
 #include "common.hpp"
@@ -111,10 +115,24 @@ __device__ __forceinline__ void upper_solve(const double* L, double* v)
 
 // ------------------------------------------------------------------ linearisation
 
+// What the weighted instantiations read and write per factor, 10 doubles each: wr and Lt [9] (posegraph_factor.hpp).
+//   lam : the factor's information, fixed for a call (k_pgo_information);
+//   eff : the information the last linearisation used, lam times the kernel's weight: what k_pgo_gather<true> sums for Hj^T L Hj;
+//   r2, wk : e^T L e and the kernel's weight at the poses last looked at.
+// A loop factor (f >= first_loop) under a kernel costs rho(r); `irls` = 0 leaves its blocks unscaled (the first solve).
+struct Weights {
+    const double* lam;
+    double *eff, *r2, *wk;
+    int first_loop, kernel, irls;
+    double k;
+};
+constexpr int kInfo = 10;
+
 // stage 2: a thread per factor
+template <bool W>
 __global__ __launch_bounds__(kThreads) void k_pgo_linearize(const double* __restrict__ T, const int* __restrict__ fi, const int* __restrict__ fj,
                                                             const double* __restrict__ Z, int F, double* __restrict__ Hii, double* __restrict__ Hij,
-                                                            double* __restrict__ gi, double* __restrict__ gj, double* __restrict__ err)
+                                                            double* __restrict__ gi, double* __restrict__ gj, double* __restrict__ err, Weights wt)
 {
     const int f = blockIdx.x * kThreads + threadIdx.x;
     if (f >= F) return;
@@ -126,7 +144,28 @@ __global__ __launch_bounds__(kThreads) void k_pgo_linearize(const double* __rest
         Tj[k] = T[(size_t)j * 12 + k];
         z[k] = Z[(size_t)f * 12 + k];
     }
-    mrs::pgo::factor_normal(Ti, Tj, z, e, hii, hij, a, b);
+    double cost = 0.0;
+    if (W) {
+        double l[kInfo], RiRij[9];
+#pragma unroll
+        for (int k = 0; k < kInfo; ++k) l[k] = wt.lam[(size_t)f * kInfo + k];
+        mrs::pgo::factor_error(Ti, Tj, z, RiRij, e);
+        const double r2 = mrs::pgo::factor_sq_weighted(e, l[0], l + 1);
+        const int kernel = f >= wt.first_loop ? wt.kernel : (int)mrs::pgo::kKernelNone;
+        const double w = mrs::pgo::kernel_weight(kernel, wt.k, r2);
+        cost = mrs::pgo::kernel_cost(kernel, wt.k, r2);
+        if (wt.irls) {
+#pragma unroll
+            for (int k = 0; k < kInfo; ++k) l[k] *= w;
+        }
+        mrs::pgo::factor_normal_weighted(Ti, Tj, z, l[0], l + 1, e, hii, hij, a, b);
+#pragma unroll
+        for (int k = 0; k < kInfo; ++k) wt.eff[(size_t)f * kInfo + k] = l[k];
+        wt.r2[f] = r2;
+        wt.wk[f] = w;
+    } else {
+        mrs::pgo::factor_normal(Ti, Tj, z, e, hii, hij, a, b);
+    }
 #pragma unroll
     for (int k = 0; k < 36; ++k) {
         Hii[(size_t)f * 36 + k] = hii[k];
@@ -137,12 +176,13 @@ __global__ __launch_bounds__(kThreads) void k_pgo_linearize(const double* __rest
         gi[(size_t)f * 6 + k] = a[k];
         gj[(size_t)f * 6 + k] = b[k];
     }
-    err[f] = mrs::pgo::factor_half_sq(e);
+    err[f] = W ? cost : mrs::pgo::factor_half_sq(e);
 }
 
 // the error alone
+template <bool W>
 __global__ __launch_bounds__(kThreads) void k_pgo_error(const double* __restrict__ T, const int* __restrict__ fi, const int* __restrict__ fj,
-                                                        const double* __restrict__ Z, int F, double* __restrict__ err)
+                                                        const double* __restrict__ Z, int F, double* __restrict__ err, Weights wt)
 {
     const int f = blockIdx.x * kThreads + threadIdx.x;
     if (f >= F) return;
@@ -155,7 +195,40 @@ __global__ __launch_bounds__(kThreads) void k_pgo_error(const double* __restrict
         z[k] = Z[(size_t)f * 12 + k];
     }
     mrs::pgo::factor_error(Ti, Tj, z, RiRij, e);
-    err[f] = mrs::pgo::factor_half_sq(e);
+    if (W) {
+        double l[kInfo];
+#pragma unroll
+        for (int k = 0; k < kInfo; ++k) l[k] = wt.lam[(size_t)f * kInfo + k];
+        const double r2 = mrs::pgo::factor_sq_weighted(e, l[0], l + 1);
+        const int kernel = f >= wt.first_loop ? wt.kernel : (int)mrs::pgo::kKernelNone;
+        wt.r2[f] = r2;
+        wt.wk[f] = mrs::pgo::kernel_weight(kernel, wt.k, r2);
+        err[f] = mrs::pgo::kernel_cost(kernel, wt.k, r2);
+    } else {
+        err[f] = mrs::pgo::factor_half_sq(e);
+    }
+}
+
+// after stage 1, a thread per factor: the information of a factor that carries a covariance, from noise [F][10] = 1 / max(C00, C11, C22)
+// and C[3:6, 3:6] + 0.01 I, and the stage-1 rotation of the factor's first pose; the unit model where noise[f][0] is 0
+__global__ __launch_bounds__(kThreads) void k_pgo_information(const double* __restrict__ T0, const int* __restrict__ fi,
+                                                              const double* __restrict__ noise, int F, double* __restrict__ lam)
+{
+    const int f = blockIdx.x * kThreads + threadIdx.x;
+    if (f >= F) return;
+    double l[kInfo] = {1.0, 1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0};
+    const double wr = noise[(size_t)f * kInfo];
+    if (wr != 0.0) {
+        double Tk[12], P[9];
+#pragma unroll
+        for (int k = 0; k < 12; ++k) Tk[k] = T0[(size_t)fi[f] * 12 + k];
+#pragma unroll
+        for (int k = 0; k < 9; ++k) P[k] = noise[(size_t)f * kInfo + 1 + k];
+        l[0] = wr;
+        mrs::pgo::translation_information(Tk, P, l + 1);
+    }
+#pragma unroll
+    for (int k = 0; k < kInfo; ++k) lam[(size_t)f * kInfo + k] = l[k];
 }
 
 // stage 1: the residual of factor (i, j) is Rij x_j - x_i per row of the rotations, so Hi^T Hj = -Rij and both diagonal blocks are I
@@ -170,9 +243,12 @@ __global__ __launch_bounds__(kThreads) void k_pgo_linearize_rot(const double* __
 }
 
 // stage 2: Hpp [36] and g [6] of pose p from its factors in ascending order; an entry of the CSR is factor << 1 | (1 if p is the factor's j)
+// Levenberg-Marquardt: `diag` (optional) receives the diagonal of Hpp, which then gains lambda times itself
+template <bool W>
 __global__ __launch_bounds__(kThreads) void k_pgo_gather(const int* __restrict__ ptr, const int* __restrict__ ent, int N, int F,
                                                          const double* __restrict__ Hii, const double* __restrict__ gi, const double* __restrict__ gj,
-                                                         double* __restrict__ Hpp, double* __restrict__ g)
+                                                         double* __restrict__ Hpp, double* __restrict__ g, const double* __restrict__ eff,
+                                                         double lambda, double* __restrict__ diag)
 {
     const int p = blockIdx.x * kThreads + threadIdx.x;
     if (p >= N) return;
@@ -186,10 +262,20 @@ __global__ __launch_bounds__(kThreads) void k_pgo_gather(const int* __restrict__
         const int f = ent[u] >> 1;
         if (f >= F) continue;                                    // the anchor's factor belongs to stage 1
         if (ent[u] & 1) {
+            if (W) {
+                const double* l = eff + (size_t)f * kInfo;
 #pragma unroll
-            for (int k = 0; k < 6; ++k) {
-                H[7 * k] += mrs::pgo::hjj_diagonal(k);
-                v[k] += gj[(size_t)f * 6 + k];
+                for (int k = 0; k < 3; ++k) H[7 * k] += l[0] * mrs::pgo::hjj_diagonal(k);
+#pragma unroll
+                for (int k = 0; k < 9; ++k) H[6 * (3 + k / 3) + 3 + k % 3] += l[1 + k];
+#pragma unroll
+                for (int k = 0; k < 6; ++k) v[k] += gj[(size_t)f * 6 + k];
+            } else {
+#pragma unroll
+                for (int k = 0; k < 6; ++k) {
+                    H[7 * k] += mrs::pgo::hjj_diagonal(k);
+                    v[k] += gj[(size_t)f * 6 + k];
+                }
             }
         } else {
 #pragma unroll
@@ -198,10 +284,32 @@ __global__ __launch_bounds__(kThreads) void k_pgo_gather(const int* __restrict__
             for (int k = 0; k < 6; ++k) v[k] += gi[(size_t)f * 6 + k];
         }
     }
+    if (diag) {
+#pragma unroll
+        for (int k = 0; k < 6; ++k) {
+            diag[(size_t)p * 6 + k] = H[7 * k];
+            H[7 * k] += lambda * H[7 * k];
+        }
+    }
 #pragma unroll
     for (int k = 0; k < 36; ++k) Hpp[(size_t)p * 36 + k] = H[k];
 #pragma unroll
     for (int k = 0; k < 6; ++k) g[(size_t)p * 6 + k] = v[k];
+}
+
+// Levenberg-Marquardt: the pose's share of delta^T (lambda diag(H) delta + g); half their sum is the predicted decrease
+__global__ __launch_bounds__(kThreads) void k_pgo_predicted(const double* __restrict__ delta, const double* __restrict__ diag,
+                                                            const double* __restrict__ g, double lambda, int N, double* __restrict__ out)
+{
+    const int p = blockIdx.x * kThreads + threadIdx.x;
+    if (p >= N) return;
+    double s = 0.0;
+#pragma unroll
+    for (int k = 0; k < 6; ++k) {
+        const double d = delta[(size_t)p * 6 + k];
+        s += d * (lambda * diag[(size_t)p * 6 + k] * d + g[(size_t)p * 6 + k]);
+    }
+    out[p] = s;
 }
 
 // stage 1: Hpp = (number of factors) I, plus I for the anchor's own prior, whose right-hand sides are the rows of the identity
@@ -778,6 +886,11 @@ struct mrs_pgo {
     int seglen = MRS_PGO_DEFAULT_SEGMENT_LENGTH;
     bool odometry_set = false;
     std::vector<double> odom, loopZ;                             // [.][16] as given
+    std::vector<double> odomC, loopC;                            // covariances [.][36]: odomC is empty or complete, loopC has an entry per loop
+    std::vector<char> loop_has_C;                                // whether loopC's entry was given
+    int kernel = MRS_PGO_KERNEL_NONE;                            // on the loop factors, under mrs_pgo_optimize_lm
+    double kernel_k = 1.0;
+    bool result_valid = false, result_weighted = false;          // the device holds the loops' state at the last result, and where
     double prior[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
     bool dirty = true;                                           // the device copy of the graph and of the topologies is behind
     bool init_valid = false;                                     // T0 holds stage 1 of the current graph
@@ -786,6 +899,8 @@ struct mrs_pgo {
     int F = 0;                                                   // factors without the anchor's
     mrs::DeviceBuffer<int> fints;                                // fi [F + 1] | fj [F + 1] | csr ptr [N + 2] | csr entries [2 (F + 1)]
     mrs::DeviceBuffer<double> Z, T0, T, delta, Hii, Hij, gi, gj, err, partial, Hpp, gp, Lk, Ak, Wk, yk, seg, S;
+    mrs::DeviceBuffer<double> noise, lam, eff, r2, wk;           // per factor: see Weights
+    mrs::DeviceBuffer<double> Tprev, diag, predv, partial_p;     // Levenberg-Marquardt: the poses before the step, diag(H), the terms of pred
     mrs::DeviceBuffer<Status> status;
     mrs::DeviceBuffer<double> err_out;
     float stage_ms[6] = {0, 0, 0, 0, 0, 0};
@@ -879,8 +994,26 @@ int pgo_sync(mrs_pgo* h)
     MRS_TRY(grow(h->yk, nodes * 9));
     MRS_TRY(grow(h->seg, nseg * (3 * 36 + 2 * 9)));
     MRS_TRY(grow(h->S, std::max((n1 + 3) * n1, (n2 + 1) * n2)));
-    MRS_TRY(h->status.reserve(1, 1));
+    // 1 / max(C00, C11, C22) and C[3:6, 3:6] + 0.01 I of the factors that carry a covariance; zeros for the others
+    std::vector<double> noise((size_t)F1 * kInfo, 0.0);
+    const auto put_noise = [&](int k, const double* C) { mrs::pgo::covariance_terms(C, noise.data() + (size_t)k * kInfo); };
+    if (!h->odomC.empty())
+        for (int k = 0; k < N - g.nr; ++k) put_noise(k, h->odomC.data() + (size_t)k * 36);
+    for (int u = 0; u < L; ++u)
+        if (h->loop_has_C[u]) put_noise(N - g.nr + u, h->loopC.data() + (size_t)u * 36);
+    MRS_TRY(grow(h->noise, noise.size()));
+    MRS_HIP_TRY(hipMemcpy(h->noise.get(), noise.data(), noise.size() * sizeof(double), hipMemcpyHostToDevice));
+    MRS_TRY(grow(h->lam, (size_t)F1 * kInfo));
+    MRS_TRY(grow(h->eff, (size_t)F1 * kInfo));
+    MRS_TRY(grow(h->r2, (size_t)F1));
+    MRS_TRY(grow(h->wk, (size_t)F1));
+    MRS_TRY(grow(h->Tprev, nodes * 12));
+    MRS_TRY(grow(h->diag, nodes * 6));
+    MRS_TRY(grow(h->predv, nodes));
+    MRS_TRY(grow(h->partial_p, (size_t)blocks_for((long long)nodes, kThreads)));
+    MRS_TRY(h->status.reserve(2, 2));                            // the second slot holds the two doubles of a Levenberg-Marquardt solve
     MRS_TRY(h->err_out.reserve(1, 1));
+    h->result_valid = false;
     h->dirty = false;
     return MRS_OK;
 }
@@ -983,16 +1116,155 @@ int pgo_stage1(mrs_pgo* h)
     return MRS_OK;
 }
 
+// the fixed two-level tree over v [n] -> *d_out on the device
+void pgo_tree_sum(const double* v, int n, double* partial, double* d_out)
+{
+    const int nb = (int)blocks_for(n, kThreads);
+    hipLaunchKernelGGL(k_pgo_sum1, dim3(nb), dim3(kThreads), 0, nullptr, v, n, partial);
+    hipLaunchKernelGGL(k_pgo_sum2, dim3(1), dim3(kThreads), 0, nullptr, partial, nb, d_out);
+}
+
 int pgo_error_sum(mrs_pgo* h, double* out)
 {
     const int F = h->F;
     *out = 0.0;
     if (F == 0) return MRS_OK;
-    const int nb = (int)blocks_for(F, kThreads);
-    hipLaunchKernelGGL(k_pgo_sum1, dim3(nb), dim3(kThreads), 0, nullptr, h->err.get(), F, h->partial.get());
-    hipLaunchKernelGGL(k_pgo_sum2, dim3(1), dim3(kThreads), 0, nullptr, h->partial.get(), nb, h->err_out.get());
+    pgo_tree_sum(h->err.get(), F, h->partial.get(), h->err_out.get());
     MRS_HIP_TRY(hipGetLastError());
     MRS_HIP_TRY(hipMemcpy(out, h->err_out.get(), sizeof(double), hipMemcpyDeviceToHost));
+    return MRS_OK;
+}
+
+// ------------------------------------------------------------------ host: the weighted and the plain instantiations behind one call each
+
+int pgo_check_separators(const Graph& g, int seglen);
+
+bool pgo_has_noise(const mrs_pgo* h)
+{
+    return !h->odomC.empty() || std::find(h->loop_has_C.begin(), h->loop_has_C.end(), (char)1) != h->loop_has_C.end();
+}
+
+struct FactorPass {
+    mrs_pgo* h;
+    bool weighted;
+    int kernel;                                                  // applies to the weighted instantiation only
+    const int *fi, *fj, *ptr, *ent;
+
+    FactorPass(mrs_pgo* handle, bool w, int kern) : h(handle), weighted(w), kernel(kern)
+    {
+        const int F1 = h->F + 1;
+        fi = h->fints.get();
+        fj = fi + F1;
+        ptr = fj + F1;
+        ent = ptr + h->g.N + 2;
+    }
+    Weights weights(bool irls) const
+    {
+        return Weights{h->lam.get(), h->eff.get(), h->r2.get(), h->wk.get(), h->g.N - h->g.nr, kernel, irls ? 1 : 0, h->kernel_k};
+    }
+    // the factors' information from the stage-1 values in T0
+    void information() const
+    {
+        if (weighted && h->F)
+            hipLaunchKernelGGL(k_pgo_information, dim3(blocks_for(h->F, kThreads)), dim3(kThreads), 0, nullptr, h->T0.get(), fi, h->noise.get(), h->F,
+                               h->lam.get());
+    }
+    void linearize(const double* T, bool irls) const
+    {
+        const int F = h->F;
+        if (!F) return;
+        if (weighted)
+            hipLaunchKernelGGL(k_pgo_linearize<true>, dim3(blocks_for(F, kThreads)), dim3(kThreads), 0, nullptr, T, fi, fj, h->Z.get(), F, h->Hii.get(),
+                               h->Hij.get(), h->gi.get(), h->gj.get(), h->err.get(), weights(irls));
+        else
+            hipLaunchKernelGGL(k_pgo_linearize<false>, dim3(blocks_for(F, kThreads)), dim3(kThreads), 0, nullptr, T, fi, fj, h->Z.get(), F, h->Hii.get(),
+                               h->Hij.get(), h->gi.get(), h->gj.get(), h->err.get(), Weights{});
+    }
+    void error(const double* T) const
+    {
+        const int F = h->F;
+        if (!F) return;
+        if (weighted)
+            hipLaunchKernelGGL(k_pgo_error<true>, dim3(blocks_for(F, kThreads)), dim3(kThreads), 0, nullptr, T, fi, fj, h->Z.get(), F, h->err.get(),
+                               weights(true));
+        else
+            hipLaunchKernelGGL(k_pgo_error<false>, dim3(blocks_for(F, kThreads)), dim3(kThreads), 0, nullptr, T, fi, fj, h->Z.get(), F, h->err.get(),
+                               Weights{});
+    }
+    // lambda enters only with `damped`
+    void gather(double lambda, bool damped) const
+    {
+        const int N = h->g.N;
+        double* diag = damped ? h->diag.get() : nullptr;
+        if (weighted)
+            hipLaunchKernelGGL(k_pgo_gather<true>, dim3(blocks_for(N, kThreads)), dim3(kThreads), 0, nullptr, ptr, ent, N, h->F, h->Hii.get(),
+                               h->gi.get(), h->gj.get(), h->Hpp.get(), h->gp.get(), h->eff.get(), lambda, diag);
+        else
+            hipLaunchKernelGGL(k_pgo_gather<false>, dim3(blocks_for(N, kThreads)), dim3(kThreads), 0, nullptr, ptr, ent, N, h->F, h->Hii.get(),
+                               h->gi.get(), h->gj.get(), h->Hpp.get(), h->gp.get(), nullptr, lambda, diag);
+    }
+};
+
+// a covariance as mrs_pgo_set_odometry_noise and mrs_pgo_add_loops_noise take it
+bool pgo_covariance_ok(const double* C, const char** why)
+{
+    for (int k = 0; k < 36; ++k)
+        if (!std::isfinite(C[k])) {
+            *why = "a covariance is not finite";
+            return false;
+        }
+    if (!(std::max(C[0], std::max(C[7], C[14])) > 0.0)) {
+        *why = "a covariance has no positive rotation variance";
+        return false;
+    }
+    double P[9];                                                 // the lower triangle of C[3:6, 3:6] + 0.01 I, factored in place
+    for (int r = 0; r < 3; ++r)
+        for (int c = 0; c < 3; ++c) P[3 * r + c] = C[6 * (3 + r) + 3 + c] + (r == c ? mrs::pgo::kTranslationFloor : 0.0);
+    for (int j = 0; j < 3; ++j) {
+        double d = P[3 * j + j];
+        for (int k = 0; k < j; ++k) d -= P[3 * j + k] * P[3 * j + k];
+        if (!(d > 0.0) || !std::isfinite(d)) {
+            *why = "a translation covariance plus 0.01 I is not positive definite";
+            return false;
+        }
+        d = std::sqrt(d);
+        P[3 * j + j] = d;
+        for (int i = j + 1; i < 3; ++i) {
+            double s = P[3 * i + j];
+            for (int k = 0; k < j; ++k) s -= P[3 * i + k] * P[3 * j + k];
+            P[3 * i + j] = s / d;
+        }
+    }
+    return true;
+}
+
+// the loops' validation and append shared by mrs_pgo_add_loops and mrs_pgo_add_loops_noise (h_C may be null)
+int pgo_add_loops(mrs_pgo* pgo, const int32_t* h_i, const int32_t* h_j, const double* h_Z, const double* h_C, int32_t n)
+{
+    for (int u = 0; u < n; ++u) {
+        MRS_REQUIRE(h_i[u] >= 0 && h_i[u] < pgo->g.N && h_j[u] >= 0 && h_j[u] < pgo->g.N, "a loop names a pose outside the graph");
+        MRS_REQUIRE(h_i[u] != h_j[u], "a loop joins a pose with itself");
+        MRS_REQUIRE(finite16(h_Z + (size_t)u * 16), "a loop pose is not finite");
+        const char* why = "";
+        if (h_C && !pgo_covariance_ok(h_C + (size_t)u * 36, &why)) {
+            mrs::set_error("bad argument: %s (loop %d of the call)", why, u);
+            return MRS_ERR_ARG;
+        }
+    }
+    if ((long long)pgo->g.li.size() + n > kMaxLoops) {
+        mrs::set_error("%zu loops held and %d more exceed the %d a pose graph holds", pgo->g.li.size(), n, kMaxLoops);
+        return MRS_ERR_UNSUPPORTED;
+    }
+    Graph g = pgo->g;
+    g.li.insert(g.li.end(), h_i, h_i + n);
+    g.lj.insert(g.lj.end(), h_j, h_j + n);
+    MRS_TRY(pgo_check_separators(g, pgo->seglen));
+    pgo->g = std::move(g);
+    pgo->loopZ.insert(pgo->loopZ.end(), h_Z, h_Z + (size_t)n * 16);
+    if (h_C) pgo->loopC.insert(pgo->loopC.end(), h_C, h_C + (size_t)n * 36);
+    else pgo->loopC.insert(pgo->loopC.end(), (size_t)n * 36, 0.0);
+    pgo->loop_has_C.insert(pgo->loop_has_C.end(), (size_t)n, h_C ? 1 : 0);
+    pgo->dirty = true;
     return MRS_OK;
 }
 
@@ -1080,22 +1352,69 @@ int mrs_pgo_add_loops(mrs_pgo* pgo, const int32_t* h_i, const int32_t* h_j, cons
     MRS_REQUIRE(n >= 0, "n must not be negative");
     if (n == 0) return MRS_OK;
     MRS_REQUIRE(h_i && h_j && h_Z, "null pointer");
-    for (int u = 0; u < n; ++u) {
-        MRS_REQUIRE(h_i[u] >= 0 && h_i[u] < pgo->g.N && h_j[u] >= 0 && h_j[u] < pgo->g.N, "a loop names a pose outside the graph");
-        MRS_REQUIRE(h_i[u] != h_j[u], "a loop joins a pose with itself");
-        MRS_REQUIRE(finite16(h_Z + (size_t)u * 16), "a loop pose is not finite");
+    return pgo_add_loops(pgo, h_i, h_j, h_Z, nullptr, n);
+}
+
+int mrs_pgo_add_loops_noise(mrs_pgo* pgo, const int32_t* h_i, const int32_t* h_j, const double* h_Z, const double* h_C, int32_t n)
+{
+    MRS_REQUIRE(pgo, "null pointer");
+    MRS_REQUIRE(n >= 0, "n must not be negative");
+    if (n == 0) return MRS_OK;
+    MRS_REQUIRE(h_i && h_j && h_Z && h_C, "null pointer");
+    return pgo_add_loops(pgo, h_i, h_j, h_Z, h_C, n);
+}
+
+int mrs_pgo_set_odometry_noise(mrs_pgo* pgo, const double* h_C, int32_t n)
+{
+    MRS_REQUIRE(pgo, "null pointer");
+    if (!h_C) {
+        MRS_REQUIRE(n == 0, "null pointer");
+        pgo->odomC.clear();
+        pgo->dirty = true;
+        return MRS_OK;
     }
-    if ((long long)pgo->g.li.size() + n > kMaxLoops) {
-        mrs::set_error("%zu loops held and %d more exceed the %d a pose graph holds", pgo->g.li.size(), n, kMaxLoops);
-        return MRS_ERR_UNSUPPORTED;
+    MRS_REQUIRE(n == pgo->g.N - pgo->g.nr, "one covariance per odometry factor");
+    for (int k = 0; k < n; ++k) {
+        const char* why = "";
+        if (!pgo_covariance_ok(h_C + (size_t)k * 36, &why)) {
+            mrs::set_error("bad argument: %s (odometry factor %d)", why, k);
+            return MRS_ERR_ARG;
+        }
     }
-    Graph g = pgo->g;
-    g.li.insert(g.li.end(), h_i, h_i + n);
-    g.lj.insert(g.lj.end(), h_j, h_j + n);
-    MRS_TRY(pgo_check_separators(g, pgo->seglen));
-    pgo->g = std::move(g);
-    pgo->loopZ.insert(pgo->loopZ.end(), h_Z, h_Z + (size_t)n * 16);
+    pgo->odomC.assign(h_C, h_C + (size_t)n * 36);
     pgo->dirty = true;
+    return MRS_OK;
+}
+
+int mrs_pgo_set_loop_kernel(mrs_pgo* pgo, int32_t kernel, double k)
+{
+    MRS_REQUIRE(pgo, "null pointer");
+    MRS_REQUIRE(kernel >= MRS_PGO_KERNEL_NONE && kernel <= MRS_PGO_KERNEL_GEMAN_MCCLURE, "the kernel must be one of MRS_PGO_KERNEL_*");
+    MRS_REQUIRE(k > 0.0 && std::isfinite(k), "the kernel's parameter must be positive and finite");
+    pgo->kernel = kernel;
+    pgo->kernel_k = k;
+    pgo->result_valid = false;
+    return MRS_OK;
+}
+
+int mrs_pgo_get_loop_state(mrs_pgo* pgo, double* h_w, double* h_r2, int32_t capacity)
+{
+    MRS_REQUIRE(pgo && h_w && h_r2, "null pointer");
+    const int L = (int)pgo->g.li.size(), first = pgo->g.N - pgo->g.nr;
+    MRS_REQUIRE(capacity >= L, "capacity is below the number of loops");
+    MRS_REQUIRE(pgo->result_valid && !pgo->dirty, "no optimisation of the graph as it stands has finished");
+    if (L == 0) return MRS_OK;
+    MRS_HIP_TRY(hipSetDevice(pgo->ctx->device));
+    if (pgo->result_weighted) {
+        MRS_HIP_TRY(hipMemcpy(h_w, pgo->wk.get() + first, (size_t)L * sizeof(double), hipMemcpyDeviceToHost));
+        MRS_HIP_TRY(hipMemcpy(h_r2, pgo->r2.get() + first, (size_t)L * sizeof(double), hipMemcpyDeviceToHost));
+    } else {                                                     // the plain pass leaves 0.5 |e|^2
+        MRS_HIP_TRY(hipMemcpy(h_r2, pgo->err.get() + first, (size_t)L * sizeof(double), hipMemcpyDeviceToHost));
+        for (int u = 0; u < L; ++u) {
+            h_r2[u] *= 2.0;
+            h_w[u] = 1.0;
+        }
+    }
     return MRS_OK;
 }
 
@@ -1105,6 +1424,8 @@ int mrs_pgo_clear_loops(mrs_pgo* pgo)
     pgo->g.li.clear();
     pgo->g.lj.clear();
     pgo->loopZ.clear();
+    pgo->loopC.clear();
+    pgo->loop_has_C.clear();
     pgo->dirty = true;
     return MRS_OK;
 }
@@ -1149,8 +1470,10 @@ int mrs_pgo_optimize(mrs_pgo* pgo, double eps, int32_t max_iterations, double* h
     MRS_REQUIRE(pgo && h_T && h_info, "null pointer");
     MRS_REQUIRE(eps >= 0.0 && std::isfinite(eps), "eps must be finite and not negative");
     MRS_REQUIRE(max_iterations >= 1, "max_iterations must be positive");
+    MRS_REQUIRE(pgo->kernel == MRS_PGO_KERNEL_NONE, "a robust kernel needs the step control of mrs_pgo_optimize_lm");
     MRS_TRY(pgo_ready(pgo));
     mrs_pgo* h = pgo;
+    h->result_valid = false;
     const bool timing = mrs::dev_env("MRS_PGO_TIMING") != nullptr;
     std::fill(h->stage_ms, h->stage_ms + 6, 0.0f);
     {
@@ -1163,11 +1486,12 @@ int mrs_pgo_optimize(mrs_pgo* pgo, double eps, int32_t max_iterations, double* h
             h->stage_ms[0] = m1.ms(0);
         }
     }
-    const int N = h->g.N, F = h->F, F1 = F + 1;
-    const int *fi = h->fints.get(), *fj = fi + F1, *ptr = fj + F1, *ent = ptr + N + 2;
+    const int N = h->g.N, F = h->F;
+    const FactorPass pass(h, pgo_has_noise(h), MRS_PGO_KERNEL_NONE);
     double* T = h->T.get();
     Status* st = h->status.get();
     MRS_HIP_TRY(hipMemcpyAsync(T, h->T0.get(), (size_t)N * 12 * sizeof(double), hipMemcpyDeviceToDevice, nullptr));
+    pass.information();
     int its = 0, converged = 0;
     double max_delta = 0.0, e0 = 0.0, e1 = 0.0;
     while (its < max_iterations) {
@@ -1175,12 +1499,10 @@ int mrs_pgo_optimize(mrs_pgo* pgo, double eps, int32_t max_iterations, double* h
         MRS_HIP_TRY(hipMemsetAsync(st, 0, sizeof(Status), nullptr));
         m.mark(0);
         if (F) {
-            hipLaunchKernelGGL(k_pgo_linearize, dim3(blocks_for(F, kThreads)), dim3(kThreads), 0, nullptr, T, fi, fj, h->Z.get(), F, h->Hii.get(),
-                               h->Hij.get(), h->gi.get(), h->gj.get(), h->err.get());
+            pass.linearize(T, true);
             if (its == 0) MRS_TRY(pgo_error_sum(h, &e0));
         }
-        hipLaunchKernelGGL(k_pgo_gather, dim3(blocks_for(N, kThreads)), dim3(kThreads), 0, nullptr, ptr, ent, N, F, h->Hii.get(), h->gi.get(),
-                           h->gj.get(), h->Hpp.get(), h->gp.get());
+        pass.gather(0.0, false);
         m.mark(1);
         MRS_TRY((pgo_solve<6, 1>(h, 2, &m, 2)));                  // marks 2 .. 5
         hipLaunchKernelGGL(k_pgo_retract, dim3(blocks_for(N, kThreads)), dim3(kThreads), 0, nullptr, T, h->delta.get(), N, st);
@@ -1208,16 +1530,135 @@ int mrs_pgo_optimize(mrs_pgo* pgo, double eps, int32_t max_iterations, double* h
         }
     }
     if (F) {
-        hipLaunchKernelGGL(k_pgo_error, dim3(blocks_for(F, kThreads)), dim3(kThreads), 0, nullptr, T, fi, fj, h->Z.get(), F, h->err.get());
+        pass.error(T);
         MRS_TRY(pgo_error_sum(h, &e1));
     }
     MRS_TRY(pgo_download(T, N, h_T));
+    h->result_valid = true;
+    h->result_weighted = pass.weighted;
     h_info[0] = its;
     h_info[1] = converged;
     h_info[2] = max_delta;
     h_info[3] = e0;
     h_info[4] = e1;
     h_info[5] = h->topo[1].E;
+    return MRS_OK;
+}
+
+// Levenberg-Marquardt step control on the same solves.  Per solve the host reads the status words and two doubles.
+int mrs_pgo_optimize_lm(mrs_pgo* pgo, double eps, int32_t max_solves, double* h_T, double* h_info)
+{
+    MRS_REQUIRE(pgo && h_T && h_info, "null pointer");
+    MRS_REQUIRE(eps >= 0.0 && std::isfinite(eps), "eps must be finite and not negative");
+    MRS_REQUIRE(max_solves >= 1, "max_solves must be positive");
+    MRS_TRY(pgo_ready(pgo));
+    mrs_pgo* h = pgo;
+    h->result_valid = false;
+    const bool timing = mrs::dev_env("MRS_PGO_TIMING") != nullptr;
+    std::fill(h->stage_ms, h->stage_ms + 6, 0.0f);
+    {
+        mrs::StageMarks m1(timing && !h->init_valid, nullptr);
+        m1.mark(0);
+        MRS_TRY(pgo_stage1(h));
+        m1.mark(1);
+        if (m1) {
+            MRS_HIP_TRY(hipStreamSynchronize(nullptr));
+            h->stage_ms[0] = m1.ms(0);
+        }
+    }
+    const int N = h->g.N, F = h->F;
+    const FactorPass pass(h, pgo_has_noise(h) || h->kernel != MRS_PGO_KERNEL_NONE, h->kernel);
+    double *T = h->T.get(), *Tprev = h->Tprev.get();
+    Status* st = h->status.get();
+    double* d_pair = reinterpret_cast<double*>(st + 1);          // the cost after the step, twice the predicted decrease
+    const size_t pose_bytes = (size_t)N * 12 * sizeof(double);
+    MRS_HIP_TRY(hipMemcpyAsync(T, h->T0.get(), pose_bytes, hipMemcpyDeviceToDevice, nullptr));
+    pass.information();
+    double c0 = 0.0;
+    if (F) {
+        pass.error(T);
+        MRS_TRY(pgo_error_sum(h, &c0));
+    }
+    double c = c0, lambda = MRS_PGO_LM_LAMBDA_INITIAL, nu = 2.0, max_delta = 0.0;
+    int solves = 0, accepted = 0, converged = 0;
+    while (solves < max_solves) {
+        const bool first = solves == 0;
+        const double lam = first ? 0.0 : lambda;
+        mrs::StageMarks m(timing, nullptr);
+        MRS_HIP_TRY(hipMemsetAsync(st, 0, 2 * sizeof(Status), nullptr));
+        m.mark(0);
+        pass.linearize(T, !first);
+        pass.gather(lam, true);
+        m.mark(1);
+        MRS_TRY((pgo_solve<6, 1>(h, 2, &m, 2)));                  // marks 2 .. 5
+        hipLaunchKernelGGL(k_pgo_predicted, dim3(blocks_for(N, kThreads)), dim3(kThreads), 0, nullptr, h->delta.get(), h->diag.get(), h->gp.get(), lam,
+                           N, h->predv.get());
+        pgo_tree_sum(h->predv.get(), N, h->partial_p.get(), d_pair + 1);
+        MRS_HIP_TRY(hipMemcpyAsync(Tprev, T, pose_bytes, hipMemcpyDeviceToDevice, nullptr));
+        hipLaunchKernelGGL(k_pgo_retract, dim3(blocks_for(N, kThreads)), dim3(kThreads), 0, nullptr, T, h->delta.get(), N, st);
+        if (F) {
+            pass.error(T);
+            pgo_tree_sum(h->err.get(), F, h->partial.get(), d_pair);
+        }
+        m.mark(6);
+        MRS_HIP_TRY(hipGetLastError());
+        struct {
+            Status st;
+            double cost, pred2;
+        } hs;
+        static_assert(sizeof(hs) == 2 * sizeof(Status), "one copy of 32 bytes per solve");
+        MRS_HIP_TRY(hipMemcpy(&hs, st, sizeof(hs), hipMemcpyDeviceToHost));
+        if (m) {
+            h->stage_ms[1] += m.ms(0);
+            h->stage_ms[2] += m.ms(1) + m.ms(4);
+            h->stage_ms[3] += m.ms(2);
+            h->stage_ms[4] += m.ms(3);
+            h->stage_ms[5] += m.ms(5);
+        }
+        ++solves;
+        MRS_TRY(pgo_check_pivots(h, hs.st, 2));
+        double step;
+        std::memcpy(&step, &hs.st.max_delta, sizeof(double));
+        const double c_new = hs.cost, pred = 0.5 * hs.pred2;
+        if (!std::isfinite(step) || !std::isfinite(c_new)) {
+            mrs::set_error("Levenberg-Marquardt solve %d produced a step or a cost that is not finite", solves);
+            return MRS_ERR_NOT_CONVERGED;
+        }
+        const bool below = pred <= MRS_PGO_LM_PRED_FLOOR * c;    // the cost cannot resolve this step: neither the decision nor the gain
+        if (first || c_new <= c || below) {
+            if (!first) {
+                const double rho = below ? 1.0 : (c - c_new) / pred, q = 2.0 * rho - 1.0;
+                double factor = 1.0 - q * q * q;
+                if (!(factor > 1.0 / 3.0)) factor = 1.0 / 3.0;   // a rho that is not a number too
+                lambda = std::min(std::max(lambda * factor, MRS_PGO_LM_LAMBDA_MIN), MRS_PGO_LM_LAMBDA_MAX);
+                nu = 2.0;
+            }
+            ++accepted;
+            c = c_new;
+            max_delta = step;
+            if (max_delta < eps) {
+                converged = 1;
+                break;
+            }
+        } else {
+            MRS_HIP_TRY(hipMemcpyAsync(T, Tprev, pose_bytes, hipMemcpyDeviceToDevice, nullptr));
+            lambda = std::min(std::max(lambda * nu, MRS_PGO_LM_LAMBDA_MIN), MRS_PGO_LM_LAMBDA_MAX);
+            nu *= 2.0;
+        }
+    }
+    if (F) pass.error(T);                                        // the loops' state at the result
+    MRS_HIP_TRY(hipGetLastError());
+    MRS_TRY(pgo_download(T, N, h_T));
+    h->result_valid = true;
+    h->result_weighted = pass.weighted;
+    h_info[0] = solves;
+    h_info[1] = accepted;
+    h_info[2] = converged;
+    h_info[3] = max_delta;
+    h_info[4] = c0;
+    h_info[5] = c;
+    h_info[6] = h->topo[1].E;
+    h_info[7] = lambda;
     return MRS_OK;
 }
 

@@ -143,6 +143,119 @@ MRS_PGO_HD void factor_normal(const double* Ti, const double* Tj, const double* 
     }
 }
 
+// ------------------------------------------------------------------ per-factor noise and robust kernels
+//
+// A factor's information is wr on the nine rotation rows and the symmetric 3 x 3 Lt on the translation rows: what
+// evaluation_utils::convertToChordalNoise (evaluation_utils.cpp:333-366) makes of a Pose3 covariance C, wr = 1 / max(C00, C11, C22) and
+// Lt = Rhat (C[3:6, 3:6] + 0.01 I)^-1 Rhat^T.  The unit model is wr = 1, Lt = I.
+
+constexpr double kTranslationFloor = 0.01;                       // evaluation_utils.cpp:361
+enum Kernel : int { kKernelNone = 0, kKernelHuber = 1, kKernelCauchy = 2, kKernelGemanMcClure = 3 };
+
+// o [10] = 1 / max(C00, C11, C22) and P = C[3:6, 3:6] + 0.01 I of the covariance C [36]: the part of the conversion that needs no pose
+MRS_PGO_HD void covariance_terms(const double* C, double* o)
+{
+    const double m = C[0] > C[7] ? C[0] : C[7];
+    o[0] = 1.0 / (m > C[14] ? m : C[14]);
+    for (int r = 0; r < 3; ++r)
+        for (int c = 0; c < 3; ++c) o[1 + 3 * r + c] = C[6 * (3 + r) + 3 + c] + (r == c ? kTranslationFloor : 0.0);
+}
+
+// Lt [9] = Rhat P^-1 Rhat^T for the positive definite P [9] (row-major, by cofactors) and the rotation block of the pose Tk [12]
+MRS_PGO_HD void translation_information(const double* Tk, const double* P, double* Lt)
+{
+    double M[9], RM[9];
+    M[0] = P[4] * P[8] - P[5] * P[7]; M[1] = P[2] * P[7] - P[1] * P[8]; M[2] = P[1] * P[5] - P[2] * P[4];
+    M[3] = P[5] * P[6] - P[3] * P[8]; M[4] = P[0] * P[8] - P[2] * P[6]; M[5] = P[2] * P[3] - P[0] * P[5];
+    M[6] = P[3] * P[7] - P[4] * P[6]; M[7] = P[1] * P[6] - P[0] * P[7]; M[8] = P[0] * P[4] - P[1] * P[3];
+    const double det = (P[0] * M[0] + P[1] * M[3]) + P[2] * M[6];
+    for (int k = 0; k < 9; ++k) M[k] /= det;
+    for (int r = 0; r < 3; ++r)
+        for (int c = 0; c < 3; ++c) RM[3 * r + c] = (Tk[4 * r] * M[c] + Tk[4 * r + 1] * M[3 + c]) + Tk[4 * r + 2] * M[6 + c];
+    for (int r = 0; r < 3; ++r)
+        for (int c = 0; c <= r; ++c) {
+            const double v = (RM[3 * r] * Tk[4 * c] + RM[3 * r + 1] * Tk[4 * c + 1]) + RM[3 * r + 2] * Tk[4 * c + 2];
+            Lt[3 * r + c] = v;
+            Lt[3 * c + r] = v;
+        }
+}
+
+// e^T Lambda e
+MRS_PGO_HD double factor_sq_weighted(const double* e, double wr, const double* Lt)
+{
+    double s = 0.0, q = 0.0;
+    for (int k = 0; k < 9; ++k) s += e[k] * e[k];
+    for (int a = 0; a < 3; ++a) q += e[9 + a] * ((Lt[3 * a] * e[9] + Lt[3 * a + 1] * e[10]) + Lt[3 * a + 2] * e[11]);
+    return wr * s + q;
+}
+
+// the weight w(r) of a robust kernel with parameter k at the squared residual r2 = e^T Lambda e: rho'(r) = w(r) r
+MRS_PGO_HD double kernel_weight(int kernel, double k, double r2)
+{
+    if (kernel == kKernelHuber) {
+        const double r = sqrt(r2);
+        return r <= k ? 1.0 : k / r;
+    }
+    if (kernel == kKernelCauchy) return (k * k) / (k * k + r2);
+    if (kernel == kKernelGemanMcClure) {
+        const double s = (k * k) / (k * k + r2);
+        return s * s;
+    }
+    return 1.0;
+}
+
+// its cost rho(r); 0.5 r2 without a kernel
+MRS_PGO_HD double kernel_cost(int kernel, double k, double r2)
+{
+    if (kernel == kKernelHuber) {
+        const double r = sqrt(r2);
+        return r <= k ? 0.5 * r2 : k * (r - 0.5 * k);
+    }
+    if (kernel == kKernelCauchy) return 0.5 * (k * k) * log1p(r2 / (k * k));
+    if (kernel == kKernelGemanMcClure) return 0.5 * (k * k) * r2 / (k * k + r2);
+    return 0.5 * r2;
+}
+
+// factor_normal under the information (wr, Lt): Hii = Hi^T L Hi, Hij = Hi^T L Hj, gi = -Hi^T L e, gj = -Hj^T L e; e is not scaled.
+// Hj^T L Hj is block diagonal, wr hjj_diagonal(k) for the rotation and Lt for the translation, whenever Rj is a rotation.
+MRS_PGO_HD void factor_normal_weighted(const double* Ti, const double* Tj, const double* Z, double wr, const double* Lt, double* e, double* Hii,
+                                       double* Hij, double* gi, double* gj)
+{
+    double RiRij[9], Ai[36], Aj[36], LK[9], Le[3];
+    factor_error(Ti, Tj, Z, RiRij, e);
+    factor_jacobians(Ti, Tj, Z, RiRij, Ai, Aj);
+    const double* K = Ai + 27;                                   // rows 9..11 of Hi's rotation columns: Ri skew(tij)
+    for (int r = 0; r < 3; ++r) {
+        for (int c = 0; c < 3; ++c) LK[3 * r + c] = (Lt[3 * r] * K[c] + Lt[3 * r + 1] * K[3 + c]) + Lt[3 * r + 2] * K[6 + c];
+        Le[r] = (Lt[3 * r] * e[9] + Lt[3 * r + 1] * e[10]) + Lt[3 * r + 2] * e[11];
+    }
+    for (int a = 0; a < 3; ++a) {
+        for (int b = 0; b < 3; ++b) {
+            double sii = 0.0, sij = 0.0, kk = 0.0;
+            for (int k = 0; k < 9; ++k) sii += Ai[3 * k + a] * Ai[3 * k + b];
+            for (int k = 0; k < 9; ++k) sij += Ai[3 * k + a] * Aj[3 * k + b];
+            for (int r = 0; r < 3; ++r) kk += K[3 * r + a] * LK[3 * r + b];
+            Hii[6 * a + b] = wr * sii + kk;
+            Hij[6 * a + b] = wr * sij;
+            // rotation rows against the translation columns: -K^T Lt in Hii, +K^T Lt in Hij (Lt is symmetric)
+            Hii[6 * a + 3 + b] = -LK[3 * b + a];
+            Hii[6 * (3 + b) + a] = -LK[3 * b + a];
+            Hij[6 * a + 3 + b] = LK[3 * b + a];
+            Hij[6 * (3 + a) + b] = 0.0;
+            Hii[6 * (3 + a) + 3 + b] = Lt[3 * a + b];
+            Hij[6 * (3 + a) + 3 + b] = -Lt[3 * a + b];
+        }
+        double si = 0.0, sj = 0.0, sk = 0.0;
+        for (int k = 0; k < 9; ++k) si += Ai[3 * k + a] * e[k];
+        for (int k = 0; k < 9; ++k) sj += Aj[3 * k + a] * e[k];
+        for (int r = 0; r < 3; ++r) sk += K[3 * r + a] * Le[r];
+        gi[a] = -(wr * si + sk);
+        gj[a] = -(wr * sj);
+        gi[3 + a] = Le[a];
+        gj[3 + a] = -Le[a];
+    }
+}
+
 // the rotation closest to X [9] (row-major) in the Frobenius norm, U diag(1, 1, det(U V^T)) V^T of X = U S V^T, as
 // X V diag(1/s1, 1/s2, d/s3) V^T from the eigenpairs of X^T X (s3 the smallest singular value, d = sign det X).  X must have full rank.
 MRS_PGO_HD void closest_rotation(const double* X, double* R)

@@ -16,11 +16,31 @@ MAX_CHAINS, MAX_POSES = _lib.header_int("MRS_PGO_MAX_CHAINS"), _lib.header_int("
 MAX_LOOPS, MAX_SEPARATORS = _lib.header_int("MRS_PGO_MAX_LOOPS"), _lib.header_int("MRS_PGO_MAX_SEPARATORS")
 DEFAULT_SEGMENT_LENGTH = _lib.header_int("MRS_PGO_DEFAULT_SEGMENT_LENGTH")
 DEFAULT_EPS, DEFAULT_MAX_ITERATIONS = 1e-9, _lib.header_int("MRS_PGO_DEFAULT_MAX_ITERATIONS")
-_INFO = _lib.header_int("MRS_PGO_INFO_DOUBLES")
+_INFO, _INFO_LM = _lib.header_int("MRS_PGO_INFO_DOUBLES"), _lib.header_int("MRS_PGO_LM_INFO_DOUBLES")
+KERNELS = {None: _lib.header_int("MRS_PGO_KERNEL_NONE"), "none": _lib.header_int("MRS_PGO_KERNEL_NONE"),
+           "huber": _lib.header_int("MRS_PGO_KERNEL_HUBER"), "cauchy": _lib.header_int("MRS_PGO_KERNEL_CAUCHY"),
+           "geman_mcclure": _lib.header_int("MRS_PGO_KERNEL_GEMAN_MCCLURE")}
+# the reference's own factor noise (global_manager.cpp:103-109: loopNoise and odometryNoise), as Pose3 covariances: rotation xyz, then
+# translation xyz
+REFERENCE_LOOP_COVARIANCE = np.diag([1e-1, 1e-1, 1e-1, 1e-2, 1e-2, 1e-2])
+REFERENCE_ODOMETRY_COVARIANCE = np.eye(6)
 
 Result = collections.namedtuple("Result", "T iterations converged max_delta error_initial error_final separators")
 Result.__doc__ = """T float64 [N, 4, 4]; iterations done; converged (max|delta| < eps was met); the last max|delta|; 0.5 sum |e|^2 at the
 stage-1 values and at T (the reference's "Initial Error" and "GN Error"); the separators of the Gauss-Newton system."""
+ResultLM = collections.namedtuple("ResultLM", "T solves accepted converged max_delta cost_initial cost_final separators lam")
+ResultLM.__doc__ = """T float64 [N, 4, 4]; solves done and steps accepted; converged (an accepted step had max|delta| < eps); the last accepted
+max|delta|; the cost (sum 0.5 r^2 over the odometry factors + sum rho(r) over the loops) at the stage-1 values and at T; the separators; the
+final lambda."""
+
+
+def _covariances(C, n, name):
+    C = np.ascontiguousarray(C, np.float64)
+    if C.shape == (6, 6):
+        C = np.ascontiguousarray(np.broadcast_to(C, (n, 6, 6)))
+    if C.shape != (n, 6, 6):
+        raise ValueError("%s must be [6, 6] or [%d, 6, 6]" % (name, n))
+    return C
 
 
 def _inverse(X):
@@ -89,14 +109,40 @@ class PoseGraph:
         Z = _poses(Z, "Z") if np.size(Z) else np.zeros((0, 4, 4))
         _lib.load().mrs_pgo_set_odometry(self._h, Z if Z.size else None, Z.shape[0])
 
-    def add_loops(self, i, j, Z):
+    def set_odometry_noise(self, C):
+        """one Pose3 covariance [6, 6] per odometry factor (or one for all); None clears them"""
+        if C is None:
+            _lib.load().mrs_pgo_set_odometry_noise(self._h, None, 0)
+            return
+        n = self.n_poses - self.chain_lengths.size
+        C = _covariances(C, n, "C")
+        _lib.load().mrs_pgo_set_odometry_noise(self._h, C if n else None, n)
+
+    def add_loops(self, i, j, Z, C=None):
+        """C: a Pose3 covariance [6, 6] per loop (or one for all); None leaves these loops at the unit model"""
         i, j = np.ascontiguousarray(i, np.int32).reshape(-1), np.ascontiguousarray(j, np.int32).reshape(-1)
         if not i.size:
             return
         Z = _poses(Z, "Z")
         if not i.size == j.size == Z.shape[0]:
             raise ValueError("i, j and Z must have one entry per loop")
-        _lib.load().mrs_pgo_add_loops(self._h, i, j, Z, i.size)
+        if C is None:
+            _lib.load().mrs_pgo_add_loops(self._h, i, j, Z, i.size)
+        else:
+            _lib.load().mrs_pgo_add_loops_noise(self._h, i, j, Z, _covariances(C, i.size, "C"), i.size)
+
+    def set_loop_kernel(self, kernel, k=1.0):
+        """a robust kernel on the loop factors for optimize(method="lm"): None, "huber", "cauchy" or "geman_mcclure" with parameter k"""
+        if kernel not in KERNELS:
+            raise ValueError("kernel must be one of %s" % sorted(n for n in KERNELS if n))
+        _lib.load().mrs_pgo_set_loop_kernel(self._h, KERNELS[kernel], float(k))
+
+    def loop_state(self):
+        """(w, r2) float64 [loops]: the kernel's weight and e^T L e of every loop at the last result"""
+        n = len(self)
+        w, r2 = np.zeros(max(n, 1)), np.zeros(max(n, 1))
+        _lib.load().mrs_pgo_get_loop_state(self._h, w, r2, w.size)
+        return w[:n], r2[:n]
 
     def clear(self):
         _lib.load().mrs_pgo_clear_loops(self._h)
@@ -113,8 +159,16 @@ class PoseGraph:
         _lib.load().mrs_pgo_initialize(self._h, T)
         return T
 
-    def optimize(self, eps=DEFAULT_EPS, max_iterations=DEFAULT_MAX_ITERATIONS):
-        """both stages -> Result; eps = 0 runs exactly max_iterations steps"""
+    def optimize(self, eps=DEFAULT_EPS, max_iterations=DEFAULT_MAX_ITERATIONS, method="gn"):
+        """both stages -> Result; eps = 0 runs exactly max_iterations steps.  method="lm": Levenberg-Marquardt step control, max_iterations
+        counts the solves (rejected ones too) -> ResultLM"""
+        if method not in ("gn", "lm"):
+            raise ValueError('method must be "gn" or "lm"')
+        if method == "lm":
+            T, info = np.zeros((self.n_poses, 4, 4)), np.zeros(_INFO_LM)
+            _lib.load().mrs_pgo_optimize_lm(self._h, float(eps), int(max_iterations), T, info)
+            return ResultLM(T, int(info[0]), int(info[1]), bool(info[2]), float(info[3]), float(info[4]), float(info[5]), int(info[6]),
+                            float(info[7]))
         T, info = np.zeros((self.n_poses, 4, 4)), np.zeros(_INFO)
         _lib.load().mrs_pgo_optimize(self._h, float(eps), int(max_iterations), T, info)
         return Result(T, int(info[0]), bool(info[1]), float(info[2]), float(info[3]), float(info[4]), int(info[5]))

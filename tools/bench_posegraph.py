@@ -6,7 +6,12 @@ line and, with --out, writes it to a file.  Run on its own.
 Both baselines are measured in the same run, never taken from the new code:
   (a) the NumPy / scipy restatement (tests/golden/posegraph_restate.py, sparse LU per iteration) with the same stop rule;
   (b) the restatement with 200 unconditional iterations, which is what the reference's loop does (evaluation_utils.cpp:321).
-gtsam itself is not in the reference tree and cannot be timed here.  Every scene also checks the result against (a)."""
+gtsam itself is not in the reference tree and cannot be timed here.  Every scene also checks the result against (a).
+
+The `robust` legs (--method, --noise, --kernel) run the same scenes with and without 10 % gross outliers among the loops
+(5 m / 0.5 rad) through the chosen optimiser, noise and loop kernel, at the default segment length.  Their baselines, again of the same run:
+the plain `optimize()` on the same graph (time per Gauss-Newton iteration, and whether it converged) and the restatement
+tests/golden/posegraph_robust_restate.py on one thread."""
 import argparse
 import json
 import os
@@ -61,8 +66,99 @@ def make_scene(n_loops, seed=0):
     return (POSES,) * ROBOTS, odom, li.astype(np.int32), lj.astype(np.int32), lZ
 
 
+def with_outliers(scene, fraction, seed=1):
+    """the scene with `fraction` of its loops (never the ones that join the robots) right-multiplied by a pose of N(0, 0.5) rad, N(0, 5) m"""
+    import posegraph_restate as R
+    chain_lengths, odom, li, lj, lZ = scene
+    rng = np.random.default_rng(seed)
+    n = int(round(fraction * li.size))
+    lZ = lZ.copy()
+    for u in (rng.choice(np.arange(ROBOTS - 1, li.size), n, replace=False) if n else ()):
+        P = np.eye(4)
+        P[:3, :3] = R.exp_so3(rng.normal(0, 0.5, 3))
+        P[:3, 3] = rng.normal(0, 5.0, 3)
+        lZ[u] = lZ[u] @ P
+    return chain_lengths, odom, li, lj, lZ
+
+
+def robust_legs(a, scene, reps):
+    """{outlier fraction: figures} for one scene"""
+    import posegraph_robust_restate as RR
+    from mr_slam_amd import posegraph
+    kinds = {"none": RR.NONE, "huber": RR.HUBER, "cauchy": RR.CAUCHY, "geman_mcclure": RR.GEMAN_MCCLURE}
+    out = {}
+    for fraction in a.outliers:
+        chain_lengths, odom, li, lj, lZ = s = with_outliers(scene, fraction)
+        oC = np.tile(posegraph.REFERENCE_ODOMETRY_COVARIANCE, (odom.shape[0], 1, 1)) if a.noise == "reference" else None
+        lC = np.tile(posegraph.REFERENCE_LOOP_COVARIANCE, (li.size, 1, 1)) if a.noise == "reference" else None
+
+        def timed(g, call):
+            call()                                               # warm: allocations
+            wall, stages = [], []
+            for _ in range(reps):
+                g.set_prior(np.eye(4))                           # stage 1 runs again, as after a new closure
+                t0 = time.perf_counter()
+                r = call()
+                wall.append((time.perf_counter() - t0) * 1e3)
+                stages.append(g.stage_ms())
+            return r, float(np.median(wall)), np.median(np.array(stages), axis=0)
+
+        e = {"loops": int(li.size), "outliers": int(round(fraction * li.size)), "method": a.method, "noise": a.noise, "kernel": a.kernel, "kernel_k": a.kernel_k}
+        plain = posegraph.PoseGraph(chain_lengths)
+        plain.set_odometry(odom)
+        plain.add_loops(li, lj, lZ)
+        try:
+            r, ms, st = timed(plain, plain.optimize)
+            e["parent_optimize"] = {"wall_ms": ms, "iterations": r.iterations, "converged": r.converged, "ms_per_iteration": ms / r.iterations,
+                                    "ms_per_iteration_without_stage1": (ms - float(st[0])) / r.iterations,
+                                    "stages_ms": {k: float(v) for k, v in zip(STAGES, st)}}
+        except Exception as err:                                 # a step that is not finite is a status, and a finding
+            e["parent_optimize"] = {"error": str(err)}
+        g = posegraph.PoseGraph(chain_lengths)
+        g.set_odometry(odom)
+        if oC is not None:
+            g.set_odometry_noise(oC)
+        g.add_loops(li, lj, lZ, lC)
+        if a.kernel != "none":
+            g.set_loop_kernel(a.kernel, a.kernel_k)
+        if a.method == "lm":
+            r, ms, st = timed(g, lambda: g.optimize(method="lm"))
+            n, e["solves"], e["accepted"], e["lambda"] = r.solves, r.solves, r.accepted, r.lam
+            e["cost_initial"], e["cost_final"] = r.cost_initial, r.cost_final
+        else:
+            r, ms, st = timed(g, g.optimize)
+            n, e["solves"], e["accepted"] = r.iterations, r.iterations, r.iterations
+            e["cost_initial"], e["cost_final"] = r.error_initial, r.error_final
+        e.update({"wall_ms": ms, "converged": r.converged, "ms_per_solve": ms / n, "ms_per_solve_without_stage1": (ms - float(st[0])) / n,
+                  "stages_ms": {k: float(v) for k, v in zip(STAGES, st)}, "separators": r.separators})
+        if "error" not in e["parent_optimize"]:
+            e["ms_per_solve_over_parent_ms_per_iteration"] = e["ms_per_solve_without_stage1"] / e["parent_optimize"]["ms_per_iteration_without_stage1"]
+        w, _ = g.loop_state()
+        e["loops_below_weight_0.1"] = int((w < 0.1).sum())
+        if a.restatement:
+            t0 = time.perf_counter()
+            if a.method == "lm":
+                want = RR.lm_optimize(*s, oC=oC, lC=None if lC is None else list(lC), kernel=kinds[a.kernel], k=a.kernel_k)
+                e["restatement"] = {"solves": want.solves, "accepted": want.accepted, "converged": want.converged}
+            else:
+                want = RR.gn_optimize(*s, oC=oC, lC=None if lC is None else list(lC))
+                e["restatement"] = {"solves": want.iterations, "accepted": want.iterations, "converged": want.converged}
+            e["restatement"]["wall_ms"] = (time.perf_counter() - t0) * 1e3
+            e["restatement"]["max_abs_T"] = float(np.abs(r.T - want.T).max())
+        out["%g" % fraction] = e
+        print("robust loops %d outliers %g: %.1f ms, %d solves (%d accepted), converged %s" % (li.size, fraction, ms, e["solves"], e["accepted"], r.converged),
+              file=sys.stderr, flush=True)
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--method", choices=("gn", "lm"), help="adds the robust legs: the optimiser they run")
+    ap.add_argument("--noise", choices=("none", "reference"), default="none", help="robust legs: the reference's loopNoise / odometryNoise on every factor")
+    ap.add_argument("--kernel", choices=("none", "huber", "cauchy", "geman_mcclure"), default="none", help="robust legs: the kernel on the loops")
+    ap.add_argument("--kernel-k", type=float, default=1.0)
+    ap.add_argument("--outliers", type=float, nargs="*", default=[0.0, 0.1], help="robust legs: fractions of grossly wrong loops")
+    ap.add_argument("--no-restatement", dest="restatement", action="store_false", help="robust legs: skip the one-thread restatement")
     ap.add_argument("--out")
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--loops", type=int, nargs="*", default=list(LOOPS))
@@ -122,6 +218,8 @@ def main():
         r["optimize_200_iterations_wall_ms"] = (time.perf_counter() - t0) * 1e3
         r["optimize_200_vs_stop_rule_max_abs"] = float(np.abs(fixed.T - want.T).max())
         r["error_initial"], r["error_final"] = got.error_initial, got.error_final
+        if a.method:
+            r["robust"] = robust_legs(a, scene, a.reps)
         out["scenes"][str(L)] = r
     print(json.dumps(out))
     if a.out:
