@@ -43,9 +43,30 @@ public:
         return order;
     }
 
+    // the upper quantile q of chi-squared with 6 degrees of freedom: the threshold of a handle with covariances
+    static double chiSquaredUpper(double q)
+    {
+        static const std::pair<int, double> table[] = {{900, 10.645}, {950, 12.592}, {990, 16.812}, {999, 22.458}};
+        const double scaled = q * 1000.0;
+        for (const auto& row : table)
+            if (scaled > row.first - 1e-9 && scaled < row.first + 1e-9) return row.second;
+        throw std::invalid_argument("PairwiseConsistency: quantile " + std::to_string(q) + " is not supported");
+    }
+
+    struct Threshold {
+        double value;
+    };
+    // a handle whose threshold is given as a number (chiSquaredUpper(q) for a handle with covariances)
+    PairwiseConsistency(int capacity, Threshold threshold, int device = 0) { create(capacity, threshold.value, device); }
+
     explicit PairwiseConsistency(int capacity = MRS_PCM_MAX_LOOPS, double pcm_threshold = 0.01, int device = 0)
     {
-        const double threshold = chiSquaredThreshold(pcm_threshold);
+        create(capacity, chiSquaredThreshold(pcm_threshold), device);
+    }
+
+private:
+    void create(int capacity, double threshold, int device)
+    {
         check(mrs_ctx_create(device, &ctx_), "mrs_ctx_create");
         const int st = mrs_pcm_create(ctx_, capacity, threshold, &h_);
         if (st != MRS_OK) {
@@ -54,6 +75,8 @@ public:
             throw std::runtime_error("mrs_pcm_create: " + why);
         }
     }
+
+public:
     ~PairwiseConsistency()
     {
         mrs_pcm_destroy(h_);
@@ -69,6 +92,19 @@ public:
     }
     // n loops: Z [n][16], the measured pose of B_kb[u] in the frame of A_ia[u]
     void addLoops(const int32_t* ia, const int32_t* kb, const double* Z, int n) { check(mrs_pcm_add_loops(h_, ia, kb, Z, n), "mrs_pcm_add_loops"); }
+    // Consistency under covariances, after setTrajectories; clears the loops.  mode: MRS_PCM_COV_SPAN (recommended),
+    // MRS_PCM_COV_REFERENCE or MRS_PCM_COV_NONE.  QA [na - 1][36], QB [nb - 1][36]: the covariance of every odometry step, first [36]: that
+    // of the first pose (REFERENCE only); row-major 6x6 in gtsam's Pose3 tangent order, nullptr: FIXED_COVARIANCE.  The threshold is then
+    // compared with the squared Mahalanobis distance: construct with chiSquaredUpper(q) through the threshold constructor.
+    void setCovariances(int mode, const double* QA = nullptr, const double* QB = nullptr, const double* first = nullptr)
+    {
+        check(mrs_pcm_set_covariances(h_, mode, QA, QB, first), "mrs_pcm_set_covariances");
+    }
+    // n loops with a covariance each, C [n][36] (nullptr: FIXED_COVARIANCE)
+    void addLoops(const int32_t* ia, const int32_t* kb, const double* Z, const double* C, int n)
+    {
+        check(mrs_pcm_add_loops_cov(h_, ia, kb, Z, C, n), "mrs_pcm_add_loops_cov");
+    }
     void clearLoops() { check(mrs_pcm_clear_loops(h_), "mrs_pcm_clear_loops"); }
     int size() const
     {

@@ -1059,8 +1059,36 @@ int mrs_pcm_get_matrix(mrs_pcm* pcm, uint8_t* h_dense);
  * used without the geometry.  Asymmetric input or a set diagonal: MRS_ERR_ARG.  Such vertices have no distances, and loops cannot be
  * appended to them: both are MRS_ERR_ARG until the loops are cleared. */
 int mrs_pcm_set_matrix(mrs_pcm* pcm, int32_t count, const uint8_t* h_dense);
-/* the consistency distances, double [count][count], recomputed by this call (they are never stored): symmetric, zero diagonal */
+/* the consistency distances, double [count][count], recomputed by this call (they are never stored): symmetric, zero diagonal.  They are
+ * the quantity compared with the threshold: |Logmap| without covariances, the squared Mahalanobis distance with them (NaN where that is
+ * not finite or the cycle covariance has no Cholesky factor). */
 int mrs_pcm_get_distances(mrs_pcm* pcm, double* h_d);
+
+/* Consistency under covariances: loops u < v are consistent iff xi^T Sigma_E^-1 xi < threshold, xi = Logmap of the cycle
+ * pose and Sigma_E the covariance computeConsistencyError propagates around the cycle (pairwise_consistency.cpp:99-128) from the odometry
+ * and loop covariances; the threshold is then an upper chi-squared quantile with 6 degrees of freedom.  Every covariance is a row-major
+ * double [6][6] in gtsam's Pose3 tangent order (rotation xyz, translation xyz) of which the lower triangle is read.
+ *   MRS_PCM_COV_SPAN      : the trajectory part is the odometry between the two poses alone, S_i,i = 0,
+ *                           S_i,m+1 = Ad(o_m^-1) S_i,m Ad(o_m^-1)^T + Q_m (the test of the PCM paper; recommended);
+ *   MRS_PCM_COV_REFERENCE : the reference's lines: marginals from the chain start (buildTrajectory, M_0 = first), and
+ *                           Ad(r^-1) M_i Ad(r^-1)^T + M_j for the pose between i and j, which treats two correlated marginals as
+ *                           independent and grows with the distance from the start;
+ *   MRS_PCM_COV_NONE      : back to the plain test. */
+#define MRS_PCM_COV_NONE 0
+#define MRS_PCM_COV_SPAN 1
+#define MRS_PCM_COV_REFERENCE 2
+/* After mrs_pcm_set_trajectories (which resets the mode to NONE); clears the loops.  h_QA double [na - 1][6][6] and h_QB [nb - 1][6][6]: the
+ * covariance of each odometry step X_m^-1 X_m+1; NULL: FIXED_COVARIANCE (graph_types.h:79-85) per step, and NULL is required for a
+ * trajectory of one pose.  h_first double [6][6]: the covariance of the first pose of either trajectory (REFERENCE only); NULL:
+ * FIXED_COVARIANCE.  A bad mode, an entry that is not finite or a matrix that is not positive definite: MRS_ERR_ARG, nothing changes. */
+int mrs_pcm_set_covariances(mrs_pcm* pcm, int32_t mode, const double* h_QA, const double* h_QB, const double* h_first);
+/* mrs_pcm_add_loops with a covariance per loop, h_C double [n][6][6]; NULL (or plain mrs_pcm_add_loops on a handle with covariances):
+ * FIXED_COVARIANCE each.  h_C on a handle in mode NONE, an entry that is not finite or a matrix that is not positive definite:
+ * MRS_ERR_ARG, nothing is added. */
+int mrs_pcm_add_loops_cov(mrs_pcm* pcm, const int32_t* h_ia, const int32_t* h_kb, const double* h_Z, const double* h_C, int32_t n);
+/* One pair recomputed in one host thread: h_xi double [6] = Logmap of the cycle pose of (min, max), h_cov double [6][6] = Sigma_E (the
+ * identity in mode NONE), h_d = the compared quantity.  u == v or a loop that does not exist: MRS_ERR_ARG. */
+int mrs_pcm_get_pair(mrs_pcm* pcm, int32_t u, int32_t v, double* h_xi, double* h_cov, double* h_d);
 
 /* ------------------------------------------------------------------------------------
  * Mapping-side DiSCO matcher

@@ -18,8 +18,12 @@
 //             arrival).  Starts below it were evaluated exactly as the sequential heuristic would; those above it are evaluated again in the
 //             next round.  Every round but the last raises the best size, so there are at most size + 1 of them.  The member list comes
 //             from running the last winner again in one wave.
+//   covariances : after mrs_pcm_set_covariances the records and rows come from k_pcm_records_cov / k_pcm_rows_cov (pcm_cov.hpp, DESIGN.md
+//             4.24): the same tiling, the squared Mahalanobis distance of the cycle pose under the covariance propagated around the cycle,
+//             from per-pose world-frame prefixes built once on the host.  A handle without covariances runs the kernels above, untouched.
 #include "common.hpp"
 #include "pcm_pose.hpp"
+#include "pcm_cov.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -31,6 +35,7 @@ using u64 = unsigned long long;
 constexpr int kMaxLoops = MRS_PCM_MAX_LOOPS;
 constexpr int kThreads = 256, kWaves = kThreads / 64;
 constexpr int kRec = mrs::pcm::kRecord;
+constexpr int kRecCov = mrs::pcm::kCovRecord, kSym = mrs::pcm::kSym;
 constexpr u64 kNoWinner = ~0ull;
 static_assert(kMaxLoops == 64 * 64, "the candidate set of k_pcm_greedy is one 64-bit word per lane");
 
@@ -71,6 +76,53 @@ __global__ __launch_bounds__(kThreads) void k_pcm_rows(const double* __restrict_
     if (v < L && v != u) bit = pair_distance_of(rec, u, v) < threshold;      // false for a distance that is not a number
     const u64 word = __ballot(bit);
     if (lane == 0) rows[(size_t)u * words + w] = word;
+}
+
+// ---- the covariance instantiations: the same tiling, a record of kRecCov doubles and the two prefix tables
+__global__ __launch_bounds__(kThreads) void k_pcm_records_cov(const double* __restrict__ XA, const double* __restrict__ XB,
+                                                              const int* __restrict__ ia, const int* __restrict__ kb, const double* __restrict__ Z,
+                                                              const double* __restrict__ Csym, int n, int first, double* __restrict__ rec)
+{
+    const int t = blockIdx.x * kThreads + threadIdx.x;
+    if (t >= n) return;
+    double r[kRecCov], c[kSym];
+#pragma unroll
+    for (int e = 0; e < kSym; ++e) c[e] = Csym[(size_t)t * kSym + e];
+    mrs::pcm::loop_record_cov(XA + (size_t)ia[t] * 16, Z + (size_t)t * 16, XB + (size_t)kb[t] * 16, c, ia[t], kb[t], r);
+#pragma unroll
+    for (int i = 0; i < kRecCov; ++i) rec[(size_t)(first + t) * kRecCov + i] = r[i];
+}
+
+// the squared Mahalanobis distance of the pair, always evaluated as (min, max); the records and tables are read where they lie
+__device__ __forceinline__ double pair_mahalanobis2_of(const double* __restrict__ rec, const double* __restrict__ WA, const double* __restrict__ WB,
+                                                       int mode, int u, int v)
+{
+    const int a = min(u, v), b = max(u, v);
+    return mrs::pcm::pair_mahalanobis2(rec + (size_t)a * kRecCov, rec + (size_t)b * kRecCov, WA, WB, mode);
+}
+
+__global__ __launch_bounds__(kThreads) void k_pcm_rows_cov(const double* __restrict__ rec, const double* __restrict__ WA,
+                                                           const double* __restrict__ WB, int mode, int L, double threshold, int row0, int nrows,
+                                                           int word0, int nwords, int words, u64* __restrict__ rows)
+{
+    const int lane = threadIdx.x & 63;
+    const long long tile = (long long)blockIdx.x * kWaves + (threadIdx.x >> 6);
+    if (tile >= (long long)nrows * nwords) return;               // the same for a whole wave
+    const int u = row0 + (int)(tile / nwords), w = word0 + (int)(tile % nwords);
+    const int v = 64 * w + lane;
+    bool bit = false;
+    if (v < L && v != u) bit = pair_mahalanobis2_of(rec, WA, WB, mode, u, v) < threshold;      // false for NaN
+    const u64 word = __ballot(bit);
+    if (lane == 0) rows[(size_t)u * words + w] = word;
+}
+
+__global__ __launch_bounds__(kThreads) void k_pcm_distances_cov(const double* __restrict__ rec, const double* __restrict__ WA,
+                                                                const double* __restrict__ WB, int mode, int L, double* __restrict__ d)
+{
+    const long long e = (long long)blockIdx.x * kThreads + threadIdx.x;
+    if (e >= (long long)L * L) return;
+    const int u = (int)(e / L), v = (int)(e % L);
+    d[e] = u == v ? 0.0 : pair_mahalanobis2_of(rec, WA, WB, mode, u, v);
 }
 
 // d [L][L], a thread per entry
@@ -367,6 +419,11 @@ struct mrs_pcm {
     bool given_matrix = false;               // the vertices came from mrs_pcm_set_matrix: no records behind them
     bool degrees_stale = true;
     mrs::DeviceBuffer<double> XA, XB, rec;
+    // covariances (mrs_pcm_set_covariances): the mode, the host poses the prefixes are built from, the per-pose prefix
+    // tables on both sides (the host side serves mrs_pcm_get_pair) and the wider records
+    int cov_mode = MRS_PCM_COV_NONE;
+    std::vector<double> h_XA, h_XB, h_WA, h_WB;
+    mrs::DeviceBuffer<double> WA, WB, rec_cov;
     mrs::DeviceBuffer<u64> rows, elig, winner;
     mrs::DeviceBuffer<int> deg, list;
     // mrs_pcm_solve_exact only, allocated by its first call and sized by the matrix it met (ExactLayout)
@@ -391,14 +448,47 @@ int pcm_clear(mrs_pcm* p)
 int pcm_fill_rows(mrs_pcm* p, int L0, int L1)
 {
     const int nw = (L1 + 63) / 64;
+    const int w0 = L0 / 64;
+    if (p->cov_mode != MRS_PCM_COV_NONE) {
+        hipLaunchKernelGGL(k_pcm_rows_cov, dim3(blocks_for((long long)(L1 - L0) * nw, kWaves)), dim3(kThreads), 0, nullptr, p->rec_cov.get(),
+                           p->WA.get(), p->WB.get(), p->cov_mode, L1, p->threshold, L0, L1 - L0, 0, nw, p->words, p->rows.get());
+        if (L0 > 0)
+            hipLaunchKernelGGL(k_pcm_rows_cov, dim3(blocks_for((long long)L0 * (nw - w0), kWaves)), dim3(kThreads), 0, nullptr, p->rec_cov.get(),
+                               p->WA.get(), p->WB.get(), p->cov_mode, L1, p->threshold, 0, L0, w0, nw - w0, p->words, p->rows.get());
+        MRS_HIP_TRY(hipGetLastError());
+        return MRS_OK;
+    }
     hipLaunchKernelGGL(k_pcm_rows, dim3(blocks_for((long long)(L1 - L0) * nw, kWaves)), dim3(kThreads), 0, nullptr, p->rec.get(), L1, p->threshold,
                        L0, L1 - L0, 0, nw, p->words, p->rows.get());
-    const int w0 = L0 / 64;
     if (L0 > 0)
         hipLaunchKernelGGL(k_pcm_rows, dim3(blocks_for((long long)L0 * (nw - w0), kWaves)), dim3(kThreads), 0, nullptr, p->rec.get(), L1,
                            p->threshold, 0, L0, w0, nw - w0, p->words, p->rows.get());
     MRS_HIP_TRY(hipGetLastError());
     return MRS_OK;
+}
+
+// ---- host side of the covariances
+// [n][6][6] lower triangles (nullptr: FIXED_COVARIANCE each) -> [n][21]; false when one is not finite or not positive definite
+bool pcm_sym_inputs(const double* h, size_t n, std::vector<double>* out)
+{
+    out->resize(n * kSym);
+    for (size_t e = 0; e < n; ++e) {
+        double* s = out->data() + e * kSym;
+        if (!h) {
+            mrs::pcm::sym_fixed(s);
+            continue;
+        }
+        mrs::pcm::sym_from_lower(h + e * 36, s);
+        if (!mrs::pcm::sym_is_pd(s)) return false;
+    }
+    return true;
+}
+
+// the world-frame prefixes of one trajectory: W_0 = base, W_m+1 = W_m + Ad(X_m+1) Q_m Ad(X_m+1)^T, in sequence
+void pcm_prefixes(const std::vector<double>& X, int n, const std::vector<double>& Q, const double* base, std::vector<double>* W)
+{
+    W->assign((size_t)n * kSym, 0.0);
+    mrs::pcm::prefix_table(X.data(), n, Q.data(), base, W->data());
 }
 
 // ---- host side of the exact search
@@ -491,6 +581,69 @@ int pcm_exact_phase(mrs_pcm* p, const ExactLayout& lay, int phase, int omega, in
     return MRS_ERR_HIP;
 }
 
+// mrs_pcm_add_loops and mrs_pcm_add_loops_cov: h_C [n][6][6] or nullptr (FIXED_COVARIANCE each; not read at all without a covariance mode)
+int pcm_add_loops(mrs_pcm* pcm, const int32_t* h_ia, const int32_t* h_kb, const double* h_Z, const double* h_C, int32_t n)
+{
+    MRS_REQUIRE(pcm, "null pointer");
+    MRS_REQUIRE(n >= 0, "n must not be negative");
+    if (n == 0) return MRS_OK;
+    MRS_REQUIRE(h_ia && h_kb && h_Z, "null pointer");
+    MRS_REQUIRE(pcm->na > 0, "set the trajectories first");
+    MRS_REQUIRE(!pcm->given_matrix, "the vertices came from mrs_pcm_set_matrix: clear them first");
+    MRS_REQUIRE(!h_C || pcm->cov_mode != MRS_PCM_COV_NONE, "loop covariances need mrs_pcm_set_covariances first");
+    for (int t = 0; t < n; ++t)
+        MRS_REQUIRE(h_ia[t] >= 0 && h_ia[t] < pcm->na && h_kb[t] >= 0 && h_kb[t] < pcm->nb, "a loop names a pose outside its trajectory");
+    if ((long long)pcm->L + n > pcm->capacity) {
+        mrs::set_error("%d loops held and %d more exceed the capacity of %d", pcm->L, n, pcm->capacity);
+        return MRS_ERR_UNSUPPORTED;
+    }
+    if (pcm->cov_mode != MRS_PCM_COV_NONE) {
+        std::vector<double> Csym;
+        MRS_REQUIRE(pcm_sym_inputs(h_C, (size_t)n, &Csym), "a loop covariance is not finite or not positive definite");
+        MRS_HIP_TRY(hipSetDevice(pcm->ctx->device));
+        // one upload: Z [n][16] | C [n][21] doubles | ia [n] | kb [n]
+        const size_t b_Z = (size_t)n * 16 * sizeof(double), b_C = (size_t)n * kSym * sizeof(double), b_idx = (size_t)n * sizeof(int32_t);
+        mrs::Scratch in;
+        MRS_TRY(in.alloc(b_Z + b_C + 2 * b_idx, nullptr));
+        double* d_Z = in.as<double>();
+        double* d_C = d_Z + (size_t)n * 16;
+        int* d_ia = reinterpret_cast<int*>(in.as<char>() + b_Z + b_C);
+        int* d_kb = d_ia + n;
+        MRS_HIP_TRY(hipMemcpy(d_Z, h_Z, b_Z, hipMemcpyHostToDevice));
+        MRS_HIP_TRY(hipMemcpy(d_C, Csym.data(), b_C, hipMemcpyHostToDevice));
+        MRS_HIP_TRY(hipMemcpy(d_ia, h_ia, b_idx, hipMemcpyHostToDevice));
+        MRS_HIP_TRY(hipMemcpy(d_kb, h_kb, b_idx, hipMemcpyHostToDevice));
+        const int L0 = pcm->L, L1 = L0 + n;
+        hipLaunchKernelGGL(k_pcm_records_cov, dim3(blocks_for(n, kThreads)), dim3(kThreads), 0, nullptr, pcm->XA.get(), pcm->XB.get(), d_ia, d_kb,
+                           d_Z, d_C, n, L0, pcm->rec_cov.get());
+        MRS_TRY(pcm_fill_rows(pcm, L0, L1));
+        MRS_HIP_TRY(hipStreamSynchronize(nullptr));
+        pcm->L = L1;
+        pcm->degrees_stale = true;
+        return MRS_OK;
+    }
+    MRS_HIP_TRY(hipSetDevice(pcm->ctx->device));
+    // one upload: Z [n][16] doubles | ia [n] | kb [n]
+    const size_t b_Z = (size_t)n * 16 * sizeof(double), b_idx = (size_t)n * sizeof(int32_t);
+    mrs::Scratch in;
+    int st = in.alloc(b_Z + 2 * b_idx, nullptr);
+    if (st != MRS_OK) return st;
+    double* d_Z = in.as<double>();
+    int* d_ia = reinterpret_cast<int*>(in.as<char>() + b_Z);
+    int* d_kb = d_ia + n;
+    MRS_HIP_TRY(hipMemcpy(d_Z, h_Z, b_Z, hipMemcpyHostToDevice));
+    MRS_HIP_TRY(hipMemcpy(d_ia, h_ia, b_idx, hipMemcpyHostToDevice));
+    MRS_HIP_TRY(hipMemcpy(d_kb, h_kb, b_idx, hipMemcpyHostToDevice));
+    const int L0 = pcm->L, L1 = L0 + n;
+    hipLaunchKernelGGL(k_pcm_records, dim3(blocks_for(n, kThreads)), dim3(kThreads), 0, nullptr, pcm->XA.get(), pcm->XB.get(), d_ia, d_kb, d_Z, n, L0,
+                       pcm->rec.get());
+    if ((st = pcm_fill_rows(pcm, L0, L1)) != MRS_OK) return st;
+    MRS_HIP_TRY(hipStreamSynchronize(nullptr));
+    pcm->L = L1;
+    pcm->degrees_stale = true;
+    return MRS_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -549,42 +702,89 @@ int mrs_pcm_set_trajectories(mrs_pcm* pcm, const double* h_XA, int32_t na, const
     MRS_HIP_TRY(hipMemcpy(pcm->XB.get(), h_XB, (size_t)nb * 16 * sizeof(double), hipMemcpyHostToDevice));
     pcm->na = na;
     pcm->nb = nb;
+    pcm->cov_mode = MRS_PCM_COV_NONE;
+    pcm->h_XA.assign(h_XA, h_XA + (size_t)na * 16);
+    pcm->h_XB.assign(h_XB, h_XB + (size_t)nb * 16);
+    return MRS_OK;
+}
+
+int mrs_pcm_set_covariances(mrs_pcm* pcm, int32_t mode, const double* h_QA, const double* h_QB, const double* h_first)
+{
+    MRS_REQUIRE(pcm, "null pointer");
+    MRS_REQUIRE(mode == MRS_PCM_COV_NONE || mode == MRS_PCM_COV_SPAN || mode == MRS_PCM_COV_REFERENCE, "mode must be MRS_PCM_COV_NONE, _SPAN or _REFERENCE");
+    MRS_REQUIRE(pcm->na > 0, "set the trajectories first");
+    MRS_REQUIRE(pcm->na > 1 || !h_QA, "a trajectory of one pose has no odometry covariances");
+    MRS_REQUIRE(pcm->nb > 1 || !h_QB, "a trajectory of one pose has no odometry covariances");
+    MRS_HIP_TRY(hipSetDevice(pcm->ctx->device));
+    if (mode == MRS_PCM_COV_NONE) {
+        MRS_TRY(pcm_clear(pcm));
+        pcm->cov_mode = mode;
+        return MRS_OK;
+    }
+    const int na = pcm->na, nb = pcm->nb;
+    std::vector<double> QA, QB, first, WA, WB;
+    MRS_REQUIRE(pcm_sym_inputs(h_QA, (size_t)na - 1, &QA), "an odometry covariance of A is not finite or not positive definite");
+    MRS_REQUIRE(pcm_sym_inputs(h_QB, (size_t)nb - 1, &QB), "an odometry covariance of B is not finite or not positive definite");
+    MRS_REQUIRE(pcm_sym_inputs(h_first, 1, &first), "the covariance of the first pose is not finite or not positive definite");
+    // REFERENCE: every prefix also carries the first pose's covariance, moved to the world frame through that pose
+    double fa[kSym], fb[kSym], x0[mrs::pcm::kPose];
+    mrs::pcm::pose_from_4x4(pcm->h_XA.data(), x0);
+    mrs::pcm::adj_conj(x0, first.data(), fa);
+    mrs::pcm::pose_from_4x4(pcm->h_XB.data(), x0);
+    mrs::pcm::adj_conj(x0, first.data(), fb);
+    const bool ref = mode == MRS_PCM_COV_REFERENCE;
+    pcm_prefixes(pcm->h_XA, na, QA, ref ? fa : nullptr, &WA);
+    pcm_prefixes(pcm->h_XB, nb, QB, ref ? fb : nullptr, &WB);
+    const size_t cap = (size_t)pcm->capacity;
+    MRS_TRY(pcm->rec_cov.reserve(cap * kRecCov, cap * kRecCov));
+    MRS_TRY(pcm->WA.reserve(WA.size(), WA.size()));
+    MRS_TRY(pcm->WB.reserve(WB.size(), WB.size()));
+    MRS_TRY(pcm_clear(pcm));
+    pcm->cov_mode = MRS_PCM_COV_NONE;                            // until the tables are in place
+    MRS_HIP_TRY(hipMemcpy(pcm->WA.get(), WA.data(), WA.size() * sizeof(double), hipMemcpyHostToDevice));
+    MRS_HIP_TRY(hipMemcpy(pcm->WB.get(), WB.data(), WB.size() * sizeof(double), hipMemcpyHostToDevice));
+    pcm->h_WA.swap(WA);
+    pcm->h_WB.swap(WB);
+    pcm->cov_mode = mode;
     return MRS_OK;
 }
 
 int mrs_pcm_add_loops(mrs_pcm* pcm, const int32_t* h_ia, const int32_t* h_kb, const double* h_Z, int32_t n)
 {
-    MRS_REQUIRE(pcm, "null pointer");
-    MRS_REQUIRE(n >= 0, "n must not be negative");
-    if (n == 0) return MRS_OK;
-    MRS_REQUIRE(h_ia && h_kb && h_Z, "null pointer");
-    MRS_REQUIRE(pcm->na > 0, "set the trajectories first");
-    MRS_REQUIRE(!pcm->given_matrix, "the vertices came from mrs_pcm_set_matrix: clear them first");
-    for (int t = 0; t < n; ++t)
-        MRS_REQUIRE(h_ia[t] >= 0 && h_ia[t] < pcm->na && h_kb[t] >= 0 && h_kb[t] < pcm->nb, "a loop names a pose outside its trajectory");
-    if ((long long)pcm->L + n > pcm->capacity) {
-        mrs::set_error("%d loops held and %d more exceed the capacity of %d", pcm->L, n, pcm->capacity);
-        return MRS_ERR_UNSUPPORTED;
-    }
+    return pcm_add_loops(pcm, h_ia, h_kb, h_Z, nullptr, n);
+}
+
+int mrs_pcm_add_loops_cov(mrs_pcm* pcm, const int32_t* h_ia, const int32_t* h_kb, const double* h_Z, const double* h_C, int32_t n)
+{
+    return pcm_add_loops(pcm, h_ia, h_kb, h_Z, h_C, n);
+}
+
+int mrs_pcm_get_pair(mrs_pcm* pcm, int32_t u, int32_t v, double* h_xi, double* h_cov, double* h_d)
+{
+    MRS_REQUIRE(pcm && h_xi && h_cov && h_d, "null pointer");
+    MRS_REQUIRE(!pcm->given_matrix, "the vertices came from mrs_pcm_set_matrix: they have no distances");
+    MRS_REQUIRE(u >= 0 && u < pcm->L && v >= 0 && v < pcm->L && u != v, "two different loops of the handle");
     MRS_HIP_TRY(hipSetDevice(pcm->ctx->device));
-    // one upload: Z [n][16] doubles | ia [n] | kb [n]
-    const size_t b_Z = (size_t)n * 16 * sizeof(double), b_idx = (size_t)n * sizeof(int32_t);
-    mrs::Scratch in;
-    int st = in.alloc(b_Z + 2 * b_idx, nullptr);
-    if (st != MRS_OK) return st;
-    double* d_Z = in.as<double>();
-    int* d_ia = reinterpret_cast<int*>(in.as<char>() + b_Z);
-    int* d_kb = d_ia + n;
-    MRS_HIP_TRY(hipMemcpy(d_Z, h_Z, b_Z, hipMemcpyHostToDevice));
-    MRS_HIP_TRY(hipMemcpy(d_ia, h_ia, b_idx, hipMemcpyHostToDevice));
-    MRS_HIP_TRY(hipMemcpy(d_kb, h_kb, b_idx, hipMemcpyHostToDevice));
-    const int L0 = pcm->L, L1 = L0 + n;
-    hipLaunchKernelGGL(k_pcm_records, dim3(blocks_for(n, kThreads)), dim3(kThreads), 0, nullptr, pcm->XA.get(), pcm->XB.get(), d_ia, d_kb, d_Z, n, L0,
-                       pcm->rec.get());
-    if ((st = pcm_fill_rows(pcm, L0, L1)) != MRS_OK) return st;
-    MRS_HIP_TRY(hipStreamSynchronize(nullptr));
-    pcm->L = L1;
-    pcm->degrees_stale = true;
+    const int a = std::min(u, v), b = std::max(u, v);
+    if (pcm->cov_mode == MRS_PCM_COV_NONE) {
+        double ra[kRec], rb[kRec];
+        MRS_HIP_TRY(hipMemcpy(ra, pcm->rec.get() + (size_t)a * kRec, sizeof(ra), hipMemcpyDeviceToHost));
+        MRS_HIP_TRY(hipMemcpy(rb, pcm->rec.get() + (size_t)b * kRec, sizeof(rb), hipMemcpyDeviceToHost));
+        double pinv[mrs::pcm::kPose], m[mrs::pcm::kPose], binv[mrs::pcm::kPose], mb[mrs::pcm::kPose], e[mrs::pcm::kPose];
+        mrs::pcm::pose_inv(ra, pinv);
+        mrs::pcm::pose_mul(pinv, rb, m);
+        mrs::pcm::pose_inv(ra + mrs::pcm::kPose, binv);
+        mrs::pcm::pose_mul(m, ra + mrs::pcm::kPose, mb);
+        mrs::pcm::pose_mul(binv, mb, e);
+        mrs::pcm::pose_logmap(e, h_xi);
+        for (int i = 0; i < 36; ++i) h_cov[i] = i % 7 == 0 ? 1.0 : 0.0;       // the reference's identity
+        *h_d = mrs::pcm::pose_log_norm(e);
+        return MRS_OK;
+    }
+    double ra[kRecCov], rb[kRecCov];
+    MRS_HIP_TRY(hipMemcpy(ra, pcm->rec_cov.get() + (size_t)a * kRecCov, sizeof(ra), hipMemcpyDeviceToHost));
+    MRS_HIP_TRY(hipMemcpy(rb, pcm->rec_cov.get() + (size_t)b * kRecCov, sizeof(rb), hipMemcpyDeviceToHost));
+    *h_d = mrs::pcm::pair_mahalanobis2_full(ra, rb, pcm->h_WA.data(), pcm->h_WB.data(), pcm->cov_mode, h_xi, h_cov);
     return MRS_OK;
 }
 
@@ -779,7 +979,11 @@ int mrs_pcm_get_distances(mrs_pcm* pcm, double* h_d)
     mrs::Scratch d;
     int st = d.alloc((size_t)L * L * sizeof(double), nullptr);
     if (st != MRS_OK) return st;
-    hipLaunchKernelGGL(k_pcm_distances, dim3(blocks_for((long long)L * L, kThreads)), dim3(kThreads), 0, nullptr, pcm->rec.get(), L, d.as<double>());
+    if (pcm->cov_mode != MRS_PCM_COV_NONE)
+        hipLaunchKernelGGL(k_pcm_distances_cov, dim3(blocks_for((long long)L * L, kThreads)), dim3(kThreads), 0, nullptr, pcm->rec_cov.get(),
+                           pcm->WA.get(), pcm->WB.get(), pcm->cov_mode, L, d.as<double>());
+    else
+        hipLaunchKernelGGL(k_pcm_distances, dim3(blocks_for((long long)L * L, kThreads)), dim3(kThreads), 0, nullptr, pcm->rec.get(), L, d.as<double>());
     MRS_HIP_TRY(hipGetLastError());
     MRS_HIP_TRY(hipMemcpy(h_d, d.p, (size_t)L * L * sizeof(double), hipMemcpyDeviceToHost));
     return MRS_OK;
