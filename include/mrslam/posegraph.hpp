@@ -142,6 +142,32 @@ public:
         return s;
     }
 
+    // ---- the sparse elimination tier in front of the dense Cholesky
+    struct SolverStats {
+        long long separators = 0, eliminated = 0, core = 0, levels = 0, blocks = 0, updates = 0, max_degree = 0;
+        int solver = MRS_PGO_SOLVER_DENSE;
+    };
+    // MRS_PGO_SOLVER_*; dense_limit -1 and max_blocks 0 are the defaults
+    void setSolver(int solver, int dense_limit = -1, int max_blocks = 0)
+    {
+        check(mrs_pgo_set_solver(h_, solver, dense_limit, max_blocks), "mrs_pgo_set_solver");
+    }
+    SolverStats solverStats(int stage = 2) const
+    {
+        int64_t st[MRS_PGO_SOLVER_STATS] = {};
+        check(mrs_pgo_get_solver_stats(h_, stage, st), "mrs_pgo_get_solver_stats");
+        SolverStats s;
+        s.separators = st[0];
+        s.eliminated = st[1];
+        s.core = st[2];
+        s.levels = st[3];
+        s.blocks = st[4];
+        s.updates = st[5];
+        s.max_degree = st[6];
+        s.solver = static_cast<int>(st[7]);
+        return s;
+    }
+
 private:
     static void check(int st, const char* what)
     {

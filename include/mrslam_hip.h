@@ -1399,6 +1399,33 @@ int mrs_pgo_optimize_lm(mrs_pgo* pgo, double eps, int32_t max_solves, double* h_
  * [capacity], capacity >= the number of loops.  MRS_ERR_ARG when the graph changed since, or nothing was optimised. */
 int mrs_pgo_get_loop_state(mrs_pgo* pgo, double* h_w, double* h_r2, int32_t capacity);
 
+/* ---- a sparse elimination tier in front of the dense Cholesky of the reduced system ----
+ * DENSE (the default) factors all separators densely and holds MRS_PGO_MAX_SEPARATORS of them.  SPARSE first eliminates separators of
+ * low degree in the block graph of the reduced system, level after level of pairwise non-adjacent ones, until at most `dense_limit` are
+ * left for the dense Cholesky; its size limit is a budget of blocks (a column's diagonal block and its blocks below it). */
+#define MRS_PGO_SOLVER_DENSE 0
+#define MRS_PGO_SOLVER_SPARSE 1
+/* a level takes the separators whose degree is at most the smallest degree plus this slack */
+#define MRS_PGO_SPARSE_DEGREE_SLACK 1
+/* the default budget of blocks of the sparse columns, per stage */
+#define MRS_PGO_MAX_SPARSE_BLOCKS 1048576
+/* entries of mrs_pgo_get_solver_stats' h_stats: separators, eliminated, core, levels, blocks = sum (d + 1),
+ * block updates = sum d (d + 1) / 2, the largest degree d, the solver in force */
+#define MRS_PGO_SOLVER_STATS 8
+/* solver: MRS_PGO_SOLVER_*.  dense_limit in [0, MRS_PGO_MAX_SEPARATORS], -1: MRS_PGO_MAX_SEPARATORS; max_blocks > 0, 0:
+ * MRS_PGO_MAX_SPARSE_BLOCKS; both are ignored under DENSE.  Anything else: MRS_ERR_ARG.  A graph that needs more blocks than max_blocks
+ * under SPARSE, or has more than MRS_PGO_MAX_SEPARATORS separators under DENSE: MRS_ERR_UNSUPPORTED.  The handle is unchanged on
+ * refusal.  Under SPARSE mrs_pgo_add_loops, mrs_pgo_add_loops_noise and mrs_pgo_set_segment_length check the block budget instead of the
+ * separator count.  With no more than dense_limit separators nothing is eliminated and the results are DENSE's bit for bit. */
+int mrs_pgo_set_solver(mrs_pgo* pgo, int32_t solver, int32_t dense_limit, int32_t max_blocks);
+/* The symbolic phase of a stage (1: rotations, 2: Gauss-Newton) for the graph as it stands: h_stats int64 [MRS_PGO_SOLVER_STATS].
+ * Host work only.  Under DENSE: eliminated, levels, blocks, updates and the degree are 0 and core is the separator count. */
+int mrs_pgo_get_solver_stats(mrs_pgo* pgo, int32_t stage, int64_t* h_stats);
+/* The sparse tier's share of the last optimisation's `dense factorisation` time (mrs_pgo_last_stage_ms), between events and summed over
+ * the solves: h_ms float [2] = milliseconds of the sparse columns with the core's update, and of the columns' way back.  Zeros unless
+ * MRS_DEV=1 and MRS_PGO_TIMING=1 were set when the call ran, and when nothing is eliminated. */
+int mrs_pgo_last_tier_ms(mrs_pgo* pgo, float* h_ms);
+
 #ifdef __cplusplus
 }
 #endif

@@ -185,21 +185,22 @@ struct Event {
 };
 
 // The development aid "events between the steps of a call" (MRS_DEV=1 with the entry point's MRS_*_TIMING switch): mark(i) records timed
-// event i on the stream, ms(from) is the time from event `from` to event from + 1, or 0 when either is missing.  Switched off it makes no
+// event i on the stream, ms(from) is the time from event `from` to event from + 1 (ms(from, to): to event `to`), or 0 when either is missing.  Switched off it makes no
 // runtime call at all; switched on, a call that fails only costs a figure.  The events are destroyed on every way out.
 class StageMarks {
 public:
-    static constexpr int kMax = 8;
+    static constexpr int kMax = 10;
     StageMarks(bool on, hipStream_t s) : on_(on), s_(s) {}
     explicit operator bool() const { return on_; }
     void mark(int i)
     {
         if (on_ && hipEventCreate(&ev_[i].e) == hipSuccess) (void)hipEventRecord(ev_[i], s_);
     }
-    float ms(int from) const
+    float ms(int from) const { return ms(from, from + 1); }
+    float ms(int from, int to) const
     {
         float t = 0.0f;
-        if (ev_[from].e && ev_[from + 1].e) (void)hipEventElapsedTime(&t, ev_[from], ev_[from + 1]);
+        if (ev_[from].e && ev_[to].e) (void)hipEventElapsedTime(&t, ev_[from], ev_[to]);
         return t;
     }
 

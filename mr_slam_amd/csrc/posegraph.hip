@@ -24,10 +24,13 @@
 // (k_pgo_information after stage 1; the <true> instantiations of k_pgo_linearize, k_pgo_error and k_pgo_gather; the <false> ones keep the
 // unit model's arithmetic), Levenberg-Marquardt step control (mrs_pgo_optimize_lm: lambda enters the gather, k_pgo_predicted and the sum
 // tree give the predicted decrease, one previous copy of the poses) and robust kernels on the loop factors (weights in the linearisation).
+// Past the dense system's MRS_PGO_MAX_SEPARATORS a handle may opt into a sparse elimination tier in front of it (DESIGN.md 4.23(j);
+// posegraph_order.hpp for the pattern, k_pgo_sp_* here).
 // No kernel waits for another workgroup, every device loop is bounded by a size known at launch, and a pivot block that is not positive
 // definite becomes a status word (the walk goes on with a unit pivot; the host ends the call).  The host reads 16 bytes per iteration.
 #include "common.hpp"
 #include "posegraph_factor.hpp"
+#include "posegraph_order.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -43,6 +46,7 @@ constexpr int kMaxChains = MRS_PGO_MAX_CHAINS, kMaxPoses = MRS_PGO_MAX_POSES, kM
 constexpr int kNB = MRS_PGO_PANEL_WIDTH;  // panel width of the dense Cholesky: a multiple of both block sizes
 constexpr int kTile = 32;                // the trailing update works on kTile x kTile tiles
 constexpr int kBig = 1 << 30;            // a failed pivot is recorded as kBig - index by atomicMax: the lowest index wins, 0 = none
+constexpr int kMarkTierDown = 8, kMarkTierUp = 9;   // StageMarks of the sparse tier: after its way down, before its way back
 constexpr int kTypeShift = 24;           // a contribution is type << 24 | index
 static_assert(kMaxPoses + kMaxLoops + 2 < (1 << kTypeShift), "a contribution's index must fit below its type");
 enum : int { kNodeDiag = 0, kFactor = 1, kFactorT = 2, kSegLL = 3, kSegRR = 4, kSegRL = 5, kSegRLT = 6 };
@@ -491,6 +495,36 @@ struct Parts {
     const double *Hpp, *g, *Hij, *Sll, *Srr, *Srl, *gl, *gr;
 };
 
+// entry e (et: of the transpose) of contribution c to a block of the reduced system
+template <int B>
+__device__ __forceinline__ double block_contribution(const Parts& P, int c, int e, int et)
+{
+    const int type = c >> kTypeShift;
+    const size_t idx = (size_t)(c & ((1 << kTypeShift) - 1)) * (B * B);
+    double v = 0.0;
+    if (type == kNodeDiag) v = P.Hpp[idx + e];
+    else if (type == kFactor) v = P.Hij[idx + e];
+    else if (type == kFactorT) v = P.Hij[idx + et];
+    else if (type == kSegLL) v = P.Sll[idx + e];
+    else if (type == kSegRR) v = P.Srr[idx + e];
+    else if (type == kSegRL) v = P.Srl[idx + e];
+    else if (type == kSegRLT) v = P.Srl[idx + et];
+    return v;
+}
+
+// entry e of contribution c (of a diagonal block's list) to the right-hand sides [NR][B] of its separator
+template <int BV>
+__device__ __forceinline__ double rhs_contribution(const Parts& P, int c, int e)
+{
+    const int type = c >> kTypeShift;
+    const size_t idx = (size_t)(c & ((1 << kTypeShift) - 1)) * BV;
+    double v = 0.0;
+    if (type == kNodeDiag) v = P.g[idx + e];
+    else if (type == kSegLL) v = P.gl[idx + e];
+    else if (type == kSegRR) v = P.gr[idx + e];
+    return v;
+}
+
 // a thread per (block, entry): the block's contributions in their listed order
 template <int B>
 __global__ __launch_bounds__(kThreads) void k_pgo_assemble(const int* __restrict__ tgt_a, const int* __restrict__ tgt_b, const int* __restrict__ tgt_ptr,
@@ -502,19 +536,7 @@ __global__ __launch_bounds__(kThreads) void k_pgo_assemble(const int* __restrict
     const int blk = t / BB, e = t % BB, r = e / B, c = e % B, et = c * B + r;
     double sum = 0.0;
     const int u1 = tgt_ptr[blk + 1];
-    for (int u = tgt_ptr[blk]; u < u1; ++u) {
-        const int type = contrib[u] >> kTypeShift;
-        const size_t idx = (size_t)(contrib[u] & ((1 << kTypeShift) - 1)) * BB;
-        double v = 0.0;
-        if (type == kNodeDiag) v = P.Hpp[idx + e];
-        else if (type == kFactor) v = P.Hij[idx + e];
-        else if (type == kFactorT) v = P.Hij[idx + et];
-        else if (type == kSegLL) v = P.Sll[idx + e];
-        else if (type == kSegRR) v = P.Srr[idx + e];
-        else if (type == kSegRL) v = P.Srl[idx + e];
-        else if (type == kSegRLT) v = P.Srl[idx + et];
-        sum += v;
-    }
+    for (int u = tgt_ptr[blk]; u < u1; ++u) sum += block_contribution<B>(P, contrib[u], e, et);
     S[((size_t)B * tgt_a[blk] + r) * ld + (size_t)B * tgt_b[blk] + c] = sum;
 }
 
@@ -529,15 +551,7 @@ __global__ __launch_bounds__(kThreads) void k_pgo_assemble_rhs(const int* __rest
     const int a = t / BV, e = t % BV, q = e / B, i = e % B;
     double sum = 0.0;
     const int u1 = tgt_ptr[a + 1];
-    for (int u = tgt_ptr[a]; u < u1; ++u) {
-        const int type = contrib[u] >> kTypeShift;
-        const size_t idx = (size_t)(contrib[u] & ((1 << kTypeShift) - 1)) * BV;
-        double v = 0.0;
-        if (type == kNodeDiag) v = P.g[idx + e];
-        else if (type == kSegLL) v = P.gl[idx + e];
-        else if (type == kSegRR) v = P.gr[idx + e];
-        sum += v;
-    }
+    for (int u = tgt_ptr[a]; u < u1; ++u) sum += rhs_contribution<BV>(P, contrib[u], e);
     rhs[q * ld + (size_t)B * a + i] = sum;
 }
 
@@ -651,6 +665,188 @@ __global__ __launch_bounds__(kThreads) void k_pgo_chol_back(double* __restrict__
                 rhs[(size_t)q * ld + r] = s;
             }
         __syncthreads();
+    }
+}
+
+// ------------------------------------------------------------------ the sparse tier in front of the dense system (posegraph_order.hpp)
+//
+// Column k (an elimination position) owns d + 1 blocks of Lb from block col_ptr[k] + k: L_k, then W_k[s] = A_rk L_k^-T for the rows r of its
+// struct, and y_k [NR][B] in ysp.  Left-looking and pulled by the target: a block subtracts the products W_m[.] W_m[.]^T of the earlier
+// columns m that reach both of its ends, found by merging the two ends' row lists, in ascending m.  Every entry has one thread and a fixed
+// order of sums.
+
+struct SpView {
+    const int *order;                                            // position -> node (reduced index of the separator)
+    const int *col_ptr, *col_struct, *col_tgt;                   // col_tgt: target << 1 | transposed, or -1
+    const int *row_ptr, *row_k, *row_blk;                        // rows(p): the columns k reaching position p, and the block of W_k there
+    int n_elim;
+};
+
+// entry (i, j) of sum over the columns m in both lists [a, a1) and [b, b1) of W_m[.] W_m[.]^T, subtracted from acc in ascending m
+template <int B>
+__device__ __forceinline__ double sp_pull(const SpView& v, int a, int a1, int b, int b1, const double* __restrict__ Lb, int i, int j, double acc)
+{
+    while (a < a1 && b < b1) {                                   // every turn moves a or b on: at most the two lengths together
+        const int ka = v.row_k[a], kb = v.row_k[b];
+        if (ka == kb) {
+            const double *Wa = Lb + (size_t)v.row_blk[a] * (B * B) + i * B, *Wb = Lb + (size_t)v.row_blk[b] * (B * B) + j * B;
+            double p = 0.0;
+#pragma unroll
+            for (int c = 0; c < B; ++c) p += Wa[c] * Wb[c];
+            acc -= p;
+        }
+        a += ka <= kb;
+        b += kb <= ka;
+    }
+    return acc;
+}
+
+// entry (q, i) of sum over rows(p) = [a, a1) of W_m[.] y_m, subtracted from acc in ascending m
+template <int B, int NR>
+__device__ __forceinline__ double sp_pull_rhs(const SpView& v, int a, int a1, const double* __restrict__ Lb, const double* __restrict__ ysp, int q,
+                                              int i, double acc)
+{
+    for (; a < a1; ++a) {
+        const double *W = Lb + (size_t)v.row_blk[a] * (B * B) + i * B, *y = ysp + (size_t)v.row_k[a] * (B * NR) + q * B;
+        double p = 0.0;
+#pragma unroll
+        for (int c = 0; c < B; ++c) p += W[c] * y[c];
+        acc -= p;
+    }
+    return acc;
+}
+
+// one launch per level, a workgroup per column k = k0 + blockIdx.x of it; tgt_ptr / contrib are the stage's own lists
+template <int B, int NR>
+__global__ __launch_bounds__(kThreads) void k_pgo_sp_column(SpView v, int k0, const int* __restrict__ tgt_ptr, const int* __restrict__ contrib,
+                                                            const int* __restrict__ sep_node, Parts P, double* __restrict__ Lb,
+                                                            double* __restrict__ ysp, Status* st)
+{
+    constexpr int BB = B * B, BV = B * NR;
+    __shared__ double Ls[BB];
+    const int k = k0 + blockIdx.x, tid = threadIdx.x, node = v.order[k], c0 = v.col_ptr[k], d = v.col_ptr[k + 1] - c0;
+    const int rk0 = v.row_ptr[k], rk1 = v.row_ptr[k + 1];
+    double* col = Lb + (size_t)(c0 + k) * BB;
+    for (int it = tid; it < (d + 1) * BB + BV; it += kThreads) {
+        if (it < (d + 1) * BB) {
+            const int blk = it / BB, e = it % BB, i = e / B, j = e % B, et = j * B + i;
+            const int ct = blk ? v.col_tgt[c0 + blk - 1] : node << 1, p = blk ? v.col_struct[c0 + blk - 1] : k;
+            double sum = 0.0;
+            if (ct >= 0) {
+                const int tgt = ct >> 1, u1 = tgt_ptr[tgt + 1];
+                for (int u = tgt_ptr[tgt]; u < u1; ++u) sum += (ct & 1) ? block_contribution<B>(P, contrib[u], et, e) : block_contribution<B>(P, contrib[u], e, et);
+            }
+            col[it] = sp_pull<B>(v, v.row_ptr[p], v.row_ptr[p + 1], rk0, rk1, Lb, i, j, sum);
+        } else {
+            const int e = it - (d + 1) * BB, q = e / B, i = e % B;
+            double sum = 0.0;
+            const int u1 = tgt_ptr[node + 1];
+            for (int u = tgt_ptr[node]; u < u1; ++u) sum += rhs_contribution<BV>(P, contrib[u], e);
+            ysp[(size_t)k * BV + e] = sp_pull_rhs<B, NR>(v, rk0, rk1, Lb, ysp, q, i, sum);
+        }
+    }
+    __syncthreads();
+    if (tid == 0) {
+        double D[BB];
+#pragma unroll
+        for (int e = 0; e < BB; ++e) D[e] = col[e];
+        if (!chol_inplace<B>(D)) atomicMax(&st->seg_fail, kBig - sep_node[node]);
+#pragma unroll
+        for (int e = 0; e < BB; ++e) {
+            col[e] = D[e];
+            Ls[e] = D[e];
+        }
+    }
+    __syncthreads();
+    for (int it = tid; it < d * B; it += kThreads) {             // a row w of a block below: w L_k^T = a
+        double* row = col + BB + (size_t)it * B;
+        double w[B];
+#pragma unroll
+        for (int j = 0; j < B; ++j) {
+            double s = row[j];
+#pragma unroll
+            for (int c = 0; c < j; ++c) s -= w[c] * Ls[j * B + c];
+            w[j] = s / Ls[j * B + j];
+        }
+#pragma unroll
+        for (int j = 0; j < B; ++j) row[j] = w[j];
+    }
+    if (tid < NR) {
+        double y[B];
+#pragma unroll
+        for (int i = 0; i < B; ++i) y[i] = ysp[(size_t)k * BV + tid * B + i];
+        lower_solve<B, 1>(Ls, y);
+#pragma unroll
+        for (int i = 0; i < B; ++i) ysp[(size_t)k * BV + tid * B + i] = y[i];
+    }
+}
+
+// after the assembly of the core's own contributions: a grid row per core separator a, a thread per entry of its blocks (a, b <= a) and of
+// its right-hand sides
+template <int B, int NR>
+__global__ __launch_bounds__(kThreads) void k_pgo_sp_core(SpView v, int core, const double* __restrict__ Lb, const double* __restrict__ ysp,
+                                                          double* __restrict__ S, size_t ld)
+{
+    constexpr int BB = B * B, BV = B * NR;
+    const int a = blockIdx.y, it = blockIdx.x * kThreads + threadIdx.x;
+    const int ra0 = v.row_ptr[v.n_elim + a], ra1 = v.row_ptr[v.n_elim + a + 1];
+    if (ra0 == ra1) return;
+    if (it < (a + 1) * BB) {
+        const int b = it / BB, e = it % BB, i = e / B, j = e % B;
+        double* s = S + ((size_t)B * a + i) * ld + (size_t)B * b + j;
+        *s = sp_pull<B>(v, ra0, ra1, v.row_ptr[v.n_elim + b], v.row_ptr[v.n_elim + b + 1], Lb, i, j, *s);
+    } else if (it < (a + 1) * BB + BV) {
+        const int e = it - (a + 1) * BB, q = e / B, i = e % B;
+        double* s = S + ((size_t)B * core + q) * ld + (size_t)B * a + i;
+        *s = sp_pull_rhs<B, NR>(v, ra0, ra1, Lb, ysp, q, i, *s);
+    }
+}
+
+// the core's solution (the right-hand-side rows of S) into X [NR][ldx], which is in the separators' own order
+template <int B, int NR>
+__global__ __launch_bounds__(kThreads) void k_pgo_sp_expand(SpView v, int core, const double* __restrict__ xr, size_t ld, double* __restrict__ X,
+                                                            size_t ldx)
+{
+    const int t = blockIdx.x * kThreads + threadIdx.x;
+    if (t >= core * B * NR) return;
+    const int a = t / (B * NR), q = (t / B) % NR, i = t % B;
+    X[q * ldx + (size_t)B * v.order[v.n_elim + a] + i] = xr[q * ld + (size_t)B * a + i];
+}
+
+// one launch per level, the levels in reverse, a workgroup per column: x_k = L_k^-T (y_k - sum_s W_k[s]^T x_r).  The sum over the d blocks
+// is dealt to kThreads / BV chunks whose partial sums are added in their order.
+template <int B, int NR>
+__global__ __launch_bounds__(kThreads) void k_pgo_sp_back(SpView v, int k0, const double* __restrict__ Lb, const double* __restrict__ ysp,
+                                                          double* __restrict__ X, size_t ldx)
+{
+    constexpr int BB = B * B, BV = B * NR, kChunks = kThreads / BV;
+    __shared__ double part[kChunks][BV];
+    const int k = k0 + blockIdx.x, tid = threadIdx.x, c0 = v.col_ptr[k], d = v.col_ptr[k + 1] - c0;
+    const double* col = Lb + (size_t)(c0 + k) * BB;
+    const int e = tid % BV, ch = tid / BV, q = e / B, i = e % B;
+    if (ch < kChunks) {
+        double s = 0.0;
+        for (int t = ch; t < d; t += kChunks) {
+            const double *W = col + BB + (size_t)t * BB, *x = X + q * ldx + (size_t)B * v.order[v.col_struct[c0 + t]];
+#pragma unroll
+            for (int c = 0; c < B; ++c) s += W[c * B + i] * x[c];
+        }
+        part[ch][e] = s;
+    }
+    __syncthreads();
+    if (tid < NR) {
+        double x[B], L[BB];
+#pragma unroll
+        for (int r = 0; r < BB; ++r) L[r] = col[r];
+#pragma unroll
+        for (int r = 0; r < B; ++r) {
+            double t = ysp[(size_t)k * BV + tid * B + r];
+            for (int c = 0; c < kChunks; ++c) t -= part[c][tid * B + r];
+            x[r] = t;
+        }
+        upper_solve<B>(L, x);
+#pragma unroll
+        for (int r = 0; r < B; ++r) X[tid * ldx + (size_t)B * v.order[k] + r] = x[r];
     }
 }
 
@@ -842,6 +1038,19 @@ void build_topology(const Graph& g, int seglen, int stage, Topology* t)
     }
 }
 
+// the symbolic phase of a stage's sparse tier (posegraph_order.hpp); a pattern past the block budget is MRS_ERR_UNSUPPORTED
+int pgo_sparse_order(const Topology& t, int stage, int dense_limit, int max_blocks, mrs::pgo::SparseOrder* o)
+{
+    long long count = 0;
+    if (!mrs::pgo::sparse_order(t.E, (int)t.tgt_a.size(), t.tgt_a.data(), t.tgt_b.data(), dense_limit, MRS_PGO_SPARSE_DEGREE_SLACK, max_blocks, o,
+                                &count)) {
+        mrs::set_error("stage %d: eliminating %d separators down to %d reached %lld blocks, past the budget of %d", stage, t.E, dense_limit, count,
+                       max_blocks);
+        return MRS_ERR_UNSUPPORTED;
+    }
+    return MRS_OK;
+}
+
 // one stage's topology on the device: a single int buffer
 struct DeviceTopology {
     mrs::DeviceBuffer<int> ints;
@@ -871,6 +1080,44 @@ struct DeviceTopology {
     }
 };
 
+// one stage's sparse tier on the device: the pattern (a single int buffer) and the core's own assembly lists
+struct DeviceSparse {
+    mrs::DeviceBuffer<int> ints;
+    SpView v = {};
+    int core = 0, n_core_tgt = 0;
+    const int *core_a = nullptr, *core_b = nullptr, *core_ptr = nullptr, *core_contrib = nullptr;
+
+    int upload(const mrs::pgo::SparseOrder& o, const Topology& t)
+    {
+        std::vector<int> h, row_blk(o.row_k.size()), ca, cb, cp(1, 0), cc;
+        for (size_t u = 0; u < o.row_k.size(); ++u) row_blk[u] = o.col_ptr[o.row_k[u]] + o.row_k[u] + 1 + o.row_slot[u];
+        std::vector<int> pos(o.E);
+        for (int p = 0; p < o.E; ++p) pos[o.order[p]] = p;
+        for (int tgt : o.core_tgt) {                             // the core's blocks in the core's numbering, their lists as they were
+            ca.push_back(pos[t.tgt_a[tgt]] - o.eliminated);
+            cb.push_back(pos[t.tgt_b[tgt]] - o.eliminated);
+            cc.insert(cc.end(), t.contrib.begin() + t.tgt_ptr[tgt], t.contrib.begin() + t.tgt_ptr[tgt + 1]);
+            cp.push_back((int)cc.size());
+        }
+        const auto put = [&](const std::vector<int>& x) {
+            const size_t at = h.size();
+            h.insert(h.end(), x.begin(), x.end());
+            return at;
+        };
+        const size_t o_ord = put(o.order), o_cp = put(o.col_ptr), o_cs = put(o.col_struct), o_ct = put(o.col_tgt), o_rp = put(o.row_ptr),
+                     o_rk = put(o.row_k), o_rb = put(row_blk), o_a = put(ca), o_b = put(cb), o_p = put(cp), o_c = put(cc);
+        h.push_back(0);                                           // never empty
+        MRS_TRY(ints.reserve(h.size(), h.size() + h.size() / 4));
+        MRS_HIP_TRY(hipMemcpy(ints.get(), h.data(), h.size() * sizeof(int), hipMemcpyHostToDevice));
+        const int* d = ints.get();
+        v = SpView{d + o_ord, d + o_cp, d + o_cs, d + o_ct, d + o_rp, d + o_rk, d + o_rb, o.eliminated};
+        core = o.core;
+        n_core_tgt = (int)ca.size();
+        core_a = d + o_a; core_b = d + o_b; core_ptr = d + o_p; core_contrib = d + o_c;
+        return MRS_OK;
+    }
+};
+
 bool finite16(const double* m)
 {
     for (int k = 0; k < 16; ++k)
@@ -884,6 +1131,7 @@ struct mrs_pgo {
     mrs_ctx* ctx = nullptr;
     Graph g;
     int seglen = MRS_PGO_DEFAULT_SEGMENT_LENGTH;
+    int solver = MRS_PGO_SOLVER_DENSE, dense_limit = MRS_PGO_MAX_SEPARATORS, max_blocks = MRS_PGO_MAX_SPARSE_BLOCKS;
     bool odometry_set = false;
     std::vector<double> odom, loopZ;                             // [.][16] as given
     std::vector<double> odomC, loopC;                            // covariances [.][36]: odomC is empty or complete, loopC has an entry per loop
@@ -896,6 +1144,9 @@ struct mrs_pgo {
     bool init_valid = false;                                     // T0 holds stage 1 of the current graph
     Topology topo[2];                                            // stage 1, stage 2
     DeviceTopology dtopo[2];
+    mrs::pgo::SparseOrder sp[2];                                 // the sparse tier of each stage; nothing eliminated under the dense solver
+    DeviceSparse dsp[2];
+    mrs::DeviceBuffer<double> Lb, ysp, X;                        // the sparse columns' blocks, their y, the separators' solution [NR][B E]
     int F = 0;                                                   // factors without the anchor's
     mrs::DeviceBuffer<int> fints;                                // fi [F + 1] | fj [F + 1] | csr ptr [N + 2] | csr entries [2 (F + 1)]
     mrs::DeviceBuffer<double> Z, T0, T, delta, Hii, Hij, gi, gj, err, partial, Hpp, gp, Lk, Ak, Wk, yk, seg, S;
@@ -904,6 +1155,7 @@ struct mrs_pgo {
     mrs::DeviceBuffer<Status> status;
     mrs::DeviceBuffer<double> err_out;
     float stage_ms[6] = {0, 0, 0, 0, 0, 0};
+    float tier_ms[2] = {0, 0};                                   // of stage 2's sparse tier: its way down with the core's update, its way back
 };
 
 namespace {
@@ -939,6 +1191,13 @@ int pgo_sync(mrs_pgo* h)
     build_topology(g, h->seglen, 2, &h->topo[1]);
     MRS_TRY(h->dtopo[0].upload(h->topo[0]));
     MRS_TRY(h->dtopo[1].upload(h->topo[1]));
+    for (int s = 0; s < 2; ++s) {
+        h->sp[s] = mrs::pgo::SparseOrder();
+        if (h->solver == MRS_PGO_SOLVER_SPARSE && h->topo[s].E > h->dense_limit) {
+            MRS_TRY(pgo_sparse_order(h->topo[s], s + 1, h->dense_limit, h->max_blocks, &h->sp[s]));
+            MRS_TRY(h->dsp[s].upload(h->sp[s], h->topo[s]));
+        }
+    }
     // factors and the CSR of factors per node, ascending (the anchor's factor F is the last of pose 0 and the only one of node N)
     std::vector<int> ints((size_t)2 * F1 + (N + 2) + 2 * (size_t)F1);
     int *fi = ints.data(), *fj = fi + F1, *ptr = fj + F1, *ent = ptr + N + 2;
@@ -976,7 +1235,11 @@ int pgo_sync(mrs_pgo* h)
     MRS_TRY(grow(h->Z, Z.size()));
     MRS_HIP_TRY(hipMemcpy(h->Z.get(), Z.data(), Z.size() * sizeof(double), hipMemcpyHostToDevice));
     const size_t nodes = (size_t)N + 1, nseg = std::max(h->topo[0].seg_first.size(), h->topo[1].seg_first.size());
-    const size_t n1 = 3 * (size_t)h->topo[0].E, n2 = 6 * (size_t)h->topo[1].E;
+    const auto dense_order = [&](int s) { return (size_t)(h->sp[s].eliminated ? h->sp[s].core : h->topo[s].E); };
+    const size_t n1 = 3 * dense_order(0), n2 = 6 * dense_order(1);
+    MRS_TRY(grow(h->Lb, std::max((size_t)h->sp[0].blocks * 9, (size_t)h->sp[1].blocks * 36)));
+    MRS_TRY(grow(h->ysp, std::max((size_t)h->sp[0].eliminated * 9, (size_t)h->sp[1].eliminated * 6)));
+    MRS_TRY(grow(h->X, std::max(9 * (size_t)h->topo[0].E, 6 * (size_t)h->topo[1].E)));
     MRS_TRY(grow(h->T0, nodes * 12));
     MRS_TRY(grow(h->T, nodes * 12));
     MRS_TRY(grow(h->delta, nodes * 9));
@@ -1018,6 +1281,74 @@ int pgo_sync(mrs_pgo* h)
     return MRS_OK;
 }
 
+// the blocked Cholesky of the dense S [n + nr][ld] with the forward substitution of its nr right-hand-side rows, and the way back
+void pgo_dense_solve(double* S, int n, int nr, size_t ld, Status* st)
+{
+    const int nt = n + nr;
+    for (int k0 = 0; k0 < n; k0 += kNB) {
+        const int nb = std::min(kNB, n - k0), k1 = k0 + nb;
+        hipLaunchKernelGGL(k_pgo_chol_panel, dim3(1), dim3(kThreads), 0, nullptr, S, n, nt, ld, k0, st);
+        if (k1 < n) {
+            const unsigned tiles = blocks_for(nt - k1, kTile);
+            hipLaunchKernelGGL(k_pgo_chol_trail, dim3(tiles, tiles), dim3(kThreads), 0, nullptr, S, n, nt, ld, k0, nb);
+        }
+    }
+    hipLaunchKernelGGL(k_pgo_chol_back, dim3(1), dim3(kThreads), 0, nullptr, S, n, ld, nr);
+}
+
+// pgo_solve from the segments' Schur contributions on, with the stage's sparse tier: the sparse columns level after
+// level, the core's dense system less what the columns send it, the columns' way back in reverse, then the separators' solution X in their
+// own order for k_pgo_scatter and k_pgo_backsolve
+template <int B, int NR>
+int pgo_solve_sparse(mrs_pgo* h, int stage, mrs::StageMarks* marks, int base)
+{
+    constexpr int BB = B * B, BV = B * NR;
+    const DeviceTopology& t = h->dtopo[stage - 1];
+    const DeviceSparse& sp = h->dsp[stage - 1];
+    const std::vector<int>& level = h->sp[stage - 1].level_ptr;
+    const int E = t.E, core = sp.core, n = B * core, nt = n + NR;
+    const size_t ld = (size_t)n, ldx = (size_t)B * E, nseg = (size_t)t.sv.n;
+    double* seg = h->seg.get();
+    double *Sll = seg, *Srr = Sll + nseg * BB, *Srl = Srr + nseg * BB, *gl = Srl + nseg * BB, *gr = gl + nseg * BV;
+    double *S = h->S.get(), *Lb = h->Lb.get(), *ysp = h->ysp.get(), *X = h->X.get();
+    Status* st = h->status.get();
+    const Parts P = {h->Hpp.get(), h->gp.get(), h->Hij.get(), Sll, Srr, Srl, gl, gr};
+    if (core) {
+        MRS_HIP_TRY(hipMemsetAsync(S, 0, (size_t)nt * ld * sizeof(double), nullptr));
+        hipLaunchKernelGGL((k_pgo_assemble<B>), dim3(blocks_for((long long)sp.n_core_tgt * BB, kThreads)), dim3(kThreads), 0, nullptr, sp.core_a,
+                           sp.core_b, sp.core_ptr, sp.core_contrib, sp.n_core_tgt, P, S, ld);
+        hipLaunchKernelGGL((k_pgo_assemble_rhs<B, NR>), dim3(blocks_for((long long)core * BV, kThreads)), dim3(kThreads), 0, nullptr, sp.core_ptr,
+                           sp.core_contrib, core, P, S + (size_t)n * ld, ld);
+    }
+    if (marks) marks->mark(base + 1);
+    for (size_t l = 0; l + 1 < level.size(); ++l)
+        hipLaunchKernelGGL((k_pgo_sp_column<B, NR>), dim3(level[l + 1] - level[l]), dim3(kThreads), 0, nullptr, sp.v, level[l], t.tgt_ptr, t.contrib,
+                           t.sep_node, P, Lb, ysp, st);
+    if (core) {
+        hipLaunchKernelGGL((k_pgo_sp_core<B, NR>), dim3(blocks_for((long long)core * BB + BV, kThreads), core), dim3(kThreads), 0, nullptr, sp.v, core,
+                           Lb, ysp, S, ld);
+        if (marks) marks->mark(kMarkTierDown);
+        pgo_dense_solve(S, n, NR, ld, st);
+        hipLaunchKernelGGL((k_pgo_sp_expand<B, NR>), dim3(blocks_for((long long)core * BV, kThreads)), dim3(kThreads), 0, nullptr, sp.v, core,
+                           S + (size_t)n * ld, ld, X, ldx);
+        if (marks) marks->mark(kMarkTierUp);
+    } else if (marks) {
+        marks->mark(kMarkTierDown);
+        marks->mark(kMarkTierUp);
+    }
+    for (size_t l = level.size() - 1; l-- > 0;)
+        hipLaunchKernelGGL((k_pgo_sp_back<B, NR>), dim3(level[l + 1] - level[l]), dim3(kThreads), 0, nullptr, sp.v, level[l], Lb, ysp, X, ldx);
+    if (marks) marks->mark(base + 2);
+    hipLaunchKernelGGL((k_pgo_scatter<B, NR>), dim3(blocks_for((long long)E * BV, kThreads)), dim3(kThreads), 0, nullptr, t.sep_node, E, X, ldx,
+                       h->delta.get());
+    if (nseg)
+        hipLaunchKernelGGL((k_pgo_backsolve<B, NR>), dim3(blocks_for((long long)nseg, 64)), dim3(64), 0, nullptr, t.sv, h->Lk.get(), h->Ak.get(),
+                           h->Wk.get(), h->yk.get(), X, ldx, h->delta.get());
+    if (marks) marks->mark(base + 3);
+    MRS_HIP_TRY(hipGetLastError());
+    return MRS_OK;
+}
+
 // One solve of the assembled per-node system (Hpp, gp, Hij) of a stage -> delta [n_nodes][NR][B]; entries of held nodes are zero.
 // `marks` (optional) gets marks base .. base + 3: after the walk, the assembly, the dense solve and the way back.
 template <int B, int NR>
@@ -1036,6 +1367,7 @@ int pgo_solve(mrs_pgo* h, int stage, mrs::StageMarks* marks, int base)
         hipLaunchKernelGGL((k_pgo_eliminate<B, NR>), dim3(blocks_for((long long)nseg, 64)), dim3(64), 0, nullptr, t.sv, h->Hpp.get(), h->gp.get(),
                            h->Hij.get(), h->Lk.get(), h->Ak.get(), h->Wk.get(), h->yk.get(), Sll, Srr, Srl, gl, gr, st);
     if (marks) marks->mark(base);
+    if (h->sp[stage - 1].eliminated) return pgo_solve_sparse<B, NR>(h, stage, marks, base);
     if (E) {
         const Parts P = {h->Hpp.get(), h->gp.get(), h->Hij.get(), Sll, Srr, Srl, gl, gr};
         MRS_HIP_TRY(hipMemsetAsync(S, 0, (size_t)nt * ld * sizeof(double), nullptr));
@@ -1044,15 +1376,7 @@ int pgo_solve(mrs_pgo* h, int stage, mrs::StageMarks* marks, int base)
         hipLaunchKernelGGL((k_pgo_assemble_rhs<B, NR>), dim3(blocks_for((long long)E * BV, kThreads)), dim3(kThreads), 0, nullptr, t.tgt_ptr, t.contrib,
                            E, P, S + (size_t)n * ld, ld);
         if (marks) marks->mark(base + 1);
-        for (int k0 = 0; k0 < n; k0 += kNB) {
-            const int nb = std::min(kNB, n - k0), k1 = k0 + nb;
-            hipLaunchKernelGGL(k_pgo_chol_panel, dim3(1), dim3(kThreads), 0, nullptr, S, n, nt, ld, k0, st);
-            if (k1 < n) {
-                const unsigned tiles = blocks_for(nt - k1, kTile);
-                hipLaunchKernelGGL(k_pgo_chol_trail, dim3(tiles, tiles), dim3(kThreads), 0, nullptr, S, n, nt, ld, k0, nb);
-            }
-        }
-        hipLaunchKernelGGL(k_pgo_chol_back, dim3(1), dim3(kThreads), 0, nullptr, S, n, ld, NR);
+        pgo_dense_solve(S, n, NR, ld, st);
         if (marks) marks->mark(base + 2);
         hipLaunchKernelGGL((k_pgo_scatter<B, NR>), dim3(blocks_for((long long)E * BV, kThreads)), dim3(kThreads), 0, nullptr, t.sep_node, E,
                            S + (size_t)n * ld, ld, h->delta.get());
@@ -1071,13 +1395,15 @@ int pgo_solve(mrs_pgo* h, int stage, mrs::StageMarks* marks, int base)
 // the status words of the solves since the last reset -> MRS_OK, or MRS_ERR_NOT_CONVERGED with the pose named
 int pgo_check_pivots(const mrs_pgo* h, const Status& st, int stage)
 {
-    if (st.seg_fail) {
-        mrs::set_error("stage %d: the pivot block of pose %d is not positive definite", stage, kBig - st.seg_fail);
+    if (st.seg_fail) {                                           // a segment walk's pose, or a separator of the sparse tier
+        if (stage == 1 && kBig - st.seg_fail == h->g.N) mrs::set_error("stage 1: the pivot block of the anchor is not positive definite");
+        else mrs::set_error("stage %d: the pivot block of pose %d is not positive definite", stage, kBig - st.seg_fail);
         return MRS_ERR_NOT_CONVERGED;
     }
     if (st.dense_fail) {
         const Topology& t = h->topo[stage - 1];
-        const int row = kBig - st.dense_fail, a = row / (stage == 1 ? 3 : 6);
+        const mrs::pgo::SparseOrder& sp = h->sp[stage - 1];
+        const int row = kBig - st.dense_fail, c = row / (stage == 1 ? 3 : 6), a = sp.eliminated && c < sp.core ? sp.order[sp.eliminated + c] : c;
         const int pose = a >= 0 && a < t.E ? t.sep_node[a] : -1;
         if (stage == 1 && pose == h->g.N) mrs::set_error("stage 1: the pivot block of the anchor is not positive definite (row %d)", row);
         else mrs::set_error("stage %d: the pivot block of pose %d is not positive definite (row %d of the reduced system)", stage, pose, row);
@@ -1137,7 +1463,7 @@ int pgo_error_sum(mrs_pgo* h, double* out)
 
 // ------------------------------------------------------------------ host: the weighted and the plain instantiations behind one call each
 
-int pgo_check_separators(const Graph& g, int seglen);
+int pgo_check_size(const mrs_pgo* h, const Graph& g, int seglen);
 
 bool pgo_has_noise(const mrs_pgo* h)
 {
@@ -1258,7 +1584,7 @@ int pgo_add_loops(mrs_pgo* pgo, const int32_t* h_i, const int32_t* h_j, const do
     Graph g = pgo->g;
     g.li.insert(g.li.end(), h_i, h_i + n);
     g.lj.insert(g.lj.end(), h_j, h_j + n);
-    MRS_TRY(pgo_check_separators(g, pgo->seglen));
+    MRS_TRY(pgo_check_size(pgo, g, pgo->seglen));
     pgo->g = std::move(g);
     pgo->loopZ.insert(pgo->loopZ.end(), h_Z, h_Z + (size_t)n * 16);
     if (h_C) pgo->loopC.insert(pgo->loopC.end(), h_C, h_C + (size_t)n * 36);
@@ -1282,8 +1608,17 @@ int pgo_download(const double* d_T, int N, double* h_T)
 }
 
 // validates on a copy: the handle changes only when everything holds
-int pgo_check_separators(const Graph& g, int seglen)
+int pgo_check_size(int solver, int dense_limit, int max_blocks, const Graph& g, int seglen)
 {
+    if (solver == MRS_PGO_SOLVER_SPARSE) {                       // the block budget of both stages' sparse tiers
+        for (int stage = 1; stage <= 2; ++stage) {
+            Topology t;
+            mrs::pgo::SparseOrder o;
+            build_topology(g, seglen, stage, &t);
+            MRS_TRY(pgo_sparse_order(t, stage, dense_limit, max_blocks, &o));
+        }
+        return MRS_OK;
+    }
     const int E = count_separators(g, seglen);
     if (E > kMaxSep) {
         mrs::set_error("%d separators (poses touched by loops and cut poses) exceed the %d the reduced system holds", E, kMaxSep);
@@ -1291,6 +1626,8 @@ int pgo_check_separators(const Graph& g, int seglen)
     }
     return MRS_OK;
 }
+
+int pgo_check_size(const mrs_pgo* h, const Graph& g, int seglen) { return pgo_check_size(h->solver, h->dense_limit, h->max_blocks, g, seglen); }
 
 }  // namespace
 
@@ -1451,7 +1788,7 @@ int mrs_pgo_set_segment_length(mrs_pgo* pgo, int32_t length)
     MRS_REQUIRE(pgo, "null pointer");
     MRS_REQUIRE(length >= 0, "the segment length must not be negative");
     if (length == pgo->seglen) return MRS_OK;
-    MRS_TRY(pgo_check_separators(pgo->g, length));
+    MRS_TRY(pgo_check_size(pgo, pgo->g, length));
     pgo->seglen = length;
     pgo->dirty = true;
     return MRS_OK;
@@ -1476,6 +1813,7 @@ int mrs_pgo_optimize(mrs_pgo* pgo, double eps, int32_t max_iterations, double* h
     h->result_valid = false;
     const bool timing = mrs::dev_env("MRS_PGO_TIMING") != nullptr;
     std::fill(h->stage_ms, h->stage_ms + 6, 0.0f);
+    std::fill(h->tier_ms, h->tier_ms + 2, 0.0f);
     {
         mrs::StageMarks m1(timing && !h->init_valid, nullptr);
         m1.mark(0);
@@ -1516,6 +1854,8 @@ int mrs_pgo_optimize(mrs_pgo* pgo, double eps, int32_t max_iterations, double* h
             h->stage_ms[3] += m.ms(2);
             h->stage_ms[4] += m.ms(3);
             h->stage_ms[5] += m.ms(5);
+            h->tier_ms[0] += m.ms(3, kMarkTierDown);
+            h->tier_ms[1] += m.ms(kMarkTierUp, 4);
         }
         ++its;
         MRS_TRY(pgo_check_pivots(h, hs, 2));
@@ -1556,6 +1896,7 @@ int mrs_pgo_optimize_lm(mrs_pgo* pgo, double eps, int32_t max_solves, double* h_
     h->result_valid = false;
     const bool timing = mrs::dev_env("MRS_PGO_TIMING") != nullptr;
     std::fill(h->stage_ms, h->stage_ms + 6, 0.0f);
+    std::fill(h->tier_ms, h->tier_ms + 2, 0.0f);
     {
         mrs::StageMarks m1(timing && !h->init_valid, nullptr);
         m1.mark(0);
@@ -1614,6 +1955,8 @@ int mrs_pgo_optimize_lm(mrs_pgo* pgo, double eps, int32_t max_solves, double* h_
             h->stage_ms[3] += m.ms(2);
             h->stage_ms[4] += m.ms(3);
             h->stage_ms[5] += m.ms(5);
+            h->tier_ms[0] += m.ms(3, kMarkTierDown);
+            h->tier_ms[1] += m.ms(kMarkTierUp, 4);
         }
         ++solves;
         MRS_TRY(pgo_check_pivots(h, hs.st, 2));
@@ -1659,6 +2002,44 @@ int mrs_pgo_optimize_lm(mrs_pgo* pgo, double eps, int32_t max_solves, double* h_
     h_info[5] = c;
     h_info[6] = h->topo[1].E;
     h_info[7] = lambda;
+    return MRS_OK;
+}
+
+int mrs_pgo_set_solver(mrs_pgo* pgo, int32_t solver, int32_t dense_limit, int32_t max_blocks)
+{
+    MRS_REQUIRE(pgo, "null pointer");
+    MRS_REQUIRE(solver == MRS_PGO_SOLVER_DENSE || solver == MRS_PGO_SOLVER_SPARSE, "the solver must be one of MRS_PGO_SOLVER_*");
+    MRS_REQUIRE(dense_limit >= -1 && dense_limit <= kMaxSep, "dense_limit must be in 0 .. MRS_PGO_MAX_SEPARATORS, or -1 for the default");
+    MRS_REQUIRE(max_blocks >= 0, "max_blocks must be positive, or 0 for the default");
+    if (dense_limit < 0 || solver == MRS_PGO_SOLVER_DENSE) dense_limit = kMaxSep;
+    if (max_blocks == 0 || solver == MRS_PGO_SOLVER_DENSE) max_blocks = MRS_PGO_MAX_SPARSE_BLOCKS;
+    if (solver == pgo->solver && dense_limit == pgo->dense_limit && max_blocks == pgo->max_blocks) return MRS_OK;
+    MRS_TRY(pgo_check_size(solver, dense_limit, max_blocks, pgo->g, pgo->seglen));
+    pgo->solver = solver;
+    pgo->dense_limit = dense_limit;
+    pgo->max_blocks = max_blocks;
+    pgo->dirty = true;
+    return MRS_OK;
+}
+
+int mrs_pgo_get_solver_stats(mrs_pgo* pgo, int32_t stage, int64_t* h_stats)
+{
+    MRS_REQUIRE(pgo && h_stats, "null pointer");
+    MRS_REQUIRE(stage == 1 || stage == 2, "the stage must be 1 or 2");
+    Topology t;
+    mrs::pgo::SparseOrder o;
+    build_topology(pgo->g, pgo->seglen, stage, &t);
+    o.E = o.core = t.E;
+    if (pgo->solver == MRS_PGO_SOLVER_SPARSE) MRS_TRY(pgo_sparse_order(t, stage, pgo->dense_limit, pgo->max_blocks, &o));
+    const int64_t stats[MRS_PGO_SOLVER_STATS] = {o.E, o.eliminated, o.core, o.levels, o.blocks, o.updates, o.max_degree, pgo->solver};
+    std::copy(stats, stats + MRS_PGO_SOLVER_STATS, h_stats);
+    return MRS_OK;
+}
+
+int mrs_pgo_last_tier_ms(mrs_pgo* pgo, float* h_ms)
+{
+    MRS_REQUIRE(pgo && h_ms, "null pointer");
+    std::copy(pgo->tier_ms, pgo->tier_ms + 2, h_ms);
     return MRS_OK;
 }
 

@@ -20,6 +20,9 @@ _INFO, _INFO_LM = _lib.header_int("MRS_PGO_INFO_DOUBLES"), _lib.header_int("MRS_
 KERNELS = {None: _lib.header_int("MRS_PGO_KERNEL_NONE"), "none": _lib.header_int("MRS_PGO_KERNEL_NONE"),
            "huber": _lib.header_int("MRS_PGO_KERNEL_HUBER"), "cauchy": _lib.header_int("MRS_PGO_KERNEL_CAUCHY"),
            "geman_mcclure": _lib.header_int("MRS_PGO_KERNEL_GEMAN_MCCLURE")}
+SOLVERS = {"dense": _lib.header_int("MRS_PGO_SOLVER_DENSE"), "sparse": _lib.header_int("MRS_PGO_SOLVER_SPARSE")}
+MAX_SPARSE_BLOCKS, SPARSE_DEGREE_SLACK = _lib.header_int("MRS_PGO_MAX_SPARSE_BLOCKS"), _lib.header_int("MRS_PGO_SPARSE_DEGREE_SLACK")
+_STATS = _lib.header_int("MRS_PGO_SOLVER_STATS")
 # the reference's own factor noise (global_manager.cpp:103-109: loopNoise and odometryNoise), as Pose3 covariances: rotation xyz, then
 # translation xyz
 REFERENCE_LOOP_COVARIANCE = np.diag([1e-1, 1e-1, 1e-1, 1e-2, 1e-2, 1e-2])
@@ -32,6 +35,10 @@ ResultLM = collections.namedtuple("ResultLM", "T solves accepted converged max_d
 ResultLM.__doc__ = """T float64 [N, 4, 4]; solves done and steps accepted; converged (an accepted step had max|delta| < eps); the last accepted
 max|delta|; the cost (sum 0.5 r^2 over the odometry factors + sum rho(r) over the loops) at the stage-1 values and at T; the separators; the
 final lambda."""
+SolverStats = collections.namedtuple("SolverStats", "separators eliminated core levels blocks updates max_degree solver")
+SolverStats.__doc__ = """the sparse tier of a stage: its separators, how many of them are eliminated before the dense Cholesky and how many are
+left to it (the core), the levels (launches per direction), the blocks sum (d + 1) and block products sum d (d + 1) / 2 of the eliminated
+columns, the largest d, and the solver in force ("dense": nothing is eliminated)."""
 
 
 def _covariances(C, n, name):
@@ -153,6 +160,21 @@ class PoseGraph:
     def set_segment_length(self, length):
         _lib.load().mrs_pgo_set_segment_length(self._h, int(length))
 
+    def set_solver(self, solver, dense_limit=None, max_blocks=None):
+        """ "dense" (the default: every separator in one dense Cholesky, MAX_SEPARATORS of them at most) or "sparse": separators of low degree
+        are eliminated first, level after level, until dense_limit (None: MAX_SEPARATORS) are left; the size limit is then max_blocks (None:
+        MAX_SPARSE_BLOCKS) blocks of the eliminated columns"""
+        if solver not in SOLVERS:
+            raise ValueError("solver must be one of %s" % sorted(SOLVERS))
+        _lib.load().mrs_pgo_set_solver(self._h, SOLVERS[solver], -1 if dense_limit is None else int(dense_limit),
+                                       0 if max_blocks is None else int(max_blocks))
+
+    def solver_stats(self, stage=2):
+        """SolverStats of stage 1 (rotations) or 2 (Gauss-Newton) for the graph as it stands; host work only"""
+        st = np.zeros(_STATS, np.int64)
+        _lib.load().mrs_pgo_get_solver_stats(self._h, int(stage), st)
+        return SolverStats(*[int(x) for x in st[:7]], {v: k for k, v in SOLVERS.items()}[int(st[7])])
+
     def initialize(self):
         """stage 1 alone -> float64 [N, 4, 4]: the relaxed rotations projected to SO(3), zero translations"""
         T = np.zeros((self.n_poses, 4, 4))
@@ -178,4 +200,11 @@ class PoseGraph:
         the development timing switch was on"""
         ms = np.zeros(6, np.float32)
         _lib.load().mrs_pgo_last_stage_ms(self._h, ms)
+        return ms
+
+    def tier_ms(self):
+        """milliseconds of the sparse tier within the last optimize's dense-solve stage (its way down with the core's update, its way
+        back); zeros unless the development timing switch was on"""
+        ms = np.zeros(2, np.float32)
+        _lib.load().mrs_pgo_last_tier_ms(self._h, ms)
         return ms
