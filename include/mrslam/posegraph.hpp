@@ -168,6 +168,54 @@ public:
         return s;
     }
 
+    // ---- marginal covariances of the last result by selected inversion
+    struct MarginalInfo {
+        long long separators = 0, order = 0, bytes = 0;
+    };
+    // the poses stage 2 keeps as separators whether or not a loop touches them; an empty list clears the set.  The last result is gone.
+    void markPoses(const std::vector<int32_t>& poses)
+    {
+        check(mrs_pgo_mark_poses(h_, poses.empty() ? nullptr : poses.data(), static_cast<int32_t>(poses.size())), "mrs_pgo_mark_poses");
+    }
+    // factors and inverts the information matrix at the last result unless that is held already
+    MarginalInfo computeMarginals()
+    {
+        int64_t info[MRS_PGO_MARGINAL_INFO] = {};
+        check(mrs_pgo_compute_marginals(h_, info), "mrs_pgo_compute_marginals");
+        MarginalInfo m;
+        m.separators = info[0];
+        m.order = info[1];
+        m.bytes = info[2];
+        return m;
+    }
+    // [n][36] of the poses named, or [poses][36] of all poses; frame: MRS_PGO_FRAME_*
+    std::vector<double> marginals(const std::vector<int32_t>& poses, int frame = MRS_PGO_FRAME_CHORDAL)
+    {
+        computeMarginals();
+        std::vector<double> cov(poses.size() * 36);
+        if (!poses.empty())
+            check(mrs_pgo_get_marginals(h_, poses.data(), static_cast<int32_t>(poses.size()), frame, cov.data()), "mrs_pgo_get_marginals");
+        return cov;
+    }
+    std::vector<double> marginals(int frame = MRS_PGO_FRAME_CHORDAL)
+    {
+        computeMarginals();
+        std::vector<double> cov(static_cast<size_t>(poses_) * 36);
+        check(mrs_pgo_get_marginals(h_, nullptr, poses_, frame, cov.data()), "mrs_pgo_get_marginals");
+        return cov;
+    }
+    // [n][144]: [[S_ii, S_ij], [S_ji, S_jj]] per pair; answered between separators (and pose 0) and between consecutive poses of a chain
+    std::vector<double> jointMarginals(const std::vector<int32_t>& i, const std::vector<int32_t>& j, int frame = MRS_PGO_FRAME_CHORDAL)
+    {
+        if (i.size() != j.size()) throw std::invalid_argument("jointMarginals: i and j must have one entry per pair");
+        computeMarginals();
+        std::vector<double> cov(i.size() * 144);
+        if (!i.empty())
+            check(mrs_pgo_get_joint_marginals(h_, i.data(), j.data(), static_cast<int32_t>(i.size()), frame, cov.data()),
+                  "mrs_pgo_get_joint_marginals");
+        return cov;
+    }
+
 private:
     static void check(int st, const char* what)
     {

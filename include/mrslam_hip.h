@@ -1426,6 +1426,39 @@ int mrs_pgo_get_solver_stats(mrs_pgo* pgo, int32_t stage, int64_t* h_stats);
  * MRS_DEV=1 and MRS_PGO_TIMING=1 were set when the call ran, and when nothing is eliminated. */
 int mrs_pgo_last_tier_ms(mrs_pgo* pgo, float* h_ms);
 
+/* ---- marginal covariances of the last result by selected inversion ----
+ * H = sum_f w_f J_f^T L_f J_f is the Gauss-Newton information matrix at the poses the last mrs_pgo_optimize / mrs_pgo_optimize_lm left:
+ * L_f the factor's information (the unit model without noise), w_f = 1 for odometry factors and the kernel's weight at the result for
+ * the loops (what mrs_pgo_get_loop_state returns), lambda = 0 also after Levenberg-Marquardt, pose 0 held.  The marginal of pose p is the
+ * 6 x 6 diagonal block of H^-1 (zero for pose 0); the joint marginal of (i, j) is [[S_ii, S_ij], [S_ji, S_jj]].  Everything is fp64 with a
+ * fixed order of sums: the same bits from call to call and from a fresh handle. */
+#define MRS_PGO_FRAME_CHORDAL 0          /* the optimiser's own tangent: R <- R Exp(d[0:3]), t <- t + d[3:6] */
+#define MRS_PGO_FRAME_POSE3 1            /* M S M^T with M = blockdiag(I, R^T) per pose: gtsam's Pose3 local coordinates to first order */
+/* the tile of the triangular inverse and of the symmetric product of the reduced system */
+#define MRS_PGO_MARGINAL_TILE 32
+/* entries of mrs_pgo_compute_marginals' h_info: separators, order of the reduced system, bytes held by the handle for the marginals, 0 */
+#define MRS_PGO_MARGINAL_INFO 4
+/* Replaces the set of poses that stage 2 treats as separators whether or not a loop touches them (joint marginals are answered between
+ * separators); NULL, 0 clears it, which is the default.  Stage 1 never sees the set.  A pose outside the graph or named twice:
+ * MRS_ERR_ARG.  More than MRS_PGO_MAX_SEPARATORS separators (under SPARSE: blocks past the budget): MRS_ERR_UNSUPPORTED.  The handle is
+ * unchanged on refusal; otherwise the last result is gone, as after mrs_pgo_set_segment_length.  Marking pose 0 changes nothing. */
+int mrs_pgo_mark_poses(mrs_pgo* pgo, const int32_t* h_poses, int32_t n);
+/* Factors H at the last result again and inverts it on the factor's pattern: the inverse of the reduced system of the separators
+ * (8 (6 E)^2 bytes) and two 6 x 6 per pose, owned by the handle until the graph, the marks, the segment length, the solver or the result
+ * change.  h_info int64 [MRS_PGO_MARGINAL_INFO] (may be NULL).  Reads the result and does not change it.  MRS_ERR_ARG without a result
+ * of the graph as it stands; MRS_ERR_UNSUPPORTED when stage 2's sparse tier eliminated something; MRS_ERR_NOT_CONVERGED with the pose
+ * named when a pivot is not positive and finite. */
+int mrs_pgo_compute_marginals(mrs_pgo* pgo, int64_t* h_info);
+/* h_cov double [n][6][6], symmetric to the bit, of the poses h_poses [n] (NULL: all poses in order, n = the number of poses) in `frame`
+ * (MRS_PGO_FRAME_*).  Needs mrs_pgo_compute_marginals of the result as it stands: MRS_ERR_ARG otherwise. */
+int mrs_pgo_get_marginals(mrs_pgo* pgo, const int32_t* h_poses, int32_t n, int32_t frame, double* h_cov);
+/* h_cov double [n][12][12] of the pairs (h_i[u], h_j[u]).  Answered when both poses are separators of stage 2 or pose 0, or consecutive
+ * poses of one chain; any other pair is MRS_ERR_ARG and names the pose to mark, as is i == j.  Nothing is written on refusal. */
+int mrs_pgo_get_joint_marginals(mrs_pgo* pgo, const int32_t* h_i, const int32_t* h_j, int32_t n, int32_t frame, double* h_cov);
+/* The last mrs_pgo_compute_marginals between events: h_ms float [4] = milliseconds of the factorisation at the result, the triangular
+ * inverse, the symmetric product and the segment walk.  Zeros unless MRS_DEV=1 and MRS_PGO_TIMING=1 were set when the call ran. */
+int mrs_pgo_last_marginal_ms(mrs_pgo* pgo, float* h_ms);
+
 #ifdef __cplusplus
 }
 #endif

@@ -25,11 +25,13 @@
 // unit model's arithmetic), Levenberg-Marquardt step control (mrs_pgo_optimize_lm: lambda enters the gather, k_pgo_predicted and the sum
 // tree give the predicted decrease, one previous copy of the poses) and robust kernels on the loop factors (weights in the linearisation).
 // Past the dense system's MRS_PGO_MAX_SEPARATORS a handle may opt into a sparse elimination tier in front of it (DESIGN.md 4.23(j);
-// posegraph_order.hpp for the pattern, k_pgo_sp_* here).
+// posegraph_order.hpp for the pattern, k_pgo_sp_* here).  The marginal covariances of a result read the same factor
+// backwards: the inverse of the dense system by tiles (k_pgo_inv_*), then the segments (k_pgo_marginal_walk, posegraph_marginal.hpp).
 // No kernel waits for another workgroup, every device loop is bounded by a size known at launch, and a pivot block that is not positive
 // definite becomes a status word (the walk goes on with a unit pivot; the host ends the call).  The host reads 16 bytes per iteration.
 #include "common.hpp"
 #include "posegraph_factor.hpp"
+#include "posegraph_marginal.hpp"
 #include "posegraph_order.hpp"
 
 #include <algorithm>
@@ -45,6 +47,8 @@ constexpr int kThreads = 256;
 constexpr int kMaxChains = MRS_PGO_MAX_CHAINS, kMaxPoses = MRS_PGO_MAX_POSES, kMaxLoops = MRS_PGO_MAX_LOOPS, kMaxSep = MRS_PGO_MAX_SEPARATORS;
 constexpr int kNB = MRS_PGO_PANEL_WIDTH;  // panel width of the dense Cholesky: a multiple of both block sizes
 constexpr int kTile = 32;                // the trailing update works on kTile x kTile tiles
+constexpr int kMT = MRS_PGO_MARGINAL_TILE;   // the tile of the reduced system's inverse (marginal covariances)
+static_assert(kThreads % kMT == 0 && kMT % (kThreads / kMT) == 0 && kMT <= kThreads, "a workgroup covers a tile in whole rows");
 constexpr int kBig = 1 << 30;            // a failed pivot is recorded as kBig - index by atomicMax: the lowest index wins, 0 = none
 constexpr int kMarkTierDown = 8, kMarkTierUp = 9;   // StageMarks of the sparse tier: after its way down, before its way back
 constexpr int kTypeShift = 24;           // a contribution is type << 24 | index
@@ -668,6 +672,227 @@ __global__ __launch_bounds__(kThreads) void k_pgo_chol_back(double* __restrict__
     }
 }
 
+// ------------------------------------------------------------------ marginal covariances (posegraph_marginal.hpp)
+//
+// The inverse of the reduced system from its Cholesky factor L (lower, in S): M = L^-1 by tiles of kMT, block row after block row, then
+// Sigma = M^T M by independent tiles.  M is zero above its diagonal (the caller clears it), rows and columns past n read as zero.
+
+// M[I, I] = L[I, I]^-1 of every diagonal tile: a column per thread, forward substitution from LDS
+__global__ __launch_bounds__(kThreads) void k_pgo_inv_diag(const double* __restrict__ S, double* __restrict__ M, int n, size_t ld)
+{
+    __shared__ double Ls[kMT][kMT + 1], Xs[kMT][kMT + 1];
+    const int tid = threadIdx.x, k0 = blockIdx.x * kMT, nb = min(kMT, n - k0);
+    for (int e = tid; e < kMT * kMT; e += kThreads) {
+        const int r = e / kMT, c = e % kMT;
+        Ls[r][c] = (r < nb && c <= r) ? S[(size_t)(k0 + r) * ld + k0 + c] : (r == c ? 1.0 : 0.0);
+    }
+    __syncthreads();
+    if (tid < nb) {
+        const int c = tid;
+        for (int i = c; i < nb; ++i) {
+            double s = i == c ? 1.0 : 0.0;
+            for (int k = c; k < i; ++k) s -= Ls[i][k] * Xs[k][c];
+            Xs[i][c] = s / Ls[i][i];
+        }
+        for (int i = c; i < nb; ++i) M[(size_t)(k0 + i) * ld + k0 + c] = Xs[i][c];
+    }
+}
+
+// block row I of M below the diagonal, a workgroup per tile J < I: M[I, J] = -M[I, I] sum_{K = J}^{I - 1} L[I, K] M[K, J], K ascending.
+// Rows K < I of M are complete when row I is launched.
+__global__ __launch_bounds__(kThreads) void k_pgo_inv_row(const double* __restrict__ S, double* __restrict__ M, int n, size_t ld, int I)
+{
+    __shared__ double As[kMT][kMT + 1], Bs[kMT][kMT + 1];
+    const int tid = threadIdx.x, J = blockIdx.x, tx = tid % kMT, ty = tid / kMT, i0 = I * kMT, j0 = J * kMT;
+    constexpr int kRows = kThreads / kMT, kPer = kMT / kRows;
+    double acc[kPer];
+#pragma unroll
+    for (int q = 0; q < kPer; ++q) acc[q] = 0.0;
+    for (int K = J; K < I; ++K) {
+        const int k0 = K * kMT;
+        __syncthreads();
+        for (int e = tid; e < kMT * kMT; e += kThreads) {
+            const int r = e / kMT, c = e % kMT;
+            As[r][c] = i0 + r < n ? S[(size_t)(i0 + r) * ld + k0 + c] : 0.0;
+            Bs[r][c] = M[(size_t)(k0 + r) * ld + j0 + c];
+        }
+        __syncthreads();
+#pragma unroll
+        for (int q = 0; q < kPer; ++q) {
+            double s = acc[q];
+#pragma unroll
+            for (int k = 0; k < kMT; ++k) s += As[ty + q * kRows][k] * Bs[k][tx];
+            acc[q] = s;
+        }
+    }
+    __syncthreads();
+    for (int e = tid; e < kMT * kMT; e += kThreads) {
+        const int r = e / kMT, c = e % kMT;
+        As[r][c] = (i0 + r < n && i0 + c < n) ? M[(size_t)(i0 + r) * ld + i0 + c] : 0.0;
+    }
+#pragma unroll
+    for (int q = 0; q < kPer; ++q) Bs[ty + q * kRows][tx] = acc[q];
+    __syncthreads();
+#pragma unroll
+    for (int q = 0; q < kPer; ++q) {
+        const int r = ty + q * kRows;
+        double s = 0.0;
+#pragma unroll
+        for (int k = 0; k < kMT; ++k) s -= As[r][k] * Bs[k][tx];
+        if (i0 + r < n) M[(size_t)(i0 + r) * ld + j0 + tx] = s;
+    }
+}
+
+// Sigma = M^T M, a workgroup per tile (I, J) of the lower triangle: sum_{K >= I} M[K, I]^T M[K, J], K and the rows within a tile ascending;
+// the tile and its mirror image are written, so Sigma is full and symmetric to the bit
+__global__ __launch_bounds__(kThreads) void k_pgo_inv_product(const double* __restrict__ M, double* __restrict__ Sig, int n, size_t ld)
+{
+    __shared__ double As[kMT][kMT + 1], Bs[kMT][kMT + 1];
+    if (blockIdx.x > blockIdx.y) return;
+    const int tid = threadIdx.x, I = blockIdx.y, J = blockIdx.x, tx = tid % kMT, ty = tid / kMT, i0 = I * kMT, j0 = J * kMT;
+    const int nblk = (n + kMT - 1) / kMT;
+    constexpr int kRows = kThreads / kMT, kPer = kMT / kRows;
+    double acc[kPer];
+#pragma unroll
+    for (int q = 0; q < kPer; ++q) acc[q] = 0.0;
+    for (int K = I; K < nblk; ++K) {
+        const int k0 = K * kMT;
+        __syncthreads();
+        for (int e = tid; e < kMT * kMT; e += kThreads) {
+            const int r = e / kMT, c = e % kMT;
+            const bool in = k0 + r < n;
+            As[r][c] = (in && i0 + c < n) ? M[(size_t)(k0 + r) * ld + i0 + c] : 0.0;
+            Bs[r][c] = (in && j0 + c < n) ? M[(size_t)(k0 + r) * ld + j0 + c] : 0.0;
+        }
+        __syncthreads();
+#pragma unroll
+        for (int q = 0; q < kPer; ++q) {
+            double s = acc[q];
+#pragma unroll
+            for (int k = 0; k < kMT; ++k) s += As[k][ty + q * kRows] * Bs[k][tx];
+            acc[q] = s;
+        }
+    }
+#pragma unroll
+    for (int q = 0; q < kPer; ++q) {
+        const int i = i0 + ty + q * kRows, j = j0 + tx;
+        if (i < n && j < n) {
+            Sig[(size_t)i * ld + j] = acc[q];
+            if (I != J) Sig[(size_t)j * ld + i] = acc[q];
+        }
+    }
+}
+
+// The segments backwards, a lane per segment (posegraph_marginal.hpp): from the blocks (r, r), (r, l), (l, l) of Sigma it leaves, per pose
+// p of the segment, Spp [p] = S_pp and Spn [p] = S_{p, p + 1}, and Spn [l] of a left separator whose successor is the segment's first pose.
+// A bounding separator that is missing (a chain's end, or the held pose 0) enters as zero blocks.
+__global__ __launch_bounds__(64) void k_pgo_marginal_walk(SegView sv, const double* __restrict__ Lk, const double* __restrict__ Ak,
+                                                          const double* __restrict__ Wk, const double* __restrict__ Sig, size_t ld,
+                                                          double* __restrict__ Spp, double* __restrict__ Spn)
+{
+    constexpr int B = 6, BB = 36;
+    const int s = blockIdx.x * 64 + threadIdx.x;
+    if (s >= sv.n) return;
+    const int first = sv.first[s], m = sv.len[s], left = sv.left[s], right = sv.right[s];
+    double Sll[BB], Snl[BB], Snn[BB], L[BB], A[BB], W[BB], pl[BB], pn[BB], pp[BB];
+#pragma unroll
+    for (int r = 0; r < B; ++r)
+#pragma unroll
+        for (int c = 0; c < B; ++c) {
+            Sll[r * B + c] = left >= 0 ? Sig[((size_t)B * left + r) * ld + (size_t)B * left + c] : 0.0;
+            Snn[r * B + c] = right >= 0 ? Sig[((size_t)B * right + r) * ld + (size_t)B * right + c] : 0.0;
+            Snl[r * B + c] = (left >= 0 && right >= 0) ? Sig[((size_t)B * right + r) * ld + (size_t)B * left + c] : 0.0;
+        }
+    for (int k = m - 1; k >= 0; --k) {
+        const int p = first + k;
+#pragma unroll
+        for (int e = 0; e < BB; ++e) {
+            L[e] = Lk[(size_t)p * BB + e];
+            A[e] = Ak[(size_t)p * BB + e];
+            W[e] = Wk[(size_t)p * BB + e];
+        }
+        mrs::pgo::marginal_step<B>(L, A, W, Sll, Snl, Snn, pl, pn, pp);
+        const bool has_next = k + 1 < m || right >= 0;
+#pragma unroll
+        for (int e = 0; e < BB; ++e) {
+            Spp[(size_t)p * BB + e] = pp[e];
+            Spn[(size_t)p * BB + e] = has_next ? pn[e] : 0.0;
+            Snl[e] = pl[e];
+            Snn[e] = pp[e];
+        }
+    }
+    if (left >= 0) {                                             // the left separator is pose first - 1: S_{l, first} = S_{first, l}^T
+#pragma unroll
+        for (int r = 0; r < B; ++r)
+#pragma unroll
+            for (int c = 0; c < B; ++c) Spn[(size_t)(first - 1) * BB + r * B + c] = Snl[c * B + r];
+    }
+}
+
+// the block S_ab [36] of two poses the queries may name: a == b, both separators (or pose 0), or |a - b| == 1 within a chain
+__device__ __forceinline__ void marginal_block(int a, int b, const int* __restrict__ sep_of, const double* __restrict__ Sig, size_t ld,
+                                               const double* __restrict__ Spp, const double* __restrict__ Spn, double* X)
+{
+    const int sa = sep_of[a], sb = sep_of[b];
+#pragma unroll
+    for (int r = 0; r < 6; ++r)
+#pragma unroll
+        for (int c = 0; c < 6; ++c) {
+            double v = 0.0;
+            if (a == 0 || b == 0) v = 0.0;                       // the held pose
+            else if (sa >= 0 && sb >= 0) v = Sig[((size_t)6 * sa + r) * ld + (size_t)6 * sb + c];
+            else if (a == b) v = Spp[(size_t)a * 36 + r * 6 + c];
+            else if (a < b) v = Spn[(size_t)a * 36 + r * 6 + c];
+            else v = Spn[(size_t)b * 36 + c * 6 + r];
+            X[r * 6 + c] = v;
+        }
+}
+
+// A thread per query.  qj null: the marginal [36] of pose qi[u] (qi null: of pose u); otherwise the joint marginal [144] of (qi[u], qj[u]).
+// The diagonal blocks are symmetric to the bit in either frame, the two cross blocks are each other's transpose.
+__global__ __launch_bounds__(kThreads) void k_pgo_marginal_gather(const int* __restrict__ qi, const int* __restrict__ qj, int nq, int frame,
+                                                                  const double* __restrict__ T, const int* __restrict__ sep_of,
+                                                                  const double* __restrict__ Sig, size_t ld, const double* __restrict__ Spp,
+                                                                  const double* __restrict__ Spn, double* __restrict__ out)
+{
+    const int u = blockIdx.x * kThreads + threadIdx.x;
+    if (u >= nq) return;
+    const int i = qi ? qi[u] : u;
+    double Ti[12], Tj[12], X[36];
+#pragma unroll
+    for (int k = 0; k < 12; ++k) Ti[k] = T[(size_t)i * 12 + k];
+    marginal_block(i, i, sep_of, Sig, ld, Spp, Spn, X);
+    if (frame == MRS_PGO_FRAME_POSE3) {
+        mrs::pgo::marginal_to_pose3(Ti, Ti, X);
+        mrs::pgo::marginal_symmetrize<6>(X);
+    }
+    if (!qj) {
+#pragma unroll
+        for (int e = 0; e < 36; ++e) out[(size_t)u * 36 + e] = X[e];
+        return;
+    }
+    const int j = qj[u];
+    double* o = out + (size_t)u * 144;
+#pragma unroll
+    for (int k = 0; k < 12; ++k) Tj[k] = T[(size_t)j * 12 + k];
+#pragma unroll
+    for (int e = 0; e < 36; ++e) o[(e / 6) * 12 + e % 6] = X[e];
+    marginal_block(j, j, sep_of, Sig, ld, Spp, Spn, X);
+    if (frame == MRS_PGO_FRAME_POSE3) {
+        mrs::pgo::marginal_to_pose3(Tj, Tj, X);
+        mrs::pgo::marginal_symmetrize<6>(X);
+    }
+#pragma unroll
+    for (int e = 0; e < 36; ++e) o[(6 + e / 6) * 12 + 6 + e % 6] = X[e];
+    marginal_block(i, j, sep_of, Sig, ld, Spp, Spn, X);
+    if (frame == MRS_PGO_FRAME_POSE3) mrs::pgo::marginal_to_pose3(Ti, Tj, X);
+#pragma unroll
+    for (int e = 0; e < 36; ++e) {
+        o[(e / 6) * 12 + 6 + e % 6] = X[e];
+        o[(6 + e % 6) * 12 + e / 6] = X[e];
+    }
+}
+
 // ------------------------------------------------------------------ the sparse tier in front of the dense system (posegraph_order.hpp)
 //
 // Column k (an elimination position) owns d + 1 blocks of Lb from block col_ptr[k] + k: L_k, then W_k[s] = A_rk L_k^-T for the rows r of its
@@ -932,13 +1157,17 @@ struct Graph {
     int nr = 0, N = 0;
     std::vector<int> start;                                      // [nr + 1]
     std::vector<int> li, lj;                                     // the loops
+    std::vector<int> marks;                                      // poses stage 2 treats as separators anyway (mrs_pgo_mark_poses), ascending
 };
 
-// is_sep [N] for the loops given: the touched poses (pose 0 too) and the cuts.  Pose 0 ends a run in both stages, so both have the same cuts.
-void mark_separators(const Graph& g, int seglen, std::vector<char>* is_sep)
+// is_sep [N] for the loops given: the touched poses (pose 0 too), in stage 2 the marked poses, and the cuts.  Pose 0 ends a run in both
+// stages, so without marks both have the same cuts.
+void mark_separators(const Graph& g, int seglen, int stage, std::vector<char>* is_sep)
 {
     is_sep->assign(g.N, 0);
     for (size_t u = 0; u < g.li.size(); ++u) (*is_sep)[g.li[u]] = (*is_sep)[g.lj[u]] = 1;
+    if (stage == 2)
+        for (int p : g.marks) (*is_sep)[p] = 1;
     (*is_sep)[0] = 1;
     for (int c = 0; c < g.nr; ++c) {
         int run = 0;
@@ -959,7 +1188,7 @@ void mark_separators(const Graph& g, int seglen, std::vector<char>* is_sep)
 int count_separators(const Graph& g, int seglen)
 {
     std::vector<char> is_sep;
-    mark_separators(g, seglen, &is_sep);
+    mark_separators(g, seglen, 2, &is_sep);
     return (int)std::count(is_sep.begin(), is_sep.end(), 1) - 1;
 }
 
@@ -968,7 +1197,7 @@ void build_topology(const Graph& g, int seglen, int stage, Topology* t)
 {
     const int N = g.N, F = N - g.nr + (int)g.li.size();
     std::vector<char> is_sep;
-    mark_separators(g, seglen, &is_sep);
+    mark_separators(g, seglen, stage, &is_sep);
     const bool rot = stage == 1;
     *t = Topology();
     t->n_nodes = rot ? N + 1 : N;
@@ -1156,6 +1385,22 @@ struct mrs_pgo {
     mrs::DeviceBuffer<double> err_out;
     float stage_ms[6] = {0, 0, 0, 0, 0, 0};
     float tier_ms[2] = {0, 0};                                   // of stage 2's sparse tier: its way down with the core's update, its way back
+    // marginal covariances of the last result (mrs_pgo_compute_marginals): in force while marg_valid && result_valid && !dirty
+    bool marg_valid = false;
+    mrs::DeviceBuffer<double> Sig, Spp, Spn;                     // the reduced system's inverse [6 E][6 E]; per pose S_pp and S_{p, p + 1}
+    mrs::DeviceBuffer<int> sep_of, query;                        // per pose its reduced index or -1; the poses of a query
+    mrs::DeviceBuffer<double> cov;                               // a query's blocks
+    std::vector<int> h_sep_of;
+    float marg_ms[4] = {0, 0, 0, 0};
+
+    // what the marginals hold is dropped with the result they belong to
+    void drop_marginals()
+    {
+        marg_valid = false;
+        Sig.reset();
+        Spp.reset();
+        Spn.reset();
+    }
 };
 
 namespace {
@@ -1187,6 +1432,7 @@ int pgo_sync(mrs_pgo* h)
     const int N = g.N, L = (int)g.li.size(), F = N - g.nr + L, F1 = F + 1;
     h->F = F;
     h->init_valid = false;
+    h->drop_marginals();
     build_topology(g, h->seglen, 1, &h->topo[0]);
     build_topology(g, h->seglen, 2, &h->topo[1]);
     MRS_TRY(h->dtopo[0].upload(h->topo[0]));
@@ -1629,6 +1875,29 @@ int pgo_check_size(int solver, int dense_limit, int max_blocks, const Graph& g, 
 
 int pgo_check_size(const mrs_pgo* h, const Graph& g, int seglen) { return pgo_check_size(h->solver, h->dense_limit, h->max_blocks, g, seglen); }
 
+// a query of the marginals: its poses to the device, k_pgo_marginal_gather, its blocks of `doubles` each back to the host
+int pgo_marginal_query(mrs_pgo* h, const int32_t* h_i, const int32_t* h_j, int n, int frame, int doubles, double* h_cov)
+{
+    MRS_HIP_TRY(hipSetDevice(h->ctx->device));
+    const size_t nq = (size_t)n, ld = (size_t)6 * h->topo[1].E;
+    MRS_TRY(h->query.reserve(2 * nq, 2 * nq + nq / 2));
+    MRS_TRY(h->cov.reserve(nq * doubles, nq * doubles + nq * doubles / 4));
+    int *qi = nullptr, *qj = nullptr;
+    if (h_i) {
+        qi = h->query.get();
+        MRS_HIP_TRY(hipMemcpy(qi, h_i, nq * sizeof(int), hipMemcpyHostToDevice));
+    }
+    if (h_j) {
+        qj = h->query.get() + nq;
+        MRS_HIP_TRY(hipMemcpy(qj, h_j, nq * sizeof(int), hipMemcpyHostToDevice));
+    }
+    hipLaunchKernelGGL(k_pgo_marginal_gather, dim3(blocks_for(n, kThreads)), dim3(kThreads), 0, nullptr, qi, qj, n, frame, h->T.get(),
+                       h->sep_of.get(), h->Sig.get(), ld, h->Spp.get(), h->Spn.get(), h->cov.get());
+    MRS_HIP_TRY(hipGetLastError());
+    MRS_HIP_TRY(hipMemcpy(h_cov, h->cov.get(), nq * doubles * sizeof(double), hipMemcpyDeviceToHost));
+    return MRS_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1731,6 +2000,7 @@ int mrs_pgo_set_loop_kernel(mrs_pgo* pgo, int32_t kernel, double k)
     pgo->kernel = kernel;
     pgo->kernel_k = k;
     pgo->result_valid = false;
+    pgo->marg_valid = false;
     return MRS_OK;
 }
 
@@ -1811,6 +2081,7 @@ int mrs_pgo_optimize(mrs_pgo* pgo, double eps, int32_t max_iterations, double* h
     MRS_TRY(pgo_ready(pgo));
     mrs_pgo* h = pgo;
     h->result_valid = false;
+    h->drop_marginals();
     const bool timing = mrs::dev_env("MRS_PGO_TIMING") != nullptr;
     std::fill(h->stage_ms, h->stage_ms + 6, 0.0f);
     std::fill(h->tier_ms, h->tier_ms + 2, 0.0f);
@@ -1894,6 +2165,7 @@ int mrs_pgo_optimize_lm(mrs_pgo* pgo, double eps, int32_t max_solves, double* h_
     MRS_TRY(pgo_ready(pgo));
     mrs_pgo* h = pgo;
     h->result_valid = false;
+    h->drop_marginals();
     const bool timing = mrs::dev_env("MRS_PGO_TIMING") != nullptr;
     std::fill(h->stage_ms, h->stage_ms + 6, 0.0f);
     std::fill(h->tier_ms, h->tier_ms + 2, 0.0f);
@@ -2047,6 +2319,152 @@ int mrs_pgo_last_stage_ms(mrs_pgo* pgo, float* h_ms)
 {
     MRS_REQUIRE(pgo && h_ms, "null pointer");
     std::copy(pgo->stage_ms, pgo->stage_ms + 6, h_ms);
+    return MRS_OK;
+}
+
+// ---- marginal covariances of the last result
+
+int mrs_pgo_mark_poses(mrs_pgo* pgo, const int32_t* h_poses, int32_t n)
+{
+    MRS_REQUIRE(pgo, "null pointer");
+    MRS_REQUIRE(n >= 0, "n must not be negative");
+    MRS_REQUIRE(h_poses || n == 0, "null pointer");
+    std::vector<int> marks(h_poses, h_poses + n);
+    std::sort(marks.begin(), marks.end());
+    MRS_REQUIRE(marks.empty() || (marks.front() >= 0 && marks.back() < pgo->g.N), "a marked pose lies outside the graph");
+    MRS_REQUIRE(std::adjacent_find(marks.begin(), marks.end()) == marks.end(), "a pose is marked twice");
+    if (marks == pgo->g.marks) return MRS_OK;
+    Graph g = pgo->g;
+    g.marks = marks;
+    MRS_TRY(pgo_check_size(pgo, g, pgo->seglen));
+    pgo->g = std::move(g);
+    pgo->dirty = true;
+    pgo->result_valid = false;
+    pgo->marg_valid = false;
+    return MRS_OK;
+}
+
+int mrs_pgo_compute_marginals(mrs_pgo* pgo, int64_t* h_info)
+{
+    MRS_REQUIRE(pgo, "null pointer");
+    MRS_REQUIRE(pgo->result_valid && !pgo->dirty, "no optimisation of the graph as it stands has finished");
+    mrs_pgo* h = pgo;
+    if (h->sp[1].eliminated > 0) {
+        mrs::set_error("marginals are not built through the sparse tier: it eliminated %d of stage 2's %d separators", h->sp[1].eliminated,
+                       h->topo[1].E);
+        return MRS_ERR_UNSUPPORTED;
+    }
+    const int N = h->g.N, F = h->F, E = h->topo[1].E, n = 6 * E, nblk = (int)blocks_for(n, kMT);
+    const size_t ld = (size_t)n, nseg = (size_t)h->dtopo[1].sv.n;
+    if (!h->marg_valid) {
+        MRS_HIP_TRY(hipSetDevice(h->ctx->device));
+        const bool timing = mrs::dev_env("MRS_PGO_TIMING") != nullptr;
+        std::fill(h->marg_ms, h->marg_ms + 4, 0.0f);
+        h->h_sep_of.assign(N, -1);
+        for (int a = 0; a < E; ++a) h->h_sep_of[h->topo[1].sep_node[a]] = a;
+        MRS_TRY(h->sep_of.reserve((size_t)N, (size_t)N));
+        MRS_TRY(h->Sig.reserve(std::max<size_t>(ld * ld, 1), std::max<size_t>(ld * ld, 1)));
+        MRS_TRY(h->Spp.reserve((size_t)N * 36, (size_t)N * 36));
+        MRS_TRY(h->Spn.reserve((size_t)N * 36, (size_t)N * 36));
+        MRS_HIP_TRY(hipMemcpy(h->sep_of.get(), h->h_sep_of.data(), (size_t)N * sizeof(int), hipMemcpyHostToDevice));
+        // the factor at the result: the weights of the loops' state, no damping, zero right-hand sides
+        const FactorPass pass(h, h->result_weighted, h->result_weighted ? h->kernel : (int)MRS_PGO_KERNEL_NONE);
+        double *T = h->T.get(), *S = h->S.get(), *M = h->Sig.get();
+        Status* st = h->status.get();
+        mrs::StageMarks m(timing, nullptr);
+        MRS_HIP_TRY(hipMemsetAsync(st, 0, sizeof(Status), nullptr));
+        m.mark(0);
+        pass.linearize(T, true);
+        pass.gather(0.0, false);
+        MRS_HIP_TRY(hipMemsetAsync(h->gp.get(), 0, (size_t)N * 6 * sizeof(double), nullptr));
+        MRS_TRY((pgo_solve<6, 1>(h, 2, nullptr, 0)));
+        if (F) pass.error(T);                                    // the loops' state as the optimiser left it
+        m.mark(1);
+        Status hs;
+        MRS_HIP_TRY(hipMemcpy(&hs, st, sizeof(hs), hipMemcpyDeviceToHost));
+        MRS_TRY(pgo_check_pivots(h, hs, 2));
+        MRS_HIP_TRY(hipMemsetAsync(h->Spp.get(), 0, (size_t)N * 36 * sizeof(double), nullptr));
+        MRS_HIP_TRY(hipMemsetAsync(h->Spn.get(), 0, (size_t)N * 36 * sizeof(double), nullptr));
+        m.mark(2);
+        if (E) {
+            MRS_HIP_TRY(hipMemsetAsync(M, 0, ld * ld * sizeof(double), nullptr));
+            hipLaunchKernelGGL(k_pgo_inv_diag, dim3(nblk), dim3(kThreads), 0, nullptr, S, M, n, ld);
+            for (int I = 1; I < nblk; ++I) hipLaunchKernelGGL(k_pgo_inv_row, dim3(I), dim3(kThreads), 0, nullptr, S, M, n, ld, I);
+            m.mark(3);
+            // Sigma takes the factor's place in S and is then copied over M: the handle keeps one array, apart from the optimiser's own
+            hipLaunchKernelGGL(k_pgo_inv_product, dim3(nblk, nblk), dim3(kThreads), 0, nullptr, M, S, n, ld);
+            MRS_HIP_TRY(hipMemcpyAsync(M, S, ld * ld * sizeof(double), hipMemcpyDeviceToDevice, nullptr));
+        } else {
+            m.mark(3);
+        }
+        m.mark(4);
+        if (nseg)
+            hipLaunchKernelGGL(k_pgo_marginal_walk, dim3(blocks_for((long long)nseg, 64)), dim3(64), 0, nullptr, h->dtopo[1].sv, h->Lk.get(),
+                               h->Ak.get(), h->Wk.get(), M, ld, h->Spp.get(), h->Spn.get());
+        m.mark(5);
+        MRS_HIP_TRY(hipGetLastError());
+        MRS_HIP_TRY(hipStreamSynchronize(nullptr));
+        if (m) {
+            h->marg_ms[0] = m.ms(0);
+            h->marg_ms[1] = m.ms(2);
+            h->marg_ms[2] = m.ms(3);
+            h->marg_ms[3] = m.ms(4);
+        }
+        h->marg_valid = true;
+    }
+    if (h_info) {
+        h_info[0] = E;
+        h_info[1] = n;
+        h_info[2] = (int64_t)((h->Sig.capacity() + h->Spp.capacity() + h->Spn.capacity()) * sizeof(double));
+        h_info[3] = 0;
+    }
+    return MRS_OK;
+}
+
+int mrs_pgo_get_marginals(mrs_pgo* pgo, const int32_t* h_poses, int32_t n, int32_t frame, double* h_cov)
+{
+    MRS_REQUIRE(pgo && h_cov, "null pointer");
+    MRS_REQUIRE(frame == MRS_PGO_FRAME_CHORDAL || frame == MRS_PGO_FRAME_POSE3, "the frame must be one of MRS_PGO_FRAME_*");
+    MRS_REQUIRE(pgo->result_valid && !pgo->dirty, "no optimisation of the graph as it stands has finished");
+    MRS_REQUIRE(pgo->marg_valid, "mrs_pgo_compute_marginals has not run on the result as it stands");
+    if (h_poses) {
+        MRS_REQUIRE(n >= 0, "n must not be negative");
+        for (int u = 0; u < n; ++u) MRS_REQUIRE(h_poses[u] >= 0 && h_poses[u] < pgo->g.N, "a query names a pose outside the graph");
+    } else {
+        MRS_REQUIRE(n == pgo->g.N, "without a list of poses n is the number of poses");
+    }
+    if (n == 0) return MRS_OK;
+    return pgo_marginal_query(pgo, h_poses, nullptr, n, frame, 36, h_cov);
+}
+
+int mrs_pgo_get_joint_marginals(mrs_pgo* pgo, const int32_t* h_i, const int32_t* h_j, int32_t n, int32_t frame, double* h_cov)
+{
+    MRS_REQUIRE(pgo && h_cov, "null pointer");
+    MRS_REQUIRE(n >= 0, "n must not be negative");
+    MRS_REQUIRE((h_i && h_j) || n == 0, "null pointer");
+    MRS_REQUIRE(frame == MRS_PGO_FRAME_CHORDAL || frame == MRS_PGO_FRAME_POSE3, "the frame must be one of MRS_PGO_FRAME_*");
+    MRS_REQUIRE(pgo->result_valid && !pgo->dirty, "no optimisation of the graph as it stands has finished");
+    MRS_REQUIRE(pgo->marg_valid, "mrs_pgo_compute_marginals has not run on the result as it stands");
+    const Graph& g = pgo->g;
+    for (int u = 0; u < n; ++u) {
+        const int i = h_i[u], j = h_j[u];
+        MRS_REQUIRE(i >= 0 && i < g.N && j >= 0 && j < g.N, "a query names a pose outside the graph");
+        MRS_REQUIRE(i != j, "a joint marginal is of two different poses");
+        const bool si = i == 0 || pgo->h_sep_of[i] >= 0, sj = j == 0 || pgo->h_sep_of[j] >= 0;
+        if (si && sj) continue;
+        if (std::abs(i - j) == 1 && pgo_chain_of(g, i) == pgo_chain_of(g, j)) continue;
+        mrs::set_error("bad argument: the joint marginal of poses %d and %d is not held: pose %d is not a separator of stage 2, mark it with "
+                       "mrs_pgo_mark_poses (pair %d of the call)", i, j, si ? j : i, u);
+        return MRS_ERR_ARG;
+    }
+    if (n == 0) return MRS_OK;
+    return pgo_marginal_query(pgo, h_i, h_j, n, frame, 144, h_cov);
+}
+
+int mrs_pgo_last_marginal_ms(mrs_pgo* pgo, float* h_ms)
+{
+    MRS_REQUIRE(pgo && h_ms, "null pointer");
+    std::copy(pgo->marg_ms, pgo->marg_ms + 4, h_ms);
     return MRS_OK;
 }
 

@@ -23,6 +23,8 @@ KERNELS = {None: _lib.header_int("MRS_PGO_KERNEL_NONE"), "none": _lib.header_int
 SOLVERS = {"dense": _lib.header_int("MRS_PGO_SOLVER_DENSE"), "sparse": _lib.header_int("MRS_PGO_SOLVER_SPARSE")}
 MAX_SPARSE_BLOCKS, SPARSE_DEGREE_SLACK = _lib.header_int("MRS_PGO_MAX_SPARSE_BLOCKS"), _lib.header_int("MRS_PGO_SPARSE_DEGREE_SLACK")
 _STATS = _lib.header_int("MRS_PGO_SOLVER_STATS")
+FRAMES = {"chordal": _lib.header_int("MRS_PGO_FRAME_CHORDAL"), "pose3": _lib.header_int("MRS_PGO_FRAME_POSE3")}
+_MARGINAL_INFO = _lib.header_int("MRS_PGO_MARGINAL_INFO")
 # the reference's own factor noise (global_manager.cpp:103-109: loopNoise and odometryNoise), as Pose3 covariances: rotation xyz, then
 # translation xyz
 REFERENCE_LOOP_COVARIANCE = np.diag([1e-1, 1e-1, 1e-1, 1e-2, 1e-2, 1e-2])
@@ -39,6 +41,38 @@ SolverStats = collections.namedtuple("SolverStats", "separators eliminated core 
 SolverStats.__doc__ = """the sparse tier of a stage: its separators, how many of them are eliminated before the dense Cholesky and how many are
 left to it (the core), the levels (launches per direction), the blocks sum (d + 1) and block products sum d (d + 1) / 2 of the eliminated
 columns, the largest d, and the solver in force ("dense": nothing is eliminated)."""
+
+
+MarginalInfo = collections.namedtuple("MarginalInfo", "separators order bytes")
+MarginalInfo.__doc__ = """what the handle holds for the marginals of the last result: the separators of stage 2, the order of the reduced
+system whose inverse is kept dense (6 per separator), and the bytes of device memory (that inverse and two 6 x 6 per pose)."""
+
+
+def _frame(frame):
+    if frame not in FRAMES:
+        raise ValueError("frame must be one of %s" % sorted(FRAMES))
+    return FRAMES[frame]
+
+
+def _adjoint(T):
+    """Ad(T) = [[R, 0], [skew(t) R, R]] in Pose3's order (rotation, translation)"""
+    R, t = T[:3, :3], T[:3, 3]
+    A = np.zeros((6, 6))
+    A[:3, :3] = A[3:, 3:] = R
+    A[3:, :3] = np.array([[0.0, -t[2], t[1]], [t[2], 0.0, -t[0]], [-t[1], t[0], 0.0]]) @ R
+    return A
+
+
+def between_covariance(joint_pose3, Ti, Tj):
+    """the 6 x 6 covariance of Z = Ti^-1 Tj in Pose3 local coordinates (rotation, translation: the order PcmGraph.set_covariances and
+    add_loops take) from the joint marginal [12, 12] of (i, j) in the "pose3" frame and the two poses [4, 4]: J S J^T with
+    J = [-Ad(Z^-1), I].  What a consistency test of a loop between i and j, or a gate on a candidate's initial pose, needs."""
+    S = np.asarray(joint_pose3, np.float64)
+    if S.shape != (12, 12):
+        raise ValueError("joint_pose3 must be [12, 12]")
+    Zi = between(Tj, Ti)                                          # Z^-1 = Tj^-1 Ti
+    J = np.hstack([-_adjoint(Zi), np.eye(6)])
+    return J @ S @ J.T
 
 
 def _covariances(C, n, name):
@@ -194,6 +228,57 @@ class PoseGraph:
         T, info = np.zeros((self.n_poses, 4, 4)), np.zeros(_INFO)
         _lib.load().mrs_pgo_optimize(self._h, float(eps), int(max_iterations), T, info)
         return Result(T, int(info[0]), bool(info[1]), float(info[2]), float(info[3]), float(info[4]), int(info[5]))
+
+    # ---- marginal covariances of the last result
+
+    def mark_poses(self, poses):
+        """replaces the set of poses that stage 2 keeps as separators whether or not a loop touches them, so that joint marginals
+        between them are answered; None or an empty list clears it.  A change of topology: the last result is gone."""
+        poses = np.ascontiguousarray([] if poses is None else poses, np.int32).reshape(-1)
+        _lib.load().mrs_pgo_mark_poses(self._h, poses if poses.size else None, poses.size)
+
+    def marginal_info(self):
+        """MarginalInfo of the marginals of the last result, computing them unless they are held already"""
+        info = np.zeros(_MARGINAL_INFO, np.int64)
+        _lib.load().mrs_pgo_compute_marginals(self._h, info)
+        return MarginalInfo(*[int(x) for x in info[:3]])
+
+    def marginals(self, poses=None, frame="chordal"):
+        """float64 [n, 6, 6]: the marginal covariance of every pose named (None: of all poses) at the last result, in the optimiser's
+        tangent ("chordal": rotation, then translation in the world frame) or in Pose3 local coordinates ("pose3").  The Gauss-Newton
+        information matrix at the result is factored and inverted on first use after a result; pose 0 is held, its marginal is zero."""
+        f = _frame(frame)
+        self.marginal_info()
+        if poses is None:
+            out = np.zeros((self.n_poses, 6, 6))
+            _lib.load().mrs_pgo_get_marginals(self._h, None, self.n_poses, f, out)
+            return out
+        poses = np.ascontiguousarray(poses, np.int32).reshape(-1)
+        out = np.zeros((poses.size, 6, 6))
+        if poses.size:
+            _lib.load().mrs_pgo_get_marginals(self._h, poses, poses.size, f, out)
+        return out
+
+    def joint_marginals(self, i, j, frame="chordal"):
+        """float64 [n, 12, 12]: [[S_ii, S_ij], [S_ji, S_jj]] per pair (i[u], j[u]).  Answered between separators of stage 2 (poses a loop
+        touches, cut poses, marked poses) and pose 0, and between consecutive poses of a chain; any other pair is refused with the pose
+        to mark named."""
+        f = _frame(frame)
+        i, j = np.ascontiguousarray(i, np.int32).reshape(-1), np.ascontiguousarray(j, np.int32).reshape(-1)
+        if i.size != j.size:
+            raise ValueError("i and j must have one entry per pair")
+        self.marginal_info()
+        out = np.zeros((i.size, 12, 12))
+        if i.size:
+            _lib.load().mrs_pgo_get_joint_marginals(self._h, i, j, i.size, f, out)
+        return out
+
+    def marginal_ms(self):
+        """milliseconds of the last computation of the marginals (the factorisation at the result, the triangular inverse, the symmetric
+        product, the segment walk); zeros unless the development timing switch was on"""
+        ms = np.zeros(4, np.float32)
+        _lib.load().mrs_pgo_last_marginal_ms(self._h, ms)
+        return ms
 
     def stage_ms(self):
         """milliseconds of the last optimize's stages (stage 1, linearise, segment walks, assembly, dense solve, retraction); zeros unless
